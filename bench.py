@@ -9,8 +9,14 @@ With --gpus N > 1 and no WORLD_SIZE in the environment this process starts the N
 ranks itself (torch.distributed.run as a child, before anything here touches the
 GPU) and exits with their code.  One step = every rank encodes and decodes its
 own shard of frames (--frames-per-gpu, independent frames, no data-path
-collective: weak scaling).  Rank 0 prints ONE JSON line.  Besides the contract
-fields it carries
+collective: weak scaling).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, primes and warms up, times the K steps and prints the line
+(plus --dump-outputs DIR: rank 0's outputs of the last timed step as .npy files,
+see dump_outputs).  --full adds everything else, after the timed steps or
+around them: the round-trip / stationarity checks and viewport metrics, the
+per-kernel event probes, two extra timed legs and the CPU baseline.  With --full
+the line also carries
   roofline      the dominant kernel (the Winograd F(4x2,3x3) tile convolution on the
                 fp32 matrix cores, csrc/wino42.hip) timed with events on its launch
                 stream during the timed steps.  `achieved` / `frac` count the
@@ -22,10 +28,12 @@ fields it carries
                 profiles/ when that summary is of the same kernel
   hbm           the gather / permute kernels of the same steps against the HBM roof
   cpu_baseline  the CPU oracle port of the same codec on a bounded sample
+  entropy       the step's phases and the entropy wavefront against its chain floor
+  value_one_frame, config.value_frames_resident, config.viewport_psnr_db / _ssim
 
 --mode analysis times the analysis transform alone (BASELINE config #3:
-SphereSlice + EncoderV2, 1x3x1024x2048) and reports a roofline table per kernel
-class instead.
+SphereSlice + EncoderV2, 1x3x1024x2048); with --full it reports a roofline
+table per kernel class instead.
 """
 import argparse
 import json
@@ -40,6 +48,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -235,6 +244,28 @@ def frame_u8(h, w, seed, content="smooth"):
     else:
         x = synthetic_frame(h, w, seed, "cpu")
     return (x[0] * 255.0 + 0.5).clamp_(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+
+
+DUMP_BUDGET = 56 << 20               # bytes of all --dump-outputs files together (< 64 MB with the .npy headers)
+
+
+def row_sample(n, row_bytes, budget, seed=20241):
+    """None when all `n` rows of `row_bytes` each fit in `budget` bytes, else the same seeded, sorted sample of
+    as many rows as fit (at least one) -- identical from run to run for the same shape"""
+    if n * row_bytes <= budget:
+        return None
+    k = max(1, int(budget // row_bytes))
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(load, path):
+    """--dump-outputs: the workload's outputs of the last timed step as `path`/<name>.npy, float32 / float64"""
+    os.makedirs(path, exist_ok=True)
+    arrays = load.outputs(DUMP_BUDGET)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
 
 
 class ConvProbe(object):
@@ -525,6 +556,36 @@ class CodecWorkload(object):
                 ssim += s
         return {"psnr_sum": psnr, "ssim_sum": ssim}
 
+    def outputs(self, budget):
+        """what a caller of the last step received: every frame's bitstream and its reconstruction (io="host": the
+        uint8 images in pinned host memory, io="resident": the float32 (n, 3, H, W) tensor in HBM).  The streams
+        are kept whole up to a quarter of `budget` bytes (beyond it the same leading bytes of every stream); the
+        images whole when they fit in the rest, otherwise the same seeded sample of rows in every frame"""
+        streams = [s for c in self.calls for s in c["streams"]]
+        lengths = [len(s) for s in streams]
+        room = budget // 4 // 4                                   # stream bytes, 4 bytes each as float32
+        keep = max(lengths) if sum(lengths) <= room else room // len(streams)
+        out = {"stream_lengths": np.array(lengths, np.float64),
+               "streams": np.concatenate([np.frombuffer(s[:keep], np.uint8) for s in streams]).astype(np.float32)}
+        rows = row_sample(self.H, self.F * self.W * 3 * 4, budget - budget // 4)
+        if rows is not None:
+            out["reconstruction_rows"] = rows.astype(np.float64)
+        recs = []
+        for i, call in enumerate(self.calls):
+            if self.io == "host":
+                # a later call of the same size through the same slot has overwritten this call's pinned images:
+                # tensor2img of its reconstruction (pseudo_codec.py:219-221), what the download carried
+                if any(c["n"] == call["n"] and c["slot"] == call["slot"] for c in self.calls[i + 1:]):
+                    img = (call["rec"] * 255.0).permute(0, 2, 3, 1).cpu().numpy().astype(np.uint8)
+                else:
+                    img = self.pipes[call["n"]]["pipe"].wait(call["slot"]).numpy()
+                recs.append((img if rows is None else img[:, rows]).astype(np.float32))
+            else:
+                rec = call["rec"] if rows is None else call["rec"][:, :, torch.from_numpy(rows).to(call["rec"].device)]
+                recs.append(rec.float().cpu().numpy())
+        out["reconstruction"] = np.concatenate(recs, 0)
+        return out
+
     def describe(self):
         per_call = "" if len(self.calls) == 1 else " in %d calls of <= %d" % (len(self.calls), max(c["n"] for c in self.calls))
         return "ERP %dx%d encode+decode, model-idx 3 --ssim (valid_dim 56), %d frame(s)/GPU/step%s" % (
@@ -545,8 +606,8 @@ class AnalysisWorkload(object):
 
     @torch.no_grad()
     def step(self):
-        for x in self.frames:
-            self.code = self.enc.encoder(self.enc.slice(x))
+        self.codes = [self.enc.encoder(self.enc.slice(x)) for x in self.frames]
+        self.code = self.codes[-1]
 
     def pixels_per_step(self):
         return float(self.F) * self.H * self.W
@@ -555,6 +616,16 @@ class AnalysisWorkload(object):
         assert self.code is not None and torch.isfinite(self.code).all()
         assert tuple(self.code.shape) == (16, 192, self.H // 256, self.W // 16)
         return {}
+
+    def outputs(self, budget):
+        """every frame's code (16, 192, H/256, W/16) of the last step, stacked; a seeded sample of its columns when
+        it is larger than `budget` bytes"""
+        code = torch.stack(self.codes, 0)
+        cols = row_sample(code.shape[-1], code[..., 0].numel() * 4, budget)
+        if cols is None:
+            return {"code": code.float().cpu().numpy()}
+        return {"code": code[..., torch.from_numpy(cols).to(code.device)].float().cpu().numpy(),
+                "code_columns": cols.astype(np.float64)}
 
     def describe(self):
         return "analysis transform only (SphereSlice + EncoderV2: 4x pseudo-conv stages + GDN), ERP %dx%d, %d frame(s)/GPU/step" % (
@@ -606,6 +677,15 @@ def parse_args(argv=None):
                     help="ONE real rank on one GPU with the host share rank 0 of N ranks on this node would get at "
                          "best: pinned to cgroup quota / N CPUs, LOCAL_WORLD_SIZE=N for the engine's thread / spin "
                          "rules (csrc/engine.cpp).  The 1 -> N curve of the HOST side without an N-GPU node")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: round-trip / stationarity checks and viewport metrics, "
+                         "per-kernel event probes in the timed steps (roofline, hbm, entropy; --mode analysis: the class "
+                         "table), the resident and one-frame legs and the CPU baseline (each still subject to its --no-* "
+                         "flag).  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's shard: bitstreams and "
+                         "reconstructions, or the analysis code) as DIR/<name>.npy in float32 / float64, < 64 MB in all "
+                         "(a fixed, seeded sample of rows when larger)")
     args = ap.parse_args(argv)
     if args.height is None:
         args.height = 2048 if args.mode == "codec" else 1024
@@ -675,8 +755,9 @@ def run(args, workload_cls=None, dist_backend="nccl", device_type="cuda"):
     for _ in range(args.prime + args.warmup):
         load.step()
     load.bits_first = None
+    full = bool(getattr(args, "full", False))
     probe = hbm = phases = None
-    if on_gpu:
+    if on_gpu and full:
         from pseudocylindrical_convolution_amd import PCONV
         probe, hbm = ConvProbe(), ConvProbe()
         PCONV.conv_probe, PCONV.hbm_probe = probe, hbm
@@ -698,11 +779,13 @@ def run(args, workload_cls=None, dist_backend="nccl", device_type="cuda"):
             d[1] += cpu
         for (name, allowed), (n, cpu) in sorted(per.items(), key=lambda kv: -kv[1][1]):
             sys.stderr.write("[bench threads] %-18s x%-3d cpus %-12s %.2f s\n" % (name, n, allowed, cpu))
-    if on_gpu:
+    if probe is not None:
         PCONV.conv_probe = PCONV.hbm_probe = None
         if phases is not None:
             load.codec.phase_probe = None
-    extra = {} if args.no_check else load.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(load, args.dump_outputs)   # before the checks and legs below run the workload again
+    extra = load.check() if full and not args.no_check else {}
 
     def timed_leg(work, steps, warm=1):
         """`steps` more timed steps of another configuration of the same codec (every rank runs them, same fences)"""
@@ -716,7 +799,7 @@ def run(args, workload_cls=None, dist_backend="nccl", device_type="cuda"):
         return (time.perf_counter() - t) / steps
 
     legs = {}
-    if on_gpu and load.name == "codec" and not args.no_extras and workload_cls is None:
+    if full and on_gpu and load.name == "codec" and not args.no_extras and workload_cls is None:
         if load.io == "host":
             # the same frames already resident in HBM, reconstructions left there (the figure of rounds 1-5)
             load.io = "resident"
@@ -782,9 +865,10 @@ def run(args, workload_cls=None, dist_backend="nccl", device_type="cuda"):
                                 "stay in host memory" if io == "host" else
                                 "frames and reconstructions resident in HBM; PCIe carries CDF rows / symbols / streams only"),
                   "weights": ("trained: %s" % args.weights) if args.weights else "seeded random (transforms seed 1234, entropy randn*0.05 seed 7)",
-                  "content": args.content,
-                  "tile_conv_s_per_step": round(conv_s, 4), "cores_per_rank": cores,
+                  "content": args.content, "cores_per_rank": cores,
                   "host_cores_busy": round(host_busy, 2)}
+        if per_kernel:
+            config["tile_conv_s_per_step"] = round(conv_s, 4)
         if totals.get("resident_s", 0.0) > 0:
             config["value_frames_resident"] = round(load.pixels_per_step() * n_joined / (totals["resident_s"] / n_joined) / 1e6, 4)
         if getattr(load, "codec", None) is not None and on_gpu:
@@ -802,7 +886,7 @@ def run(args, workload_cls=None, dist_backend="nccl", device_type="cuda"):
             config["share_gpu"] = "REHEARSAL: %d ranks on ONE GPU (gloo); not a scaling figure" % n_joined
         if load.name == "codec":
             config["bpp"] = round(totals["bits"] / (frames_total * load.H * load.W), 4)
-            if not args.no_check:
+            if full and not args.no_check:
                 config["viewport_psnr_db"] = round(totals["psnr_sum"] / frames_total, 3)
                 config["viewport_ssim"] = round(totals["ssim_sum"] / frames_total, 5)
                 config["roundtrip"] = "decoded symbols == encoded symbols, bits constant over the timed steps"
@@ -822,9 +906,9 @@ def run(args, workload_cls=None, dist_backend="nccl", device_type="cuda"):
         if hbm is not None and hbm.records:
             # the gather / permute kernels of the same timed steps against the HBM roof
             out["hbm"] = hbm_table(hbm.summarise())
-        if load.name == "analysis" or os.environ.get("PCONV_BENCH_TABLE"):
+        if full and (load.name == "analysis" or os.environ.get("PCONV_BENCH_TABLE")):
             out["roofline_table"] = table
-        if world == 1 and on_gpu and not args.no_cpu_baseline and load.name == "codec":
+        if full and world == 1 and on_gpu and not args.no_cpu_baseline and load.name == "codec":
             sh, sw = (int(v) for v in args.cpu_sample.split("x"))
             out["cpu_baseline"] = cpu_baseline(sh, sw, args.weights, args.content)
         print(json.dumps(out), flush=True)

@@ -5,6 +5,8 @@ authoring container:
   coder_*.npz     bitstreams written by the reference arithmetic coder, compiled
                   from its own sources into oracle/_ref/libcoder_ref.so
                   (oracle/Makefile), for seeded (tables, symbols)
+  ref_coder_live.npz  the same coder on the seeded cases of test_coder.py's live
+                  comparison
   set_weight.npz  PCONV_operator/base.py:set_weight outputs (imported by path)
   torch_helpers.npz  GDN.LowerBound, pytorch_ssim.SSIM(11,3), StubMask.Extract
                   outputs on seeded inputs (pure-torch files imported by path)
@@ -77,6 +79,33 @@ def coder_fixtures():
             stream = np.frombuffer(f.read(), dtype=np.uint8)
         np.savez_compressed(os.path.join(OUT, "coder_%s.npz" % name), tables=tab, symbols=sym, stream=stream)
         print("coder", name, len(sym), "symbols ->", len(stream), "bytes")
+
+
+def coder_live_fixture():
+    """ref_coder_live.npz: the reference coder's streams for the cases of tests/test_coder.py's live comparison
+    (the same seeded draw), so that the comparison also runs where oracle/_ref cannot be built"""
+    from oracle import coder_cpu
+    assert coder_cpu.ref_lib() is not None, "build oracle/_ref first: make -C oracle ref"
+    rng = np.random.default_rng(42)
+    tmp = tempfile.mkdtemp()
+    out = {}
+    for i, (n, skew) in enumerate([(1, False), (7, True), (5000, True), (5000, False)]):
+        w = (rng.gamma(0.2, 1.0, size=(n, 8)) + 1e-7) if skew else (rng.random((n, 8)) + 0.01)
+        w = w / w.sum(1, keepdims=True)
+        c = np.floor(np.cumsum(w, 1) * (65536 - 8)).astype(np.int64) + np.arange(1, 9)
+        tab = np.concatenate([np.zeros((n, 1), np.int64), c], 1).astype(np.int32)
+        tab[:, 8] = 65536
+        sym = (rng.integers(0, 65536, n)[:, None] >= tab[:, 1:]).sum(1).astype(np.int32)
+        path = os.path.join(tmp, "live_%d" % i)
+        c = coder_cpu.RefCoder(path)
+        c.start_encoder()
+        c.encodes(torch.from_numpy(tab), 8, torch.from_numpy(sym), n)
+        c.end_encoder()
+        with open(path, "rb") as f:
+            out["stream_%d" % i] = np.frombuffer(f.read(), dtype=np.uint8)
+        out["tables_%d" % i], out["symbols_%d" % i] = tab, sym
+        print("coder live case", i, n, "symbols ->", len(out["stream_%d" % i]), "bytes")
+    np.savez_compressed(os.path.join(OUT, "ref_coder_live.npz"), **out)
 
 
 def weight_fixtures():
@@ -181,6 +210,7 @@ if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     if "--graph-only" not in sys.argv:
         coder_fixtures()
+        coder_live_fixture()
         weight_fixtures()
         torch_fixtures()
     graph_fixtures()

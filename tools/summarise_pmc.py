@@ -1,6 +1,10 @@
 """Per-kernel summary of rocprofv3 --pmc passes (counter_collection CSVs) -> JSON.
 
     python tools/summarise_pmc.py OUT.json DIR [DIR ...] [--trace STATS_DIR] [--flops KERNEL=FLOPS_PER_LAUNCH ...]
+                                  [--bench-json FILE]
+
+--bench-json FILE: the JSON line of a `PCONV_BENCH_TABLE=1 python3 bench.py --full ...` pass (a plain bench run
+carries no per-kernel table).
 
 Every DIR holds one pass (`rocprofv3 --pmc <counters> --output-format csv -d DIR -- python3 bench.py ...`;
 separate passes as MI355X_MICROARCH.md prescribes: FETCH_SIZE and WRITE_SIZE do not fit
@@ -56,10 +60,13 @@ def main():
             trace = args[i + 1]
             i += 2
         elif args[i] == "--bench-json":
-            # the JSON line bench.py printed in one of the passes (PCONV_BENCH_TABLE=1): algorithmic
-            # flops per launch of every conv kernel, averaged over its launches
+            # the JSON line `PCONV_BENCH_TABLE=1 bench.py --full ...` printed in one of the passes: algorithmic
+            # flops per launch of every conv kernel, averaged over its launches (a plain run has no probes)
             with open(args[i + 1]) as f:
                 line = [l for l in f.read().splitlines() if l.startswith("{")][-1]
+            if "roofline_table" not in json.loads(line):
+                raise SystemExit("--bench-json %s: no roofline_table (run the pass as PCONV_BENCH_TABLE=1 bench.py --full)"
+                                 % args[i + 1])
             per = {}
             for r in json.loads(line).get("roofline_table", []):
                 d = per.setdefault(r["kernel"], [0.0, 0])
