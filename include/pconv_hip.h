@@ -166,6 +166,27 @@ int pconv_leaky_clip(float *x, long long n, void *stream);
 int pconv_frames_u8_to_f32(const uint8_t *in, float *out, int n, int height, int width, void *stream);
 int pconv_frames_f32_to_u8(const float *in, uint8_t *out, int n, int height, int width, void *stream);
 
+/* Panoramas of any size (csrc/erp_size.hip).  An h x w ERP frame (h, w >= 2) is coded at H = 256*ceil(h/256),
+ * W = 16*ceil(w/16), padded by a pure gather: with top = (H - h) / 2 and m = (W - w + 1) / 2, coded pixel (y', x')
+ * reads the image at
+ *     y = y' - top; flip = 0;
+ *     if (y < 0)       { y = -1 - y;        flip = 1; }   across the north pole
+ *     else if (y >= h) { y = 2*h - 1 - y;   flip = 1; }   across the south pole
+ *     y = clamp(y, 0, h - 1);                             only when the pad exceeds h
+ *     x = x' < w ? x' : (x' - w < m ? w - 1 : 0);         seam: left half repeats column w-1, right half column 0
+ *     if (flip) x = (x + w / 2) % w;                      half-turn of longitude across a pole
+ * and the decoder crops rows top..top+h-1, columns 0..w-1.  A codable size (h % 256 == 0, w % 16 == 0) maps to
+ * itself.  pconv_erp_coded_size is the single definition of (H, W, top): host only, 0 or PCONV_EINVAL (h or w
+ * below 2 or above 2^20).  The three kernels take any width (w <= 21834) and any uint8 byte alignment:
+ *   frames_u8_to_f32_erp: uint8 (n, h, w, 3) -> float32 (n, 3, H, W), float(u8) / 255.f as pconv_frames_u8_to_f32;
+ *   erp_pad_f32:          float32 (n, 3, h, w) -> float32 (n, 3, H, W);
+ *   frames_f32_to_u8_crop: float32 (n, 3, H, W) -> uint8 (n, h, w, 3), the crop with pconv_frames_f32_to_u8's cast.
+ * Float tensors of the coded size 16-byte aligned; n <= 65535. */
+int pconv_erp_coded_size(int h, int w, int *H, int *W, int *top);
+int pconv_frames_u8_to_f32_erp(const uint8_t *in, float *out, int n, int h, int w, void *stream);
+int pconv_erp_pad_f32(const float *in, float *out, int n, int h, int w, void *stream);
+int pconv_frames_f32_to_u8_crop(const float *in, uint8_t *out, int n, int h, int w, void *stream);
+
 /* PseudoDQuantOp.forward  (pseudo_dquant_cuda.cu:24-70)
  * weight (wc, levels) raw parameter, level_tab (wc, levels) scratch */
 int pconv_dquant(const float *x, const float *weight, float *level_tab, float *out,

@@ -1276,6 +1276,66 @@ def frames_f32_to_u8(x, out=None):
     return out
 
 
+def erp_coded_size(h, w):
+    """(H, W, top) of an h x w ERP frame under the pole / seam padding rule (pconv_erp_coded_size)"""
+    H, W, top = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    call("pconv_erp_coded_size", int(h), int(w), ctypes.byref(H), ctypes.byref(W), ctypes.byref(top))
+    return H.value, W.value, top.value
+
+
+def frames_u8_to_f32_erp(img, out=None):
+    """frames_u8_to_f32 for any ERP size: uint8 (n, h, w, 3) GPU tensor (any width, any byte offset) -> float32
+    (n, 3, H, W) padded by the pole / seam rule (erp_size.py), float(u8) / 255 as img2tensor"""
+    if not img.is_cuda:
+        raise PconvError("frames_u8_to_f32_erp: expected a GPU tensor (this build has no CPU path), got %s" % img.device)
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3 or not img.is_contiguous():
+        raise PconvError("frames_u8_to_f32_erp: contiguous uint8 (n, h, w, 3) expected")
+    n, h, w, _ = img.shape
+    H, W, _top = erp_coded_size(h, w)
+    if out is None:
+        out = torch.empty((n, 3, H, W), dtype=torch.float32, device=img.device)
+    elif tuple(out.shape) != (n, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != img.device:
+        raise PconvError("frames_u8_to_f32_erp: out must be contiguous float32 (n, 3, %d, %d) on the image's device" % (H, W))
+    with _HbmTimed("frames_u8_to_f32_erp_pad_kernel", "img2tensor+pad n%d" % n, img.numel() + 4.0 * out.numel(), img.device):
+        call("pconv_frames_u8_to_f32_erp", _ptr(img), _ptr(out), n, h, w, _stream(img.device))
+    return out
+
+
+def erp_pad_f32(x, out=None):
+    """float32 (n, 3, h, w) GPU tensor -> (n, 3, H, W) padded by the pole / seam rule (erp_size.py)"""
+    _require_gpu(x, "erp_pad_f32")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise PconvError("erp_pad_f32: float32 (n, 3, h, w) expected")
+    n, _, h, w = x.shape
+    H, W, _top = erp_coded_size(h, w)
+    if out is None:
+        out = torch.empty((n, 3, H, W), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise PconvError("erp_pad_f32: out must be contiguous float32 (n, 3, %d, %d) on the input's device" % (H, W))
+    with _HbmTimed("erp_pad_f32_kernel", "ErpPad n%d" % n, 4.0 * (x.numel() + out.numel()), x.device):
+        call("pconv_erp_pad_f32", _ptr(x), _ptr(out), n, h, w, _stream(x.device))
+    return out
+
+
+def frames_f32_to_u8_crop(x, height, width, out=None):
+    """frames_f32_to_u8 and the decoder's crop in one pass: float32 (n, 3, H, W) coded frames -> uint8
+    (n, height, width, 3) of rows top..top+height-1, columns 0..width-1 (any width, any byte offset of out)"""
+    _require_gpu(x, "frames_f32_to_u8_crop")
+    H, W, _top = erp_coded_size(height, width)
+    if x.dim() != 4 or tuple(x.shape[1:]) != (3, H, W):
+        raise PconvError("frames_f32_to_u8_crop: float32 (n, 3, %d, %d) expected for %dx%d, got %s"
+                         % (H, W, width, height, tuple(x.shape)))
+    n = x.shape[0]
+    if out is None:
+        out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=x.device)
+    elif tuple(out.shape) != (n, height, width, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device:
+        raise PconvError("frames_f32_to_u8_crop: out must be contiguous uint8 (n, %d, %d, 3) on the tensor's device"
+                         % (height, width))
+    with _HbmTimed("frames_f32_to_u8_crop_kernel", "tensor2img+crop n%d" % n, 5.0 * out.numel(), x.device):
+        call("pconv_frames_f32_to_u8_crop", _ptr(x), _ptr(out), n, height, width, _stream(x.device))
+    return out
+
+
 def tile_gdn(owner, x, gamma, beta, inverse, col_limit=None, npart=0, residual=None, ring=0):
     """PseudoGDNV2.forward in one launch: x / sqrt(beta + gamma x^2) (inverse: x * sqrt)
     (+ residual), zeros from each tile's col_limit on.  gamma (ch, ch), beta (ch):

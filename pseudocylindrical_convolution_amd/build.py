@@ -24,6 +24,7 @@ HIP_SOURCES = [
     "resample.hip",
     "tilepad.hip",
     "pointwise.hip",
+    "erp_size.hip",    # pole / seam padding of ERP frames of any size, and the crop back
     "entropy.hip",
     "entropy_engine.hip",
     "entropy_mfma.hip",

@@ -16,6 +16,20 @@ payload -- the payload itself is byte for byte the reference-format stream:
     10      2     ERP width / 16, little endian
     12      4     payload length in bytes, little endian
 
+Version 2 (20 bytes) carries an ERP size the codec does not take as it is -- any h x w, coded at
+erp_size.coded_size(h, w) under the pole / seam padding rule of erp_size.py, the decoder crops back:
+
+    0       4     magic  b"PCVC"
+    4       1     version (2)
+    5..7          flags, model index, ngroup as in version 1
+    8       4     exact ERP height, little endian
+    12      4     exact ERP width, little endian
+    16      4     payload length in bytes, little endian
+
+`pack` writes version 1 only; `pack_any` writes version 1 (the same bytes as `pack`) for a codable size and
+version 2 otherwise.  `unpack`, `sniff` and `read` take both and return the same dict: height / width are the
+original size.
+
 The command line writes the reference's headerless files unless `--container` is given;
 decoding recognises a container by `sniff` (magic, version and a payload length that
 matches the file), so headerless files produced by the reference decode as before.
@@ -27,6 +41,9 @@ MAGIC = b"PCVC"
 VERSION = 1
 HEADER_BYTES = 16
 _FMT = "<4sBBBBHHI"
+VERSION_ANY = 2
+HEADER_BYTES_ANY = 20
+_FMT_ANY = "<4sBBBBIII"
 
 
 class ContainerError(ValueError):
@@ -48,40 +65,83 @@ def pack(payload, height, width, model_idx, ssim, valid_dim):
     return head + bytes(payload)
 
 
+def pack_any(payload, height, width, model_idx, ssim, valid_dim):
+    """header + payload for an ERP of any size: `pack` (version 1) when the codec takes height x width as it
+    is, else version 2 with the exact size (coded at erp_size.coded_size under the padding rule)"""
+    from .erp_size import codable
+    if codable(height, width):
+        return pack(payload, height, width, model_idx, ssim, valid_dim)
+    if not (2 <= height <= 1 << 20 and 2 <= width <= 1 << 20):
+        raise ContainerError("ERP size %dx%d does not fit the header (2 .. 2^20 per side)" % (width, height))
+    if valid_dim % 4 or not 0 < valid_dim // 4 < 256:
+        raise ContainerError("valid_dim %d does not fit the header" % valid_dim)
+    if not 0 <= model_idx < 256:
+        raise ContainerError("model index %d does not fit the header" % model_idx)
+    if len(payload) >= 1 << 32:
+        raise ContainerError("payload too long")
+    head = struct.pack(_FMT_ANY, MAGIC, VERSION_ANY, 1 if ssim else 0, model_idx, valid_dim // 4, height, width,
+                       len(payload))
+    return head + bytes(payload)
+
+
+def _parse(head, size):
+    """(fields dict, header bytes) of a header whose file (header + payload) is `size` bytes, or a reason string"""
+    if len(head) < HEADER_BYTES:
+        return "file shorter than the %d-byte header" % HEADER_BYTES
+    if head[:4] != MAGIC:
+        return "no container magic: a headerless reference-format stream?"
+    version = head[4]
+    if version == VERSION:
+        magic, version, flags, model_idx, ngroup, h16, w16, n = struct.unpack(_FMT, head[:HEADER_BYTES])
+        nhead, height, width = HEADER_BYTES, h16 * 16, w16 * 16
+    elif version == VERSION_ANY:
+        if len(head) < HEADER_BYTES_ANY:
+            return "file shorter than the %d-byte version-2 header" % HEADER_BYTES_ANY
+        magic, version, flags, model_idx, ngroup, height, width, n = struct.unpack(_FMT_ANY, head[:HEADER_BYTES_ANY])
+        nhead = HEADER_BYTES_ANY
+        if not (2 <= height <= 1 << 20 and 2 <= width <= 1 << 20):
+            return "ERP size %dx%d in the header is out of range" % (width, height)
+    else:
+        return "container version %d, this build reads %d and %d" % (version, VERSION, VERSION_ANY)
+    if size - nhead != n:
+        return "payload is %d bytes, header says %d" % (size - nhead, n)
+    if not (height and width and ngroup):
+        return "empty field in the header"
+    return {"height": height, "width": width, "model_idx": model_idx, "ssim": bool(flags & 1),
+            "valid_dim": ngroup * 4}, nhead
+
+
 def unpack(data):
-    """-> (dict(height, width, model_idx, ssim, valid_dim), payload bytes)"""
-    if len(data) < HEADER_BYTES:
-        raise ContainerError("file shorter than the %d-byte header" % HEADER_BYTES)
-    magic, version, flags, model_idx, ngroup, h16, w16, n = struct.unpack(_FMT, data[:HEADER_BYTES])
-    if magic != MAGIC:
-        raise ContainerError("no container magic: a headerless reference-format stream?")
-    if version != VERSION:
-        raise ContainerError("container version %d, this build reads %d" % (version, VERSION))
-    if len(data) - HEADER_BYTES != n:
-        raise ContainerError("payload is %d bytes, header says %d" % (len(data) - HEADER_BYTES, n))
-    if not (h16 and w16 and ngroup):
-        raise ContainerError("empty field in the header")
-    return ({"height": h16 * 16, "width": w16 * 16, "model_idx": model_idx, "ssim": bool(flags & 1),
-             "valid_dim": ngroup * 4}, bytes(data[HEADER_BYTES:]))
+    """-> (dict(height, width, model_idx, ssim, valid_dim), payload bytes); version 1 or 2"""
+    got = _parse(bytes(data[:HEADER_BYTES_ANY]), len(data))
+    if isinstance(got, str):
+        raise ContainerError(got)
+    head, nhead = got
+    return head, bytes(data[nhead:])
 
 
-def sniff(path):
-    """header dict when the file is a well-formed container, else None (a headerless stream).
-    A raw arithmetic-coded stream passes for a container only if its first 16 bytes happen to
-    spell the magic, the version and its own length: 2^-72 for random bytes."""
+def _sniff(path):
     try:
         size = os.path.getsize(path)
         with open(path, "rb") as f:
-            head = f.read(HEADER_BYTES)
-        if len(head) < HEADER_BYTES or head[:4] != MAGIC:
-            return None
-        magic, version, flags, model_idx, ngroup, h16, w16, n = struct.unpack(_FMT, head)
-        if version != VERSION or n != size - HEADER_BYTES or not (h16 and w16 and ngroup):
-            return None
-        return {"height": h16 * 16, "width": w16 * 16, "model_idx": model_idx, "ssim": bool(flags & 1),
-                "valid_dim": ngroup * 4}
+            head = f.read(HEADER_BYTES_ANY)
     except OSError:
-        return None
+        return "unreadable"
+    return _parse(head, size)
+
+
+def sniff(path):
+    """header dict when the file is a well-formed container (version 1 or 2), else None (a headerless stream).
+    A raw arithmetic-coded stream passes for a container only if its first bytes happen to spell the magic,
+    a version and its own length: 2^-72 for random bytes."""
+    got = _sniff(path)
+    return None if isinstance(got, str) else got[0]
+
+
+def header_bytes(path):
+    """16 or 20 when `path` is a well-formed container, else 0"""
+    got = _sniff(path)
+    return 0 if isinstance(got, str) else got[1]
 
 
 def read(path):
@@ -92,3 +152,8 @@ def read(path):
 def write(path, payload, **fields):
     with open(path, "wb") as f:
         f.write(pack(payload, **fields))
+
+
+def write_any(path, payload, **fields):
+    with open(path, "wb") as f:
+        f.write(pack_any(payload, **fields))

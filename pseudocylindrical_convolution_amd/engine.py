@@ -18,6 +18,7 @@ from . import _native
 from ._native import PconvError, call
 from .PCONV_operator import backend, set_weight
 from . import pseudo_codec as PC
+from . import erp_size
 
 
 class EntropyEngine(object):
@@ -278,7 +279,11 @@ class CodecEngine(object):
         """(n, 3, H, W) frames on the GPU -> n byte strings.  The frames of a chunk go through the
         entropy wavefront in lock-step; the chunks are pipelined: chunk k's CDF tables are coded by
         host threads while the GPU computes the symbols of chunk k+1 (each chunk has its own
-        engine: the coder reads the engine's pinned buffers until encode_end)."""
+        engine: the coder reads the engine's pinned buffers until encode_end).  Frames of a size
+        the codec does not take as it is are first padded on the device to their coded size
+        (erp_size.py: poles and seam); decode(streams, h, w) crops back."""
+        if not erp_size.codable(frames.shape[2], frames.shape[3]):
+            frames = erp_size.pad(frames)
         n = frames.shape[0]
         chunk = self.ENCODE_CHUNK if n > self.ENCODE_CHUNK else n
         tiles = self.enc.ent.npart
@@ -326,7 +331,11 @@ class CodecEngine(object):
         """n byte strings -> (n, 3, H, W).  With DECODE_CHUNK = c > 0 and more than c frames the call
         is pipelined: while the synthesis transform of chunk k runs, the entropy decoder of chunk k+1
         (a latency chain that leaves most of the GPU idle) runs beside it on a second stream, driven
-        by a host thread; two engines alternate."""
+        by a host thread; two engines alternate.  A size the codec does not take as it is: the streams
+        of encode() of such frames, decoded at the coded size and cropped to (n, 3, height, width)."""
+        if not erp_size.codable(height, width):
+            hc, wc, _ = erp_size.coded_size(height, width)
+            return erp_size.crop(self.decode(streams, hc, wc), height, width)
         h, w = PC.latent_shape(height, width, self.dec.npart)
         n = len(streams)
         tiles = self.dec.npart
@@ -378,13 +387,24 @@ class FramePipe(object):
     uploaded and batch k - 1's reconstruction is downloaded.  img2tensor's division and tensor2img's cast run on
     the device with the reference's arithmetic (PCONV.frames_u8_to_f32 / frames_f32_to_u8).  Copies are issued
     frame by frame (25 MB at 4096x2048: half a millisecond each) so that the entropy engine's small, latency-bound
-    transfers never queue behind one long DMA."""
+    transfers never queue behind one long DMA.
 
-    def __init__(self, n, height, width, device):
+    Any ERP size (pad=True): the uint8 (n, height, width, 3) frames cross the bus as they are; take() returns them
+    padded to the coded size (erp_size.py: poles and seam) by PCONV.frames_u8_to_f32_erp, and give() takes a
+    reconstruction of the coded size (CodecEngine.decode(streams, *pipe.coded)) and crops it with
+    PCONV.frames_f32_to_u8_crop.  pad=None (default): padded only where the frame kernels above refuse the width
+    (width % 4 != 0); other sizes keep them and pass frames through at their own size (CodecEngine.encode pads
+    those itself).  Codable sizes never pad."""
+
+    def __init__(self, n, height, width, device, pad=None):
         self.n, self.h, self.w = int(n), int(height), int(width)
+        if pad is None:
+            pad = self.w % 4 != 0
+        self.native = not pad or erp_size.codable(self.h, self.w)
+        self.coded = (self.h, self.w) if self.native else erp_size.coded_size(self.h, self.w)[:2]
         self.device = torch.device(device)
         self.ops = backend.ops()
-        if not hasattr(self.ops, "frames_u8_to_f32"):
+        if not hasattr(self.ops, "frames_u8_to_f32" if self.native else "frames_u8_to_f32_erp"):
             raise PconvError("FramePipe needs the HIP backend")
         shape = (self.n, self.h, self.w, 3)
         # one copy stream per direction, created through the C ABI (pconv_stream_create) rather than taken from
@@ -398,7 +418,7 @@ class FramePipe(object):
         self.dev_in = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(2)]
         self.dev_out = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(2)]
         self.host_out = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self.frames = torch.empty((self.n, 3, self.h, self.w), dtype=torch.float32, device=self.device)
+        self.frames = torch.empty((self.n, 3) + tuple(self.coded), dtype=torch.float32, device=self.device)
         ev = lambda: [torch.cuda.Event() for _ in range(2)]
         self.up_done, self.in_free, self.out_ready, self.down_done = ev(), ev(), ev(), ev()
         self._in_used, self._out_used = [False, False], [False, False]
@@ -422,21 +442,29 @@ class FramePipe(object):
             self.up_done[slot].record(self.up)
 
     def take(self, slot):
-        """the uploaded batch of `slot` as float32 (n, 3, H, W) in the caller's stream (img2tensor's arithmetic)"""
+        """the uploaded batch of `slot` as float32 (n, 3, H, W) in the caller's stream (img2tensor's arithmetic;
+        padded to the coded size when the pipe's size is not codable)"""
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(self.up_done[slot])
-        self.ops.frames_u8_to_f32(self.dev_in[slot], self.frames)
+        if self.native:
+            self.ops.frames_u8_to_f32(self.dev_in[slot], self.frames)
+        else:
+            self.ops.frames_u8_to_f32_erp(self.dev_in[slot], self.frames)
         self.in_free[slot].record(cur)
         self._in_used[slot] = True
         return self.frames
 
     def give(self, rec, slot):
         """queue tensor2img + the download of a reconstruction (n, 3, H, W) into host_out[slot]; returns that
-        pinned tensor (valid once down_done[slot] has completed: wait(slot))"""
+        pinned tensor (valid once down_done[slot] has completed: wait(slot)).  For a size that is not codable,
+        rec has the coded size (CodecEngine.decode(streams, *pipe.coded)) and is cropped on the way"""
         cur = torch.cuda.current_stream(self.device)
         if self._out_used[slot]:
             cur.wait_event(self.down_done[slot])           # the previous download out of this slot has finished
-        self.ops.frames_f32_to_u8(rec.contiguous(), self.dev_out[slot])
+        if self.native:
+            self.ops.frames_f32_to_u8(rec.contiguous(), self.dev_out[slot])
+        else:
+            self.ops.frames_f32_to_u8_crop(rec.contiguous(), self.h, self.w, self.dev_out[slot])
         self.out_ready[slot].record(cur)
         with torch.cuda.stream(self.down):
             self.down.wait_event(self.out_ready[slot])

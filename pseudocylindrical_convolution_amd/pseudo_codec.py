@@ -6,6 +6,9 @@ Differences from the reference, all additive:
   * any ERP size with height % 256 == 0 and width % 16 == 0 (the reference
     hard-codes 512x1024 latents, pseudo_codec.py:206,209,229-234); the defaults
     reproduce the reference exactly;
+  * any other ERP size h x w through the pole / seam padding rule of erp_size.py:
+    coded at coded_size(h, w), the decoder crops back (container version 2,
+    command line --native-size);
   * images are read/written with PIL (cv2 is not required) in the reference's BGR
     channel order, so its checkpoints stay valid.
 Module / parameter names are the reference's, so `{idx}_encoder.pt`,
@@ -26,6 +29,8 @@ from .PCONV_operator import (DExtract2, DExtract2Batch, DInput2, Dtow, EntropyAd
                              SphereUslice, SSIM, backend)
 from .model_zoo_v2 import ClipData, DecoderV2, EncoderV2
 from . import container
+from .erp_size import coded_size  # noqa: F401  (re-exported beside latent_shape)
+from . import erp_size
 
 psnr_f = lambda xa: 10 * math.log10(1. / xa)
 
@@ -197,7 +202,9 @@ class PseudoEncoder(nn.Module):
         byte for byte what the op-by-op loop of `forward_per_op` writes
         (tests/test_gpu_engine.py).  PCONV_ENTROPY=per-op forces the loop.
         header: dict(model_idx=, ssim=) -> the file gets the 16-byte container header
-        (container.py) in front of the same payload; None = the reference's raw stream."""
+        (container.py) in front of the same payload; None = the reference's raw stream.
+        header["size"] = (h, w): x is an h x w frame padded to its coded size (erp_size.py); the
+        header records the original size (container version 2 unless h x w is codable)."""
         with torch.no_grad():
             hcode_i = self.symbols(x)
             eng = _native_engine(self, "enc", hcode_i)
@@ -211,8 +218,15 @@ class PseudoEncoder(nn.Module):
             if header is not None:
                 with open(code_name, "rb") as f:
                     payload = f.read()
-                container.write(code_name, payload, height=x.shape[2], width=x.shape[3],
-                                model_idx=header["model_idx"], ssim=header["ssim"], valid_dim=self.valid_dim)
+                if "size" in header:
+                    h, w = header["size"]
+                    if erp_size.coded_size(h, w)[:2] != tuple(x.shape[2:]):
+                        raise ValueError("frame %s is not the coded size of %dx%d" % (tuple(x.shape[2:]), w, h))
+                    container.write_any(code_name, payload, height=h, width=w, model_idx=header["model_idx"],
+                                        ssim=header["ssim"], valid_dim=self.valid_dim)
+                else:
+                    container.write(code_name, payload, height=x.shape[2], width=x.shape[3],
+                                    model_idx=header["model_idx"], ssim=header["ssim"], valid_dim=self.valid_dim)
 
     def forward_per_op(self, x, code_name):
         """the reference's loop (pseudo_codec.py:97-114): ~36 op calls per wavefront step"""
@@ -253,8 +267,11 @@ class PseudoDecoder(nn.Module):
         (see PseudoEncoder.forward).  raw=True: the reference's headerless stream, size from the
         arguments; raw=False: the file carries the container header (container.py) and height /
         width are read from it; raw=None (default): a file that starts with a valid container
-        header is read as one, anything else as a raw stream."""
+        header is read as one, anything else as a raw stream.  A container of a size the codec does not
+        take as it is (version 2) is decoded at its coded size and cropped to the original size
+        (erp_size.py)."""
         with torch.no_grad():
+            payload = None
             if raw is None:
                 raw = container.sniff(code_name) is None
             if not raw:
@@ -263,6 +280,13 @@ class PseudoDecoder(nn.Module):
                     raise container.ContainerError("file was coded with valid_dim %d, this decoder has %d"
                                                    % (head["valid_dim"], self.valid_dim))
                 height, width = head["height"], head["width"]
+                if not erp_size.codable(height, width):
+                    hc, wc, _ = erp_size.coded_size(height, width)
+                    return erp_size.crop(self._decode(code_name, hc, wc, raw, payload), height, width)
+            return self._decode(code_name, height, width, raw, payload)
+
+    def _decode(self, code_name, height, width, raw, payload):
+        with torch.no_grad():
             h, w = latent_shape(height, width, self.npart)
             eng = _native_engine(self, "dec", None, 2 * h, 2 * w)
             if eng is None:
@@ -358,24 +382,33 @@ def _pick(model_idx, mse):
 def bitrate(path, height=512, width=1024):
     """bits per pixel of the coded payload (a container header is not counted, so the figure is
     the reference's `os.path.getsize(fc)*8/1024./512.` for the same stream, pseudo_codec.py:247,283)"""
-    head = container.sniff(path)
-    nbytes = os.path.getsize(path) - (container.HEADER_BYTES if head is not None else 0)
+    nbytes = os.path.getsize(path) - container.header_bytes(path)
     return nbytes * 8 / float(width) / float(height)
 
 
-def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, boxed=False):
+def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, boxed=False,
+             native=False):
     """reference: pseudo_codec.py:236-247.  The files are the reference's headerless streams unless
     boxed=True (--container): then the 16-byte header of container.py goes in front of the same
-    payload and the file decodes without any size / model argument."""
+    payload and the file decodes without any size / model argument.  native=True (--native-size,
+    needs boxed): every image is coded at its own size, padded by the pole / seam rule of erp_size.py
+    instead of resized; height / width are ignored."""
+    if native and not boxed:
+        raise ValueError("--native-size needs --container: a headerless file cannot carry the image size")
     prex, vd, model_dir = _pick(model_idx, mse)
     dev = backend.device_of(device_id)
     t1 = PseudoEncoder(vd, device_id=device_id).to(dev)
     load_models(t1, '{}/{}_encoder.pt'.format(model_dir, prex), '{}/{}_ent.pt'.format(model_dir, prex), dev)
     header = {"model_idx": model_idx, "ssim": not mse} if boxed else None
     for fn, fo in zip(img_list, out_list):
-        data = img2tensor(check_img(read_image(fn), height, width), dev)
-        t1(data, fo, header)
-        print('Encoding {}, bitrate: {:.3f}bpp'.format(fn, bitrate(fo, height, width)))
+        if native:
+            img = read_image(fn)
+            h, w = img.shape[:2]
+            t1(erp_size.pad(img2tensor(img, dev)), fo, dict(header, size=(h, w)))
+        else:
+            h, w = height, width
+            t1(img2tensor(check_img(read_image(fn), height, width), dev), fo, header)
+        print('Encoding {}, bitrate: {:.3f}bpp'.format(fn, bitrate(fo, h, w)))
 
 
 def _decoder_for(code_list, model_idx, mse, device_id, raw):
@@ -479,6 +512,10 @@ def main(argv=None):
                         help='Encoding: put a 16-byte header (size, model, valid_dim, length) in front of the stream, so '
                              "that the file decodes without --height/--width/--model-idx/--ssim.  Default: the reference's "
                              'headerless files.  Decoding recognises such files by their magic')
+    parser.add_argument('--native-size', action='store_true', default=False,
+                        help='Encoding: code every image at its own size (any height and width, no resize; '
+                             '--height/--width are ignored): the frame is padded at the poles and the seam to '
+                             'the next codable size and the decoder crops back.  Needs --container')
     parser.add_argument('--raw', action='store_true', default=False,
                         help='Decoding: never look for a container header (size and model from the flags)')
     args = parser.parse_args(argv)
@@ -498,7 +535,9 @@ def main(argv=None):
         assert img_list is not None, 'No input images for encoding'
         assert code_list is not None, 'No code files for saving the codes'
         assert len(img_list) == len(code_list), 'The number of images and codes should be the same'
-        encoding(img_list, code_list, midx, not args.ssim, args.gpu_id, boxed=args.container and not args.raw, **size)
+        assert not args.native_size or (args.container and not args.raw), '--native-size needs --container'
+        encoding(img_list, code_list, midx, not args.ssim, args.gpu_id, boxed=args.container and not args.raw,
+                 native=args.native_size, **size)
     else:
         assert code_list is not None, 'No code files for decoding'
         if args.dec:
