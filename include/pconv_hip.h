@@ -485,6 +485,11 @@ int pconv_ee_host_plan(int nimg, int *groups, int *group_threads, int *queued_ch
  * waits on blocking events (hipEventBlockingSync; the plan's blocking_sync, fixed at pconv_ee_create).  No device-wide
  * schedule flag is set either way. */
 int pconv_ee_wait_mode(const pconv_entropy_engine *e);
+/* Which kernel THIS engine's encoder runs for `layer` (0 .. 11), decided at pconv_ee_create: 0 = the vector kernel,
+ * 1 = the 16x16x4 matrix-core form, 2 = the four-block matrix-core form (v_mfma_f32_16x16x1_4b_f32).  Matrix forms
+ * need an even width and 14, 28 or 48 groups (28 / 48: hidden layers 1 .. 11 only); PCONV_EE_BULK=valu keeps the
+ * vector kernel everywhere.  PCONV_EINVAL (pconv_last_error) for a bad layer. */
+int pconv_ee_encoder_form(const pconv_entropy_engine *e, int layer);
 /* Explicit, process-wide opt-in: hipSetDeviceFlags(hipDeviceScheduleBlockingSync) on the current device (enable != 0),
  * then the flag is read back: returns 1 when every runtime wait on the device now sleeps, 0 when it does not (not asked
  * for, or refused by the runtime on a live context -- the engine's blocking events still apply then).  Never called by

@@ -93,7 +93,9 @@ int ee_conv_bulk_mfma(const EeGeom *g, const void *blocks, int nblocks, int rp_n
                       int shared_input, const float *wfrag, const float *bias, const float *slope,
                       const float *residual, float *y, int cin, int cout, int pad_out, int s_lo, int s_hi,
                       void *stream);
-// the same 42 -> 42 layer, four lane classes per instruction (v_mfma_f32_16x16x1_4b_f32), nt = 1 block shapes only
+// the same 42 -> 42 layer, four lane classes per instruction (v_mfma_f32_16x16x1_4b_f32), nt = 1 block shapes only;
+// also the wide nets' hidden layers (84 -> 84 at 28 groups, 144 -> 144 at 48 groups): `waves` = rp_n * ct_n position
+// tiles x the output slices (2 / 3), ee_mfma_block_shape(h, 84 | 144, ...) gives the shape
 int ee_mfma4_packed_floats(int nset, int cin);
 int ee_pack_weight_mfma4(const float *w, float *packed, int nset, int cout, int cin, int ngroup, int constrain,
                          void *stream);

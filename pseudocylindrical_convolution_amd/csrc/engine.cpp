@@ -546,8 +546,12 @@ struct pconv_entropy_engine {
       int rp = 0, ct = 0, wv = 0, nt = 0;
       // even widths only: the patch goes to LDS in 16-byte pieces and a padded row of an odd width ends on half a
       // piece (a pixel is 14 / 42 floats) -- the codec's symbol planes are Dtow(2) outputs, always even; direct
-      // pconv_ee_create users with an odd w get the vector kernel
-      if (!(env && env[0] == 'v') && ngroup == 14 && (w & 1) == 0 && ee_mfma_block_shape(h, 3 * ngroup, &rp, &ct, &wv, &nt)) {
+      // pconv_ee_create users with an odd w get the vector kernel.  The wide nets (28 / 48 groups) take the four-block
+      // form for their hidden layers only (the input layer stays on the vector kernel; the 14-group knobs below do
+      // not apply to them)
+      const bool wide = ngroup == 28 || ngroup == 48;
+      if (!(env && env[0] == 'v') && (ngroup == 14 || wide) && (w & 1) == 0 &&
+          ee_mfma_block_shape(h, 3 * ngroup, &rp, &ct, &wv, &nt)) {
         std::vector<int32_t> blk;
         for (int t = 0; t < npart; t++)
           for (int r0 = 0; r0 < h; r0 += nt * rp)
@@ -563,11 +567,11 @@ struct pconv_entropy_engine {
           // PCONV_EE_BULK0=valu keeps the vector kernel for it)
           const char *env0 = getenv("PCONV_EE_BULK0");
           const char *wsrc = getenv("PCONV_EE_MFMA_WSRC");
-          const bool layer0 = nt == 1 && !(wsrc && wsrc[0] == 'r') && !(env0 && env0[0] == 'v');
+          const bool layer0 = !wide && nt == 1 && !(wsrc && wsrc[0] == 'r') && !(env0 && env0[0] == 'v');
           // the hidden layers: four lane classes per instruction (one row per wave, weights fetched directly) unless
           // PCONV_EE_MFMA_FORM=16x4 asks for the 16 x 16 x 4 form (round-5 A/B: profiles/round5_entropy_mfma_variants.txt)
           const char *form = getenv("PCONV_EE_MFMA_FORM");
-          const bool four = nt == 1 && !(wsrc && wsrc[0] == 'r') && !(form && form[0] == '1');
+          const bool four = wide || (nt == 1 && !(wsrc && wsrc[0] == 'r') && !(form && form[0] == '1'));
           for (int l = layer0 ? 0 : 1; l < kLayers; l++)
             if (l == 0 || !four) HIP_TRY(hipMalloc(&lwf[l], (size_t)ee_mfma_packed_floats(3, layer_cin(l)) * 4));
           if (four)
@@ -1024,6 +1028,12 @@ int pconv_ee_host_plan(int nimg, int *groups, int *group_threads, int *queued_ch
 int pconv_ee_wait_mode(const pconv_entropy_engine *e) {
   PCONV_REQUIRE(e, "ee_wait_mode: null engine");
   return e->plan.blocking_sync ? 1 : 0;
+}
+
+int pconv_ee_encoder_form(const pconv_entropy_engine *e, int layer) {
+  PCONV_REQUIRE(e && layer >= 0 && layer < kLayers, "ee_encoder_form: bad argument");
+  if (!e->mfma_waves) return 0;
+  return e->lwf4[layer] ? 2 : (e->lwf[layer] ? 1 : 0);
 }
 
 // step ranges the LAST group of the following encode calls is evaluated in (1: one piece; 0: back to the default,

@@ -394,26 +394,31 @@ __host__ __device__ constexpr int bitrev2(int v) { return ((v & 1) << 1) | ((v >
 __host__ __device__ constexpr int slots4_of(int cin) { return iter_of(cin) * kMT; }           // 51
 __host__ __device__ constexpr int quads4_of(int cin) { return (slots4_of(cin) + 3) / 4; }     // 13
 __host__ __device__ constexpr int frag4_floats(int cin) { return quads4_of(cin) * kWave * 4; }
+// output slices of three 16-row tiles: 42 -> one, 84 -> two of 42, 144 -> three of 48
+__host__ __device__ constexpr int nslice_of(int cout) { return cout <= 16 * kMT ? 1 : (cout + 16 * kMT - 1) / (16 * kMT); }
 
-// weights (nset, cout, cin, 5, 5) -> [set][group order index i4][quad][lane][4]: slot 4 q + e = 3 j + mt
+// weights (nset, cout, cin, 5, 5) -> [set][slice][group order index i4][quad][lane][4]: slot 4 q + e = 3 j + mt, output
+// slice * cout / nslice + 16 mt + (lane & 15) (one slice at 42 channels: the layout of the 42 -> 42 kernel)
 __global__ void pack_weight_mfma4_kernel(const float *__restrict__ w, float *__restrict__ packed, int cin, int cout,
-                                         int ngroup, int slack, long long total) {
+                                         int ngroup, int slack, int nslice, long long total) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
-  const int quads = quads4_of(cin), red = cin * KK;
+  const int quads = quads4_of(cin), red = cin * KK, per_slice = cout / nslice;
   const int e = (int)(i & 3), lane = (int)((i >> 2) & 63);
   long long r = i >> 8;
   const int quad = (int)(r % quads);
   r /= quads;
-  const int i4 = (int)(r & 15), set = (int)(r >> 4);
+  const int i4 = (int)(r & 15);
+  r >>= 4;
+  const int slice = (int)(r % nslice), set = (int)(r / nslice);
   const int slot = quad * 4 + e;
   float v = 0.f;
   if (slot < slots4_of(cin)) {
     const int j = slot / kMT, mt = slot - j * kMT;
     const int l0 = 4 * bitrev2(i4 & 3) + bitrev2(i4 >> 2);
     const int kk = l0 + kDcls[lane >> 4] + kWave * j;
-    const int out = 16 * mt + (lane & 15);
-    if (kk < red && out < cout) {
+    const int os = 16 * mt + (lane & 15), out = slice * per_slice + os;
+    if (kk < red && os < per_slice) {
       const int tc = out / GO, o = out - tc * GO, group_in = cin / ngroup;
       const int tap = kk / cin, ci = kk - tap * cin;
       const int kh = tap / K5, kw = tap - kh * K5;
@@ -633,6 +638,223 @@ __global__ __launch_bounds__(WAVES * kWave, 2) void ee_conv_bulk_mfma4_kernel(
   }
 }
 
+// ---- the four-block form for the wide nets: 84 -> 84 (28 groups) and 144 -> 144 channels (48 groups) -----------
+//
+// The same classes, groups, chains and butterfly as ee_conv_bulk_mfma4_kernel, only longer chains: ITER = 33 (84
+// channels, 2100 = 64 * 32 + 52: classes l >= 52 end on a zero weight) or 57 (144: 3600 = 64 * 56 + 16).  The outputs
+// are NS slices of three 16-row tiles (84 = 2 x 42, 144 = 3 x 48); a workgroup is TILES position tiles (rp_n rows x
+// ct_n column tiles) x NS slices of waves around ONE LDS patch, wave = slice * TILES + tile.  Registers: a group's
+// fragments (99 / 171 floats) and patch entries (33 / 57) do not fit beside the accumulators, so both are STREAMED
+// at a fixed distance: piece qd + DA is requested as soon as piece qd's last instruction has issued, the patch entry
+// of step j + DB after step j (across the group boundary: the next group's first pieces / entries), and the
+// compiler's counted waits (vmcnt / lgkmcnt) find each one in the order of its use.
+constexpr int kWideDA84 = 12, kWideDA144 = 6;  // weight pieces in flight (of 25 / 43 per group)
+constexpr int kWideDB = 8;                     // patch entries in flight
+constexpr int kWideMinW84 = 2;                 // waves per SIMD the 84-channel kernel is compiled for
+template <int CIN, int TILES, int DA, int DB, int MINW>
+__global__ __launch_bounds__(TILES * nslice_of(CIN) * kWave, MINW) void ee_conv_bulk_mfma4w_kernel(
+    EeGeom g, const int4 *__restrict__ blocks, int rp_n, int ct_n, const float *__restrict__ x, int shared_input,
+    const float *__restrict__ wfrag, const float *__restrict__ bias, const float *__restrict__ slope,
+    const float *__restrict__ residual, float *__restrict__ y, int pad_out, int s_lo, int s_hi) {
+  constexpr int ITER = iter_of(CIN), QUADS = quads4_of(CIN), FRAG = frag4_floats(CIN);
+  constexpr int NS = nslice_of(CIN), SO = CIN / NS, WAVES = TILES * NS, COUT = CIN, LAST = ITER * kMT - 1;
+  static_assert(SO <= 16 * kMT && SO % GO == 0 && SO % 2 == 0 && K5 * CIN > kWave, "shape");
+  static_assert(DA >= 1 && DA <= QUADS && DB >= 1 && DB <= ITER, "streaming distances");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float *patch = smem;
+  typedef const __attribute__((address_space(4))) int32_t const_i32_t;
+  const_i32_t *brec = (const_i32_t *)(blocks + blockIdx.x);
+  const int tile = brec[0], row0 = brec[1], col0 = brec[2];
+  const int pn = blockIdx.y;
+  const int set = pn / g.nimg;
+  const int h = g.h, w = g.w;
+  const int BR = rp_n, BC = 16 * ct_n, PW = BC + 4, PR = BR + 4;
+  const int width = ((const_i32_t *)g.widths)[tile];
+  {
+    const int cmax = (col0 + BC < width ? col0 + BC : width) - 1;
+    const int pmin = tile * h + row0 + col0, pmax = tile * h + row0 + BR - 1 + cmax;
+    if (pmax + g.ngroup - 1 < s_lo || pmin >= s_hi) return;
+  }
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+  {
+    // the patch by LDS-DMA (see ee_conv_bulk_mfma_kernel)
+    typedef __attribute__((address_space(3))) void lds_ptr_t;
+    typedef const __attribute__((address_space(1))) void glb_ptr_t;
+    const int xi = shared_input ? pn % g.nimg : pn;
+    const size_t tile_elems = (size_t)(h + 2 * PAD) * (w + 2 * PAD) * CIN;
+    const float *xt = x + ((size_t)xi * g.npart + tile) * tile_elems + ((size_t)row0 * (w + 2 * PAD) + col0) * CIN;
+    const int row16 = PW * CIN / 4;
+    const int lim16 = (w + 2 * PAD - col0) * CIN / 4;
+    const int npiece = PR * row16;
+    const size_t buf_pitch = (size_t)(w + 2 * PAD) * CIN;
+    int pr = tid / row16, j = tid - pr * row16;
+    const int dpr = (WAVES * kWave) / row16, dj = (WAVES * kWave) - dpr * row16;
+    for (int p0 = 0; p0 < npiece; p0 += WAVES * kWave) {
+      const bool in = p0 + tid < npiece;
+      const int prc = in ? pr : PR - 1, jc = in ? j : row16 - 1;
+      const float *src = xt + prc * buf_pitch + 4 * (jc < lim16 ? jc : lim16 - 1);
+      __builtin_amdgcn_global_load_lds((glb_ptr_t *)src, (lds_ptr_t *)(patch + (size_t)(p0 + wave * kWave) * 4), 16, 0, 0);
+      pr += dpr;
+      j += dj;
+      if (j >= row16) {
+        j -= row16;
+        pr++;
+      }
+    }
+    const int rounded = (npiece + WAVES * kWave - 1) / (WAVES * kWave) * (WAVES * kWave) * 4;
+    for (int k = tid; k < kPatchSlack; k += WAVES * kWave) patch[rounded + k] = 0.f;
+  }
+  const int slice = wave / TILES, wt = wave - slice * TILES;
+  const int rp = wt % rp_n, ct = wt / rp_n;
+  const int q = lane >> 4;
+  const bool live = col0 + 16 * ct < width;
+  // the first DA weight pieces of the slice and the residual of this wave's outputs travel with the patch
+  const float *wsl = wfrag + ((size_t)set * NS + slice) * 16 * FRAG;
+  // (the streamed pieces and entries in two half arrays each: an array of more than 32 elements stayed in scratch at
+  // 144 channels -- the compiler splits an array into registers only up to that many slices)
+  constexpr int QH = (QUADS + 1) / 2, BH = (ITER + 1) / 2;
+  float4 aq0[QH], aq1[QUADS - QH];
+  float bj0[BH], bj1[ITER - BH];
+  auto AQ = [&](int k) -> float4 & { return k < QH ? aq0[k] : aq1[k - QH]; };
+  auto BJ = [&](int k) -> float & { return k < BH ? bj0[k] : bj1[k - BH]; };
+  auto load_a = [&](int i4, int qd) { AQ(qd) = *(reinterpret_cast<const float4 *>(wsl + (size_t)i4 * FRAG) + qd * kWave + lane); };
+#pragma unroll
+  for (int qd = 0; qd < DA; qd++) load_a(0, qd);
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  const int row = row0 + rp, col = col0 + 16 * ct + (lane & 15);
+  const int colc = col < width ? col : width - 1;
+  const size_t ob0 = ((((size_t)pn * g.npart + tile) * (h + 2 * pad_out) + row + pad_out) * (w + 2 * pad_out) + colc + pad_out) * COUT +
+                     (size_t)slice * SO;  // (this slice's outputs)
+  f2 r01[kMT], r23[kMT];
+#pragma unroll
+  for (int mt = 0; mt < kMT; mt++) {
+    r01[mt] = r23[mt] = (f2){0.f, 0.f};
+    if (residual) {
+      const int o0 = 16 * mt + 4 * q;
+      r01[mt] = *reinterpret_cast<const f2 *>(residual + ob0 + (o0 < SO ? o0 : SO - 2));
+      r23[mt] = *reinterpret_cast<const f2 *>(residual + ob0 + (o0 + 2 < SO ? o0 + 2 : SO - 2));
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the patch DMA of every wave
+  if (!live) return;                                                         // (no barrier from here on)
+  const int dcls = q == 0 ? kDcls[0] : (q == 1 ? kDcls[1] : (q == 2 ? kDcls[2] : kDcls[3]));
+  const unsigned kh4 = 4u * (unsigned)((PW - K5) * CIN);
+  // byte offset of entry kk = l + 64 j (l = l0 + dcls: this lane's class) of its window: 4 (lane_base + kk) + kh kh4,
+  // kh = the window row of kk (4 past the reduction length) = K_j + (l >= T_j): entries 64 j .. 64 j + 63 cross at most
+  // one row end (5 CIN > 64); K_j and T_j are compile-time per step
+  const unsigned base_b = 4u * (unsigned)((rp * PW + 16 * ct + (lane & 15)) * CIN);
+  auto load_b = [&](int l, int j) {
+    const int c = kWave * j;
+    const int k0 = c / (K5 * CIN), kj = k0 < K5 - 1 ? k0 : K5 - 1;
+    const int tj = kj < K5 - 1 ? (kj + 1) * K5 * CIN - c : kWave;
+    const unsigned off = base_b + 4u * (unsigned)(c + l) + (unsigned)kj * kh4 + (l >= tj ? kh4 : 0u);
+    BJ(j) = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(patch) + off);
+  };
+#pragma unroll
+  for (int j = 0; j < DB; j++) load_b(dcls, j);
+
+  // One turn of the loop = one group (3 ITER instructions, unrolled); the four levels of the stack over the group
+  // index i4 = 4 a + b fold by selects -- the same additions in the same order as ee_conv_bulk_mfma4_kernel's
+  // branches (xor 8: T1 + s2, xor 4: T2 + that, xor 2: T3 + that, xor 1: T4 + that; tot of the last group is the
+  // total), one basic block per turn
+  f32x4 T1[kMT], T2[kMT], T3[kMT], T4[kMT], tot[kMT];
+#pragma unroll
+  for (int t = 0; t < kMT; t++) T1[t] = T2[t] = T3[t] = T4[t] = tot[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int i4 = 0; i4 < 16; i4++) {
+    const int n4 = i4 + 1 < 16 ? i4 + 1 : 15;  // (behind the last group: a dummy, group 15 again)
+    const int lc = 4 * bitrev2(i4 & 3) + bitrev2(i4 >> 2) + dcls, ln = 4 * bitrev2(n4 & 3) + bitrev2(n4 >> 2) + dcls;
+    f32x16 acc[kMT];
+#pragma unroll
+    for (int t = 0; t < kMT; t++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[t][r] = 0.f;
+    auto step = [&](int j) {
+#pragma unroll
+      for (int mt = 0; mt < kMT; mt++) {
+        const int s = j * kMT + mt;
+        const float4 &pc = AQ(s / 4);
+        const float av = s % 4 == 0 ? pc.x : (s % 4 == 1 ? pc.y : (s % 4 == 2 ? pc.z : pc.w));
+        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x1f32(av, BJ(j), acc[mt], 0, 0, 0);
+        if (s % 4 == 3 || s == LAST) {  // (this piece's last step has issued: the piece DA further on)
+          const int p = s / 4 + DA;
+          if (p < QUADS)
+            load_a(i4, p);
+          else
+            load_a(n4, p - QUADS);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if (j + DB < ITER)
+        load_b(lc, j + DB);
+      else
+        load_b(ln, j + DB - ITER);
+    };
+    // (two loops: 57 steps in one exceeded the compiler's budget for a full unroll, and a rolled step loop indexes
+    // the streamed arrays at run time, i.e. in scratch)
+#pragma unroll
+    for (int j = 0; j < BH; j++) step(j);
+#pragma unroll
+    for (int j = BH; j < ITER; j++) step(j);
+    // the butterfly: xor 32 and xor 16 inside the lane, then the stack over the group index
+    const int b = i4 & 3, a = i4 >> 2;
+    const bool k1 = (b & 1) == 0, k2 = b == 1, k3 = b == 3 && (a & 1) == 0, k4 = b == 3 && a == 1;
+#pragma unroll
+    for (int t = 0; t < kMT; t++) {
+      f32x4 s2;
+#pragma unroll
+      for (int r = 0; r < 4; r++) s2[r] = (acc[t][r] + acc[t][4 + r]) + (acc[t][8 + r] + acc[t][12 + r]);
+      const f32x4 u1 = T1[t] + s2, u2 = T2[t] + u1, u3 = T3[t] + u2;
+      tot[t] = T4[t] + u3;
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        T1[t][r] = k1 ? s2[r] : T1[t][r];
+        T2[t][r] = k2 ? u1[r] : T2[t][r];
+        T3[t][r] = k3 ? u2[r] : T3[t][r];
+        T4[t][r] = k4 ? u3[r] : T4[t][r];
+      }
+    }
+  }
+  // way out (bias, slope, the residual fetched in the prologue), 8-byte stores
+  if (col >= width) return;
+  const bool whole = s_lo <= 0 && s_hi >= g.h * g.npart + g.w + g.ngroup - 2;
+  const float *bset = bias + set * COUT + slice * SO, *sset = slope ? slope + set * COUT + slice * SO : nullptr;
+  const int plane = tile * h + row + col;
+#pragma unroll
+  for (int mt = 0; mt < kMT; mt++) {
+    const int o0 = 16 * mt + 4 * q;  // within the slice
+    if (o0 >= SO) continue;
+    const bool second = o0 + 2 < SO;
+    const f2 b01 = *reinterpret_cast<const f2 *>(bset + o0);
+    const f2 b23 = second ? *reinterpret_cast<const f2 *>(bset + o0 + 2) : (f2){0.f, 0.f};
+    f2 s01 = {1.f, 1.f}, s23 = {1.f, 1.f};
+    if (sset) {
+      s01 = *reinterpret_cast<const f2 *>(sset + o0);
+      if (second) s23 = *reinterpret_cast<const f2 *>(sset + o0 + 2);
+    }
+    const size_t ob = ob0 + o0;
+    const f32x4 t = tot[mt];
+    float v[4] = {t[0] + b01[0], t[1] + b01[1], t[2] + b23[0], t[3] + b23[1]};
+    const float sl[4] = {s01[0], s01[1], s23[0], s23[1]}, rs[4] = {r01[mt][0], r01[mt][1], r23[mt][0], r23[mt][1]};
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      if (v[r] < 0) v[r] = v[r] * sl[r];
+      if (residual) v[r] = v[r] + rs[r];
+    }
+    if (whole) {
+      *reinterpret_cast<f2 *>(y + ob) = (f2){v[0], v[1]};
+      if (second) *reinterpret_cast<f2 *>(y + ob + 2) = (f2){v[2], v[3]};
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int step = plane + (slice * SO + o0 + r) / GO;
+        if (o0 + r < SO && step >= s_lo && step < s_hi) y[ob + r] = v[r];
+      }
+    }
+  }
+}
+
 }  // namespace
 
 int ee_mfma_packed_floats(int nset, int cin) { return nset * 64 * frag_floats(cin); }
@@ -650,24 +872,74 @@ int ee_pack_weight_mfma(const float *w, float *packed, int nset, int cout, int c
 
 // a block is nt * rp_n rows x 16 ct_n columns, rp_n * ct_n = waves of a workgroup, nt = rows of a wave (1 or 2;
 // PCONV_EE_MFMA_NT); rows per tile must be a multiple of nt * rp_n
-int ee_mfma4_packed_floats(int nset, int cin) { return nset * 16 * frag4_floats(cin); }
+// (hidden layers: cout == cin; the wide nets' fragments are nslice_of(cin) slices)
+int ee_mfma4_packed_floats(int nset, int cin) { return nset * nslice_of(cin) * 16 * frag4_floats(cin); }
 
 int ee_pack_weight_mfma4(const float *w, float *packed, int nset, int cout, int cin, int ngroup, int constrain,
                          void *stream) {
-  PCONV_REQUIRE(cout == GO * ngroup && cin % ngroup == 0 && (constrain == 5 || constrain == 6) && cout <= 16 * kMT,
+  const int nslice = nslice_of(cout);
+  PCONV_REQUIRE(cout == GO * ngroup && cin % ngroup == 0 && (constrain == 5 || constrain == 6) && cout == cin &&
+                    cout % (GO * nslice) == 0 && cout / nslice <= 16 * kMT,
                 "ee_pack_weight_mfma4: bad layer shape");
   const long long total = (long long)ee_mfma4_packed_floats(nset, cin);
   hipLaunchKernelGGL(pack_weight_mfma4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), w,
-                     packed, cin, cout, ngroup, constrain == 5 ? 0 : 1, total);
+                     packed, cin, cout, ngroup, constrain == 5 ? 0 : 1, nslice, total);
   PCONV_LAUNCH_CHECK("ee_pack_weight_mfma4");
   return PCONV_OK;
 }
 
-// the four-classes-per-instruction form (42 channels, one row per wave)
+// the wide nets (84 / 144 channels): rp_n * ct_n position tiles x nslice_of(cin) output slices of waves
+static int ee_conv_bulk_mfma4w(const EeGeom *g, const void *blocks, int nblocks, int rp_n, int ct_n, int waves,
+                               const float *x, const float *wfrag4, const float *bias, const float *slope,
+                               const float *residual, float *y, int cin, int pad_out, int s_lo, int s_hi, void *stream) {
+  const int tiles = rp_n * ct_n, ns = nslice_of(cin);
+  PCONV_REQUIRE(rp_n > 0 && ct_n > 0 && waves == tiles * ns && g->h % rp_n == 0 &&
+                    (cin == 84 ? tiles == 4 : (tiles == 4 || tiles == 2)),
+                "ee_conv_bulk_mfma4: bad block shape");
+  const size_t round = (size_t)waves * kWave * 16;
+  const size_t patch_bytes = ((size_t)(rp_n + 4) * (16 * ct_n + 4) * cin * sizeof(float) + round - 1) / round * round;
+  const size_t smem = patch_bytes + kPatchSlack * sizeof(float);
+  PCONV_REQUIRE(smem <= 160 * 1024, "ee_conv_bulk_mfma4: block needs %zu bytes of LDS", smem);
+  const dim3 grid((unsigned)nblocks, (unsigned)(3 * g->nimg));
+  PCONV_REQUIRE(grid.y <= 65535u, "ee_conv_bulk_mfma4: too many images for one launch");
+  typedef void (*kernel_t)(EeGeom, const int4 *, int, int, const float *, int, const float *, const float *, const float *,
+                           const float *, float *, int, int, int);
+  static const kernel_t kernels[3] = {ee_conv_bulk_mfma4w_kernel<84, 4, kWideDA84, kWideDB, kWideMinW84>,
+                                      ee_conv_bulk_mfma4w_kernel<144, 4, kWideDA144, kWideDB, 3>,
+                                      ee_conv_bulk_mfma4w_kernel<144, 2, kWideDA144, kWideDB, 3>};
+  const int kind = cin == 84 ? 0 : (tiles == 4 ? 1 : 2);
+  {
+    static std::atomic<unsigned long long> raised[3];
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) device = 0;
+    const unsigned long long bit = 1ULL << (device & 63);
+    if (!(raised[kind].load(std::memory_order_acquire) & bit)) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernels[kind]),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e != hipSuccess) {
+        pconv_set_error("ee_conv_bulk_mfma4: cannot raise dynamic LDS: %s", hipGetErrorString(e));
+        return PCONV_ELAUNCH;
+      }
+      raised[kind].fetch_or(bit, std::memory_order_release);
+    }
+  }
+  hipLaunchKernelGGL(kernels[kind], grid, dim3(waves * kWave), smem, as_stream(stream), *g, (const int4 *)blocks, rp_n, ct_n, x,
+                     0, wfrag4, bias, slope, residual, y, pad_out, s_lo, s_hi);
+  PCONV_LAUNCH_CHECK("ee_conv_bulk_mfma4");
+  return PCONV_OK;
+}
+
+// the four-classes-per-instruction form (42 channels, one row per wave; 84 / 144 channels: ee_conv_bulk_mfma4w)
 int ee_conv_bulk_mfma4(const EeGeom *g, const void *blocks, int nblocks, int rp_n, int ct_n, int waves, const float *x,
                        const float *wfrag4, const float *bias, const float *slope, const float *residual, float *y,
                        int cin, int cout, int pad_out, int s_lo, int s_hi, void *stream) {
-  PCONV_REQUIRE(cin == 42 && cout == 42 && g->ngroup == 14, "ee_conv_bulk_mfma4: 42 -> 42 channels only");
+  if ((cin == 84 && g->ngroup == 28) || (cin == 144 && g->ngroup == 48)) {
+    PCONV_REQUIRE(cout == cin, "ee_conv_bulk_mfma4: hidden layers only");
+    PCONV_REQUIRE(s_lo < s_hi && nblocks > 0, "ee_conv_bulk_mfma4: bad range");
+    return ee_conv_bulk_mfma4w(g, blocks, nblocks, rp_n, ct_n, waves, x, wfrag4, bias, slope, residual, y, cin, pad_out,
+                               s_lo, s_hi, stream);
+  }
+  PCONV_REQUIRE(cin == 42 && cout == 42 && g->ngroup == 14, "ee_conv_bulk_mfma4: 42, 84 or 144 -> as many channels only");
   PCONV_REQUIRE(rp_n > 0 && ct_n > 0 && rp_n * ct_n == waves && (waves == 4 || waves == 8) && g->h % rp_n == 0,
                 "ee_conv_bulk_mfma4: bad block shape");
   PCONV_REQUIRE(s_lo < s_hi && nblocks > 0, "ee_conv_bulk_mfma4: bad range");
@@ -709,6 +981,18 @@ static bool mfma_direct(int nt) {
 }
 
 int ee_mfma_block_shape(int h, int cin, int *rp_n, int *ct_n, int *waves, int *nt) {
+  if (cin == 84 || cin == 144) {
+    // the wide nets' four-block form: four position tiles (up to four rows) x the output slices; at 144 channels a
+    // one-row block takes two column tiles (four: 5 x 68 x 144 floats = 196 KB of patch, past the 160 KB of LDS)
+    if (h < 1) return 0;
+    int rp = h % 4 == 0 ? 4 : (h % 2 == 0 ? 2 : 1);
+    const int tiles = (cin == 144 && rp == 1) ? 2 : 4;
+    *rp_n = rp;
+    *ct_n = tiles / rp;
+    *waves = tiles * nslice_of(cin);
+    *nt = 1;
+    return 1;
+  }
   const int wv = getenv("PCONV_EE_MFMA_WAVES") ? atoi(getenv("PCONV_EE_MFMA_WAVES")) : 4;  // (per engine)
   // measured (MI355X, 4096x2048, one frame x 3 sets per launch, profiles/round5_entropy_mfma_variants.txt): one row per
   // wave 452 us per full launch (two rows: 474; eight waves per workgroup: 509 / 550), 591 / 715 us for a frame

@@ -74,6 +74,11 @@ class EntropyEngine(object):
             self.lib.pconv_ee_destroy(h)
 
     @property
+    def encoder_forms(self):
+        """the encoder's kernel per layer (12 values): 0 vector, 1 matrix cores 16x16x4, 2 matrix cores four-block"""
+        return tuple(call("pconv_ee_encoder_form", self.handle, layer) for layer in range(12))
+
+    @property
     def symbols_per_image(self):
         return int(self.lib.pconv_ee_symbols_per_image(self.handle))
 
