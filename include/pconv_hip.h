@@ -187,6 +187,30 @@ int pconv_frames_u8_to_f32_erp(const uint8_t *in, float *out, int n, int h, int 
 int pconv_erp_pad_f32(const float *in, float *out, int n, int h, int w, void *stream);
 int pconv_frames_f32_to_u8_crop(const float *in, uint8_t *out, int n, int h, int w, void *stream);
 
+/* Sphere-weighted quality of ERP frames (csrc/sphere_metrics.hip): WS-PSNR / WS-SSIM (Sun, Lu, Yu, IEEE SPL 2017).
+ * x and y are n frames of h x w (h, w >= 1, any size, smaller than the SSIM window included):
+ *   _f32: float32 (n, c, h, w), contiguous, 4-byte aligned, values as they are (nominally [0, 1], not clamped);
+ *   _u8:  uint8 (n, h, w, 3) interleaved, c must be 3, each value read as float(u8) / 255.f like
+ *         pconv_frames_u8_to_f32 (the same image gives the same bits in both forms).
+ * Row j of h weighs w_j = cos(((j + 0.5)/h - 0.5)·pi) in double (weighting PCONV_WS_WEIGHT_SPHERE) or 1
+ * (PCONV_WS_WEIGHT_UNIFORM: plain PSNR / SSIM over the ERP grid).  Per frame, with the sums over channels, rows
+ * and columns in fp64 and N = c · w · Σ_j w_j:
+ *   out[2f]     = Σ w_j·(x - y)² / N            the WS-MSE (difference and square in fp32); WS-PSNR = 10·log10(1/out)
+ *   out[2f + 1] = Σ w_j·ssim_map / N            the WS-SSIM
+ * ssim_map is pytorch_ssim's: 11-tap Gaussian (sigma 1.5) window g⊗g, zero padding of 5 on all four borders (the
+ * seam is not wrapped), C1 = 0.01², C2 = 0.03², sigma² = blur(x²) - mu²; computed in fp32 with a separable filter.
+ * workspace: device memory of pconv_ws_metrics_workspace_bytes(n, h, w) bytes (one fp64 pair per tile and frame),
+ * 8-byte aligned; out: n x 2 doubles on the device.  The entry points allocate nothing.  No atomics: each frame's
+ * partials are added in a fixed order, so a frame gives the same bits alone, inside any batch and on every run.
+ * n <= 65535, h, w <= 2^20; PCONV_EINVAL otherwise (workspace_bytes: a negative value). */
+#define PCONV_WS_WEIGHT_SPHERE 0
+#define PCONV_WS_WEIGHT_UNIFORM 1
+long long pconv_ws_metrics_workspace_bytes(int n, int h, int w);
+int pconv_ws_metrics_f32(const float *x, const float *y, int n, int c, int h, int w, int weighting, void *workspace,
+                         double *out, void *stream);
+int pconv_ws_metrics_u8(const uint8_t *x, const uint8_t *y, int n, int c, int h, int w, int weighting,
+                        void *workspace, double *out, void *stream);
+
 /* PseudoDQuantOp.forward  (pseudo_dquant_cuda.cu:24-70)
  * weight (wc, levels) raw parameter, level_tab (wc, levels) scratch */
 int pconv_dquant(const float *x, const float *weight, float *level_tab, float *out,

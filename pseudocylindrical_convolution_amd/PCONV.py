@@ -1336,6 +1336,40 @@ def frames_f32_to_u8_crop(x, height, width, out=None):
     return out
 
 
+WS_WEIGHTINGS = {"ws": 0, "uniform": 1}   # PCONV_WS_WEIGHT_SPHERE, PCONV_WS_WEIGHT_UNIFORM
+
+
+def ws_metrics(x, y, weighting="ws"):
+    """WS-MSE and WS-SSIM of each frame (pconv_ws_metrics_f32 / _u8, sphere_metrics.py): x, y GPU tensors of the
+    same shape, both contiguous float32 (n, C, h, w) or both uint8 (n, h, w, 3) (read as float(u8) / 255).
+    Returns a float64 CPU tensor (n, 2): [:, 0] the weighted MSE, [:, 1] the weighted SSIM"""
+    if weighting not in WS_WEIGHTINGS:
+        raise PconvError("ws_metrics: weighting must be one of %s, got %r" % (sorted(WS_WEIGHTINGS), weighting))
+    if not (x.is_cuda and y.is_cuda):
+        raise PconvError("ws_metrics: expected GPU tensors (this build has no CPU path), got %s and %s"
+                         % (x.device, y.device))
+    if x.device != y.device or x.dtype != y.dtype or x.shape != y.shape:
+        raise PconvError("ws_metrics: the two batches differ: %s %s %s vs %s %s %s"
+                         % (x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
+    if not (x.is_contiguous() and y.is_contiguous()) or x.dim() != 4:
+        raise PconvError("ws_metrics: contiguous 4-D tensors expected")
+    if x.dtype == torch.float32:
+        n, c, h, w = x.shape
+        fn = "pconv_ws_metrics_f32"
+    elif x.dtype == torch.uint8 and x.shape[3] == 3:
+        n, h, w, c = x.shape
+        fn = "pconv_ws_metrics_u8"
+    else:
+        raise PconvError("ws_metrics: float32 (n, C, h, w) or uint8 (n, h, w, 3) expected, got %s %s"
+                         % (x.dtype, tuple(x.shape)))
+    nbytes = call("pconv_ws_metrics_workspace_bytes", n, h, w)
+    workspace = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    out = torch.empty((n, 2), dtype=torch.float64, device=x.device)
+    with _HbmTimed("ws_metrics_kernel", "WsMetrics n%d" % n, 2.0 * x.numel() * x.element_size(), x.device):
+        call(fn, _ptr(x), _ptr(y), n, c, h, w, WS_WEIGHTINGS[weighting], _ptr(workspace), _ptr(out), _stream(x.device))
+    return out.cpu()
+
+
 def tile_gdn(owner, x, gamma, beta, inverse, col_limit=None, npart=0, residual=None, ring=0):
     """PseudoGDNV2.forward in one launch: x / sqrt(beta + gamma x^2) (inverse: x * sqrt)
     (+ residual), zeros from each tile's col_limit on.  gamma (ch, ch), beta (ch):

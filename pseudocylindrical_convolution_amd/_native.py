@@ -44,6 +44,9 @@ _HIP_SIGNATURES = {
     "pconv_frames_u8_to_f32_erp": [P, P, I, I, I, P],
     "pconv_erp_pad_f32": [P, P, I, I, I, P],
     "pconv_frames_f32_to_u8_crop": [P, P, I, I, I, P],
+    "pconv_ws_metrics_workspace_bytes": [I, I, I],
+    "pconv_ws_metrics_f32": [P, P, I, I, I, I, I, P, P, P],
+    "pconv_ws_metrics_u8": [P, P, I, I, I, I, I, P, P, P],
     "pconv_project": [P, P, P, I, I, I, I, I, I, I, I, P],
     "pconv_context_reshape": [P, P, I, I, I, I, I, P],
     "pconv_mask_constrain": [P, I, I, I, I, I, P],
@@ -159,6 +162,7 @@ def hip_lib():
         lib.pconv_ee_stream.restype = POINTER(c_uint8)
         lib.pconv_wino_packed_size.restype = c_longlong
         lib.pconv_wino42_packed_size.restype = c_longlong
+        lib.pconv_ws_metrics_workspace_bytes.restype = c_longlong
         _hip = lib
     return _hip
 

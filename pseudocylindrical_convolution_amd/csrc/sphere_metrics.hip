@@ -1,0 +1,267 @@
+// WS-PSNR / WS-SSIM of ERP frames (include/pconv_hip.h).  Every row j of an h-row frame is weighted
+// by the area it covers on the sphere, w_j = cos(((j + 0.5)/h - 0.5)·pi) (or 1: "uniform"); the two per-frame sums
+//   Σ_c Σ_j Σ_i w_j·(x - y)²   and   Σ_c Σ_j Σ_i w_j·ssim_map
+// come out of one fused kernel that reads each frame once.  The SSIM map is pytorch_ssim's: 11-tap Gaussian
+// (sigma 1.5) as the window g⊗g, zero padding of 5 on all four borders (the seam is not wrapped), C1 = 0.01²,
+// C2 = 0.03², sigma² = blur(x²) - mu².  It is computed in fp32 with a separable filter; every sum is fp64.
+//
+// One workgroup per (tile of 32 rows x 64 columns, frame).  Per channel it stages the 42 x 74 tile with its halo in
+// LDS (zeros outside the frame), runs the horizontal pass into five moment planes (mu_x, mu_y, x², y², xy: 42 x 64
+// each, in LDS), then the vertical pass, 8 rows x 1 column per lane, evaluates the map and adds w_j·map and
+// w_j·(x - y)² into two fp64 registers.  A wave butterfly and a fixed-order sum over the four waves give the tile's
+// partials, stored to partials[frame][tile].  No atomics: a second launch adds each frame's partials in a fixed
+// order, so a frame gives the same bits alone, in any batch and on every run.
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr int kTileRows = 32, kTileCols = 64;
+constexpr int kHalo = 5, kTaps = 2 * kHalo + 1;
+constexpr int kInRows = kTileRows + 2 * kHalo;  // 42
+constexpr int kInCols = kTileCols + 2 * kHalo;  // 74
+constexpr int kLd = 76;                         // staged row stride: 16-byte rows, the last float4 read ends at 75
+constexpr int kQuads = kTileCols / 4;           // horizontal pass: 4 adjacent outputs per lane
+constexpr int kRowsPerLane = 8;                 // vertical pass: 8 rows of one column per lane
+constexpr int kStage = (kInRows * kInCols + kBlock - 1) / kBlock;  // staged elements per lane and input
+constexpr int kPlane = kInRows * kTileCols;
+constexpr int kMaxSide = 1 << 20;
+static_assert(kBlock == kTileCols * (kTileRows / kRowsPerLane), "vertical pass: one lane per (column, row group)");
+static_assert(4 * (kQuads - 1) + 16 <= kLd, "horizontal pass: the last float4 read stays inside the staged row");
+
+struct WsGeom {
+  int c, h, w, tiles_x, tiles, uniform;
+  float g[kTaps];  // the normalised 1-D Gaussian in fp32
+};
+
+__host__ __device__ inline double row_weight(int j, int h) {
+  // ((j + 0.5)/h - 0.5)·pi with an exact integer numerator: rows j and h-1-j get the same weight bit for bit
+  return cos((double)(2 * j + 1 - h) / (2.0 * h) * M_PI);
+}
+
+// the frame's plane (f, ch) as a uniform base, a pixel as a 32-bit offset from it (a plane is below 2^31 bytes)
+__device__ __forceinline__ const float *plane_of(const float *__restrict__ p, const WsGeom &G, int f, int ch) {
+  return p + ((long long)f * G.c + ch) * G.h * G.w;
+}
+__device__ __forceinline__ float load_px(const float *__restrict__ plane, const WsGeom &G, int ch, int r, int col) {
+  return plane[(unsigned)(r * G.w + col)];
+}
+
+// uint8 (n, h, w, 3): the frame as the base; float(u8) / 255.f, correctly rounded, as pconv_frames_u8_to_f32
+__device__ __forceinline__ const uint8_t *plane_of(const uint8_t *__restrict__ p, const WsGeom &G, int f, int) {
+  return p + (long long)f * G.h * G.w * 3;
+}
+__device__ __forceinline__ float load_px(const uint8_t *__restrict__ frame, const WsGeom &G, int ch, int r, int col) {
+  return __fdiv_rn((float)frame[(unsigned)((r * G.w + col) * 3 + ch)], 255.f);
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock, 2) void ws_metrics_kernel(const T *__restrict__ x, const T *__restrict__ y,
+                                                            double *__restrict__ partials, WsGeom G) {
+  __shared__ __attribute__((aligned(16))) float sx[kInRows * kLd];
+  __shared__ __attribute__((aligned(16))) float sy[kInRows * kLd];
+  __shared__ __attribute__((aligned(16))) float mom[5][kPlane];
+  __shared__ double wrow[kTileRows];
+  __shared__ double red[2][kWaves];
+  const int tid = threadIdx.x, tile = blockIdx.x, f = blockIdx.y;
+  const int ty = tile / G.tiles_x;
+  const int r0 = ty * kTileRows, c0 = (tile - ty * G.tiles_x) * kTileCols;
+  if (tid < kTileRows) wrow[tid] = G.uniform ? 1.0 : row_weight(min(r0 + tid, G.h - 1), G.h);
+  const int col = tid & 63, rg = (tid >> 6) * kRowsPerLane;  // vertical pass: column, first row of the group
+  double acc_e = 0.0, acc_s = 0.0;
+  for (int ch = 0; ch < G.c; ch++) {
+    const T *xp = plane_of(x, G, f, ch), *yp = plane_of(y, G, f, ch);
+    float xv[kStage], yv[kStage];
+#pragma unroll
+    for (int k = 0; k < kStage; k++) {
+      const int e = tid + k * kBlock;
+      const int rr = e / kInCols, cc = e - rr * kInCols;
+      const int gr = r0 - kHalo + rr, gc = c0 - kHalo + cc;
+      const bool in = e < kInRows * kInCols && gr >= 0 && gr < G.h && gc >= 0 && gc < G.w;
+      xv[k] = in ? load_px(xp, G, ch, gr, gc) : 0.f;
+      yv[k] = in ? load_px(yp, G, ch, gr, gc) : 0.f;
+    }
+    __syncthreads();  // the previous channel's vertical pass has read sx / sy / mom
+#pragma unroll
+    for (int k = 0; k < kStage; k++) {
+      const int e = tid + k * kBlock;
+      if (e < kInRows * kInCols) {
+        const int rr = e / kInCols, o = rr * kLd + (e - rr * kInCols);
+        sx[o] = xv[k];
+        sy[o] = yv[k];
+      }
+    }
+    __syncthreads();
+    // horizontal pass: 4 adjacent outputs of one staged row per lane, from 14 inputs read as four float4
+    for (int u = tid; u < kInRows * kQuads; u += kBlock) {
+      const int rr = u / kQuads, q = u - rr * kQuads;
+      float a[16], b[16];
+#pragma unroll
+      for (int v = 0; v < 4; v++) {
+        const float4 av = *reinterpret_cast<const float4 *>(sx + rr * kLd + 4 * q + 4 * v);
+        const float4 bv = *reinterpret_cast<const float4 *>(sy + rr * kLd + 4 * q + 4 * v);
+        a[4 * v] = av.x, a[4 * v + 1] = av.y, a[4 * v + 2] = av.z, a[4 * v + 3] = av.w;
+        b[4 * v] = bv.x, b[4 * v + 1] = bv.y, b[4 * v + 2] = bv.z, b[4 * v + 3] = bv.w;
+      }
+      float m[5][4];
+#pragma unroll
+      for (int o = 0; o < 4; o++) {
+#pragma unroll
+        for (int t = 0; t < 5; t++) m[t][o] = 0.f;
+#pragma unroll
+        for (int k = 0; k < kTaps; k++) {
+          const float p = a[o + k], s = b[o + k], g = G.g[k];
+          m[0][o] = fmaf(g, p, m[0][o]);
+          m[1][o] = fmaf(g, s, m[1][o]);
+          m[2][o] = fmaf(g, p * p, m[2][o]);
+          m[3][o] = fmaf(g, s * s, m[3][o]);
+          m[4][o] = fmaf(g, p * s, m[4][o]);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 5; t++)
+        *reinterpret_cast<float4 *>(&mom[t][rr * kTileCols + 4 * q]) = make_float4(m[t][0], m[t][1], m[t][2], m[t][3]);
+    }
+    __syncthreads();
+    // vertical pass: rows rg..rg+7 of column col, from moment rows rg..rg+17
+    float acc[kRowsPerLane][5];
+#pragma unroll
+    for (int o = 0; o < kRowsPerLane; o++)
+#pragma unroll
+      for (int t = 0; t < 5; t++) acc[o][t] = 0.f;
+#pragma unroll
+    for (int i = 0; i < kRowsPerLane + 2 * kHalo; i++) {
+      float v[5];
+#pragma unroll
+      for (int t = 0; t < 5; t++) v[t] = mom[t][(rg + i) * kTileCols + col];
+#pragma unroll
+      for (int o = 0; o < kRowsPerLane; o++) {
+        if (i - o >= 0 && i - o < kTaps) {
+#pragma unroll
+          for (int t = 0; t < 5; t++) acc[o][t] = fmaf(G.g[i - o], v[t], acc[o][t]);
+        }
+      }
+    }
+    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+#pragma unroll
+    for (int o = 0; o < kRowsPerLane; o++) {
+      const int r = rg + o;
+      if (r0 + r < G.h && c0 + col < G.w) {
+        const float mu1 = acc[o][0], mu2 = acc[o][1];
+        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
+        const float s1 = acc[o][2] - mu1_sq, s2 = acc[o][3] - mu2_sq, s12 = acc[o][4] - mu1_mu2;
+        const float map = ((2.f * mu1_mu2 + C1) * (2.f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
+        const int centre = (r + kHalo) * kLd + col + kHalo;
+        const float d = sx[centre] - sy[centre];
+        const float e2 = d * d;
+        acc_e += wrow[r] * (double)e2;
+        acc_s += wrow[r] * (double)map;
+      }
+    }
+  }
+  acc_e = wave_sum(acc_e);
+  acc_s = wave_sum(acc_s);
+  if ((tid & 63) == 0) {
+    red[0][tid >> 6] = acc_e;
+    red[1][tid >> 6] = acc_s;
+  }
+  __syncthreads();
+  if (tid < 2) {
+    double s = red[tid][0];
+#pragma unroll
+    for (int k = 1; k < kWaves; k++) s += red[tid][k];
+    partials[((long long)f * G.tiles + tile) * 2 + tid] = s;
+  }
+}
+
+// one workgroup per frame: its tiles' partials and Σ_j w_j, each in a fixed order, then the normalisation
+__global__ __launch_bounds__(kBlock) void ws_metrics_sum_kernel(const double *__restrict__ partials,
+                                                                double *__restrict__ out, WsGeom G) {
+  __shared__ double red[3][kBlock];
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const double *p = partials + (long long)f * G.tiles * 2;
+  double se = 0.0, ss = 0.0, sw = 0.0;
+  for (int b = tid; b < G.tiles; b += kBlock) {
+    se += p[2 * b];
+    ss += p[2 * b + 1];
+  }
+  for (int j = tid; j < G.h; j += kBlock) sw += G.uniform ? 1.0 : row_weight(j, G.h);
+  red[0][tid] = se;
+  red[1][tid] = ss;
+  red[2][tid] = sw;
+  __syncthreads();
+  for (int s = kBlock / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+#pragma unroll
+      for (int t = 0; t < 3; t++) red[t][tid] += red[t][tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid < 2) out[2 * f + tid] = red[tid][0] / ((double)G.c * (double)G.w * red[2][0]);
+}
+
+int ws_geom(const char *what, int n, int c, int h, int w, int weighting, WsGeom *G) {
+  PCONV_REQUIRE(n >= 1 && n <= 65535, "%s: bad frame count %d", what, n);
+  PCONV_REQUIRE(c >= 1 && c <= 4096, "%s: bad channel count %d", what, c);
+  PCONV_REQUIRE(h >= 1 && w >= 1 && h <= kMaxSide && w <= kMaxSide, "%s: bad frame size %dx%d", what, w, h);
+  PCONV_REQUIRE(3LL * h * w < (1LL << 31), "%s: a %dx%d frame exceeds 2^31 bytes per plane", what, w, h);
+  PCONV_REQUIRE(weighting == PCONV_WS_WEIGHT_SPHERE || weighting == PCONV_WS_WEIGHT_UNIFORM,
+                "%s: unknown weighting %d", what, weighting);
+  G->c = c, G->h = h, G->w = w;
+  G->tiles_x = (w + kTileCols - 1) / kTileCols;
+  G->tiles = G->tiles_x * ((h + kTileRows - 1) / kTileRows);
+  G->uniform = weighting == PCONV_WS_WEIGHT_UNIFORM;
+  // pytorch_ssim.gaussian(11, 1.5): exp(-(k - 5)² / (2·1.5²)) in double, normalised; here in fp32
+  double g[kTaps], sum = 0.0;
+  for (int k = 0; k < kTaps; k++) sum += g[k] = exp(-(double)((k - kHalo) * (k - kHalo)) / (2.0 * 1.5 * 1.5));
+  for (int k = 0; k < kTaps; k++) G->g[k] = (float)(g[k] / sum);
+  return PCONV_OK;
+}
+
+template <typename T>
+int ws_metrics(const char *what, const T *x, const T *y, int n, int c, int h, int w, int weighting, void *workspace,
+               double *out, void *stream) {
+  PCONV_REQUIRE(x && y && workspace && out, "%s: null pointer", what);
+  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
+                "%s: workspace and out must be 8-byte aligned", what);
+  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(x) % sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(y) % sizeof(T)) == 0,
+                "%s: misaligned frames", what);
+  WsGeom G;
+  if (ws_geom(what, n, c, h, w, weighting, &G) != PCONV_OK) return PCONV_EINVAL;
+  double *partials = static_cast<double *>(workspace);
+  hipLaunchKernelGGL(ws_metrics_kernel<T>, dim3(G.tiles, n), dim3(kBlock), 0, as_stream(stream), x, y, partials, G);
+  PCONV_LAUNCH_CHECK(what);
+  hipLaunchKernelGGL(ws_metrics_sum_kernel, dim3(n), dim3(kBlock), 0, as_stream(stream), partials, out, G);
+  PCONV_LAUNCH_CHECK(what);
+  return PCONV_OK;
+}
+
+}  // namespace
+
+extern "C" long long pconv_ws_metrics_workspace_bytes(int n, int h, int w) {
+  PCONV_REQUIRE(n >= 1 && n <= 65535, "ws_metrics_workspace_bytes: bad frame count %d", n);
+  PCONV_REQUIRE(h >= 1 && w >= 1 && h <= kMaxSide && w <= kMaxSide, "ws_metrics_workspace_bytes: bad frame size %dx%d",
+                w, h);
+  const long long tiles = (long long)((w + kTileCols - 1) / kTileCols) * ((h + kTileRows - 1) / kTileRows);
+  return (long long)n * tiles * 2 * (long long)sizeof(double);
+}
+
+extern "C" int pconv_ws_metrics_f32(const float *x, const float *y, int n, int c, int h, int w, int weighting,
+                                    void *workspace, double *out, void *stream) {
+  return ws_metrics("ws_metrics_f32", x, y, n, c, h, w, weighting, workspace, out, stream);
+}
+
+extern "C" int pconv_ws_metrics_u8(const uint8_t *x, const uint8_t *y, int n, int c, int h, int w, int weighting,
+                                   void *workspace, double *out, void *stream) {
+  PCONV_REQUIRE(c == 3, "ws_metrics_u8: interleaved (n, h, w, 3) frames have 3 channels, got %d", c);
+  return ws_metrics("ws_metrics_u8", x, y, n, c, h, w, weighting, workspace, out, stream);
+}

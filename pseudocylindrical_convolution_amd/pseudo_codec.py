@@ -9,6 +9,7 @@ Differences from the reference, all additive:
   * any other ERP size h x w through the pole / seam padding rule of erp_size.py:
     coded at coded_size(h, w), the decoder crops back (container version 2,
     command line --native-size);
+  * --test --ws adds WS-PSNR / WS-SSIM (sphere_metrics.py) beside the viewport figures;
   * images are read/written with PIL (cv2 is not required) in the reference's BGR
     channel order, so its checkpoints stay valid.
 Module / parameter names are the reference's, so `{idx}_encoder.pt`,
@@ -31,6 +32,7 @@ from .model_zoo_v2 import ClipData, DecoderV2, EncoderV2
 from . import container
 from .erp_size import coded_size  # noqa: F401  (re-exported beside latent_shape)
 from . import erp_size
+from . import sphere_metrics
 
 psnr_f = lambda xa: 10 * math.log10(1. / xa)
 
@@ -460,22 +462,52 @@ class ViewportMetrics(object):
         return psnr_f(mse_loss), self.sim_func(x, y).item()
 
 
-def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False):
-    """reference: pseudo_codec.py:263-290"""
+class SphericalMetrics(object):
+    """WS-PSNR / WS-SSIM of an ERP image (sphere_metrics.py): every row weighted by the area it covers on the sphere.
+    Called on (original, decoded) -- uint8 (h, w, 3) images as read_image / tensor2img give them, or batches of one
+    frame in either layout sphere_metrics takes -- it returns (WS-PSNR in dB, WS-SSIM), computed on the GPU by the
+    HIP kernel, on the CPU by the float64 torch path (oracle backend)."""
+
+    def __init__(self, device_id=0, weighting="ws"):
+        self.dev = backend.device_of(device_id)
+        self.weighting = weighting
+
+    def _frames(self, img):
+        if isinstance(img, np.ndarray):
+            img = torch.from_numpy(np.ascontiguousarray(img))[None]
+        return img.to(self.dev).contiguous()
+
+    def __call__(self, original, decoded):
+        wmse, wssim = sphere_metrics.metrics(self._frames(original), self._frames(decoded), self.weighting)[0].tolist()
+        return sphere_metrics.psnr(wmse), wssim
+
+
+def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False,
+                      ws=False):
+    """reference: pseudo_codec.py:263-290.  ws=True (--ws): each row also carries the WS-PSNR and WS-SSIM of the
+    decoded image as written (tensor2img) against the source at the image's own size: (bpp, vpsnr, vssim, ws_psnr,
+    ws_ssim), with a WS line per image and for the average"""
     t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     metrics = ViewportMetrics(device_id)
+    spherical = SphericalMetrics(device_id) if ws else None
     rows = []
     for fc, fn in zip(code_list, img_list):
         h, w, is_raw = _file_geometry(fc, model_idx, mse, height, width, raw)
         rdata = t1(fc, h, w, is_raw)
-        data = img2tensor(check_img(read_image(fn), h, w), dev)
+        img = check_img(read_image(fn), h, w)
+        data = img2tensor(img, dev)
         pr, vssim = metrics(data, rdata)
         rt = bitrate(fc, h, w)
         rows.append((rt, pr, vssim))
         print('Decoding {}, compare it to {} \n Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(fc, fn, rt, pr, vssim))
+        if ws:
+            rows[-1] += spherical(img, tensor2img(rdata))
+            print(' WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*rows[-1][3:]))
     print('-' * 53 + '\nAverage Performance\n' + '-' * 53)
-    rt, pr, vssim = np.average(np.array(rows), axis=0)
-    print('Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(rt, pr, vssim))
+    avg = np.average(np.array(rows), axis=0)
+    print('Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(*avg[:3]))
+    if ws:
+        print('WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*avg[3:]))
     return rows
 
 
@@ -518,7 +550,11 @@ def main(argv=None):
                              'the next codable size and the decoder crops back.  Needs --container')
     parser.add_argument('--raw', action='store_true', default=False,
                         help='Decoding: never look for a container header (size and model from the flags)')
+    parser.add_argument('--ws', action='store_true', default=False,
+                        help='Testing: also report WS-PSNR / WS-SSIM (rows weighted by their area on the sphere) of '
+                             'each decoded image at its own size.  Needs --test')
     args = parser.parse_args(argv)
+    assert not args.ws or (args.test and not args.enc and not args.dec), '--ws needs --test'
     check_models()
     midx = args.model_idx
     if args.ssim:
@@ -547,7 +583,7 @@ def main(argv=None):
         else:
             assert img_list is not None, 'No source images for evaluation.'
             assert len(code_list) == len(img_list), 'The number of codes and corresponding source images should be the same'
-            decoding_and_test(code_list, img_list, midx, not args.ssim, args.gpu_id, raw=args.raw, **size)
+            decoding_and_test(code_list, img_list, midx, not args.ssim, args.gpu_id, raw=args.raw, ws=args.ws, **size)
 
 
 if __name__ == '__main__':
