@@ -9,6 +9,7 @@ libpconv_hip.so through the C ABI in include/pconv_hip.h.
 
 There is no CPU path here: every forward needs the HIP library and a GPU tensor.
 """
+import collections
 import ctypes
 import functools
 import os
@@ -1096,67 +1097,101 @@ def conv_col_limit(ctx_op, h, base, extra, like):
     return cache[key], ctx_op.npart_
 
 
-def packed_conv_weight(owner, weight, stream):
-    """[k][cout] fp32 slab of a conv weight for pconv_conv2d, cached on `owner`
-    until the parameter is modified (in place, by load_state_dict, or -- for writes
-    through `.data` -- after backend.invalidate_derived())."""
-    from .PCONV_operator import backend
-    key = (weight.data_ptr(), weight._version, weight.device, backend.param_epoch())
-    cached = getattr(owner, "_pconv_packed", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    cout, cin, k, k2 = weight.shape
-    size = _native.hip_lib().pconv_conv_packed_size(cout, cin, k, None, None)
-    packed = torch.empty(size, dtype=torch.float32, device=weight.device)
-    call("pconv_conv_pack_weight", _ptr(weight.detach().contiguous()), _ptr(packed), cout, cin, k, stream)
-    owner._pconv_packed = (key, packed)
-    return packed
-
-
-def packed_wino_weight(owner, weight, stream):
-    """U = G g Gt of a 3x3 weight in the layout of pconv_conv3x3_wino, cached like packed_conv_weight"""
-    from .PCONV_operator import backend
-    key = (weight.data_ptr(), weight._version, weight.device, backend.param_epoch())
-    cached = getattr(owner, "_pconv_packed_wino", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    cout, cin = weight.shape[0], weight.shape[1]
-    size = int(_native.hip_lib().pconv_wino_packed_size(cout, cin))
-    packed = torch.empty(size, dtype=torch.float32, device=weight.device)
-    call("pconv_wino_pack_weight", _ptr(weight.detach().contiguous()), _ptr(packed), cout, cin, stream)
-    owner._pconv_packed_wino = (key, packed)
-    return packed
-
-
 CONV3X3_DEFAULT = "wino42"
 WINO_ROW_SPLIT = os.environ.get("PCONV_WINO_SPLIT", "1") == "1"
 WINO_FLAT_REMAINDER = os.environ.get("PCONV_WINO_FLAT", "1") == "1"   # 2-row launches on csrc/wino_flat.hip (0: the 4-row tile)
+
+# the tile convolution kernels: C entry point, the two symbols of its weight packer, its shape predicate (the direct
+# kernel takes every layer), the name its launches carry in conv_probe (direct: conv_kernel_name()), and the attribute
+# of the layer that caches its packed weight (a layer may hold all three at once)
+ConvKernel = collections.namedtuple("ConvKernel", "entry packed_size pack_weight supported probe_name slot")
+CONV_KERNELS = {
+    "direct": ConvKernel("pconv_conv2d", "pconv_conv_packed_size", "pconv_conv_pack_weight", None, None, "_pconv_packed"),
+    # Winograd F(2x2, 3x3) (csrc/wino.hip), packed as U = G g Gt
+    "wino": ConvKernel("pconv_conv3x3_wino", "pconv_wino_packed_size", "pconv_wino_pack_weight", "pconv_wino_supported",
+                       "wino_conv3x3_kernel", "_pconv_packed_wino"),
+    # ... its 2 x 128-pixel workgroup tile (csrc/wino_flat.hip): same layers, same weights
+    "wino_flat": ConvKernel("pconv_conv3x3_wino_flat", "pconv_wino_packed_size", "pconv_wino_pack_weight",
+                            "pconv_wino_supported", "wino_conv3x3_kernel", "_pconv_packed_wino"),
+    # Winograd F(4x2, 3x3) (csrc/wino42.hip), packed as U = G6 g G4t
+    "wino42": ConvKernel("pconv_conv3x3_wino42", "pconv_wino42_packed_size", "pconv_wino42_pack_weight",
+                         "pconv_wino42_supported", "wino42_conv3x3_kernel", "_pconv_packed_wino42"),
+}
+
+
+def _packed_weight(owner, weight, kind, stream):
+    """a conv weight in the layout of CONV_KERNELS[kind] (direct: the [k][cout] fp32 slab), cached on `owner`
+    until the parameter is modified (in place, by load_state_dict, or -- for writes
+    through `.data` -- after backend.invalidate_derived())."""
+    from .PCONV_operator import backend
+    kernel = CONV_KERNELS[kind]
+    key = (weight.data_ptr(), weight._version, weight.device, backend.param_epoch())
+    cached = getattr(owner, kernel.slot, None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    cout, cin, k = weight.shape[:3]
+    size_fn = getattr(_native.hip_lib(), kernel.packed_size)
+    if kind == "direct":   # 1x1 or 3x3; the size call could also report the padded extents
+        dims, size = (cout, cin, k), size_fn(cout, cin, k, None, None)
+    else:                  # the Winograd packers are 3x3 by construction
+        dims, size = (cout, cin), size_fn(cout, cin)
+    packed = torch.empty(int(size), dtype=torch.float32, device=weight.device)
+    call(kernel.pack_weight, _ptr(weight.detach().contiguous()), _ptr(packed), *dims + (stream,))
+    setattr(owner, kernel.slot, (key, packed))
+    return packed
+
+
+def packed_conv_weight(owner, weight, stream):
+    """[k][cout] fp32 slab of a conv weight for pconv_conv2d / pconv_gdn (see _packed_weight)"""
+    return _packed_weight(owner, weight, "direct", stream)
 
 
 def conv3x3_mode():
     """which kernel takes the 3x3 stride-1 layers (PCONV_CONV3X3): 'wino42' = Winograd F(4x2, 3x3)
     (csrc/wino42.hip) where it takes the layer, F(2x2, 3x3) elsewhere; 'wino' = F(2x2, 3x3)
     (csrc/wino.hip); 'direct' = the fmaf-chain kernel the oracle restates bit for bit"""
-    import os
     mode = os.environ.get("PCONV_CONV3X3", CONV3X3_DEFAULT)
     if mode[0] == "d":
         return "direct"
     return mode if mode in ("wino42", "wino42!") else "wino"   # "wino42!": every layer the kernel takes (tests / probes)
 
 
-def packed_wino42_weight(owner, weight, stream):
-    """U = G6 g G4t of a 3x3 weight in the layout of pconv_conv3x3_wino42, cached like packed_conv_weight"""
-    from .PCONV_operator import backend
-    key = (weight.data_ptr(), weight._version, weight.device, backend.param_epoch())
-    cached = getattr(owner, "_pconv_packed_wino42", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    cout, cin = weight.shape[0], weight.shape[1]
-    size = int(_native.hip_lib().pconv_wino42_packed_size(cout, cin))
-    packed = torch.empty(size, dtype=torch.float32, device=weight.device)
-    call("pconv_wino42_pack_weight", _ptr(weight.detach().contiguous()), _ptr(packed), cout, cin, stream)
-    owner._pconv_packed_wino42 = (key, packed)
-    return packed
+def conv_plan(cin, h, w, cout, k, stride, d2w=False, fused=False, aligned=True):
+    """The launches of one tile_conv2d call, as pure arithmetic on the layer: ([(kernel, r0, rows)], fallback) with
+    kernel a key of CONV_KERNELS and [r0, r0 + rows) its output rows.  fused: a sigmoid or a gate follows (direct kernel
+    only); aligned: output and residual rows start on 8-byte boundaries.  fallback: Winograd was selected for the layer
+    and nothing took it (counted in conv_fallbacks).
+    3x3 stride-1 layers go to Winograd on the matrix cores unless PCONV_CONV3X3=direct asks for the fmaf-chain kernel
+    (the bit-exact form the oracle restates); what a kernel takes is the library's pconv_*_supported alone."""
+    ho = (h - k) // stride + 1
+    direct = [("direct", 0, ho)]
+    mode = conv3x3_mode()
+    if k != 3 or stride != 1 or fused or mode == "direct":
+        return direct, False
+    if not aligned:
+        return direct, True
+    lib, d2 = _native.hip_lib(), 1 if d2w else 0
+    wino42_takes = getattr(lib, CONV_KERNELS["wino42"].supported)
+    wino_takes = getattr(lib, CONV_KERNELS["wino"].supported)     # (the flat build takes the same layers)
+    # a launch of exactly two output rows (the split's remainder) takes the 2 x 128-pixel workgroup tile
+    flat = "wino_flat" if WINO_FLAT_REMAINDER else "wino"
+    # F(4x2, 3x3) works on 64-cout blocks: a 96-cout layer would run a third of them empty (and its 24 chunks are
+    # head and tail of the unrolled loop, no steady state): measured 0.475 vs 0.374 ms, it stays with F(2x2, 3x3)
+    # ... and on 8-row blocks.  Row counts that leave a remainder of up to four rows (66, 34, 18, 10: the "+1 halo"
+    # layers of ResidualBlockV2) are SPLIT (r6): the whole 8-row blocks on F(4x2), the remainder as one 4-row block
+    # row of F(2x2) in a second launch over row views of the same tensors -- before, 66 rows ran a ninth F(4x2) block
+    # for two rows and 34 / 18 / 10 rows went to F(2x2) altogether.  PCONV_WINO_SPLIT=0: the round-5 rule (A/B).
+    blocks = ho // 8 * 8
+    if mode == "wino42" and cout % 64 == 0 and ho > 8 and 0 < ho % 8 <= 4 and WINO_ROW_SPLIT and \
+            wino42_takes(cin, blocks + 2, w, cout, d2) == 1 and wino_takes(cin, ho - blocks + 2, w, cout, d2) == 1:
+        return [("wino42", 0, blocks), (flat if ho - blocks == 2 else "wino", blocks, ho - blocks)], False
+    # ... otherwise F(4x2) where the output rows fill its 8-row blocks to 8/9 at least
+    if (mode == "wino42!" or (mode == "wino42" and cout % 64 == 0 and (ho + 7) // 8 * 8 * 8 <= 9 * ho)) and \
+            wino42_takes(cin, h, w, cout, d2) == 1:
+        return [("wino42", 0, ho)], False
+    if wino_takes(cin, h, w, cout, d2) == 1:
+        return [(flat if ho == 2 else "wino", 0, ho)], False
+    return direct, True
 
 
 def _aligned8(t):
@@ -1174,12 +1209,36 @@ conv_fallbacks = {}
 conv_probe = None
 
 
+class _ConvTimed(object):
+    """conv_probe's bracket around one launch, like _HbmTimed.  describe() -> (kernel, label, flops, nbytes) is
+    called only when a probe is set"""
+    __slots__ = ("probe", "describe", "stream", "e0")
+
+    def __init__(self, device, describe):
+        self.probe = conv_probe
+        if self.probe is not None:
+            self.describe, self.stream = describe, torch.cuda.current_stream(device)
+
+    def __enter__(self):
+        if self.probe is not None:
+            self.e0 = torch.cuda.Event(enable_timing=True)
+            self.e0.record(self.stream)
+        return self
+
+    def __exit__(self, *exc):
+        if self.probe is not None and exc[0] is None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record(self.stream)
+            kernel, label, flops, nbytes = self.describe()
+            self.probe.records.append((kernel, label, flops, self.e0, e1, nbytes))
+        return False
+
+
 def conv_kernel_name(cout, k, stride, squared=False, cin=0, pixels=0):
     """the kernel instantiation pconv_conv2d / pconv_gdn pick for a layer (csrc/conv.hip), as
     rocprofv3 prints it: conv_mfma_kernel<MT, NT, WM, WN, KS, S, KC, SQ>, or -- only when
     PCONV_CONV1X1=resident asks for it -- the weight-resident conv1x1_rb_kernel<WM, SQ> for 1x1
     stride-1 layers whose slab fits LDS (use_resident_1x1 in conv.hip)"""
-    import os
     sq = "true" if squared else "false"
     mode = os.environ.get("PCONV_CONV1X1", "auto")[0]
     if k == 1 and stride == 1 and cin >= 32 and cin % 16 == 0 and cout > 32 and mode == "r" and \
@@ -1381,18 +1440,16 @@ def tile_gdn(owner, x, gamma, beta, inverse, col_limit=None, npart=0, residual=N
     out = _ring_output((tn, ch, h, w), ring, x)
     residual = _like_output(residual, out, "tile_gdn: residual")
     views = _views(x, out, residual)
-    probe = conv_probe
-    if probe is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream(x.device))
-    call("pconv_gdn", _ptr(x), _ptr(packed), _ptr(beta.detach().contiguous()), _ptr(out), tn, ch, h, w,
-         1 if inverse else 0, _ptr(col_limit), int(npart), _ptr(residual), ctypes.addressof(views), stream)
-    if probe is not None:
-        e1.record(torch.cuda.current_stream(x.device))
+
+    def describe():
         # (+ algorithmic HBM bytes: x in, y out, the residual: each once)
-        probe.records.append((conv_kernel_name(ch, 1, 1, True, cin=ch, pixels=tn * h * w), "GDN %d w%d" % (ch, w),
-                              2.0 * ch * ch * tn * h * w * _VALID_FRACTION, e0, e1,
-                              4.0 * ch * tn * h * w * _VALID_FRACTION * (3 if residual is not None else 2)))
+        return (conv_kernel_name(ch, 1, 1, True, cin=ch, pixels=tn * h * w), "GDN %d w%d" % (ch, w),
+                2.0 * ch * ch * tn * h * w * _VALID_FRACTION,
+                4.0 * ch * tn * h * w * _VALID_FRACTION * (3 if residual is not None else 2))
+
+    with _ConvTimed(x.device, describe):
+        call("pconv_gdn", _ptr(x), _ptr(packed), _ptr(beta.detach().contiguous()), _ptr(out), tn, ch, h, w,
+             1 if inverse else 0, _ptr(col_limit), int(npart), _ptr(residual), ctypes.addressof(views), stream)
     return out
 
 
@@ -1422,81 +1479,53 @@ def tile_conv2d(owner, x, weight, bias, stride, slope=None, col_limit=None, npar
         raise PconvError("tile_conv2d: d2w takes no sigmoid / gate / residual / trim and needs cout % 4 == 0")
     gate = _like_output(gate, out, "tile_conv2d: gate")
     residual = _like_output(residual, out, "tile_conv2d: residual")
-    # 3x3 stride-1 layers: Winograd F(2x2, 3x3) on the matrix cores (csrc/wino.hip) unless
-    # PCONV_CONV3X3=direct asks for the fmaf-chain kernel (the bit-exact form the oracle restates)
-    mode = conv3x3_mode()
-    want_wino = k == 3 and stride == 1 and not sigmoid and gate is None and mode != "direct"
-    aligned = want_wino and _aligned8(out) and (residual is None or _aligned8(residual))
-    # F(4x2, 3x3) works on 64-cout blocks: a 96-cout layer would run a third of them empty (and its 24 chunks are
-    # head and tail of the unrolled loop, no steady state): measured 0.475 vs 0.374 ms, it stays with F(2x2, 3x3)
-    # ... and on 8-row blocks.  Row counts that leave a remainder of up to four rows (66, 34, 18, 10: the "+1 halo"
-    # layers of ResidualBlockV2) are SPLIT (r6): the whole 8-row blocks on F(4x2), the remainder as one 4-row block
-    # row of F(2x2) in a second launch over row views of the same tensors -- before, 66 rows ran a ninth F(4x2) block
-    # for two rows and 34 / 18 / 10 rows went to F(2x2) altogether.  PCONV_WINO_SPLIT=0: the round-5 rule (A/B).
-    lib = _native.hip_lib()
-    d2 = 1 if d2w else 0
-    main_rows = 0
-    if aligned and mode == "wino42" and cout % 64 == 0 and ho > 8 and 0 < ho % 8 <= 4 and WINO_ROW_SPLIT and \
-            lib.pconv_wino42_supported(cin, ho // 8 * 8 + 2, w, cout, d2) == 1 and \
-            lib.pconv_wino_supported(cin, ho % 8 + 2, w, cout, d2) == 1:
-        main_rows = ho // 8 * 8
-    wino42 = (aligned and main_rows == 0 and
-              (mode == "wino42!" or (mode == "wino42" and cout % 64 == 0 and (ho + 7) // 8 * 8 * 8 <= 9 * ho)) and
-              lib.pconv_wino42_supported(cin, h, w, cout, d2) == 1)
-    wino = aligned and main_rows == 0 and not wino42 and lib.pconv_wino_supported(cin, h, w, cout, d2) == 1
-    if want_wino and not (wino or wino42 or main_rows):
+    # (only a 3x3 layer can go to the kernels that ask for it)
+    aligned = k == 3 and _aligned8(out) and (residual is None or _aligned8(residual))
+    launches, fallback = conv_plan(cin, h, w, cout, k, stride, d2w, sigmoid or gate is not None, aligned)
+    if fallback:
         # a plain 3x3 stride-1 layer that Winograd was selected for went to the direct kernel (shape not
         # taken, or output / residual rows not 8-byte aligned): counted, so that the choice is never silent
         key = (cin, h, w, cout, bool(d2w))
         conv_fallbacks[key] = conv_fallbacks.get(key, 0) + 1
-    probe = conv_probe
+    act = 4 if sigmoid else (1 if slope is not None else 0)
+    bias_p, slope_p = _ptr(bias.detach()) if bias is not None else None, _ptr(slope.detach()) if slope is not None else None
 
-    def winograd(use42, r0, rows):
+    def winograd(kind, r0, rows):
         """output rows [r0, r0 + rows) by one Winograd launch over row views (whole tensors: r0 = 0, rows = ho)"""
+        kernel = CONV_KERNELS[kind]
         whole = r0 == 0 and rows == ho
         rs = 2 if d2w else 1
         xv = x if whole else x[:, :, r0:r0 + rows + 2]
         ov = out if whole else out[:, :, rs * r0:rs * (r0 + rows)]
         rv = residual if (whole or residual is None) else residual[:, :, r0:r0 + rows]
-        if probe is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(x.device))
-        views = _views(xv, ov, rv)
-        # a launch of exactly two output rows (the split's remainder) takes the 2 x 128-pixel workgroup tile
-        entry = "pconv_conv3x3_wino42" if use42 else ("pconv_conv3x3_wino_flat" if (rows == 2 and WINO_FLAT_REMAINDER) else "pconv_conv3x3_wino")
-        call(entry, _ptr(xv),
-             _ptr(packed_wino42_weight(owner, weight, stream) if use42 else packed_wino_weight(owner, weight, stream)),
-             _ptr(bias.detach()) if bias is not None else None, _ptr(ov), tn, cin, rows + 2, w, cout,
-             1 if slope is not None else 0, _ptr(slope.detach()) if slope is not None else None, _ptr(col_limit),
-             int(npart), _ptr(rv), 1 if trim else 0, d2, ctypes.addressof(views), stream)
-        if probe is not None:
-            e1.record(torch.cuda.current_stream(x.device))
-            flops = 2.0 * cin * 9 * cout * tn * rows * wo * _VALID_FRACTION
-            nbytes = 4.0 * tn * _VALID_FRACTION * (cin * (rows + 2) * w + cout * rows * wo * (1 + (residual is not None)))
-            label = "3x3 s1 %d->%d w%d" % (cin, cout, wo) + ("" if whole else (" rows %d of %d" % (rows, ho)))
-            probe.records.append(("wino42_conv3x3_kernel" if use42 else "wino_conv3x3_kernel", label, flops, e0, e1, nbytes))
 
-    if main_rows:
-        winograd(True, 0, main_rows)
-        winograd(False, main_rows, ho - main_rows)
-        return out
-    if wino or wino42:
-        winograd(wino42, 0, ho)
-        return out
-    if probe is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream(x.device))
-    packed = packed_conv_weight(owner, weight, stream)
-    views = _views(x, out, residual, gate)
-    call("pconv_conv2d", _ptr(x), _ptr(packed), _ptr(bias.detach()) if bias is not None else None, _ptr(out),
-         tn, cin, h, w, cout, k, int(stride), 4 if sigmoid else (1 if slope is not None else 0),
-         _ptr(slope.detach()) if slope is not None else None, _ptr(col_limit), int(npart),
-         _ptr(residual), _ptr(gate), 1 if trim else 0, 1 if d2w else 0, ctypes.addressof(views), stream)
-    if probe is not None:
-        e1.record(torch.cuda.current_stream(x.device))
-        flops = 2.0 * cin * k * k * cout * tn * ho * wo * _VALID_FRACTION
-        kernel = conv_kernel_name(cout, k, stride, cin=cin, pixels=tn * h * w)
-        # algorithmic HBM bytes: the input once, the output once, residual / gate once each
-        nbytes = 4.0 * tn * _VALID_FRACTION * (cin * h * w + cout * ho * wo * (1 + (residual is not None) + (gate is not None)))
-        probe.records.append((kernel, "%dx%d s%d %d->%d w%d" % (k, k, stride, cin, cout, wo), flops, e0, e1, nbytes))
+        def describe():
+            return (kernel.probe_name, "3x3 s1 %d->%d w%d" % (cin, cout, wo) + ("" if whole else (" rows %d of %d" % (rows, ho))),
+                    2.0 * cin * 9 * cout * tn * rows * wo * _VALID_FRACTION,
+                    4.0 * tn * _VALID_FRACTION * (cin * (rows + 2) * w + cout * rows * wo * (1 + (residual is not None))))
+
+        with _ConvTimed(x.device, describe):
+            views = _views(xv, ov, rv)
+            call(kernel.entry, _ptr(xv), _ptr(_packed_weight(owner, weight, kind, stream)), bias_p, _ptr(ov), tn, cin,
+                 rows + 2, w, cout, act, slope_p, _ptr(col_limit), int(npart), _ptr(rv), 1 if trim else 0,
+                 1 if d2w else 0, ctypes.addressof(views), stream)
+
+    def direct():
+        def describe():
+            # algorithmic HBM bytes: the input once, the output once, residual / gate once each
+            return (conv_kernel_name(cout, k, stride, cin=cin, pixels=tn * h * w),
+                    "%dx%d s%d %d->%d w%d" % (k, k, stride, cin, cout, wo), 2.0 * cin * k * k * cout * tn * ho * wo * _VALID_FRACTION,
+                    4.0 * tn * _VALID_FRACTION * (cin * h * w + cout * ho * wo * (1 + (residual is not None) + (gate is not None))))
+
+        with _ConvTimed(x.device, describe):
+            views = _views(x, out, residual, gate)
+            call("pconv_conv2d", _ptr(x), _ptr(_packed_weight(owner, weight, "direct", stream)), bias_p, _ptr(out),
+                 tn, cin, h, w, cout, k, int(stride), act, slope_p, _ptr(col_limit), int(npart),
+                 _ptr(residual), _ptr(gate), 1 if trim else 0, 1 if d2w else 0, ctypes.addressof(views), stream)
+
+    for kind, r0, rows in launches:
+        if kind == "direct":   # always the whole layer
+            direct()
+        else:
+            winograd(kind, r0, rows)
     return out

@@ -1,6 +1,7 @@
 // Shared helpers of libpconv_hip.so: error reporting and launch geometry.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/pconv_hip.h"
@@ -35,3 +36,24 @@ static inline unsigned pconv_grid(long long work_items, int block = 256) {
 }
 
 static inline hipStream_t as_stream(void *s) { return (hipStream_t)s; }
+
+// The dynamic-LDS limit is a per-device attribute of the function: raise it once on every device
+// this process launches `kernel` on (one process may drive several GPUs: nn.DataParallel replicas
+// of BaseOpModule).  `raised` is the caller's static mask of that kernel instantiation, one bit
+// per device; `what` prefixes the error text.
+template <typename Kernel>
+static inline int pconv_raise_lds(Kernel kernel, size_t bytes, std::atomic<unsigned long long> &raised, const char *what) {
+  int device = 0;
+  if (hipGetDevice(&device) != hipSuccess) device = 0;
+  const unsigned long long bit = 1ULL << (device & 63);
+  if (!(raised.load(std::memory_order_acquire) & bit)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) {
+      pconv_set_error("%s: cannot raise dynamic LDS to %zu: %s", what, bytes, hipGetErrorString(e));
+      return PCONV_ELAUNCH;
+    }
+    raised.fetch_or(bit, std::memory_order_release);
+  }
+  return PCONV_OK;
+}

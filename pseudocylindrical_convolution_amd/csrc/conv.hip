@@ -27,7 +27,7 @@
 #include <atomic>
 #include <utility>
 #include <stdlib.h>
-#include "common.h"
+#include "conv_host.h"
 
 namespace {
 
@@ -107,13 +107,6 @@ struct ConvCfg {
 // gate and residual have the output's shape.  This replaces up to four
 // element-wise passes over the activation that follow the convolution in the
 // reference's graph (sigmoid, mul, add, fill).
-// element strides of a (tile, channel, row, column) tensor whose columns are contiguous:
-// lets a convolution read from / write into the interior of a padded buffer
-struct ConvView {
-  long long ts, cs;
-  int rs;
-};
-
 struct ConvEpilogue {
   const float *bias, *slope, *residual, *gate;
   const int32_t *col_limit;  // per latitude tile: first dead output column (may be null)
@@ -1133,18 +1126,7 @@ int launch_conv1x1(const float *in, const float *wp, float *out, int tn, int cin
   auto kern = conv1x1_rb_kernel<WM, SQ, RES>;
   if (smem > 64 * 1024) {
     static std::atomic<unsigned long long> raised{0};
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) device = 0;
-    const unsigned long long bit = 1ULL << (device & 63);
-    if (!(raised.load(std::memory_order_acquire) & bit)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) {
-        pconv_set_error("conv2d: cannot raise dynamic LDS to %zu: %s", smem, hipGetErrorString(e));
-        return PCONV_ELAUNCH;
-      }
-      raised.fetch_or(bit, std::memory_order_release);
-    }
+    if (int rc = pconv_raise_lds(kern, smem, raised, "conv2d")) return rc;
   }
   // second wave of every SIMD held back (units of 127 x 64 cycles); PCONV_CONV1X1_STAGGER: experiment knob
   static const int stagger_env = getenv("PCONV_CONV1X1_STAGGER") ? atoi(getenv("PCONV_CONV1X1_STAGGER")) : -1;
@@ -1416,22 +1398,8 @@ int launch_conv(const float *in, const float *wp, float *out, int tn, int cin, i
   const size_t smem = (size_t)2 * C::STAGE * sizeof(float);
   auto kern = conv_mfma_kernel<MT, NT, WM, WN, KS, S, KC, SQ, WAY>;
   if (smem > 64 * 1024) {
-    // the dynamic-LDS limit is a per-device attribute of the function: raise it once on
-    // every device this process launches the instantiation on (one process may drive
-    // several GPUs: nn.DataParallel replicas of BaseOpModule)
     static std::atomic<unsigned long long> raised{0};
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) device = 0;
-    const unsigned long long bit = 1ULL << (device & 63);
-    if (!(raised.load(std::memory_order_acquire) & bit)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) {
-        pconv_set_error("conv2d: cannot raise dynamic LDS to %zu: %s", smem, hipGetErrorString(e));
-        return PCONV_ELAUNCH;
-      }
-      raised.fetch_or(bit, std::memory_order_release);
-    }
+    if (int rc = pconv_raise_lds(kern, smem, raised, "conv2d")) return rc;
   }
   // PCONV_CONV_XCD=1 turns the XCD-grouped order on.  Measured on the analysis transform of a
   // 4096x2048 frame (same box, alternating runs): HBM reads of the 3x3 192-cout kernel 1.46 GB per
@@ -1447,18 +1415,6 @@ int launch_conv(const float *in, const float *wp, float *out, int tn, int cin, i
 }
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-inline ConvView dense_view(int c, int h, int w) { return {(long long)c * h * w, (long long)h * w, w}; }
-
-// views[3*i .. 3*i+2] = (tile, channel, row) strides of tensor i, or a dense view when views is null
-inline ConvView view_at(const long long *views, int i, int c, int h, int w) {
-  if (!views) return dense_view(c, h, w);
-  return {views[3 * i], views[3 * i + 1], (int)views[3 * i + 2]};
-}
-
-inline bool view_ok(const ConvView &v, int c, int h, int w) {
-  return v.rs >= w && v.cs >= (long long)(h - 1) * v.rs + w && v.ts >= (long long)(c - 1) * v.cs + (long long)(h - 1) * v.rs + w;
-}
 
 }  // namespace
 
@@ -1506,9 +1462,7 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
   const ConvView vin = view_at(views, 0, cin, h, w), vout = view_at(views, 1, oc, oh, ow);
   const ConvEpilogue ep = {bias,  slope, residual, gate, col_limit, npart, act, trim,
                            view_at(views, 2, cout, ho, wo), view_at(views, 3, cout, ho, wo), d2w};
-  PCONV_REQUIRE(!d2w || (vout.rs % 2 == 0 && vout.cs % 2 == 0 && vout.ts % 2 == 0 &&
-                         (reinterpret_cast<uintptr_t>(out) & 7) == 0),
-                "conv2d: depth-to-width output must be 8-byte aligned row by row");
+  PCONV_REQUIRE(!d2w || view_aligned8(vout, out), "conv2d: depth-to-width output must be 8-byte aligned row by row");
   PCONV_REQUIRE(view_ok(vin, cin, h, w) && view_ok(vout, oc, oh, ow) &&
                     (!residual || view_ok(ep.vres, cout, ho, wo)) && (!gate || view_ok(ep.vgate, cout, ho, wo)),
                 "conv2d: strides overlap");

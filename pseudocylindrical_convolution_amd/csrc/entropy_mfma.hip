@@ -910,18 +910,7 @@ static int ee_conv_bulk_mfma4w(const EeGeom *g, const void *blocks, int nblocks,
   const int kind = cin == 84 ? 0 : (tiles == 4 ? 1 : 2);
   {
     static std::atomic<unsigned long long> raised[3];
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) device = 0;
-    const unsigned long long bit = 1ULL << (device & 63);
-    if (!(raised[kind].load(std::memory_order_acquire) & bit)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernels[kind]),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) {
-        pconv_set_error("ee_conv_bulk_mfma4: cannot raise dynamic LDS: %s", hipGetErrorString(e));
-        return PCONV_ELAUNCH;
-      }
-      raised[kind].fetch_or(bit, std::memory_order_release);
-    }
+    if (int rc = pconv_raise_lds(kernels[kind], 160 * 1024, raised[kind], "ee_conv_bulk_mfma4")) return rc;
   }
   hipLaunchKernelGGL(kernels[kind], grid, dim3(waves * kWave), smem, as_stream(stream), *g, (const int4 *)blocks, rp_n, ct_n, x,
                      0, wfrag4, bias, slope, residual, y, pad_out, s_lo, s_hi);
@@ -955,18 +944,7 @@ int ee_conv_bulk_mfma4(const EeGeom *g, const void *blocks, int nblocks, int rp_
   const int kind = waves == 8;
   {
     static std::atomic<unsigned long long> raised[2];
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) device = 0;
-    const unsigned long long bit = 1ULL << (device & 63);
-    if (!(raised[kind].load(std::memory_order_acquire) & bit)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernels[kind]),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) {
-        pconv_set_error("ee_conv_bulk_mfma4: cannot raise dynamic LDS: %s", hipGetErrorString(e));
-        return PCONV_ELAUNCH;
-      }
-      raised[kind].fetch_or(bit, std::memory_order_release);
-    }
+    if (int rc = pconv_raise_lds(kernels[kind], 160 * 1024, raised[kind], "ee_conv_bulk_mfma4")) return rc;
   }
   hipLaunchKernelGGL(kernels[kind], grid, dim3(waves * kWave), smem, as_stream(stream), *g, (const int4 *)blocks, rp_n, ct_n, x,
                      0, wfrag4, bias, slope, residual, y, pad_out, s_lo, s_hi);
@@ -1038,20 +1016,8 @@ int ee_conv_bulk_mfma(const EeGeom *g, const void *blocks, int nblocks, int rp_n
                                       ee_conv_bulk_mfma_kernel<42, 4, 1, true>,  ee_conv_bulk_mfma_kernel<42, 8, 1, true>,
                                       ee_conv_bulk_mfma_kernel<14, 4, 1, true>,  ee_conv_bulk_mfma_kernel<14, 8, 1, true>};
   {
-    // the dynamic-LDS limit is a per-device attribute of the function (conv.hip)
     static std::atomic<unsigned long long> raised[8];
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) device = 0;
-    const unsigned long long bit = 1ULL << (device & 63);
-    if (!(raised[kind].load(std::memory_order_acquire) & bit)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernels[kind]),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) {
-        pconv_set_error("ee_conv_bulk_mfma: cannot raise dynamic LDS: %s", hipGetErrorString(e));
-        return PCONV_ELAUNCH;
-      }
-      raised[kind].fetch_or(bit, std::memory_order_release);
-    }
+    if (int rc = pconv_raise_lds(kernels[kind], 160 * 1024, raised[kind], "ee_conv_bulk_mfma")) return rc;
   }
   hipLaunchKernelGGL(kernels[kind], grid, dim3(waves * kWave), smem, as_stream(stream), *g, (const int4 *)blocks, rp_n, ct_n, x,
                      shared_input, wfrag, bias, slope, residual, y, pad_out, s_lo, s_hi);

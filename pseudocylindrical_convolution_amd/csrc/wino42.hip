@@ -35,7 +35,7 @@
 #include <atomic>
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "conv_host.h"
 
 namespace {
 
@@ -80,18 +80,6 @@ static_assert(kLdsFloats * 4 <= 160 * 1024, "LDS of a CU");
 static_assert(PSZ <= PBUF && USZ % 256 == 0, "stage sizes");
 static_assert(PLD + 2 * ULD < 64, "vmcnt counts to 63");
 static_assert(KC == 4 && NXI == 24, "transform: waves 0-3 take one channel of the stage each; three GEMMs per wave");
-
-struct WView {
-  long long ts, cs;
-  int rs;
-};
-
-struct WEpilogue {
-  const float *bias, *slope, *residual;
-  const int32_t *col_limit;
-  int npart, act, trim, d2w;
-  WView vres;
-};
 
 // (cout, cin, 3, 3) -> U[cblock][wave][ci_pad][x][64] = (G6 g G4t)[xi = 3 wave + x], zero past cout / cin
 __global__ void wino42_pack_kernel(const float *__restrict__ w, float *__restrict__ upk, int cout, int cin, int cin_pad,
@@ -581,15 +569,6 @@ __global__ __launch_bounds__(kThreads) void wino42_conv3x3_kernel(
 #endif
 }
 
-inline WView dense_view(int c, int h, int w) { return {(long long)c * h * w, (long long)h * w, w}; }
-inline WView view_at(const long long *views, int i, int c, int h, int w) {
-  if (!views) return dense_view(c, h, w);
-  return {views[3 * i], views[3 * i + 1], (int)views[3 * i + 2]};
-}
-inline bool view_ok(const WView &v, int c, int h, int w) {
-  return v.rs >= w && v.cs >= (long long)(h - 1) * v.rs + w && v.ts >= (long long)(c - 1) * v.cs + (long long)(h - 1) * v.rs + w;
-}
-
 }  // namespace
 
 #ifdef PCONV_W42_STAMP
@@ -628,28 +607,14 @@ extern "C" int pconv_conv3x3_wino42(const float *in, const float *packed_u, cons
                                     int h, int w, int cout, int act, const float *slope, const int32_t *col_limit,
                                     int npart, const float *residual, int trim, int d2w, const long long *views,
                                     void *stream) {
-  PCONV_REQUIRE(in && packed_u && out, "conv3x3_wino42: null pointer");
-  PCONV_REQUIRE(pconv_wino42_supported(cin, h, w, cout, d2w), "conv3x3_wino42: unsupported shape %d x %d x %d -> %d", cin, h,
-                w, cout);
-  PCONV_REQUIRE(act == 0 || (act == 1 && slope), "conv3x3_wino42: bad activation %d", act);
-  PCONV_REQUIRE(!d2w || (!residual && !trim), "conv3x3_wino42: depth-to-width takes no residual / trim");
-  PCONV_REQUIRE(!col_limit || npart > 0, "conv3x3_wino42: col_limit needs npart");
-  PCONV_REQUIRE(!trim || col_limit, "conv3x3_wino42: trim needs col_limit");
-  PCONV_REQUIRE(residual != out, "conv3x3_wino42: residual must not alias the output");
+  WView vin, vout;
+  WEpilogue ep;
+  // float2 accesses: rows of the output / residual views start on even element offsets (not asked of a
+  // depth-to-width output)
+  if (int rc = wino_check_args("conv3x3_wino42", pconv_wino42_supported, KC, true, in, packed_u, bias, out, cin, h, w, cout,
+                               act, slope, col_limit, npart, residual, trim, d2w, views, &vin, &vout, &ep))
+    return rc;
   const int ho = h - 2, wo = w - 2;
-  const int oc = d2w ? cout / 4 : cout, oh = d2w ? 2 * ho : ho, ow = d2w ? 2 * wo : wo;
-  const WView vin = view_at(views, 0, cin, h, w), vout = view_at(views, 1, oc, oh, ow);
-  const WEpilogue ep = {bias, slope, residual, col_limit, npart, act, trim, d2w, view_at(views, 2, cout, ho, wo)};
-  PCONV_REQUIRE(view_ok(vin, cin, h, w) && view_ok(vout, oc, oh, ow) && (!residual || view_ok(ep.vres, cout, ho, wo)),
-                "conv3x3_wino42: strides overlap");
-  PCONV_REQUIRE(((long long)(KC - 1) * vin.cs + (long long)(h - 1) * vin.rs + w) * 4 < (1LL << 32),
-                "conv3x3_wino42: input channel stride too large for 32-bit byte offsets inside a chunk");
-  // float2 accesses: rows of the output / residual views start on even element offsets
-  PCONV_REQUIRE(d2w || (vout.rs % 2 == 0 && vout.cs % 2 == 0 && vout.ts % 2 == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0),
-                "conv3x3_wino42: output rows must be 8-byte aligned");
-  PCONV_REQUIRE(!residual || (ep.vres.rs % 2 == 0 && ep.vres.cs % 2 == 0 && ep.vres.ts % 2 == 0 &&
-                              (reinterpret_cast<uintptr_t>(residual) & 7) == 0),
-                "conv3x3_wino42: residual rows must be 8-byte aligned");
   const int tiles_r = (ho + OROWS - 1) / OROWS, tiles_c = (wo + OCOLS - 1) / OCOLS;
   const int cblocks = (cout + CO - 1) / CO, cin_pad = (cin + KC - 1) / KC * KC;
   const long long grid = (long long)tn * tiles_r * tiles_c * cblocks;
@@ -660,21 +625,8 @@ extern "C" int pconv_conv3x3_wino42(const float *in, const float *packed_u, cons
   static const kernel_t kernels[3] = {wino42_conv3x3_kernel<false, false>, wino42_conv3x3_kernel<true, false>,
                                       wino42_conv3x3_kernel<false, true>};
   const int kind = d2w ? 2 : (residual ? 1 : 0);
-  {
-    static std::atomic<unsigned long long> raised[3];
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) device = 0;
-    const unsigned long long bit = 1ULL << (device & 63);
-    if (!(raised[kind].load(std::memory_order_acquire) & bit)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernels[kind]),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) {
-        pconv_set_error("conv3x3_wino42: cannot raise dynamic LDS to %zu: %s", smem, hipGetErrorString(e));
-        return PCONV_ELAUNCH;
-      }
-      raised[kind].fetch_or(bit, std::memory_order_release);
-    }
-  }
+  static std::atomic<unsigned long long> raised[3];
+  if (int rc = pconv_raise_lds(kernels[kind], smem, raised[kind], "conv3x3_wino42")) return rc;
   hipLaunchKernelGGL(kernels[kind], dim3((unsigned)grid), dim3(kThreads), smem, as_stream(stream), in, packed_u, out, cin,
                      cin_pad, h, w, cout, ho, wo, tiles_r, tiles_c, cblocks, vin, vout, ep);
   PCONV_LAUNCH_CHECK("conv3x3_wino42");
