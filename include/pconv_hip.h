@@ -536,6 +536,23 @@ int pconv_ee_encode_end(pconv_entropy_engine *e, void *stream);
 const uint8_t *pconv_ee_stream(const pconv_entropy_engine *e, int img, size_t *nbytes);
 int pconv_ee_decode(pconv_entropy_engine *e, const uint8_t *const *streams, const size_t *nbytes,
                     float *symbols_out, void *stream);
+/* Rate without coding.  For a coded symbol let c[0..8] be the integer CDF row the engine hands to the coder for it
+ * (8 symbols, c[0] = 0, c[8] = 65536) and s its label.  Its CODE LENGTH is 16 - log2(c[s+1] - c[s]) bits, evaluated
+ * in float64.
+ *   bits_dev (nimg, npart, ngroup) float64: bits[n][tile][group] = the sum of the code lengths of the symbols of frame
+ *     n, latitude tile `tile`, channel group `group`, over the positions the coder receives (the engine's schedule:
+ *     pconv_ee_symbols_per_image symbols per frame; dead columns are not symbols);
+ *   map_dev_or_null (nimg, npart*h, w) float32: map[n][tile*h + row][col] = the float64 sum over the groups of that
+ *     position in group order 0 .. ngroup - 1, rounded once; 0 at dead positions;
+ *   invalid input -- a label outside 0 .. 7, or a row whose label has zero frequency: what the coder refuses -- makes
+ *     the bits entry it belongs to and its map entry NaN, and nothing else;
+ *   the rate of a frame in bits per pixel is the sum of bits[n] over height * width of the frame as given (a frame
+ *     padded to its coded size counts its own pixels).
+ * The sums are taken in a fixed order without atomics: a frame's figures are the same bits alone, in any batch and
+ * on every run.  symbols as for pconv_ee_encode.  The call is stream-ordered: it queues the encoder's network and
+ * the rate kernels behind `stream` and returns; no row is stored, nothing is copied to the host, no coder runs.
+ * Refused while an encode_begin is pending and for engines whose rows are not 8 symbols of total 65536. */
+int pconv_ee_rate(pconv_entropy_engine *e, const float *symbols, double *bits_dev, float *map_dev_or_null, void *stream);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,7 @@ _HIP_SIGNATURES = {
     "pconv_ee_set_encode_ranges": [P, I],
     "pconv_ee_encode_end": [P, P],
     "pconv_ee_decode": [P, P, P, P, P],
+    "pconv_ee_rate": [P, P, P, P, P],
 }
 
 _CODER_SIGNATURES = {

@@ -108,6 +108,14 @@ int ee_conv_bulk_mfma4(const EeGeom *g, const void *blocks, int nblocks, int rp_
 int ee_tables_bulk(const EeGeom *g, const float *y_last, const float *symbols, int32_t *table, int32_t *labels,
                    int nstep, float bias, float total, float beta, int first_idx, int n_idx, int s_lo, int s_hi,
                    int packed, void *stream);
+// Rate without coding: the code length 16 - log2(c[s+1] - c[s]) (float64) of every symbol of the group's frames, from
+// the rows ee_tables_bulk computes (same device function) but never stored.  bits: (nimg, npart, ngroup) float64 sums
+// in a fixed order; map (may be null): (nimg, npart*h, w) float32, a position's sum over its groups, 0 in dead
+// columns; partial: workspace of nimg * npart * ee_rate_blocks(h, w) * ngroup doubles.  Invalid input (label outside
+// 0 .. 7, zero frequency) makes the entries it belongs to NaN.
+int ee_rate_blocks(int h, int w);
+int ee_rate_bulk(const EeGeom *g, const float *y_last, const float *symbols, double *partial, double *bits, float *map,
+                 int nstep, float bias, float total, float beta, void *stream);
 
 // decoder (r6): the LAST layer of a step (no activation, no residual, unpadded output nobody else reads) and the packed
 // CDF rows of its positions in one launch; x = the last layer's input (3*ngroup channels, padded by 2), rows as

@@ -292,6 +292,7 @@ struct Group {
   int32_t *flags_h = nullptr;                        // pinned, coherent: decoder chain flags (entropy_engine.hip)
   int32_t *counter_d = nullptr;                      // device: finished blocks of the running table kernel
   int32_t *step_row_d = nullptr;
+  double *rate_partial = nullptr;                    // device: per-workgroup sums of pconv_ee_rate (ee_rate_bulk)
   std::vector<int32_t> step_row;  // first table row of each step (x nimg), +1 end
   std::vector<int32_t> sym;
   StepPool *pool = nullptr;
@@ -345,6 +346,8 @@ struct pconv_entropy_engine {
   // codec's shape; PCONV_ENGINE_ROWS=int32 keeps the wide rows (A/B); the step-by-step debugging encoder needs them
   bool packed = false;
   size_t row_bytes() const { return packed ? 16 : (size_t)(nlevels + 1) * 4; }
+  // code lengths are defined for the codec's rows (8 symbols, total 65536), whichever way they cross PCIe
+  bool rate_capable() const { return nlevels == 8 && total == 65536.f && ngroup <= 64; }
 
   size_t ctx_elems(int n) const { return (size_t)n * npart * ngroup * (h + 2 * kPad) * (w + 2 * kPad); }
   size_t act_elems(int l, int n) const {
@@ -408,6 +411,8 @@ struct pconv_entropy_engine {
     HIP_TRY(hipHostMalloc(&g.flags_h, 64, hipHostMallocCoherent | hipHostMallocMapped));
     HIP_TRY(hipMalloc(&g.counter_d, 64));
     HIP_TRY(hipMemset(g.counter_d, 0, 64));
+    if (rate_capable())  // (a few hundred KB: here, so that pconv_ee_rate never allocates)
+      HIP_TRY(hipMalloc(&g.rate_partial, (size_t)n * npart * ee_rate_blocks(h, w) * ngroup * sizeof(double)));
     return PCONV_OK;
   }
 
@@ -618,6 +623,7 @@ struct pconv_entropy_engine {
       if (g.packed_h) (void)hipHostFree(g.packed_h);
       if (g.flags_h) (void)hipHostFree(g.flags_h);
       freed(g.counter_d);
+      freed(g.rate_partial);
       if (g.done) (void)hipEventDestroy(g.done);
       if (g.step_done) (void)hipEventDestroy(g.step_done);
       for (hipEvent_t &ev : g.enc_done)
@@ -1227,6 +1233,45 @@ int pconv_ee_encode_end(pconv_entropy_engine *e, void *stream) {
 int pconv_ee_encode(pconv_entropy_engine *e, const float *symbols, void *stream) {
   PC_TRY(pconv_ee_encode_begin(e, symbols, stream));
   return pconv_ee_encode_end(e, stream);
+}
+
+// The rate of the frames without coding them (include/pconv_hip.h).  Per group: the encoder's prologue, the bulk
+// network over ALL steps and the rate kernels, which read the last layer's output and the symbols and store nothing but
+// sums.  No row is written, nothing is copied to the host, no coder thread is started and the host waits for nothing:
+// the call returns once everything is queued.  The groups run where encode runs them -- one after the other IN the
+// caller's stream (the bulk kernels fill the GPU on their own; see pconv_ee_encode_begin) -- unless
+// PCONV_ENGINE_RATE_STREAMS=group puts each on its own stream, forked from and joined to the caller's with events:
+// measured (8 frames of 4096x2048 in four chunks, behind their analysis transform; profiles/rate_estimate.txt) the
+// group streams' event waits, queued while the transform still runs, cost 27 ms (rate() 287 against 260 ms).  The buffers the call leaves
+// behind are what an encode of the same symbols leaves (clear()'s invariant holds).
+int pconv_ee_rate(pconv_entropy_engine *e, const float *symbols, double *bits_dev, float *map_dev_or_null, void *stream) {
+  PCONV_REQUIRE(e && symbols && bits_dev, "ee_rate: bad argument");
+  PCONV_REQUIRE(!e->enc_thread.joinable(), "ee_rate: the previous encode has not been ended");
+  PCONV_REQUIRE(e->rate_capable(), "ee_rate: code lengths are defined for rows of 8 symbols, total 65536");
+  for (int l = 0; l < kLayers; l++) PCONV_REQUIRE(e->bound[l], "ee_rate: layer %d has no weights", l);
+  hipStream_t caller = as_stream(stream);
+  const char *env = getenv("PCONV_ENGINE_RATE_STREAMS");
+  const bool own_streams = env && env[0] == 'g';
+  if (own_streams) PC_TRY(e->fork(caller));
+  int rc = PCONV_OK;
+  for (size_t k = 0; k < e->groups.size() && rc >= 0; k++) {
+    Group &g = e->groups[k];
+    const hipStream_t own = g.stream;
+    if (!own_streams) g.stream = caller;
+    rc = e->encode_prologue(g, symbols);
+    if (rc >= 0) rc = e->network_bulk(g, 0, e->nsteps);
+    if (rc >= 0)
+      rc = ee_rate_bulk(&g.geom, g.act[kLayers - 1], symbols + (size_t)g.first * e->image_symbols(), g.rate_partial,
+                        bits_dev + (size_t)g.first * e->npart * e->ngroup,
+                        map_dev_or_null ? map_dev_or_null + (size_t)g.first * e->rows * e->w : nullptr, e->nlevels,
+                        e->bias, e->total, e->beta, g.stream);
+    g.stream = own;
+  }
+  if (rc < 0) e->distrust_buffers();
+  // (also after a failed launch: what was queued still orders the caller's stream)
+  const int jrc = own_streams ? e->join(caller) : PCONV_OK;
+  PC_TRY(rc);
+  return jrc;
 }
 
 const uint8_t *pconv_ee_stream(const pconv_entropy_engine *e, int img, size_t *nbytes) {

@@ -1079,6 +1079,29 @@ __global__ void ee_tables8_kernel(EeGeom g, const float *__restrict__ y, int32_t
   }
 }
 
+// The integer CDF row of symbol (frame n, position p, group tc) from the last layer's output y, and the symbol's
+// label: the ONE place where the bulk (encoder) kernels turn the network's output into what the coder gets --
+// ee_tables_bulk_kernel stores the row, ee_rate_bulk_kernel only measures it.  Two halves, so that the table kernel
+// keeps its loads in front of its packed / int32 branch: the GMM parameters (prepared) and the label ...
+__device__ __forceinline__ int32_t bulk_row_inputs(const EeGeom &g, const float *__restrict__ y,
+                                                   const float *__restrict__ symbols, int n, const Pos &p, int tc,
+                                                   float beta, float (&par)[3][3]) {
+  const int cout = g.ngroup * 3;
+#pragma unroll
+  for (int rep = 0; rep < 3; rep++) {
+    const float *base =
+        y + ((((size_t)(rep * g.nimg + n) * g.npart + p.tg) * g.h + p.th) * g.w + p.tw) * cout + tc * 3;
+#pragma unroll
+    for (int k = 0; k < 3; k++) par[rep][k] = base[k];
+  }
+  gmm_prepare_row(par[0], par[1], 3, beta);
+  return (int32_t)symbols[((((size_t)n * g.npart + p.tg) * g.ngroup + tc) * g.h + p.th) * g.w + p.tw];
+}
+// ... and the row of nstep + 1 entries from them
+__device__ __forceinline__ void bulk_row_cdf(float (&par)[3][3], int nstep, float bias, float total, int32_t *row) {
+  gmm_cdf_row<int32_t>(par[0], par[1], par[2], 3, nstep, bias, total, 1, row);
+}
+
 // all symbols at once, rows in stream order [step][img][position in the step's window]
 __global__ void ee_tables_bulk_kernel(EeGeom g, const float *__restrict__ y, const float *__restrict__ symbols,
                                       int32_t *__restrict__ table, int32_t *__restrict__ labels, int nstep,
@@ -1098,26 +1121,102 @@ __global__ void ee_tables_bulk_kernel(EeGeom g, const float *__restrict__ y, con
     const int len = g.plane_start[end] - g.plane_start[st];
     const size_t r = (size_t)g.step_row[s] + (size_t)n * len + (idx - g.plane_start[st]);
     const Pos p = decode_pos(g.order[idx], g.h, g.w);
-    const int cout = g.ngroup * 3;
     float par[3][3];
-#pragma unroll
-    for (int rep = 0; rep < 3; rep++) {
-      const float *base =
-          y + ((((size_t)(rep * g.nimg + n) * g.npart + p.tg) * g.h + p.th) * g.w + p.tw) * cout + tc * 3;
-#pragma unroll
-      for (int k = 0; k < 3; k++) par[rep][k] = base[k];
-    }
-    gmm_prepare_row(par[0], par[1], 3, beta);
-    const int32_t label = (int32_t)symbols[((((size_t)n * g.npart + p.tg) * g.ngroup + tc) * g.h + p.th) * g.w + p.tw];
+    const int32_t label = bulk_row_inputs(g, y, symbols, n, p, tc, beta, par);
     if (packed) {  // (nstep == 8: checked on the host)
       int32_t row[9];
-      gmm_cdf_row<int32_t>(par[0], par[1], par[2], 3, 8, bias, total, 1, row);
+      bulk_row_cdf(par, 8, bias, total, row);
       reinterpret_cast<uint4 *>(table)[r] = pack_row16(row, label);
     } else {
-      gmm_cdf_row<int32_t>(par[0], par[1], par[2], 3, nstep, bias, total, 1, table + r * (nstep + 1));
+      bulk_row_cdf(par, nstep, bias, total, table + r * (nstep + 1));
       labels[r] = label;
     }
   }
+}
+
+// ---- rate without coding (include/pconv_hip.h, "code length") -----------------------------------------------------
+// The code length of every symbol of a group's frames from the very rows ee_tables_bulk_kernel would store
+// (bulk_row_inputs, bulk_row_cdf), summed per (frame, tile, group) in float64 in a FIXED order: no row leaves the registers, nothing
+// is added atomically.  Grid (blocks of a tile, tile, frame); a lane owns one latent position (row, col) of the tile
+// and walks its groups 0 .. ngroup - 1:
+//   per group   the lane's term -> wave butterfly (xor 32 .. 1: every lane ends with the same total) -> LDS slot of
+//               the wave; after the walk, thread tc adds the kRateWaves wave totals of group tc in wave order and
+//               stores the block's partial;
+//   per lane    the float64 sum over its groups in group order, rounded once: the map entry (0 in dead columns).
+// ee_rate_sum_kernel then adds a (frame, tile, group)'s partials in block order.  The decomposition of a frame
+// depends on (h, w) alone, so a frame's figures are the same bits alone or in any batch.
+constexpr int kRateBlock = 256, kRateWaves = kRateBlock / kWave;
+
+__device__ __forceinline__ double butterfly_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
+  return v;
+}
+
+// 16 - log2(c[s+1] - c[s]) in float64; NaN for what the coder refuses (label outside 0 .. 7, zero frequency)
+__device__ __forceinline__ double code_length_bits(const int32_t *row, int32_t label) {
+  int32_t lo = 0, hi = 0;  // (selects instead of a dynamic index: the row stays in registers)
+#pragma unroll
+  for (int k = 0; k < 8; k++)
+    if (k == label) {
+      lo = row[k];
+      hi = row[k + 1];
+    }
+  const int32_t f = hi - lo;
+  if (label < 0 || label > 7 || f <= 0) return __longlong_as_double(0x7ff8000000000000LL);
+  return 16.0 - log2((double)f);
+}
+
+__global__ __launch_bounds__(kRateBlock) void ee_rate_bulk_kernel(EeGeom g, const float *__restrict__ y,
+                                                                  const float *__restrict__ symbols,
+                                                                  double *__restrict__ partial,
+                                                                  float *__restrict__ map, float bias, float total,
+                                                                  float beta) {
+  __shared__ double wave_sum[kRateWaves][64];  // [wave][group] (ngroup <= 64: checked on the host)
+  const int tile = blockIdx.y, n = blockIdx.z;
+  const int q = blockIdx.x * kRateBlock + threadIdx.x;  // position of the tile, row-major
+  const int wave = threadIdx.x / kWave;
+  Pos p;
+  p.tg = tile;
+  p.th = q / g.w;
+  p.tw = q - p.th * g.w;
+  p.row = tile * g.h + p.th;
+  const bool inside = p.th < g.h;
+  const bool live = inside && p.tw < g.widths[tile];  // the schedule holds exactly these (pconv_host_wavefront)
+  double mine = 0.0;
+  for (int tc = 0; tc < g.ngroup; tc++) {
+    double bits = 0.0;
+    if (live) {
+      float par[3][3];
+      int32_t row[9];
+      const int32_t label = bulk_row_inputs(g, y, symbols, n, p, tc, beta, par);
+      bulk_row_cdf(par, 8, bias, total, row);
+      bits = code_length_bits(row, label);
+    }
+    mine += bits;
+    const double sum = butterfly_sum_f64(bits);
+    if ((threadIdx.x & (kWave - 1)) == 0) wave_sum[wave][tc] = sum;
+  }
+  if (map && inside) map[((size_t)n * g.npart * g.h + p.row) * g.w + p.tw] = (float)mine;
+  __syncthreads();
+  if ((int)threadIdx.x < g.ngroup) {
+    double sum = wave_sum[0][threadIdx.x];
+#pragma unroll
+    for (int k = 1; k < kRateWaves; k++) sum += wave_sum[k][threadIdx.x];
+    partial[(((size_t)n * g.npart + tile) * gridDim.x + blockIdx.x) * g.ngroup + threadIdx.x] = sum;
+  }
+}
+
+// bits[n][tile][group] = the partials of its blocks, added in block order
+__global__ void ee_rate_sum_kernel(const double *__restrict__ partial, double *__restrict__ bits, int ngroup, int nblock,
+                                   int count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // (n*npart + tile)*ngroup + group
+  if (i >= count) return;
+  const int tc = i % ngroup;
+  const double *src = partial + (size_t)(i / ngroup) * nblock * ngroup + tc;
+  double sum = src[0];
+  for (int k = 1; k < nblock; k++) sum += src[(size_t)k * ngroup];
+  bits[i] = sum;
 }
 
 }  // namespace
@@ -1132,6 +1231,25 @@ int ee_tables_bulk(const EeGeom *g, const float *y_last, const float *symbols, i
   hipLaunchKernelGGL(ee_tables_bulk_kernel, dim3(pconv_grid(count)), dim3(256), 0, as_stream(stream), *g, y_last,
                      symbols, table, labels, nstep, bias, total, beta, count, first_idx, n_idx, s_lo, s_hi, packed);
   PCONV_LAUNCH_CHECK("ee_tables_bulk");
+  return PCONV_OK;
+}
+
+int ee_rate_blocks(int h, int w) { return (h * w + kRateBlock - 1) / kRateBlock; }
+
+int ee_rate_bulk(const EeGeom *g, const float *y_last, const float *symbols, double *partial, double *bits, float *map,
+                 int nstep, float bias, float total, float beta, void *stream) {
+  PCONV_REQUIRE(y_last && symbols && partial && bits, "ee_rate_bulk: null pointer");
+  PCONV_REQUIRE(nstep == 8 && total == 65536.f, "ee_rate_bulk: code lengths are defined for rows of 8 symbols, total 65536");
+  PCONV_REQUIRE(g->ngroup >= 1 && g->ngroup <= 64, "ee_rate_bulk: at most 64 channel groups");
+  PCONV_REQUIRE(g->npart <= 65535 && g->nimg <= 65535, "ee_rate_bulk: too many tiles or frames for one grid");
+  const int nblock = ee_rate_blocks(g->h, g->w);
+  hipLaunchKernelGGL(ee_rate_bulk_kernel, dim3(nblock, g->npart, g->nimg), dim3(kRateBlock), 0, as_stream(stream), *g,
+                     y_last, symbols, partial, map, bias, total, beta);
+  PCONV_LAUNCH_CHECK("ee_rate_bulk");
+  const int count = g->nimg * g->npart * g->ngroup;
+  hipLaunchKernelGGL(ee_rate_sum_kernel, dim3((count + 255) / 256), dim3(256), 0, as_stream(stream), partial, bits,
+                     g->ngroup, nblock, count);
+  PCONV_LAUNCH_CHECK("ee_rate_sum");
   return PCONV_OK;
 }
 

@@ -138,6 +138,21 @@ class EntropyEngine(object):
                  out.data_ptr(), stream)
         return out
 
+    def rate(self, symbols, rate_map=False):
+        """symbols as for encode -> bits (nimg, npart, ngroup) float64 on the GPU: per frame, latitude tile and
+        channel group the sum of the code lengths 16 - log2(c[s+1] - c[s]) of the rows the coder would get
+        (rate.py, pconv_ee_rate); rate_map=True: also map (nimg, npart*h, w) float32, the bits of every latent
+        position (0 in dead columns).  Stream-ordered: no coder runs and nothing reaches the host."""
+        self._check_symbols(symbols)
+        bits = torch.empty((self.nimg, self.npart, self.ngroup), dtype=torch.float64, device=self.device)
+        pos = torch.empty((self.nimg, self.npart * self.h, self.w), dtype=torch.float32, device=self.device) \
+            if rate_map else None
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            call("pconv_ee_rate", self.handle, symbols.data_ptr(), bits.data_ptr(),
+                 pos.data_ptr() if rate_map else None, stream)
+        return (bits, pos) if rate_map else bits
+
 
 class CodecEngine(object):
     """frames in, byte streams out, and back: PseudoEncoder / PseudoDecoder
@@ -326,6 +341,51 @@ class CodecEngine(object):
             self._phase("analysis", t0, t1)
             self._phase("entropy_encode", t1, self._mark())
         return out
+
+    def _rate_of_symbols(self, sym, n, rate_map):
+        """bits (n, npart, ngroup) [, map] of the symbols of n frames, through the chunks -- and the engines --
+        encode() takes them through"""
+        chunk = self.ENCODE_CHUNK if n > self.ENCODE_CHUNK else n
+        tiles = self.enc.ent.npart
+        bits, maps = [], []
+        for k, lo in enumerate(range(0, n, chunk)):
+            part = sym[lo * tiles:(lo + chunk) * tiles]
+            eng = self._engine("enc", part.shape[2], part.shape[3], part.shape[0] // tiles, slot=k)
+            res = eng.rate(part, rate_map)
+            bits.append(res[0] if rate_map else res)
+            if rate_map:
+                maps.append(res[1])
+        cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+        return (cat(bits), cat(maps)) if rate_map else cat(bits)
+
+    @torch.no_grad()
+    def rate(self, frames, rate_map=False):
+        """(n, 3, H, W) frames on the GPU -> bits (n, npart, ngroup) float64 on the GPU: what encode() would spend
+        per frame, latitude tile and channel group, from the CDF rows alone (rate.py) -- no arithmetic coder, no
+        copy to the host, no file.  rate.bpp(bits, H, W) is the frame rate.  rate_map=True: also the bits of every
+        latent position, (n, npart*2h, 2w) float32.  Sizes the codec does not take as they are are padded as
+        encode() pads them (their bpp still counts their own pixels)."""
+        if not erp_size.codable(frames.shape[2], frames.shape[3]):
+            frames = erp_size.pad(frames)
+        return self._rate_of_symbols(self.symbols(frames).contiguous(), frames.shape[0], rate_map)
+
+    @torch.no_grad()
+    def evaluate(self, frames, rate_map=False):
+        """one rate-distortion point without a file: (bits, reconstruction[, map]).  The symbols are computed once;
+        bits (and map) are rate()'s, the reconstruction is decode(encode(frames), H, W)'s -- the entropy decoder
+        returns exactly the symbols the encoder holds (tests/test_gpu_engine.py), so neither it nor the arithmetic
+        coder has to run."""
+        height, width = frames.shape[2], frames.shape[3]
+        native = erp_size.codable(height, width)
+        if not native:
+            frames = erp_size.pad(frames)
+        n = frames.shape[0]
+        sym = self.symbols(frames).contiguous()
+        res = self._rate_of_symbols(sym, n, rate_map)
+        rec = self.reconstruct(sym, n)
+        if not native:
+            rec = erp_size.crop(rec, height, width)
+        return (res[0], rec, res[1]) if rate_map else (res, rec)
 
     # frames per pipeline stage of decode(); 0 = decode all frames of a call together, then run the
     # synthesis transforms (PCONV_DECODE_CHUNK overrides)

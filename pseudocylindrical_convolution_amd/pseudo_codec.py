@@ -10,6 +10,8 @@ Differences from the reference, all additive:
     coded at coded_size(h, w), the decoder crops back (container version 2,
     command line --native-size);
   * --test --ws adds WS-PSNR / WS-SSIM (sphere_metrics.py) beside the viewport figures;
+  * --rd scores images without writing a file: the rate from the CDF rows (rate.py), the distortion from the
+    reconstruction of the encoder's own symbols -- no arithmetic coder, no entropy decoder;
   * images are read/written with PIL (cv2 is not required) in the reference's BGR
     channel order, so its checkpoints stay valid.
 Module / parameter names are the reference's, so `{idx}_encoder.pt`,
@@ -511,6 +513,46 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
     return rows
 
 
+def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False):
+    """--rd: what encoding() + decoding_and_test() report for the images, without a file in between.  The rate is
+    the code length of the CDF rows the coder would get (rate.py: within a few bits of the stream), the
+    reconstruction is the synthesis of the encoder's own symbols -- what the entropy decoder would hand back.
+    Needs the native engine (GPU).  native=True (--native-size): every image at its own size, padded by the rule of
+    erp_size.py; otherwise resized to height x width as --enc does.  Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim])."""
+    from .engine import CodecEngine
+    from . import rate
+    prex, vd, model_dir = _pick(model_idx, mse)
+    dev = backend.device_of(device_id)
+    enc = PseudoEncoder(vd, device_id=device_id).to(dev)
+    load_models(enc, '{}/{}_encoder.pt'.format(model_dir, prex), '{}/{}_ent.pt'.format(model_dir, prex), dev)
+    dec = PseudoDecoder(vd, device_id=device_id).to(dev)
+    load_models(dec, '{}/{}_decoder.pt'.format(model_dir, prex), '{}/{}_ent.pt'.format(model_dir, prex), dev)
+    codec = CodecEngine(vd, device_id, enc, dec)
+    metrics = ViewportMetrics(device_id)
+    spherical = SphericalMetrics(device_id) if ws else None
+    rows = []
+    for fn in img_list:
+        img = read_image(fn)
+        if not native:
+            img = check_img(img, height, width)
+        h, w = img.shape[:2]
+        data = img2tensor(img, dev)
+        bits, rdata = codec.evaluate(data)
+        pr, vssim = metrics(data, rdata)
+        rt = rate.bpp(bits, h, w)[0].item()
+        rows.append((rt, pr, vssim))
+        print('Estimating {} \n Bitrate:{:.3f}bpp (tables), PSNR:{:.2f}dB, SSIM:{:.4f}'.format(fn, rt, pr, vssim))
+        if ws:
+            rows[-1] += spherical(img, tensor2img(rdata))
+            print(' WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*rows[-1][3:]))
+    print('-' * 53 + '\nAverage Performance\n' + '-' * 53)
+    avg = np.average(np.array(rows), axis=0)
+    print('Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(*avg[:3]))
+    if ws:
+        print('WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*avg[3:]))
+    return rows
+
+
 def read_list(fname):
     with open(fname) as f:
         return [line.rstrip('\n') for line in f.readlines()]
@@ -535,6 +577,9 @@ def main(argv=None):
     parser.add_argument('--enc', action='store_true', default=False, help='Encoding flag, set for encoding phase.')
     parser.add_argument('--dec', action='store_true', default=False, help='Decoding flag, set for decoding phase.')
     parser.add_argument('--test', action='store_true', default=False, help='Testing flag, set for decoding and evalating the performance.')
+    parser.add_argument('--rd', action='store_true', default=False,
+                        help='Rate-distortion flag: score the images without writing code files (rate from the CDF '
+                             'tables, reconstruction from the encoder\'s own symbols).  Takes --img-list/--img-file only')
     parser.add_argument('--ssim', action='store_true', default=False,
                         help='Default with models optimized for VMSE, set this flag for choosing the models optimized for VSSIM')
     parser.add_argument('--gpu-id', type=int, default=0, help='The graphic card id for encoding and decoding.')
@@ -547,27 +592,32 @@ def main(argv=None):
     parser.add_argument('--native-size', action='store_true', default=False,
                         help='Encoding: code every image at its own size (any height and width, no resize; '
                              '--height/--width are ignored): the frame is padded at the poles and the seam to '
-                             'the next codable size and the decoder crops back.  Needs --container')
+                             'the next codable size and the decoder crops back.  Needs --container '
+                             '(--rd: needs nothing, no file is written)')
     parser.add_argument('--raw', action='store_true', default=False,
                         help='Decoding: never look for a container header (size and model from the flags)')
     parser.add_argument('--ws', action='store_true', default=False,
                         help='Testing: also report WS-PSNR / WS-SSIM (rows weighted by their area on the sphere) of '
-                             'each decoded image at its own size.  Needs --test')
+                             'each decoded image at its own size.  Needs --test or --rd')
     args = parser.parse_args(argv)
-    assert not args.ws or (args.test and not args.enc and not args.dec), '--ws needs --test'
+    assert not args.ws or ((args.test or args.rd) and not args.enc and not args.dec), '--ws needs --test or --rd'
+    assert not args.rd or not (args.enc or args.dec or args.test), '--rd excludes --enc, --dec and --test'
     check_models()
     midx = args.model_idx
     if args.ssim:
         assert 0 <= midx < 9, '(0-8) for VSSIM'
     else:
         assert 0 <= midx < 10, '(0-9) for VMSE'
-    assert args.enc or args.dec or args.test, \
-        'Should set one flag, (--enc) for encoding, (--dec) for decoding, (--test) for testing.'
+    assert args.enc or args.dec or args.test or args.rd, \
+        'Should set one flag, (--enc) for encoding, (--dec) for decoding, (--test) for testing, (--rd) for scoring.'
     pick = lambda lst, fil: lst if lst is not None else (read_list(fil) if fil is not None else None)
     img_list, code_list, out_list = pick(args.img_list, args.img_file), pick(args.code_list, args.code_file), \
         pick(args.out_list, args.out_file)
     size = dict(height=args.height, width=args.width)
-    if args.enc:
+    if args.rd:
+        assert img_list is not None, 'No input images for scoring'
+        rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws, **size)
+    elif args.enc:
         assert img_list is not None, 'No input images for encoding'
         assert code_list is not None, 'No code files for saving the codes'
         assert len(img_list) == len(code_list), 'The number of images and codes should be the same'
