@@ -495,7 +495,8 @@ int pconv_ee_steps(const pconv_entropy_engine *e);
  * on = min(affinity mask, cgroup CPU quota / LOCAL_WORLD_SIZE).  pconv_ee_spin_us: microseconds an
  * idle decode worker polls before it blocks when a call runs `call_threads` host threads (one per
  * frame): 2000 (through the GPU part of a step) only if call_threads + 1 <= pconv_ee_host_cpus(),
- * else 60; PCONV_ENGINE_SPIN_US overrides.  Neither touches the GPU. */
+ * else 60; PCONV_ENGINE_SPIN_US overrides.  Neither touches the GPU.  Like pconv_ee_host_plan they read the
+ * environment when they are called; an engine keeps what pconv_ee_create read (pconv_option). */
 int pconv_ee_host_cpus(void);
 int pconv_ee_spin_us(int call_threads);
 /* How an engine of `nimg` frames lays out its host side here (any pointer may be NULL): lock-step groups (= decoder
@@ -514,6 +515,25 @@ int pconv_ee_wait_mode(const pconv_entropy_engine *e);
  * need an even width and 14, 28 or 48 groups (28 / 48: hidden layers 1 .. 11 only); PCONV_EE_BULK=valu keeps the
  * vector kernel everywhere.  PCONV_EINVAL (pconv_last_error) for a bad layer. */
 int pconv_ee_encoder_form(const pconv_entropy_engine *e, int layer);
+/* The tuning options of the library (PCONV_* environment variables; every one, its default and the measurement
+ * behind it: DESIGN.md, "What runs by default").  Two lifetimes: an ENGINE keeps the options pconv_ee_create read
+ * (PCONV_ENGINE_*, PCONV_EE_*) -- no later call of that engine looks at the environment -- and a stateless entry
+ * point (pconv_conv2d, pconv_gdn: PCONV_CONV*; pconv_sphere_slice / _uslice: PCONV_RESAMPLE_ROWS; the host queries
+ * above) reads its options when it is called.  pconv_option stores in *value what engine `e` holds for the
+ * variable `name`, or with e == NULL (and for the per-call options) what a create or call made now would read;
+ * PCONV_EINVAL (pconv_last_error) for an unknown name.  Values are the integers the code branches on:
+ *   numbers as written (atoi): PCONV_EE_BLOCK, _PPW (<= 0: by frame count), _JOINT, _CONTIG, _XCD, _FUSE_PPW,
+ *     _MFMA_WAVES, _MFMA_NT, PCONV_ENGINE_ENCODE_RANGES, PCONV_CONV1X1_STAGGER (< 0: none), PCONV_CONV_XCD,
+ *     PCONV_RESAMPLE_ROWS;
+ *   numbers, or PCONV_OPTION_AUTO when unset (the host plan / pconv_ee_spin_us decides): PCONV_ENGINE_GROUPS,
+ *     _WORKERS, _SPIN_US, _BLOCKING_SYNC (0 / 1), _CHAIN (1 queued: anything but h..., 0 host-driven);
+ *   0 / 1 switches: PCONV_ENGINE_ROWS (1 = int32), _STEPWISE_ENCODER and _TIMING (1 = set at all),
+ *     _CLEAR_EVERY_CALL, _ENCODE_INTERLEAVE, _RATE_STREAMS (1 = group), PCONV_EE_BULK and _BULK0 (1 = valu),
+ *     _MFMA_FORM (1 = 16x4), _MFMA_WSRC (1 = ring), _FUSE_TABLES, PCONV_CONV_SMALL (0 = off);
+ *   PCONV_CONV1X1: 0 auto, 1 tiled, 2 resident; PCONV_CONV1X1_WAYOUT: 0 quads, 1 pipe, 2 batch;
+ *   PCONV_ENGINE_CU_MASK=first:count is reported under the two names PCONV_ENGINE_CU_MASK_FIRST and _COUNT. */
+#define PCONV_OPTION_AUTO (-2147483647 - 1)
+int pconv_option(const pconv_entropy_engine *e, const char *name, int *value);
 /* Explicit, process-wide opt-in: hipSetDeviceFlags(hipDeviceScheduleBlockingSync) on the current device (enable != 0),
  * then the flag is read back: returns 1 when every runtime wait on the device now sleeps, 0 when it does not (not asked
  * for, or refused by the runtime on a live context -- the engine's blocking events still apply then).  Never called by

@@ -96,6 +96,7 @@ _HIP_SIGNATURES = {
     "pconv_ee_host_plan": [I, P, P, P, P],
     "pconv_ee_wait_mode": [P],
     "pconv_ee_encoder_form": [P, I],
+    "pconv_option": [P, c_char_p, P],
     "pconv_device_blocking_sync": [I],
     "pconv_stream_create": [P],
     "pconv_stream_destroy": [P],
@@ -201,3 +202,11 @@ def check(rc, what=""):
 def call(fn, *args):
     lib = hip_lib()
     return check(getattr(lib, fn)(*args), fn)
+
+
+def option(name, engine=None):
+    """The parsed value of the tuning option `name` (pconv_option, include/pconv_hip.h): what the engine handle
+    `engine` holds, or without one what a create or call made now would read from the environment."""
+    value = c_int(0)
+    call("pconv_option", engine, name.encode(), ctypes.addressof(value))
+    return value.value

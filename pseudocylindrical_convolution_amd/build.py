@@ -34,6 +34,7 @@ HIP_SOURCES = [
     "wino_flat.hip",   # wino.hip again with a 2-row x 128-column workgroup tile (the row split's remainders)
     "wino42.hip",
     "backward.hip",
+    "options.cpp",  # the one reader of the library's PCONV_ variables, and pconv_option
     "engine.cpp",
     "coder.cpp",  # the engine drives the arithmetic coder natively
 ]

@@ -26,7 +26,7 @@
 // chain), then + bias, then the activation.  The oracle restates exactly that.
 #include <atomic>
 #include <utility>
-#include <stdlib.h>
+#include "options.h"
 #include "conv_host.h"
 
 namespace {
@@ -1107,7 +1107,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_rb_kernel(
 template <int WM, bool SQ, bool RES>
 int launch_conv1x1(const float *in, const float *wp, float *out, int tn, int cin, int h, int w, int cout,
                    int cout_pad, const ConvView &vin, const ConvView &vout, const ConvEpilogue &ep,
-                   hipStream_t stream) {
+                   const ConvOptions &opt, hipStream_t stream) {
   constexpr int BM = 96 * WM, ROWS = (8 / WM) / 2;
   const int kpad = (cin + 15) / 16 * 16;
   const int tiles_c = (w + 255) / 256;
@@ -1129,8 +1129,7 @@ int launch_conv1x1(const float *in, const float *wp, float *out, int tn, int cin
     if (int rc = pconv_raise_lds(kern, smem, raised, "conv2d")) return rc;
   }
   // second wave of every SIMD held back (units of 127 x 64 cycles); PCONV_CONV1X1_STAGGER: experiment knob
-  static const int stagger_env = getenv("PCONV_CONV1X1_STAGGER") ? atoi(getenv("PCONV_CONV1X1_STAGGER")) : -1;
-  const int stagger = stagger_env >= 0 ? stagger_env : 0;
+  const int stagger = opt.stagger >= 0 ? opt.stagger : 0;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, in, wp, out, kpad, h, w, cout, cout_pad,
                      tiles_r, tiles_c, cblocks, passes, stagger, vin, vout, ep);
   return PCONV_OK;
@@ -1141,14 +1140,13 @@ int launch_conv1x1(const float *in, const float *wp, float *out, int tn, int cin
 // strides and bases to be multiples of 2 floats... they only need 4-byte alignment on
 // gfx950 (unaligned dwordx4 access is enabled), so any view qualifies
 // (PCONV_CONV1X1=tiled forces the tiled kernel: A/B measurements and the parity tests)
-inline bool use_resident_1x1(int cin, int cout, int tn, int h, int w) {
-  const char *env = getenv("PCONV_CONV1X1");
-  if (env && env[0] == 't') return false;
+inline bool use_resident_1x1(const ConvOptions &opt, int cin, int cout, int tn, int h, int w) {
+  if (opt.conv1x1 == 1) return false;
   const int kpad = (cin + 15) / 16 * 16;
   const int bm = cout > 96 ? 192 : 96;
   if (!(cin >= 32 && cin % 16 == 0 && cout > 32 && ((size_t)kpad * bm + 2 * bm) * sizeof(float) <= 160 * 1024)) return false;
   if (w < 4) return false;
-  if (env && env[0] == 'r') return true;  // forced (tests, A/B measurements)
+  if (opt.conv1x1 == 2) return true;  // forced (tests, A/B measurements)
   // Measured (MI355X, layers of a 4096x2048 frame).  Against the tiled kernel of round 2's first
   // half this form gained 10-25 % on 96->192, 192->192 and the GDN.  Since the tiled kernel reads
   // its LDS operands with counted waits and requests what its way out reads in batches, it is the
@@ -1333,10 +1331,7 @@ __global__ __launch_bounds__(512, 2) void conv_small_kernel(const float *__restr
 }
 
 // PCONV_CONV_SMALL=0: the 32-cout tile of conv_mfma_kernel keeps the layers with <= 16 couts (A/B, parity test)
-inline bool use_small_cout() {
-  const char *env = getenv("PCONV_CONV_SMALL");  // (read per call: the parity test switches it)
-  return !(env && env[0] == '0');
-}
+inline bool use_small_cout(const ConvOptions &opt) { return opt.small_cout != 0; }
 
 int launch_conv_small(const float *in, const float *wp, float *out, int tn, int cin, int h, int w, int cout, int cout_pad,
                       int ho, int wo, const ConvView &vin, const ConvView &vout, const ConvEpilogue &ep, hipStream_t stream) {
@@ -1360,16 +1355,10 @@ extern "C" int pconv_conv_read_stamps(unsigned long long *out) {
 #endif
 
 // PCONV_CONV1X1_WAYOUT=batch: the 1x1 / GDN layers keep conv_epilogue (A/B measurements)
-inline bool pipe_way_out() {
-  const char *env = getenv("PCONV_CONV1X1_WAYOUT");  // (read per call: the parity test switches it)
-  return !(env && env[0] == 'b');
-}
+inline bool pipe_way_out(const ConvOptions &opt) { return opt.wayout != 2; }
 // default: full tiles leave through the stage memory in 16-byte quads (conv_epilogue_quads);
 // PCONV_CONV1X1_WAYOUT=pipe / batch: the element-wise ways out (A/B measurements, parity tests)
-inline bool quad_way_out() {
-  const char *env = getenv("PCONV_CONV1X1_WAYOUT");
-  return !(env && (env[0] == 'p' || env[0] == 'b'));
-}
+inline bool quad_way_out(const ConvOptions &opt) { return opt.wayout == 0; }
 
 // (cout, cin, k, k) -> [k_pad][cout_pad], k = (ci*KS + kh)*KS + kw, zero padded
 __global__ void pack_weight_kernel(const float *__restrict__ w, float *__restrict__ packed, int cout,
@@ -1383,7 +1372,7 @@ __global__ void pack_weight_kernel(const float *__restrict__ w, float *__restric
 template <int MT, int NT, int WM, int WN, int KS, int S, int KC, bool SQ = false, int WAY = 0>
 int launch_conv(const float *in, const float *wp, float *out, int tn, int cin, int h, int w, int cout,
                 int cout_pad, int ho, int wo, const ConvView &vin, const ConvView &vout, const ConvEpilogue &ep,
-                hipStream_t stream) {
+                const ConvOptions &opt, hipStream_t stream) {
   using C = ConvCfg<MT, NT, WM, WN, KS, S, KC>;
   constexpr int kThreads = C::THREADS;
   constexpr int kTileRows = C::ROWS;
@@ -1401,14 +1390,9 @@ int launch_conv(const float *in, const float *wp, float *out, int tn, int cin, i
     static std::atomic<unsigned long long> raised{0};
     if (int rc = pconv_raise_lds(kern, smem, raised, "conv2d")) return rc;
   }
-  // PCONV_CONV_XCD=1 turns the XCD-grouped order on.  Measured on the analysis transform of a
-  // 4096x2048 frame (same box, alternating runs): HBM reads of the 3x3 192-cout kernel 1.46 GB per
-  // launch instead of 1.82 GB (FETCH_SIZE, profiles/), but 59.3-59.5 ms per frame instead of
-  // 58.4-58.5: the kernel is not bandwidth-bound (0.3 TB/s) and the grouped order starts the
-  // stripes of a tile one after the other on an XCD.  Off by default; the order is kept as the
-  // measured alternative.
-  static const bool xcd_order = getenv("PCONV_CONV_XCD") && atoi(getenv("PCONV_CONV_XCD")) == 1;
-  const int xcd_group = (xcd_order && KS == 3) ? cblocks * tiles_r : 0;  // 1x1 tiles share no rows
+  // PCONV_CONV_XCD=1 turns the XCD-grouped order on: fewer HBM reads, a slower transform ("What runs by
+  // default"); off by default, kept as the measured alternative
+  const int xcd_group = (opt.xcd == 1 && KS == 3) ? cblocks * tiles_r : 0;  // 1x1 tiles share no rows
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), smem, stream, in, wp, out, cin, h, w, cout,
                      cout_pad, ho, wo, tiles_r, tiles_c, cblocks, xcd_group, vin, vout, ep);
   return PCONV_OK;
@@ -1458,6 +1442,7 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
   int cp, rp;
   pconv_conv_packed_size(cout, cin, k, &cp, &rp);
   hipStream_t s = as_stream(stream);
+  const ConvOptions opt = ConvOptions::from_env();  // a stateless entry point reads its options when it is called
   const int oc = d2w ? cout / 4 : cout, oh = d2w ? 2 * ho : ho, ow = d2w ? 2 * wo : wo;  // stored geometry
   const ConvView vin = view_at(views, 0, cin, h, w), vout = view_at(views, 1, oc, oh, ow);
   const ConvEpilogue ep = {bias,  slope, residual, gate, col_limit, npart, act, trim,
@@ -1474,7 +1459,7 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
                     (!residual || ((long long)(32 - 1) * ep.vres.cs + (long long)(ho - 1) * ep.vres.rs + wo) * 4 < (1LL << 32)),
                 "conv2d: output / residual channel stride too large for 32-bit byte offsets inside a round");
   int rc;
-#define ARGS in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, s
+#define ARGS in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, opt, s
   // workgroup tiles (measured on MI355X, 192->192 3x3 at 16 x 64 x 2048: 127 TFLOP/s):
   //   cout > 96 : 192 couts x (2 rows x 64 px), 8 waves of 96 x 32: 135.8 TFLOP/s (4 waves of 96 x 64 px
   //               = 3 x 2 accumulator tiles each: 128.3; 6 such waves on 3 rows x 64 px: 97)
@@ -1487,11 +1472,11 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
     rc = launch_conv<3, 1, 1, 8, KS, S, KC>(ARGS);                 \
   else                                                             \
     rc = launch_conv<1, 1, 1, 4, KS, S, KC>(ARGS);
-  if (k == 3 && stride == 1 && cout <= 16 && !residual && !gate && act != 4 && (!d2w || cout % 4 == 0) && use_small_cout()) {
+  if (k == 3 && stride == 1 && cout <= 16 && !residual && !gate && act != 4 && (!d2w || cout % 4 == 0) && use_small_cout(opt)) {
     rc = launch_conv_small(in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, s);
   } else if (k == 3 && stride == 1) {
     BY_TILE(3, 1, 4)
-  } else if (k == 3 && stride == 2 && cout > 32 && !gate && !d2w && act != 4 && quad_way_out()) {
+  } else if (k == 3 && stride == 2 && cout > 32 && !gate && !d2w && act != 4 && quad_way_out(opt)) {
     // (the stride-2 3x3 layers of the Down blocks: the same workgroup tiles, the same quad way out)
     if (cout > 96)
       rc = residual ? launch_conv<3, 1, 2, 4, 3, 2, 4, false, 4>(ARGS) : launch_conv<3, 1, 2, 4, 3, 2, 4, false, 3>(ARGS);
@@ -1499,27 +1484,27 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
       rc = residual ? launch_conv<3, 1, 1, 8, 3, 2, 4, false, 4>(ARGS) : launch_conv<3, 1, 1, 8, 3, 2, 4, false, 3>(ARGS);
   } else if (k == 3 && stride == 2) {
     BY_TILE(3, 2, 4)
-  } else if (k == 1 && stride == 1 && !gate && !d2w && act != 4 && use_resident_1x1(cin, cout, tn, h, w)) {
+  } else if (k == 1 && stride == 1 && !gate && !d2w && act != 4 && use_resident_1x1(opt, cin, cout, tn, h, w)) {
     if (cout > 96 && residual)
-      rc = launch_conv1x1<2, false, true>(in, packed_w, out, tn, cin, h, w, cout, cp, vin, vout, ep, s);
+      rc = launch_conv1x1<2, false, true>(in, packed_w, out, tn, cin, h, w, cout, cp, vin, vout, ep, opt, s);
     else if (cout > 96)
-      rc = launch_conv1x1<2, false, false>(in, packed_w, out, tn, cin, h, w, cout, cp, vin, vout, ep, s);
+      rc = launch_conv1x1<2, false, false>(in, packed_w, out, tn, cin, h, w, cout, cp, vin, vout, ep, opt, s);
     else if (residual)
-      rc = launch_conv1x1<1, false, true>(in, packed_w, out, tn, cin, h, w, cout, cp, vin, vout, ep, s);
+      rc = launch_conv1x1<1, false, true>(in, packed_w, out, tn, cin, h, w, cout, cp, vin, vout, ep, opt, s);
     else
-      rc = launch_conv1x1<1, false, false>(in, packed_w, out, tn, cin, h, w, cout, cp, vin, vout, ep, s);
-  } else if (k == 1 && stride == 1 && d2w && cout > 32 && quad_way_out()) {
+      rc = launch_conv1x1<1, false, false>(in, packed_w, out, tn, cin, h, w, cout, cp, vin, vout, ep, opt, s);
+  } else if (k == 1 && stride == 1 && d2w && cout > 32 && quad_way_out(opt)) {
     // (d2w implies no gate / residual / sigmoid / trim: checked above)
     if (cout > 96)
       rc = launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, false, 5>(ARGS);
     else
       rc = launch_conv<3, 1, 1, 8, 1, 1, PCONV_KC1, false, 5>(ARGS);
-  } else if (k == 1 && stride == 1 && !gate && !d2w && act != 4 && cout > 32 && quad_way_out()) {
+  } else if (k == 1 && stride == 1 && !gate && !d2w && act != 4 && cout > 32 && quad_way_out(opt)) {
     if (cout > 96)
       rc = residual ? launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, false, 4>(ARGS) : launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, false, 3>(ARGS);
     else
       rc = residual ? launch_conv<3, 1, 1, 8, 1, 1, PCONV_KC1, false, 4>(ARGS) : launch_conv<3, 1, 1, 8, 1, 1, PCONV_KC1, false, 3>(ARGS);
-  } else if (k == 1 && stride == 1 && !gate && !d2w && act != 4 && residual && pipe_way_out()) {
+  } else if (k == 1 && stride == 1 && !gate && !d2w && act != 4 && residual && pipe_way_out(opt)) {
     // (the pipelined way out, see conv_epilogue_pipe; PCONV_CONV1X1_WAYOUT=batch: the generic one)
     if (cout > 96)
       rc = launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, false, 2>(ARGS);
@@ -1529,7 +1514,7 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
       rc = launch_conv<1, 1, 1, 4, 1, 1, PCONV_KC1, false, 2>(ARGS);
   } else if (k == 1 && stride == 1) {
     BY_TILE(1, 1, PCONV_KC1)
-  } else if (cout > 32 && !gate && !d2w && act != 4 && quad_way_out()) {
+  } else if (cout > 32 && !gate && !d2w && act != 4 && quad_way_out(opt)) {
     // (1x1 stride 2, the shortcuts of the Down blocks: same tiles, same quad way out)
     if (cout > 96)
       rc = residual ? launch_conv<3, 1, 2, 4, 1, 2, PCONV_KC1, false, 4>(ARGS) : launch_conv<3, 1, 2, 4, 1, 2, PCONV_KC1, false, 3>(ARGS);
@@ -1559,6 +1544,7 @@ extern "C" int pconv_gdn(const float *in, const float *packed_gamma, const float
   int cp, rp;
   pconv_conv_packed_size(ch, ch, 1, &cp, &rp);
   hipStream_t s = as_stream(stream);
+  const ConvOptions opt = ConvOptions::from_env();
   // views: in, out, residual
   const ConvView vin = view_at(views, 0, ch, h, w), vout = view_at(views, 1, ch, h, w);
   const ConvEpilogue ep = {beta, nullptr, residual, nullptr, col_limit, npart, inverse ? 3 : 2, 1,
@@ -1566,27 +1552,27 @@ extern "C" int pconv_gdn(const float *in, const float *packed_gamma, const float
   PCONV_REQUIRE(view_ok(vin, ch, h, w) && view_ok(vout, ch, h, w) && (!residual || view_ok(ep.vres, ch, h, w)),
                 "gdn: strides overlap");
   int rc;
-  if (use_resident_1x1(ch, ch, tn, h, w) && ch > 96 && residual)
-    rc = launch_conv1x1<2, true, true>(in, packed_gamma, out, tn, ch, h, w, ch, cp, vin, vout, ep, s);
-  else if (use_resident_1x1(ch, ch, tn, h, w) && ch > 96)
-    rc = launch_conv1x1<2, true, false>(in, packed_gamma, out, tn, ch, h, w, ch, cp, vin, vout, ep, s);
-  else if (use_resident_1x1(ch, ch, tn, h, w) && residual)
-    rc = launch_conv1x1<1, true, true>(in, packed_gamma, out, tn, ch, h, w, ch, cp, vin, vout, ep, s);
-  else if (use_resident_1x1(ch, ch, tn, h, w))
-    rc = launch_conv1x1<1, true, false>(in, packed_gamma, out, tn, ch, h, w, ch, cp, vin, vout, ep, s);
-  else if (quad_way_out() && ch > 96)
-    rc = residual ? launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, true, 4>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, s)
-                  : launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, true, 3>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, s);
-  else if (pipe_way_out() && ch > 96 && residual)
-    rc = launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, true, 2>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, s);
-  else if (pipe_way_out() && ch > 96)
-    rc = launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, true, 1>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, s);
+  if (use_resident_1x1(opt, ch, ch, tn, h, w) && ch > 96 && residual)
+    rc = launch_conv1x1<2, true, true>(in, packed_gamma, out, tn, ch, h, w, ch, cp, vin, vout, ep, opt, s);
+  else if (use_resident_1x1(opt, ch, ch, tn, h, w) && ch > 96)
+    rc = launch_conv1x1<2, true, false>(in, packed_gamma, out, tn, ch, h, w, ch, cp, vin, vout, ep, opt, s);
+  else if (use_resident_1x1(opt, ch, ch, tn, h, w) && residual)
+    rc = launch_conv1x1<1, true, true>(in, packed_gamma, out, tn, ch, h, w, ch, cp, vin, vout, ep, opt, s);
+  else if (use_resident_1x1(opt, ch, ch, tn, h, w))
+    rc = launch_conv1x1<1, true, false>(in, packed_gamma, out, tn, ch, h, w, ch, cp, vin, vout, ep, opt, s);
+  else if (quad_way_out(opt) && ch > 96)
+    rc = residual ? launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, true, 4>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, opt, s)
+                  : launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, true, 3>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, opt, s);
+  else if (pipe_way_out(opt) && ch > 96 && residual)
+    rc = launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, true, 2>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, opt, s);
+  else if (pipe_way_out(opt) && ch > 96)
+    rc = launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, true, 1>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, opt, s);
   else if (ch > 96)
-    rc = launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, true>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, s);
+    rc = launch_conv<3, 1, 2, 4, 1, 1, PCONV_KC1, true>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, opt, s);
   else if (ch > 32)
-    rc = launch_conv<3, 1, 1, 8, 1, 1, PCONV_KC1, true>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, s);
+    rc = launch_conv<3, 1, 1, 8, 1, 1, PCONV_KC1, true>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, opt, s);
   else
-    rc = launch_conv<1, 1, 1, 4, 1, 1, PCONV_KC1, true>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, s);
+    rc = launch_conv<1, 1, 1, 4, 1, 1, PCONV_KC1, true>(in, packed_gamma, out, tn, ch, h, w, ch, cp, h, w, vin, vout, ep, opt, s);
   if (rc != PCONV_OK) return rc;
   PCONV_LAUNCH_CHECK("gdn");
   return PCONV_OK;

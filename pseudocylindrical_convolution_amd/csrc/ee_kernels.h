@@ -15,6 +15,7 @@
 // a plain 5 x 5 x C block of the padded tile (no edge path in the consumers).
 #pragma once
 #include <stdint.h>
+#include "options.h"  // EeLaunchOptions: the launch shapes, as the engine read them when it was created
 
 // One record per schedule entry (wavefront position), built once on the host: what a
 // step kernel needs to find a position's window, output and halos without integer
@@ -73,7 +74,8 @@ int ee_pack_weight(const float *w, float *packed, int nset, int cout, int cin, i
 // (layer 0), otherwise 3*nimg.  Output group of plane p is psum - p.
 int ee_conv(const EeGeom *g, const float *x, int shared_input, const float *packed_w, const float *bias,
             const float *slope, const float *residual, float *y, int cin, int cout, int constrain,
-            int pad_out, int first_plane, int nplane, int longest_plane, int psum, void *stream);
+            int pad_out, int first_plane, int nplane, int longest_plane, int psum, const EeLaunchOptions &opt,
+            void *stream);
 // the same layer for ALL (plane, group) pairs at once (encoder: every symbol is
 // known, the causal masks make each output equal to the step-by-step one)
 int ee_conv_bulk(const EeGeom *g, const float *x, int shared_input, const float *packed_w, const float *bias,
@@ -85,14 +87,14 @@ int ee_conv_bulk(const EeGeom *g, const float *x, int shared_input, const float 
 // ee_mfma_block_shape: 1 and the block shape (nt rp_n rows x 16 ct_n columns per workgroup of
 // `waves` waves, nt = 1 or 2 rows per wave) when the kernel takes the layer, else 0.  blocks: device int4 records (tile, first row, first
 // column, 0) covering every live position; wfrag: ee_pack_weight_mfma's fragments (ee_mfma_packed_floats floats).
-int ee_mfma_block_shape(int h, int cin, int *rp_n, int *ct_n, int *waves, int *nt);
+int ee_mfma_block_shape(int h, int cin, const EeLaunchOptions &opt, int *rp_n, int *ct_n, int *waves, int *nt);
 int ee_mfma_packed_floats(int nset, int cin);
 int ee_pack_weight_mfma(const float *w, float *packed, int nset, int cout, int cin, int ngroup, int constrain,
                         void *stream);
 int ee_conv_bulk_mfma(const EeGeom *g, const void *blocks, int nblocks, int rp_n, int ct_n, int waves, int nt, const float *x,
                       int shared_input, const float *wfrag, const float *bias, const float *slope,
                       const float *residual, float *y, int cin, int cout, int pad_out, int s_lo, int s_hi,
-                      void *stream);
+                      const EeLaunchOptions &opt, void *stream);
 // the same 42 -> 42 layer, four lane classes per instruction (v_mfma_f32_16x16x1_4b_f32), nt = 1 block shapes only;
 // also the wide nets' hidden layers (84 -> 84 at 28 groups, 144 -> 144 at 48 groups): `waves` = rp_n * ct_n position
 // tiles x the output slices (2 / 3), ee_mfma_block_shape(h, 84 | 144, ...) gives the shape
@@ -122,7 +124,7 @@ int ee_rate_bulk(const EeGeom *g, const float *y_last, const float *symbols, dou
 // ee_tables(packed) writes them.  The codec's shape only: 14 groups, 8 symbols, total 65536.
 int ee_conv_tables(const EeGeom *g, const float *x, const float *packed_w, const float *bias, int32_t *table, int cin,
                    int first_plane, int nplane, int longest_plane, int psum, int lo, int len, float gbias, float total,
-                   float beta, int32_t *counter, int32_t *flags, int publish, void *stream);
+                   float beta, int32_t *counter, int32_t *flags, int publish, const EeLaunchOptions &opt, void *stream);
 
 // halos and wrap columns of a whole buffer of `nrep` images with C channels from
 // its interior (bulk mode, after a layer has been evaluated everywhere)

@@ -41,6 +41,7 @@
 #include "../../include/pconv_coder.h"
 #include "common.h"
 #include "ee_kernels.h"
+#include "options.h"
 
 namespace {
 
@@ -87,7 +88,7 @@ static int affinity_cpus() {
 // threads can really run.  cgroup v2 `cpu.max` ("quota period" | "max period"), then v1
 // cfs_quota_us / cfs_period_us; PCONV_CGROUP_CPU_MAX names another cpu.max-format file (tests).
 static int cgroup_cpu_quota() {
-  const char *override_path = getenv("PCONV_CGROUP_CPU_MAX");
+  const char *override_path = option_cgroup_cpu_max();
   if (FILE *f = fopen(override_path ? override_path : "/sys/fs/cgroup/cpu.max", "r")) {
     char quota[64] = {0};
     long long period = 0;
@@ -134,14 +135,15 @@ static int allowed_cpus() {
 // spinning: the same speed at half the CPU time (8 ranks x 2 spinning cores would exhaust a 16-CPU quota).
 static bool host_constrained(int call_threads) { return call_threads + 1 > allowed_cpus(); }
 
-// The host side of a call of `nimg` frames, decided in ONE place (pconv_ee_host_plan exports it for the tests):
+// The host side of a call of `nimg` frames, decided in ONE place (pconv_ee_host_plan exports it for the tests);
+// `o`: the overrides PCONV_ENGINE_GROUPS / _WORKERS / _CHAIN / _BLOCKING_SYNC
 struct HostPlan {
   int groups;         // lock-step groups = decoder chains = driver threads
   int group_threads;  // threads that arithmetic-decode a group's frames (the driver included); 0 = one per frame
   int queued_chain;   // 1: the queued-ahead chain, 0: the host-driven one
   int blocking_sync;  // 1: the runtime's waits sleep instead of spinning
 };
-static HostPlan host_plan(int nimg) {
+static HostPlan host_plan(int nimg, const EngineOptions &o) {
   HostPlan p;
   const bool constrained = host_constrained(nimg);
   // two groups up to five frames, four from six on (r3, profiles/round3_decode_groups.txt); eight make the chains
@@ -149,18 +151,18 @@ static HostPlan host_plan(int nimg) {
   // CPUs when the frames do not fit anyway
   p.groups = nimg >= 6 ? 4 : (nimg >= 2 ? 2 : 1);
   if (constrained) p.groups = std::min(p.groups, std::max(1, allowed_cpus()));
-  if (const char *env = getenv("PCONV_ENGINE_GROUPS")) p.groups = atoi(env);
+  if (o.groups != kOptionAuto) p.groups = o.groups;
   p.groups = std::max(1, std::min(p.groups, nimg));
   p.group_threads = constrained ? 1 : 0;
-  if (const char *env = getenv("PCONV_ENGINE_WORKERS")) p.group_threads = std::max(1, atoi(env));
+  if (o.workers != kOptionAuto) p.group_threads = std::max(1, o.workers);
   const int largest = (nimg + p.groups - 1) / p.groups;
   // queued / host-driven, measured (MI355X, 4096x2048, two groups): 94 / 103 ms for one frame, 110 / 113 for two,
   // 141 / 137 for four, 212 / 197 for eight; the queued chain keeps two host threads per group busy (one queues,
   // one polls): with fewer CPUs than frames it loses badly (8 frames on 2 CPUs: 1 956 ms against 220)
   p.queued_chain = largest < 4 && nimg < 6 && !constrained;
-  if (const char *env = getenv("PCONV_ENGINE_CHAIN")) p.queued_chain = env[0] != 'h';
+  if (o.chain != kOptionAuto) p.queued_chain = o.chain;
   p.blocking_sync = constrained;
-  if (const char *env = getenv("PCONV_ENGINE_BLOCKING_SYNC")) p.blocking_sync = atoi(env) != 0;
+  if (o.blocking_sync != kOptionAuto) p.blocking_sync = o.blocking_sync;
   return p;
 }
 
@@ -169,10 +171,9 @@ static HostPlan host_plan(int nimg) {
 // part of a step (2 ms covers it) only when every one of them AND the caller's own thread have a
 // CPU of this rank's share; otherwise about the host part of a step, so that the GPU waits do not
 // keep frames - groups cores busy that other ranks (or other threads of this one) need.
-static int step_pool_spin_us(int call_threads) {
-  int spin = call_threads + 1 <= allowed_cpus() ? 2000 : 60;
-  if (const char *env = getenv("PCONV_ENGINE_SPIN_US")) spin = atoi(env);
-  return spin;
+static int step_pool_spin_us(int call_threads, const EngineOptions &o) {
+  if (o.spin_us != kOptionAuto) return o.spin_us;
+  return call_threads + 1 <= allowed_cpus() ? 2000 : 60;
 }
 
 // Persistent helpers for the per-step arithmetic decoding: job(i) runs for
@@ -190,8 +191,8 @@ static int step_pool_spin_us(int call_threads) {
 class StepPool {
  public:
   // njobs jobs per run() on `threads` threads (the caller included): thread k takes jobs k, k + threads, ...
-  StepPool(int njobs, int threads, int call_threads) : njobs_(njobs), n_(std::max(1, std::min(threads, njobs))) {
-    spin_us_ = step_pool_spin_us(call_threads);
+  StepPool(int njobs, int threads, int call_threads, int spin_us)
+      : njobs_(njobs), n_(std::max(1, std::min(threads, njobs))), spin_us_(spin_us) {
     // more runnable threads than CPUs: a polling thread gives its time slice away instead of keeping the
     // thread it waits for off the core
     polite_ = call_threads + 1 > allowed_cpus();
@@ -249,8 +250,7 @@ class StepPool {
       done_.fetch_add(1, std::memory_order_release);
     }
   }
-  int njobs_, n_;
-  int spin_us_ = 60;
+  int njobs_, n_, spin_us_;
   bool polite_ = false;
   std::vector<std::thread> workers_;
   const std::function<void(int)> *job_ = nullptr;
@@ -312,9 +312,8 @@ struct pconv_entropy_engine {
   uint32_t *tap_in_d = nullptr, *tap_hid_d = nullptr;
   float *vh_wgt = nullptr;
   int32_t *pos_plane_d = nullptr;
+  EngineOptions opt;              // read ONCE (pconv_ee_create): no call of this engine looks at the environment
   HostPlan plan;                  // the host side of this engine's calls, decided ONCE (pconv_ee_create)
-  bool fuse_tables = false;       // decoder: last layer + table kernel as one launch (PCONV_EE_FUSE_TABLES, at creation)
-  bool stepwise_encoder = false;  // debugging aid: encode step by step like the decoder
   int encode_ranges = -1;         // step ranges of a call's last group (pconv_ee_set_encode_ranges); -1: the default
   float *lw[kLayers] = {nullptr};  // engine-owned packed weights
   // matrix-core form of the encoder's hidden layers (entropy_mfma.hip): weights as MFMA fragments, the list of
@@ -376,11 +375,9 @@ struct pconv_entropy_engine {
     // PCONV_ENGINE_CU_MASK=first:count -- the group's stream on `count` compute units from bit `first` of the CU
     // mask on (consecutive bits alternate over the XCDs and their shader engines): a partition of the chip for
     // the chains, so that they can run beside another stream's transforms (which hold whole CUs)
-    int cu_first = 0, cu_count = 0;
-    if (const char *m = getenv("PCONV_ENGINE_CU_MASK")) (void)sscanf(m, "%d:%d", &cu_first, &cu_count);
-    if (cu_count > 0) {
+    if (opt.cu_count > 0) {
       uint32_t mask[8] = {0};
-      for (int b = cu_first; b < cu_first + cu_count && b < 256; b++)
+      for (int b = opt.cu_first; b < opt.cu_first + opt.cu_count && b < 256; b++)
         if (b >= 0) mask[b >> 5] |= 1u << (b & 31);
       HIP_TRY(hipExtStreamCreateWithCUMask(&g.stream, 8, mask));
     } else {
@@ -419,11 +416,7 @@ struct pconv_entropy_engine {
   int init(const float *tile_weight) {
     rows = h * npart;
     nsteps = rows + w + ngroup - 2;
-    stepwise_encoder = getenv("PCONV_ENGINE_STEPWISE_ENCODER") != nullptr;
-    {
-      const char *env = getenv("PCONV_ENGINE_ROWS");
-      packed = nlevels == 8 && total == 65536.f && !stepwise_encoder && !(env && env[0] == 'i');
-    }
+    packed = nlevels == 8 && total == 65536.f && !opt.stepwise_encoder && !opt.rows_int32;
     widths.assign(npart, 0);
     PC_TRY(pconv_host_tile_widths(tile_weight, npart, rows, w, widths.data()));
     std::vector<int32_t> order((size_t)rows * w);
@@ -547,7 +540,6 @@ struct pconv_entropy_engine {
     for (int l = 0; l < kLayers; l++) HIP_TRY(hipMalloc(&lw[l], ee_packed_floats(3, 3 * ngroup, layer_cin(l)) * 4));
     {
       // PCONV_EE_BULK=valu keeps the vector kernel for every layer of the encoder (A/B; identical streams)
-      const char *env = getenv("PCONV_EE_BULK");
       int rp = 0, ct = 0, wv = 0, nt = 0;
       // even widths only: the patch goes to LDS in 16-byte pieces and a padded row of an odd width ends on half a
       // piece (a pixel is 14 / 42 floats) -- the codec's symbol planes are Dtow(2) outputs, always even; direct
@@ -555,8 +547,8 @@ struct pconv_entropy_engine {
       // form for their hidden layers only (the input layer stays on the vector kernel; the 14-group knobs below do
       // not apply to them)
       const bool wide = ngroup == 28 || ngroup == 48;
-      if (!(env && env[0] == 'v') && (ngroup == 14 || wide) && (w & 1) == 0 &&
-          ee_mfma_block_shape(h, 3 * ngroup, &rp, &ct, &wv, &nt)) {
+      if (!opt.bulk_valu && (ngroup == 14 || wide) && (w & 1) == 0 &&
+          ee_mfma_block_shape(h, 3 * ngroup, opt.launch, &rp, &ct, &wv, &nt)) {
         std::vector<int32_t> blk;
         for (int t = 0; t < npart; t++)
           for (int r0 = 0; r0 < h; r0 += nt * rp)
@@ -570,13 +562,10 @@ struct pconv_entropy_engine {
           HIP_TRY(hipMemcpy(mfma_blocks_d, blk.data(), blk.size() * 4, hipMemcpyHostToDevice));
           // (the input layer -- 14 channels, one context for the three sets -- only in the one-row direct form;
           // PCONV_EE_BULK0=valu keeps the vector kernel for it)
-          const char *env0 = getenv("PCONV_EE_BULK0");
-          const char *wsrc = getenv("PCONV_EE_MFMA_WSRC");
-          const bool layer0 = !wide && nt == 1 && !(wsrc && wsrc[0] == 'r') && !(env0 && env0[0] == 'v');
+          const bool layer0 = !wide && nt == 1 && !opt.launch.mfma_ring && !opt.bulk0_valu;
           // the hidden layers: four lane classes per instruction (one row per wave, weights fetched directly) unless
           // PCONV_EE_MFMA_FORM=16x4 asks for the 16 x 16 x 4 form (round-5 A/B: profiles/round5_entropy_mfma_variants.txt)
-          const char *form = getenv("PCONV_EE_MFMA_FORM");
-          const bool four = wide || (nt == 1 && !(wsrc && wsrc[0] == 'r') && !(form && form[0] == '1'));
+          const bool four = wide || (nt == 1 && !opt.launch.mfma_ring && !opt.mfma_16x4);
           for (int l = layer0 ? 0 : 1; l < kLayers; l++)
             if (l == 0 || !four) HIP_TRY(hipMalloc(&lwf[l], (size_t)ee_mfma_packed_floats(3, layer_cin(l)) * 4));
           if (four)
@@ -664,8 +653,7 @@ struct pconv_entropy_engine {
   int clear(Group &g) {
     HIP_TRY(hipMemsetAsync(g.counter_d, 0, 64, g.stream));  // table-kernel block counter, scatter relay word
     // PCONV_ENGINE_CLEAR_EVERY_CALL=1: the pre-r4 behaviour (every call starts from zeroed buffers)
-    static const bool every_call = getenv("PCONV_ENGINE_CLEAR_EVERY_CALL") && atoi(getenv("PCONV_ENGINE_CLEAR_EVERY_CALL"));
-    if (g.zeroed && !every_call) return PCONV_OK;
+    if (g.zeroed && !opt.clear_every_call) return PCONV_OK;
     HIP_TRY(hipMemsetAsync(g.ctx, 0, ctx_elems(g.nimg) * 4, g.stream));
     for (int l = 0; l < kLayers; l++) HIP_TRY(hipMemsetAsync(g.act[l], 0, act_elems(l, g.nimg) * 4, g.stream));
     g.zeroed = true;
@@ -682,7 +670,7 @@ struct pconv_entropy_engine {
       // second conv of a residual block: += block input, folded into the epilogue
       const float *res = (l >= 2 && l <= 10 && (l % 2) == 0) ? g.act[l - 2] : nullptr;
       PC_TRY(ee_conv(&g.geom, in, l == 0, lw[l], lb[l], la[l], res, g.act[l], layer_cin(l), hid, l == 0 ? 5 : 6,
-                     l == kLayers - 1 ? 0 : kPad, cur.first, cur.nplane, longest_plane, s, g.stream));
+                     l == kLayers - 1 ? 0 : kPad, cur.first, cur.nplane, longest_plane, s, opt.launch, g.stream));
     }
     return PCONV_OK;
   }
@@ -749,7 +737,7 @@ struct pconv_entropy_engine {
       else if (mfma_waves && lwf[l])
         PC_TRY(ee_conv_bulk_mfma(&g.geom, blist, nblist, mfma_rp, mfma_ct, mfma_waves, mfma_nt, in, l == 0, lwf[l], lb[l],
                                  la[l], res, g.act[l], layer_cin(l), hid, l == kLayers - 1 ? 0 : kPad, s_lo, s_hi,
-                                 g.stream));
+                                 opt.launch, g.stream));
       else
         PC_TRY(ee_conv_bulk(&g.geom, in, l == 0, lw[l], lb[l], la[l], res, g.act[l], layer_cin(l), hid,
                             l == 0 ? 5 : 6, l == kLayers - 1 ? 0 : kPad, first, count, s_lo, s_hi, g.stream));
@@ -837,14 +825,13 @@ struct pconv_entropy_engine {
     if (s > 0)
       PC_TRY(ee_scatter(&g.geom, g.packed_h, g.ctx, prev.lo, prev.len, s - 1, -bias, flags, g.counter_d + 8, s, g.stream));
     if (cur.len > 0) {
-      // PCONV_EE_FUSE_TABLES=1 (read when the engine is created): the last layer and the table kernel as one launch
-      // (ee_conv_tables; the codec's shape with packed rows only).  Identical rows -- and 2-8 % SLOWER decodes
-      // (profiles/round6_fused_tables.txt): off by default
-      if (fuse_tables && packed && ngroup == 14 && nlevels == 8 && total == 65536.f) {
+      // PCONV_EE_FUSE_TABLES=1: the last layer and the table kernel as one launch (ee_conv_tables; the codec's
+      // shape with packed rows only).  Identical rows
+      if (opt.fuse_tables && packed && ngroup == 14 && nlevels == 8 && total == 65536.f) {
         PC_TRY(network_step(g, s, cur, kLayers - 1));
         PC_TRY(ee_conv_tables(&g.geom, g.act[kLayers - 2], lw[kLayers - 1], lb[kLayers - 1], g.tables_h,
                               layer_cin(kLayers - 1), cur.first, cur.nplane, longest_plane, s, cur.lo, cur.len, bias, total,
-                              beta, g.counter_d, flags, s + 1, g.stream));
+                              beta, g.counter_d, flags, s + 1, opt.launch, g.stream));
       } else {
         PC_TRY(network_step(g, s, cur));
         PC_TRY(ee_tables(&g.geom, g.act[kLayers - 1], nullptr, g.tables_h, nullptr, cur.lo, cur.len, s, nlevels, bias,
@@ -931,6 +918,8 @@ struct pconv_entropy_engine {
   }
 };
 
+const EngineOptions &engine_options(const pconv_entropy_engine *e) { return e->opt; }
+
 extern "C" {
 
 pconv_entropy_engine *pconv_ee_create(int npart, int ngroup, int h, int w, int nimg, const float *tile_weight,
@@ -940,11 +929,12 @@ pconv_entropy_engine *pconv_ee_create(int npart, int ngroup, int h, int w, int n
     return nullptr;
   }
   pconv_entropy_engine *e = new pconv_entropy_engine();
-  // The host side of every call of this engine -- groups, threads per group, chain, sleeping or spinning waits --
-  // is decided here, once, from the rank's share of the host as it is NOW; decode reuses it (a changed affinity
-  // mask or LOCAL_WORLD_SIZE between create and decode cannot disagree with the groups that exist).
-  e->plan = host_plan(nimg);
-  if (const char *env = getenv("PCONV_EE_FUSE_TABLES")) e->fuse_tables = atoi(env) != 0;
+  // The options and the host side of every call of this engine -- groups, threads per group, chain, sleeping or
+  // spinning waits -- are decided here, once, from the environment and the rank's share of the host as they are
+  // NOW; every call reuses them (a changed variable, affinity mask or LOCAL_WORLD_SIZE between create and decode
+  // cannot disagree with the groups and buffers that exist).
+  e->opt = EngineOptions::from_env();
+  e->plan = host_plan(nimg, e->opt);
   e->npart = npart; e->ngroup = ngroup; e->h = h; e->w = w; e->nimg = nimg;
   e->bias = bias; e->nlevels = nlevels; e->total = total; e->beta = beta;
   if (e->init(tile_weight) != PCONV_OK) {
@@ -1020,10 +1010,10 @@ int pconv_ee_set_layer(pconv_entropy_engine *e, int layer, const float *weight, 
 
 // host-side sizing of the engine, exported so that it can be checked without a GPU (tests/test_host_share.py)
 int pconv_ee_host_cpus(void) { return allowed_cpus(); }
-int pconv_ee_spin_us(int call_threads) { return step_pool_spin_us(call_threads); }
+int pconv_ee_spin_us(int call_threads) { return step_pool_spin_us(call_threads, EngineOptions::from_env()); }
 int pconv_ee_host_plan(int nimg, int *groups, int *group_threads, int *queued_chain, int *blocking_sync) {
   PCONV_REQUIRE(nimg > 0, "ee_host_plan: bad argument");
-  const HostPlan p = host_plan(nimg);
+  const HostPlan p = host_plan(nimg, EngineOptions::from_env());
   if (groups) *groups = p.groups;
   if (group_threads) *group_threads = p.group_threads;
   if (queued_chain) *queued_chain = p.queued_chain;
@@ -1075,14 +1065,12 @@ int pconv_ee_encode_begin(pconv_entropy_engine *e, const float *symbols, void *s
   // first group's tables are on the host half-way and its frames are coded on the CPU while
   // the GPU works on the second group and on what the caller queues after this call.
   // PCONV_ENGINE_ENCODE_RANGES: step ranges of the call's last group (default 4; 1 = as one piece)
-  const int last_ranges = e->encode_ranges > 0 ? e->encode_ranges
-                          : (getenv("PCONV_ENGINE_ENCODE_RANGES") ? atoi(getenv("PCONV_ENGINE_ENCODE_RANGES")) : 4);
+  const int last_ranges = e->encode_ranges > 0 ? e->encode_ranges : e->opt.encode_ranges;
   // A call whose coding nothing hides (ranges asked for) takes ALL its groups through the ranges together, range by
   // range: every frame's coder starts after the first range of its group, and the last frame's GPU work no longer
   // ends a whole frame's coding before its coder does (r5: the tail behind an 8-frame encode 9 -> 3 ms).
   // PCONV_ENGINE_ENCODE_INTERLEAVE=0: group by group, ranges on the last group only (the round-4 order).
-  const bool interleave = last_ranges > 1 && e->groups.size() > 1 && !e->stepwise_encoder &&
-                          !(getenv("PCONV_ENGINE_ENCODE_INTERLEAVE") && atoi(getenv("PCONV_ENGINE_ENCODE_INTERLEAVE")) == 0);
+  const bool interleave = last_ranges > 1 && e->groups.size() > 1 && !e->opt.stepwise_encoder && e->opt.encode_interleave;
   {
     std::vector<hipStream_t> own;
     for (Group &g : e->groups) {
@@ -1091,7 +1079,7 @@ int pconv_ee_encode_begin(pconv_entropy_engine *e, const float *symbols, void *s
     }
     int rc = PCONV_OK;
     const size_t ng = e->groups.size();
-    if (e->stepwise_encoder) {
+    if (e->opt.stepwise_encoder) {
       for (size_t k = 0; k < ng && rc >= 0; k++) {
         e->set_encode_ranges(e->groups[k], 1);
         rc = e->encode_prologue(e->groups[k], symbols);
@@ -1210,7 +1198,7 @@ int pconv_ee_encode_end(pconv_entropy_engine *e, void *stream) {
   PCONV_REQUIRE(e, "ee_encode: bad argument");
   PCONV_REQUIRE(e->enc_thread.joinable(), "ee_encode_end: no encode in flight");
   e->enc_thread.join();
-  if (getenv("PCONV_ENGINE_TIMING"))
+  if (e->opt.timing)
     fprintf(stderr, "[pconv engine] encode %d frame(s) in %d group(s): %.1f ms, of which GPU wait %.1f ms, coder %.1f ms\n",
             e->nimg, (int)e->groups.size(),
             std::chrono::duration<double>(std::chrono::steady_clock::now() - e->enc_begin).count() * 1e3,
@@ -1250,8 +1238,7 @@ int pconv_ee_rate(pconv_entropy_engine *e, const float *symbols, double *bits_de
   PCONV_REQUIRE(e->rate_capable(), "ee_rate: code lengths are defined for rows of 8 symbols, total 65536");
   for (int l = 0; l < kLayers; l++) PCONV_REQUIRE(e->bound[l], "ee_rate: layer %d has no weights", l);
   hipStream_t caller = as_stream(stream);
-  const char *env = getenv("PCONV_ENGINE_RATE_STREAMS");
-  const bool own_streams = env && env[0] == 'g';
+  const bool own_streams = e->opt.rate_group_streams != 0;
   if (own_streams) PC_TRY(e->fork(caller));
   int rc = PCONV_OK;
   for (size_t k = 0; k < e->groups.size() && rc >= 0; k++) {
@@ -1293,7 +1280,7 @@ int pconv_ee_decode(pconv_entropy_engine *e, const uint8_t *const *streams, cons
       return PCONV_EINVAL;
     }
   // PCONV_ENGINE_TIMING=1: where the decoder's wall time goes, printed once per call
-  const bool timing = getenv("PCONV_ENGINE_TIMING") != nullptr;
+  const bool timing = e->opt.timing != 0;
   const auto t_begin = std::chrono::steady_clock::now();
   PC_TRY(e->fork(caller));
   // A group's step is a chain -- scatter, 12 layers, tables on the GPU, then arithmetic
@@ -1363,7 +1350,7 @@ int pconv_ee_decode(pconv_entropy_engine *e, const uint8_t *const *streams, cons
     // one thread per frame of the call, unless the frames do not have CPUs of their own (host_plan: then the
     // driver decodes its frames one after the other) or PCONV_ENGINE_WORKERS says otherwise
     const int cap = plan.group_threads > 0 ? plan.group_threads : g.nimg;
-    StepPool pool(g.nimg, cap, e->nimg);
+    StepPool pool(g.nimg, cap, e->nimg, step_pool_spin_us(e->nimg, e->opt));
     g.pool = &pool;
     int rc = PCONV_OK;
     if (chained) {

@@ -1266,35 +1266,22 @@ int ee_pack_weight(const float *w, float *packed, int nset, int cout, int cin, i
 
 int ee_conv(const EeGeom *g, const float *x, int shared_input, const float *packed_w, const float *bias,
             const float *slope, const float *residual, float *y, int cin, int cout, int constrain, int pad_out,
-            int first_plane, int nplane, int longest_plane, int psum, void *stream) {
+            int first_plane, int nplane, int longest_plane, int psum, const EeLaunchOptions &opt, void *stream) {
   if (nplane <= 0 || longest_plane <= 0) return PCONV_OK;
   PCONV_REQUIRE(cout == 3 * g->ngroup, "ee_conv: cout must be 3 per group");
   PCONV_REQUIRE(cin == g->ngroup || cin == 3 * g->ngroup, "ee_conv: cin must be 1 or 3 per group");
   (void)constrain;  // the causal mask is part of the packed slab
-  // workgroups per (set, plane, image): enough to fill the chip, few enough that a staged
-  // slab serves several positions.  PCONV_EE_BLOCK (threads per workgroup: 256 / 512 / 1024)
-  // and PCONV_EE_PPW (positions a wave walks) are tuning knobs.
-  static const int block = getenv("PCONV_EE_BLOCK") ? atoi(getenv("PCONV_EE_BLOCK")) : kConvBlock;
-  // measured (MI355X, 4096x2048, decode of 1 / 2 / 4 / 8 frames in two groups, contiguous shares, two
-  // positions per loop body): 2 positions per wave 93 / 109 / - / - ms, 4: 96 / 110 / 150 / 222,
-  // 8: 116 / 126 / 140 / 211, 16: - / 137 / 164 / 213; 512- and 1024-thread workgroups are slower
-  // at every batch size
-  static const int ppw_env = getenv("PCONV_EE_PPW") ? atoi(getenv("PCONV_EE_PPW")) : 0;
-  const int ppw = ppw_env > 0 ? ppw_env : (g->nimg <= 1 ? 2 : 2 * kPosPerWave);
-  // PCONV_EE_JOINT: positions a wave takes through the loop body together (1 or 2)
-  static const int joint = getenv("PCONV_EE_JOINT") ? atoi(getenv("PCONV_EE_JOINT")) : 2;
-  // PCONV_EE_CONTIG: contiguous (1) or interleaved (0) shares of a plane per workgroup
-  // (2 = contiguous shares AND the positions of one loop body neighbours on the anti-diagonal: r6)
-  static const int contig = getenv("PCONV_EE_CONTIG") ? atoi(getenv("PCONV_EE_CONTIG")) : 1;
+  // workgroups per (set, plane, image): enough to fill the chip, few enough that a staged slab serves several
+  // positions.  opt (options.h; the measurements: DESIGN.md, "What runs by default"): block = threads per workgroup,
+  // ppw = positions a wave walks, joint = positions per loop body, contig = shares of a plane per workgroup,
+  // xcd = the 1-D XCD-major workgroup order (see the kernel) instead of the 3-D grid
+  static_assert(EeLaunchOptions{}.block == kConvBlock, "the default workgroup is the step kernel's");
+  const int block = opt.block, joint = opt.joint, contig = opt.contig, xcd = opt.xcd;
+  const int ppw = opt.ppw > 0 ? opt.ppw : (g->nimg <= 1 ? 2 : 2 * kPosPerWave);
   const int waves = block / kWave;
   int split = (longest_plane + waves * ppw - 1) / (waves * ppw);
   if (split < 1) split = 1;
   const uint32_t *tap = cin == g->ngroup ? g->tap_in : g->tap_hid;
-  // PCONV_EE_XCD: 1 = the 1-D XCD-major workgroup order (see the kernel), 0 (default) = the 3-D grid of rounds 3-5.
-  // Measured (r6, profiles/round6_step_kernel_pmc.txt): XCD-major + neighbour pairs cut the L1 -> L2 requests by a
-  // third and the fabric reads by a sixth, and the decode takes the same time at 8 frames (176-183 vs 176-180 ms) and
-  // LONGER at one frame (95-97 vs 91 ms): the launch is a chain of dependent round trips, not a bandwidth problem.
-  static const int xcd = getenv("PCONV_EE_XCD") ? atoi(getenv("PCONV_EE_XCD")) : 0;
   const long long nb = (long long)split * nplane * 3 * g->nimg;
   PCONV_REQUIRE(3 * g->nimg <= 65535 && nplane <= 65535 && nb < (1LL << 30), "ee_conv: too many images for one launch");
   const dim3 grid = xcd ? dim3((unsigned)(8 * ((nb + 7) / 8)), 1, 1) : dim3((unsigned)split, (unsigned)nplane, (unsigned)(3 * g->nimg));
@@ -1341,11 +1328,11 @@ int ee_conv(const EeGeom *g, const float *x, int shared_input, const float *pack
 
 int ee_conv_tables(const EeGeom *g, const float *x, const float *packed_w, const float *bias, int32_t *table, int cin,
                    int first_plane, int nplane, int longest_plane, int psum, int lo, int len, float gbias, float total,
-                   float beta, int32_t *counter, int32_t *flags, int publish, void *stream) {
+                   float beta, int32_t *counter, int32_t *flags, int publish, const EeLaunchOptions &opt, void *stream) {
   if (nplane <= 0 || longest_plane <= 0 || len <= 0) return PCONV_OK;
   PCONV_REQUIRE(cin == 42 && g->ngroup == 14 && total == 65536.f, "ee_conv_tables: the codec's shape only (14 groups, 8 x 65536 rows)");
-  // positions a wave takes: two per loop body; PCONV_EE_FUSE_PPW positions per wave (default 4: two bodies)
-  static const int ppw = getenv("PCONV_EE_FUSE_PPW") ? atoi(getenv("PCONV_EE_FUSE_PPW")) : 4;
+  // positions a wave takes: two per loop body; opt.fuse_ppw positions per wave (default 4: two bodies)
+  const int ppw = opt.fuse_ppw;
   const int waves = kConvBlock / kWave;
   int split = (longest_plane + waves * ppw - 1) / (waves * ppw);
   if (split < 1) split = 1;

@@ -952,13 +952,10 @@ int ee_conv_bulk_mfma4(const EeGeom *g, const void *blocks, int nblocks, int rp_
   return PCONV_OK;
 }
 
-// PCONV_EE_MFMA_WSRC=ring: the LDS-ring form of the one-row kernel (default: direct fetch)
-static bool mfma_direct(int nt) {
-  const bool ring = getenv("PCONV_EE_MFMA_WSRC") && getenv("PCONV_EE_MFMA_WSRC")[0] == 'r';  // (per call: tests switch it)
-  return nt == 1 && !ring;
-}
+// opt.mfma_ring (PCONV_EE_MFMA_WSRC=ring): the LDS-ring form of the one-row kernel (default: direct fetch)
+static bool mfma_direct(int nt, const EeLaunchOptions &opt) { return nt == 1 && !opt.mfma_ring; }
 
-int ee_mfma_block_shape(int h, int cin, int *rp_n, int *ct_n, int *waves, int *nt) {
+int ee_mfma_block_shape(int h, int cin, const EeLaunchOptions &opt, int *rp_n, int *ct_n, int *waves, int *nt) {
   if (cin == 84 || cin == 144) {
     // the wide nets' four-block form: four position tiles (up to four rows) x the output slices; at 144 channels a
     // one-row block takes two column tiles (four: 5 x 68 x 144 floats = 196 KB of patch, past the 160 KB of LDS)
@@ -971,13 +968,11 @@ int ee_mfma_block_shape(int h, int cin, int *rp_n, int *ct_n, int *waves, int *n
     *nt = 1;
     return 1;
   }
-  const int wv = getenv("PCONV_EE_MFMA_WAVES") ? atoi(getenv("PCONV_EE_MFMA_WAVES")) : 4;  // (per engine)
   // measured (MI355X, 4096x2048, one frame x 3 sets per launch, profiles/round5_entropy_mfma_variants.txt): one row per
   // wave 452 us per full launch (two rows: 474; eight waves per workgroup: 509 / 550), 591 / 715 us for a frame
   // in four step ranges
-  const int nt_env = getenv("PCONV_EE_MFMA_NT") ? atoi(getenv("PCONV_EE_MFMA_NT")) : 1;
-  const int nw = wv == 8 ? 8 : 4;
-  const int n = (nt_env == 1 || (h & 1)) ? 1 : 2;
+  const int nw = opt.mfma_waves == 8 ? 8 : 4;
+  const int n = (opt.mfma_nt == 1 || (h & 1)) ? 1 : 2;
   if ((cin != 42 && cin != 14) || h < n) return 0;
   const int rows = h / n;  // wave rows per tile
   int rp = rows;
@@ -993,9 +988,9 @@ int ee_mfma_block_shape(int h, int cin, int *rp_n, int *ct_n, int *waves, int *n
 int ee_conv_bulk_mfma(const EeGeom *g, const void *blocks, int nblocks, int rp_n, int ct_n, int waves, int nt, const float *x,
                       int shared_input, const float *wfrag, const float *bias, const float *slope,
                       const float *residual, float *y, int cin, int cout, int pad_out, int s_lo, int s_hi,
-                      void *stream) {
+                      const EeLaunchOptions &opt, void *stream) {
   PCONV_REQUIRE((cin == 42 || cin == 14) && cout == 42 && g->ngroup == 14, "ee_conv_bulk_mfma: 14 / 42 -> 42 channels only");
-  PCONV_REQUIRE(cin == 42 || (nt == 1 && mfma_direct(nt)), "ee_conv_bulk_mfma: the input layer takes the one-row direct form");
+  PCONV_REQUIRE(cin == 42 || (nt == 1 && mfma_direct(nt, opt)), "ee_conv_bulk_mfma: the input layer takes the one-row direct form");
   PCONV_REQUIRE(rp_n > 0 && ct_n > 0 && rp_n * ct_n == waves && (waves == 4 || waves == 8) && (nt == 1 || nt == 2) &&
                     g->h % (nt * rp_n) == 0,
                 "ee_conv_bulk_mfma: bad block shape");
@@ -1003,7 +998,7 @@ int ee_conv_bulk_mfma(const EeGeom *g, const void *blocks, int nblocks, int rp_n
   // ring + patch, the patch rounded up to whole DMA rounds of the workgroup (16 bytes per thread)
   const size_t round = (size_t)waves * kWave * 16;
   const size_t patch_bytes = ((size_t)(nt * rp_n + 4) * (16 * ct_n + 4) * cin * sizeof(float) + round - 1) / round * round;
-  const bool direct = mfma_direct(nt);
+  const bool direct = mfma_direct(nt, opt);
   const size_t smem = (direct ? 0 : (size_t)kRing * frag_floats(42) * sizeof(float)) + patch_bytes + kPatchSlack * sizeof(float);
   PCONV_REQUIRE(smem <= 160 * 1024, "ee_conv_bulk_mfma: block needs %zu bytes of LDS", smem);
   const dim3 grid((unsigned)nblocks, (unsigned)(3 * g->nimg));

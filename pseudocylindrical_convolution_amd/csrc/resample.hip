@@ -7,7 +7,7 @@
 // reuses it for all RB rows, so the tap table (20 B/column, L2 resident) costs
 // 20/RB bytes per output element.  Lanes map to consecutive output columns, so
 // stores are contiguous 256 B per wave.
-#include <stdlib.h>
+#include "options.h"
 #include "common.h"
 
 namespace {
@@ -156,10 +156,10 @@ __global__ __launch_bounds__(kBlock) void uslice_kernel(
 }
 
 int rows_per_block(int tile_rows, int width) {
-  // PCONV_RESAMPLE_ROWS (1 / 2 / 4): rows a workgroup stages -- fewer rows = less LDS per workgroup = more of them
-  // resident per CU against 20 / rows bytes of tap table per output element
+  // PCONV_RESAMPLE_ROWS (1 / 2 / 4), read per call: rows a workgroup stages -- fewer rows = less LDS per workgroup =
+  // more of them resident per CU against 20 / rows bytes of tap table per output element
   // (measured, 1x3x2048x4096: 4 rows 3.47 / 3.20 TB/s slice / uslice, 2 rows 3.92 / 3.71, 1 row 3.79 / 3.51)
-  static const int cap = getenv("PCONV_RESAMPLE_ROWS") ? atoi(getenv("PCONV_RESAMPLE_ROWS")) : 2;
+  const int cap = ResampleOptions::from_env().rows;
   int rb = cap >= 1 && cap <= kMaxRows ? cap : kMaxRows;
   while (rb > 1 && (tile_rows % rb != 0 || (size_t)rb * width * 4 > 64 * 1024)) rb >>= 1;
   return rb;

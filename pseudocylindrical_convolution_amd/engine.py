@@ -78,6 +78,10 @@ class EntropyEngine(object):
         """the encoder's kernel per layer (12 values): 0 vector, 1 matrix cores 16x16x4, 2 matrix cores four-block"""
         return tuple(call("pconv_ee_encoder_form", self.handle, layer) for layer in range(12))
 
+    def option(self, name):
+        """the value this engine holds for the PCONV_ENGINE_* / PCONV_EE_* variable `name`, as read when it was created"""
+        return _native.option(name, self.handle)
+
     @property
     def symbols_per_image(self):
         return int(self.lib.pconv_ee_symbols_per_image(self.handle))

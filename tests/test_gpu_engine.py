@@ -127,26 +127,37 @@ def test_engine_full_size_properties(hip_backend):
 def test_queued_chain_equals_host_driven_chain(hip_backend, monkeypatch):
     """the decoder's queued-ahead chain (scatter kernels wait in pinned memory for the host's
     symbols, table kernels announce their rows there) returns exactly what the host-driven
-    loop returns, for one frame and for a lock-step batch in two groups"""
-    from pseudocylindrical_convolution_amd.engine import CodecEngine
+    loop returns, for one frame and for a lock-step batch in two groups.  The chain belongs to the engine (the
+    host plan of pconv_ee_create): one engine per chain, and each reports the chain it holds."""
+    from pseudocylindrical_convolution_amd import _native
+    from pseudocylindrical_convolution_amd.engine import CodecEngine, EntropyEngine
     enc, dec = _codec()
     eng = CodecEngine(56, 0, enc, dec)
     x = _frames(3, 256, 512, seed=13)
     streams = eng.encode(x)
     sym = eng.symbols(x)
+    h, w = sym.shape[2], sym.shape[3]
+    auto = -2 ** 31                                          # PCONV_OPTION_AUTO: the plan picks by frames per group
     for n in (1, 3):
-        e = eng._engine("dec", sym.shape[2], sym.shape[3], n)
-        monkeypatch.setenv("PCONV_ENGINE_CHAIN", "queued")   # (the default picks by frames per group)
-        queued = e.decode(streams[:n])
-        monkeypatch.setenv("PCONV_ENGINE_CHAIN", "host")
-        host = e.decode(streams[:n])
         monkeypatch.setenv("PCONV_ENGINE_CHAIN", "queued")
+        q = EntropyEngine(dec.ent, h, w, n, "cuda:0")
+        monkeypatch.setenv("PCONV_ENGINE_CHAIN", "host")
+        hd = EntropyEngine(dec.ent, h, w, n, "cuda:0")
+        # (read while the variable says "host": the queued engine keeps what it was created with)
+        assert q.option("PCONV_ENGINE_CHAIN") == 1 and hd.option("PCONV_ENGINE_CHAIN") == 0
+        assert _native.option("PCONV_ENGINE_CHAIN") == 0
+        queued = q.decode(streams[:n])
+        host = hd.decode(streams[:n])
         assert torch.equal(queued, host)
         assert torch.equal(queued, sym[:16 * n])
-        again = e.decode(streams[:n])   # flags and counters are back in their initial state
+        again = q.decode(streams[:n])   # flags and counters are back in their initial state
         assert torch.equal(again, queued)
+        assert torch.equal(hd.decode(streams[:n]), queued)
         monkeypatch.delenv("PCONV_ENGINE_CHAIN")
-        assert torch.equal(e.decode(streams[:n]), queued)
+        plain = EntropyEngine(dec.ent, h, w, n, "cuda:0")
+        assert plain.option("PCONV_ENGINE_CHAIN") == auto
+        assert torch.equal(plain.decode(streams[:n]), queued)
+        assert q.option("PCONV_ENGINE_CHAIN") == 1 and hd.option("PCONV_ENGINE_CHAIN") == 0
 
 
 def test_eight_frames_take_the_host_driven_chain_by_default(hip_backend):
@@ -276,13 +287,27 @@ def test_engine_knobs_that_must_not_change_a_stream(hip_backend, monkeypatch):
     """PCONV_ENGINE_ROWS (16-byte packed CDF rows or int32[9] rows + labels across PCIe), the order of the tail
     encode's step ranges (interleaved over the groups or group by group) and their number, the step-by-step
     debugging encoder, the engine's streams on a partition of the compute units, the other matrix-core form of the
-    encoder's hidden layers: the same streams, and every decoder configuration returns the coded symbols."""
+    encoder's hidden layers: the same streams, and every decoder configuration returns the coded symbols.  Every
+    engine reports the values it was created under (pconv_option).  The longest wavefront plane of this shape has
+    60 positions (pconv_host_wavefront, checked below): the fused launch splits a plane into ceil(60 / 16) = 4
+    workgroups at 4 positions per wave and into 8 at PCONV_EE_FUSE_PPW=2, so the last case is a launch shape of
+    its own."""
+    import numpy as np
+    from pseudocylindrical_convolution_amd import _native
+    from pseudocylindrical_convolution_amd.PCONV_operator.base import set_weight
     from pseudocylindrical_convolution_amd.engine import EntropyEngine
     enc, _ = _codec()
     ent = enc.ent
     h, w, n = 4, 128, 3
     sym = torch.randint(0, 8, (16 * n, 14, h, w), generator=torch.Generator().manual_seed(29)).float().cuda()
     sym = ent.fill(sym).contiguous()
+    weight = np.asarray(set_weight(16, True), dtype=np.float32)
+    widths, order, start = np.zeros(16, np.int32), np.zeros(16 * h * w, np.int32), np.zeros(16 * h + w, np.int32)
+    _native.call("pconv_host_tile_widths", weight.ctypes.data, 16, 16 * h, w, widths.ctypes.data)
+    _native.call("pconv_host_wavefront", widths.ctypes.data, 16, h, w, order.ctypes.data, start.ctypes.data)
+    assert np.diff(start).max() == 60 and -(-60 // (4 * 2)) != -(-60 // (4 * 4))   # (4 waves per workgroup)
+    # what an engine reports for a variable set to the value on the left
+    reported = {"int32": 1, "host": 0, "queued": 1, "16x4": 1}
     for name in ("PCONV_ENGINE_ROWS", "PCONV_ENGINE_ENCODE_INTERLEAVE", "PCONV_ENGINE_ENCODE_RANGES",
                  "PCONV_ENGINE_STEPWISE_ENCODER", "PCONV_ENGINE_CHAIN", "PCONV_ENGINE_CU_MASK", "PCONV_EE_MFMA_FORM",
                  "PCONV_EE_FUSE_TABLES", "PCONV_EE_FUSE_PPW"):
@@ -301,10 +326,54 @@ def test_engine_knobs_that_must_not_change_a_stream(hip_backend, monkeypatch):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         e = EntropyEngine(ent, h, w, n, "cuda:0")
+        for k, v in env.items():
+            if k == "PCONV_ENGINE_CU_MASK":
+                assert (e.option(k + "_FIRST"), e.option(k + "_COUNT")) == (0, 64), env
+            else:
+                assert e.option(k) == reported.get(v, int(v) if v.isdigit() else None), (env, k)
         assert e.encode(sym) == ref, env
         assert torch.equal(e.decode(ref), sym), env
         for k in env:
             monkeypatch.delenv(k)
+        assert all(ref_engine.option(k) != e.option(k) for k in env if k != "PCONV_ENGINE_CU_MASK"), env
     # the per-engine setter wins over the environment and is reset by a plain encode()
     ref_engine.encode_begin(sym, ranges=5)
     assert ref_engine.encode_end() == ref
+
+
+def test_an_engine_keeps_the_options_it_was_created_with(hip_backend, monkeypatch):
+    """pconv_ee_create reads the environment once: engine A, created under three variables (one the old code read at
+    creation, one it read on every call, one a launcher read), and engine B, created without them, report different
+    values; other values set afterwards change neither report nor any stream; both write the same streams and decode
+    them to the symbols."""
+    from pseudocylindrical_convolution_amd import _native
+    from pseudocylindrical_convolution_amd.engine import EntropyEngine
+    enc, _ = _codec()
+    ent = enc.ent
+    h, w, n = 4, 128, 3
+    sym = torch.randint(0, 8, (16 * n, 14, h, w), generator=torch.Generator().manual_seed(37)).float().cuda()
+    sym = ent.fill(sym).contiguous()
+    created = {"PCONV_ENGINE_ROWS": "int32", "PCONV_ENGINE_ENCODE_RANGES": "3", "PCONV_EE_BULK": "valu"}
+    later = {"PCONV_ENGINE_ROWS": "packed", "PCONV_ENGINE_ENCODE_RANGES": "7", "PCONV_EE_BULK": "mfma",
+             "PCONV_ENGINE_CHAIN": "host", "PCONV_EE_FUSE_TABLES": "1", "PCONV_EE_MFMA_WSRC": "ring"}
+    names = sorted(later)
+    for name in names:
+        monkeypatch.delenv(name, raising=False)
+    for k, v in created.items():
+        monkeypatch.setenv(k, v)
+    a = EntropyEngine(ent, h, w, n, "cuda:0")
+    for k in created:
+        monkeypatch.delenv(k)
+    b = EntropyEngine(ent, h, w, n, "cuda:0")
+    held_a, held_b = [a.option(k) for k in names], [b.option(k) for k in names]
+    assert [a.option(k) for k in sorted(created)] == [1, 3, 1]            # BULK = valu, RANGES = 3, ROWS = int32
+    assert [b.option(k) for k in sorted(created)] == [0, 4, 0]
+    assert a.encoder_forms == (0,) * 12 and b.encoder_forms != a.encoder_forms
+    sa, sb = a.encode(sym), b.encode(sym)
+    assert sa == sb and len(set(sa)) == n
+    for k, v in later.items():
+        monkeypatch.setenv(k, v)
+    assert _native.option("PCONV_ENGINE_ENCODE_RANGES") == 7 and _native.option("PCONV_ENGINE_CHAIN") == 0
+    assert [a.option(k) for k in names] == held_a and [b.option(k) for k in names] == held_b
+    assert a.encode(sym) == sa and b.encode(sym) == sa
+    assert torch.equal(a.decode(sa), sym) and torch.equal(b.decode(sa), sym)

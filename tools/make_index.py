@@ -79,7 +79,8 @@ out = ["# tools/ -- index", "",
        "is ONE gpurun call of round N (`gpurun -- 'bash tools/gpu_roundN_x.sh'`), kept so that every figure in `profiles/`,",
        "`DESIGN.md` and `HISTORY.md` can be traced to the command that produced it.  Column 3: the `profiles/` files that",
        "came out of the script (where the file or the design documents name it).  `tools/experiments/` holds archived kernel",
-       "variants that were measured and not kept; `tools/_build/` is scratch (git-ignored).", "",
+       "variants that were measured and not kept; `tools/_build/` is scratch (git-ignored).  The `PCONV_*` variables the",
+       "scripts set: defaults, other values and lifetimes are in DESIGN.md, \"What runs by default\".", "",
        "Regenerate with `python tools/make_index.py`: the descriptions are the scripts' own header comments.", ""]
 for k, v in groups.items():
     if not v:
