@@ -831,3 +831,52 @@ def conv2d_chain(x, weight, bias, stride, slope=None):
                            _p(slope.detach().contiguous()) if slope is not None else None, _p(out), I(tn), I(cin),
                            I(h), I(w), I(cout), I(k), I(stride))
     return out
+
+
+def _trim_cols(y, col_limit, npart):
+    """zeros from col_limit[t % npart] on for tile t (what PseudoFill leaves of a block output)"""
+    if col_limit is not None:
+        for t in range(y.shape[0]):
+            y[t, :, :, int(col_limit[t % npart]):] = 0
+    return y
+
+
+def gdn_norm_chain(x, gamma, beta):
+    """the norm of gdn_chain: beta + gamma x^2 as the k-ascending fmaf chain over the squares (each x * x rounded
+    on its own), beta added at the end like a bias"""
+    x = x.detach().to(torch.float32).contiguous()
+    ch = x.shape[1]
+    sq = torch.empty_like(x)
+    lib().orc_square(_p(x), _p(sq), L(x.numel()))
+    return conv2d_chain(sq, gamma.detach().to(torch.float32).reshape(ch, ch, 1, 1), beta.detach().to(torch.float32), 1)
+
+
+def gdn_chain(x, gamma, beta, inverse, residual=None, col_limit=None, npart=0, norm=None):
+    """bit-exact reference of the fused GDN (tile_gdn), all arithmetic in float32: norm = gdn_norm_chain(x, gamma,
+    beta), then x / sqrt(norm) (inverse: x * sqrt(norm)), residual + y, zeros from each tile's col_limit on.
+    The square root, the divide and the add are C's sqrtf, / and + in the oracle library (correctly rounded on every
+    host), not an array library's; gamma (ch, ch), beta (ch): effective values.
+    norm: gdn_norm_chain of the same x, gamma and beta, for a caller that evaluates many variants of one input
+    (the chain is all of the cost)."""
+    x = x.detach().to(torch.float32).contiguous()
+    norm = (gdn_norm_chain(x, gamma, beta) if norm is None else norm).contiguous()
+    assert norm.shape == x.shape and norm.dtype == torch.float32
+    if residual is not None:
+        residual = residual.detach().to(torch.float32).contiguous()
+        assert residual.shape == x.shape
+    y = torch.empty_like(x)
+    lib().orc_gdn_finish(_p(x), _p(norm), _p(residual), _p(y), L(x.numel()), I(1 if inverse else 0))
+    return _trim_cols(y, col_limit, npart)
+
+
+def gdn_f64(x, gamma, beta, inverse, residual=None, col_limit=None, npart=0):
+    """the same formula in float64 throughout, the contraction as a plain matmul: the independent check of
+    gdn_chain (and of the module's formula)"""
+    x = x.detach().to(torch.float64)
+    tn, ch, h, w = x.shape
+    norm = torch.matmul(gamma.detach().to(torch.float64), (x * x).reshape(tn, ch, h * w)).reshape(tn, ch, h, w)
+    root = torch.sqrt(norm + beta.detach().to(torch.float64).view(1, ch, 1, 1))
+    y = x * root if inverse else x / root
+    if residual is not None:
+        y = residual.detach().to(torch.float64) + y
+    return _trim_cols(y, col_limit, npart)

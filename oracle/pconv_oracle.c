@@ -1148,6 +1148,25 @@ void orc_conv2d_chain(const float *in, const float *w, const float *bias, const 
   }
 }
 
+/* ---- fused GDN (the product's tile_gdn): every operation of its float32 contract, one IEEE operation per
+ * statement (sqrtf, / and + of C are correctly rounded; contraction is off).  Not left to an array library:
+ * a vectorised square root or divide may come from a math library whose rounding depends on the host CPU. ---- */
+void orc_square(const float *x, float *out, long long n) {
+#pragma omp parallel for
+  for (i64 i = 0; i < n; i++) out[i] = x[i] * x[i];
+}
+
+/* out = x / sqrt(norm) (inverse: x * sqrt(norm)), then residual + out when there is a residual */
+void orc_gdn_finish(const float *x, const float *norm, const float *residual, float *out, long long n, int inverse) {
+#pragma omp parallel for
+  for (i64 i = 0; i < n; i++) {
+    const float root = sqrtf(norm[i]);
+    float v = inverse ? x[i] * root : x[i] / root;
+    if (residual) v = residual[i] + v;
+    out[i] = v;
+  }
+}
+
 /* ========================================================================================
  * Backward of the linear geometry ops (training path).  The reference sums
  * through float atomics / atomics-built inverse lists, i.e. in no defined order; these

@@ -342,7 +342,12 @@ def test_tile_conv_dead_column_skip():
 @pytest.mark.parametrize("inverse", [False, True])
 def test_gdn_fused_matches_reference_formula(hip_backend, inverse):
     """PseudoGDNV2 on the GPU (one fused launch) against the reference's op-by-op
-    formula (PseudoContextV2.py:133-216) evaluated with torch on the same device"""
+    formula (PseudoContextV2.py:133-216) evaluated with torch on the same device.
+    The kernel's arithmetic is held bit for bit, on every dispatch branch, by
+    tests/test_gpu_gdn.py (O.gdn_chain); what this test still adds is the module
+    plumbing at the production shape (16 tiles x 192 channels x 8 x 256): the fused
+    path and the autograd formula of the same module object agree, and the
+    context's limits reach the kernel"""
     import torch
     from pseudocylindrical_convolution_amd.PCONV_operator import PseudoContextV2, PseudoGDNV2
     torch.manual_seed(3)
