@@ -187,6 +187,52 @@ int pconv_frames_u8_to_f32_erp(const uint8_t *in, float *out, int n, int h, int 
 int pconv_erp_pad_f32(const float *in, float *out, int n, int h, int w, void *stream);
 int pconv_frames_f32_to_u8_crop(const float *in, uint8_t *out, int n, int h, int w, void *stream);
 
+/* YUV 4:2:0 frames (csrc/yuv.hip; pseudocylindrical_convolution_amd/yuv.py states the same definition in torch).
+ * Formats.  A frame is one contiguous buffer, as a raw .yuv file holds it; h and w are even and at least 2:
+ *   PCONV_YUV_420P      uint8.  Y (h, w), then U (h/2, w/2), then V (h/2, w/2).
+ *   PCONV_YUV_NV12      uint8.  Y (h, w), then interleaved UV (h/2, w/2, 2).
+ *   PCONV_YUV_420P10LE  uint16 (host little-endian).  The planes of 420P, values 0..1023; a sample above 1023 is
+ *                       taken modulo 1024.
+ * d is the bit depth (8 or 10), s = 2^(d-8).
+ * Range.   PCONV_YUV_LIMITED: yo = 16s, ys = 219s, co = 128s, cs = 224s.
+ *          PCONV_YUV_FULL:    yo = 0, ys = 2^d - 1, co = 2^(d-1), cs = 2^d - 1.
+ * Matrix.  PCONV_YUV_BT709: Kr = 0.2126, Kb = 0.0722.  PCONV_YUV_BT601: Kr = 0.299, Kb = 0.114.  In double, in
+ *          this order: Kg = 1.0 - Kr - Kb, a = 2*(1 - Kr), dd = 2*(1 - Kb), b = Kb*dd/Kg, c = Kr*a/Kg; each of Kr,
+ *          Kg, Kb, a, b, c, dd is then rounded once to float32.
+ * Chroma siting is H.26x type 0: a chroma sample is co-sited with the even luma columns and sits midway between
+ * luma rows 2j and 2j+1.  The longitude seam wraps, the poles clamp.  All arithmetic is fp32, one rounding per
+ * operation (no contraction), divisions correctly rounded.
+ * Ingest (yuv420_to_f32): float32 RGB (n, 3, H, W) at the coded size of pconv_erp_coded_size(h, w).
+ *   chroma up, vertical first:  luma row 2j   reads 0.25f*C[max(j-1, 0)] + 0.75f*C[j],
+ *                               luma row 2j+1 reads 0.75f*C[j] + 0.25f*C[min(j+1, h/2-1)];
+ *   then horizontal:            column 2i is V[i], column 2i+1 is 0.5f*(V[i] + V[(i+1) % (w/2)])
+ *                               (for code values up to 1023 every intermediate is exact);
+ *   normalise:  y = (Y - yo)/ys, cb = (Cb_up - co)/cs, cr = (Cr_up - co)/cs;
+ *   matrix:     R = y + a*cr, G = (y - b*cb) - c*cr, B = y + dd*cb, each clamped to [0, 1];
+ *   pad:        coded pixel (y', x') is the converted pixel at the source row and column of the pole / seam rule
+ *               above (the rule's gather applied to converted pixels); a codable size maps to itself.
+ * Egress (f32_to_yuv420): float32 RGB (n, 3, H, W) at the coded size -> the frame buffers of h x w.
+ *   crop rows top..top+h-1, columns 0..w-1; clamp to [0, 1];
+ *   y = (Kr*R + Kg*G) + Kb*B, cb = (B - y)/dd, cr = (R - y)/a;
+ *   chroma down: v = 0.5f*(p[2j] + p[2j+1]) per column, then
+ *                C[i] = (0.25f*v[(2i-1) mod w] + 0.5f*v[2i]) + 0.25f*v[2i+1]  (the seam wraps);
+ *   quantise:    q = clamp(floorf((p*scale + offset) + 0.5f), 0, 2^d - 1), (ys, yo) for luma, (cs, co) for chroma.
+ * Both refuse on the host, before any launch, with PCONV_EINVAL: null pointers, odd h or w or a side below 2,
+ * w > PCONV_YUV_MAX_WIDTH (the row staging in LDS), n > 65535, unknown enums, a float tensor that is not 16-byte
+ * aligned.  The sample buffers take any alignment their element size allows. */
+#define PCONV_YUV_420P 0
+#define PCONV_YUV_NV12 1
+#define PCONV_YUV_420P10LE 2
+#define PCONV_YUV_BT709 0
+#define PCONV_YUV_BT601 1
+#define PCONV_YUV_LIMITED 0
+#define PCONV_YUV_FULL 1
+#define PCONV_YUV_MAX_WIDTH 11520
+int pconv_frames_yuv420_to_f32(const void *in, float *out, int n, int h, int w, int fmt, int matrix, int range,
+                               void *stream);
+int pconv_frames_f32_to_yuv420(const float *in, void *out, int n, int h, int w, int fmt, int matrix, int range,
+                               void *stream);
+
 /* Sphere-weighted quality of ERP frames (csrc/sphere_metrics.hip): WS-PSNR / WS-SSIM (Sun, Lu, Yu, IEEE SPL 2017).
  * x and y are n frames of h x w (h, w >= 1, any size, smaller than the SSIM window included):
  *   _f32: float32 (n, c, h, w), contiguous, 4-byte aligned, values as they are (nominally [0, 1], not clamped);

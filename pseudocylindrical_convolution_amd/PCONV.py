@@ -1395,6 +1395,68 @@ def frames_f32_to_u8_crop(x, height, width, out=None):
     return out
 
 
+# name -> (PCONV_YUV_* constant, dtype, bit depth) / PCONV_YUV_BT* / PCONV_YUV_LIMITED, _FULL (include/pconv_hip.h)
+YUV_FORMATS = {"yuv420p": (0, torch.uint8, 8), "nv12": (1, torch.uint8, 8), "yuv420p10le": (2, torch.uint16, 10)}
+YUV_MATRICES = {"bt709": 0, "bt601": 1}
+YUV_RANGES = {"limited": 0, "full": 1}
+
+
+def _yuv_args(what, h, w, fmt, matrix, range):
+    if fmt not in YUV_FORMATS or matrix not in YUV_MATRICES or range not in YUV_RANGES:
+        raise PconvError("%s: unknown pixel format, matrix or range: %r, %r, %r (formats %s; matrices %s; ranges %s)"
+                         % (what, fmt, matrix, range, sorted(YUV_FORMATS), sorted(YUV_MATRICES), sorted(YUV_RANGES)))
+    h, w = int(h), int(w)
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise PconvError("%s: a 4:2:0 frame needs even sides of at least 2, got %dx%d" % (what, w, h))
+    code, dtype, depth = YUV_FORMATS[fmt]
+    return h, w, code, dtype, (depth + 7) // 8, h * w * 3 // 2
+
+
+def frames_yuv420_to_f32(buf, h, w, fmt, matrix="bt709", range="limited", out=None):
+    """YUV 4:2:0 frames -> RGB at the coded size (yuv.py, pconv_frames_yuv420_to_f32): buf a GPU tensor (n, h*w*3/2)
+    of the format's dtype (any offset its element size allows) -> float32 (n, 3, H, W), the colour conversion fused
+    with the pole / seam pad"""
+    if not buf.is_cuda:
+        raise PconvError("frames_yuv420_to_f32: expected a GPU tensor (this build has no CPU path), got %s" % buf.device)
+    h, w, code, dtype, size, elems = _yuv_args("frames_yuv420_to_f32", h, w, fmt, matrix, range)
+    if buf.dtype != dtype or buf.dim() != 2 or buf.shape[1] != elems or not buf.is_contiguous():
+        raise PconvError("frames_yuv420_to_f32: contiguous %s (n, %d) expected for %s frames of %dx%d, got %s %s"
+                         % (dtype, elems, fmt, w, h, buf.dtype, tuple(buf.shape)))
+    n = buf.shape[0]
+    H, W, _top = erp_coded_size(h, w)
+    if out is None:
+        out = torch.empty((n, 3, H, W), dtype=torch.float32, device=buf.device)
+    elif tuple(out.shape) != (n, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != buf.device:
+        raise PconvError("frames_yuv420_to_f32: out must be contiguous float32 (n, 3, %d, %d) on the frames' device" % (H, W))
+    with _HbmTimed("frames_yuv420_to_f32_kernel", "yuv2tensor+pad %s n%d" % (fmt, n), size * buf.numel() + 4.0 * out.numel(),
+                   buf.device):
+        call("pconv_frames_yuv420_to_f32", _ptr(buf), _ptr(out), n, h, w, code, YUV_MATRICES[matrix], YUV_RANGES[range],
+             _stream(buf.device))
+    return out
+
+
+def frames_f32_to_yuv420(x, h, w, fmt, matrix="bt709", range="limited", out=None):
+    """RGB at the coded size -> YUV 4:2:0 frames (yuv.py, pconv_frames_f32_to_yuv420): float32 (n, 3, H, W) coded
+    frames -> (n, h*w*3/2) of the format's dtype, rows top..top+h-1 and columns 0..w-1 converted, the chroma filtered
+    down with the seam wrapped (any offset of out its element size allows)"""
+    _require_gpu(x, "frames_f32_to_yuv420")
+    h, w, code, dtype, size, elems = _yuv_args("frames_f32_to_yuv420", h, w, fmt, matrix, range)
+    H, W, _top = erp_coded_size(h, w)
+    if x.dim() != 4 or tuple(x.shape[1:]) != (3, H, W):
+        raise PconvError("frames_f32_to_yuv420: float32 (n, 3, %d, %d) expected for %dx%d, got %s"
+                         % (H, W, w, h, tuple(x.shape)))
+    n = x.shape[0]
+    if out is None:
+        out = torch.empty((n, elems), dtype=dtype, device=x.device)
+    elif tuple(out.shape) != (n, elems) or out.dtype != dtype or not out.is_contiguous() or out.device != x.device:
+        raise PconvError("frames_f32_to_yuv420: out must be contiguous %s (n, %d) on the tensor's device" % (dtype, elems))
+    with _HbmTimed("frames_f32_to_yuv420_kernel", "tensor2yuv+crop %s n%d" % (fmt, n), 12.0 * n * h * w + size * out.numel(),
+                   x.device):
+        call("pconv_frames_f32_to_yuv420", _ptr(x), _ptr(out), n, h, w, code, YUV_MATRICES[matrix], YUV_RANGES[range],
+             _stream(x.device))
+    return out
+
+
 WS_WEIGHTINGS = {"ws": 0, "uniform": 1}   # PCONV_WS_WEIGHT_SPHERE, PCONV_WS_WEIGHT_UNIFORM
 
 

@@ -44,6 +44,8 @@ _HIP_SIGNATURES = {
     "pconv_frames_u8_to_f32_erp": [P, P, I, I, I, P],
     "pconv_erp_pad_f32": [P, P, I, I, I, P],
     "pconv_frames_f32_to_u8_crop": [P, P, I, I, I, P],
+    "pconv_frames_yuv420_to_f32": [P, P, I, I, I, I, I, I, P],
+    "pconv_frames_f32_to_yuv420": [P, P, I, I, I, I, I, I, P],
     "pconv_ws_metrics_workspace_bytes": [I, I, I],
     "pconv_ws_metrics_f32": [P, P, I, I, I, I, I, P, P, P],
     "pconv_ws_metrics_u8": [P, P, I, I, I, I, I, P, P, P],

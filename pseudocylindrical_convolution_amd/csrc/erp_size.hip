@@ -7,53 +7,11 @@
 // with tensor2img's cast.  One workgroup per (frame, row); the interleaved uint8 row (3w bytes, any alignment, any w)
 // goes through LDS so that the global side moves aligned dwords, bytes only at the row's two ragged ends.
 #include "common.h"
+#include "erp_rule.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kMaxRowBytes = 65536 - 32;  // LDS of one row: 3w + 12 bytes, at most 64 KiB per workgroup
-
-struct ErpGeom {
-  int h, w, H, W, top, m, half;
-};
-
-__device__ __forceinline__ int erp_src_row(const ErpGeom &g, int yc, bool &flip) {
-  int y = yc - g.top;
-  flip = false;
-  if (y < 0) {
-    y = -1 - y;
-    flip = true;
-  } else if (y >= g.h) {
-    y = 2 * g.h - 1 - y;
-    flip = true;
-  }
-  return min(max(y, 0), g.h - 1);
-}
-
-__device__ __forceinline__ int erp_src_col(const ErpGeom &g, int xc, bool flip) {
-  int x = xc < g.w ? xc : (xc - g.w < g.m ? g.w - 1 : 0);
-  if (flip) {
-    x += g.half;
-    if (x >= g.w) x -= g.w;
-  }
-  return x;
-}
-
-// bytes [0, nbytes) of `src` (any alignment) -> lds[a + i], a = src & 3: the row's whole dwords are read as dwords
-// and land on aligned LDS dwords, the head and tail bytes one by one
-__device__ __forceinline__ void stage_row_bytes(const uint8_t *__restrict__ src, int nbytes, uint8_t *lds) {
-  const int a = (int)(reinterpret_cast<uintptr_t>(src) & 3);
-  const int i0 = (4 - a) & 3;  // first byte of the row on a dword boundary
-  const int nd = nbytes > i0 ? (nbytes - i0) >> 2 : 0;
-  const uint32_t *body = reinterpret_cast<const uint32_t *>(src + i0);
-  uint32_t *lds_body = reinterpret_cast<uint32_t *>(lds + a + i0);
-  for (int k = threadIdx.x; k < nd; k += kBlock) lds_body[k] = body[k];
-  const int tail0 = i0 + 4 * nd, ragged = i0 + (nbytes - tail0);
-  for (int k = threadIdx.x; k < ragged; k += kBlock) {
-    const int i = k < i0 ? k : tail0 + (k - i0);
-    if (i < nbytes) lds[a + i] = src[i];
-  }
-}
 
 // uint8 (n, h, w, 3) -> float32 (n, 3, H, W) = float(u8) / 255.f (correctly rounded) under the padding rule
 __global__ __launch_bounds__(kBlock) void frames_u8_to_f32_erp_pad_kernel(const uint8_t *__restrict__ in,

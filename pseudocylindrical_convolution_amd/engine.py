@@ -19,6 +19,7 @@ from ._native import PconvError, call
 from .PCONV_operator import backend, set_weight
 from . import pseudo_codec as PC
 from . import erp_size
+from . import yuv
 
 
 class EntropyEngine(object):
@@ -463,19 +464,32 @@ class FramePipe(object):
     reconstruction of the coded size (CodecEngine.decode(streams, *pipe.coded)) and crops it with
     PCONV.frames_f32_to_u8_crop.  pad=None (default): padded only where the frame kernels above refuse the width
     (width % 4 != 0); other sizes keep them and pass frames through at their own size (CodecEngine.encode pads
-    those itself).  Codable sizes never pad."""
+    those itself).  Codable sizes never pad.
 
-    def __init__(self, n, height, width, device, pad=None):
+    YUV 4:2:0 frames (pix_fmt="yuv420p", "nv12" or "yuv420p10le", with matrix and range as yuv.py defines them): the
+    bus carries the frame buffers as a raw .yuv file holds them, (n, h*w*3/2) uint8 / uint16 -- half of the RGB
+    bytes; take() converts and pads in one kernel (PCONV.frames_yuv420_to_f32) and always returns the coded size,
+    give() crops and converts back (PCONV.frames_f32_to_yuv420) and host_out holds frame buffers.  pix_fmt=None
+    (default) is the RGB pipe above."""
+
+    def __init__(self, n, height, width, device, pad=None, pix_fmt=None, matrix="bt709", range="limited"):
         self.n, self.h, self.w = int(n), int(height), int(width)
-        if pad is None:
+        self.pix_fmt, self.matrix, self.range = pix_fmt, matrix, range
+        if pix_fmt is not None:
+            pad = True   # the YUV kernels work at the coded size (the identity for a codable one)
+        elif pad is None:
             pad = self.w % 4 != 0
-        self.native = not pad or erp_size.codable(self.h, self.w)
+        self.native = pix_fmt is None and (not pad or erp_size.codable(self.h, self.w))
         self.coded = (self.h, self.w) if self.native else erp_size.coded_size(self.h, self.w)[:2]
         self.device = torch.device(device)
         self.ops = backend.ops()
-        if not hasattr(self.ops, "frames_u8_to_f32" if self.native else "frames_u8_to_f32_erp"):
+        need = "frames_yuv420_to_f32" if pix_fmt is not None else ("frames_u8_to_f32" if self.native else "frames_u8_to_f32_erp")
+        if not hasattr(self.ops, need):
             raise PconvError("FramePipe needs the HIP backend")
-        shape = (self.n, self.h, self.w, 3)
+        shape, dtype = (self.n, self.h, self.w, 3), torch.uint8
+        if pix_fmt is not None:
+            shape, dtype = (self.n, yuv.frame_elems(self.h, self.w)), yuv.dtype(pix_fmt)
+            yuv.coefficients(matrix, range, pix_fmt)   # refuses an unknown matrix or range here, not at the first take()
         # one copy stream per direction, created through the C ABI (pconv_stream_create) rather than taken from
         # torch's pool (whose first use creates 64 streams in the process).  NOTE for processes that SHARE one GPU
         # (bench.py --share-gpu, never a deployment): the HIP runtime multiplexes a process's streams onto 4 hardware
@@ -484,11 +498,11 @@ class FramePipe(object):
         # process per GPU is indifferent to the knob at 1 / 2 / 4 / 8 frames per call (profiles/round6_rehearsal.txt)
         self._raw = []
         self.up, self.down = self._stream(), self._stream()
-        self.dev_in = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(2)]
-        self.dev_out = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(2)]
-        self.host_out = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.dev_in = [torch.empty(shape, dtype=dtype, device=self.device) for _ in (0, 1)]
+        self.dev_out = [torch.empty(shape, dtype=dtype, device=self.device) for _ in (0, 1)]
+        self.host_out = [torch.empty(shape, dtype=dtype).pin_memory() for _ in (0, 1)]
         self.frames = torch.empty((self.n, 3) + tuple(self.coded), dtype=torch.float32, device=self.device)
-        ev = lambda: [torch.cuda.Event() for _ in range(2)]
+        ev = lambda: [torch.cuda.Event() for _ in (0, 1)]
         self.up_done, self.in_free, self.out_ready, self.down_done = ev(), ev(), ev(), ev()
         self._in_used, self._out_used = [False, False], [False, False]
 
@@ -496,13 +510,17 @@ class FramePipe(object):
         handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             call("pconv_stream_create", ctypes.byref(handle))
-        self._raw.append(handle)   # (lives as long as the process: a pipe is created once per workload)
+        # (lives as long as the process: a pipe is created once per workload.  The two streams must not be destroyed while
+        # a pinned tensor that was copied on them is alive: torch's pinned-memory allocator records an event on every
+        # stream a block was used on when the block is FREED, and the prefetched batches belong to the caller)
+        self._raw.append(handle)
         return torch.cuda.ExternalStream(handle.value, device=self.device)
 
     def prefetch(self, host_u8, slot):
-        """queue the upload of a batch (pinned uint8 (n, H, W, 3)) into input slot `slot` on the upload stream"""
-        if tuple(host_u8.shape) != tuple(self.dev_in[slot].shape) or host_u8.dtype != torch.uint8:
-            raise PconvError("FramePipe.prefetch: uint8 %s expected" % (tuple(self.dev_in[slot].shape),))
+        """queue the upload of a batch (pinned uint8 (n, H, W, 3); with a pix_fmt the frame buffers (n, h*w*3/2) of its
+        dtype) into input slot `slot` on the upload stream"""
+        if tuple(host_u8.shape) != tuple(self.dev_in[slot].shape) or host_u8.dtype != self.dev_in[slot].dtype:
+            raise PconvError("FramePipe.prefetch: %s %s expected" % (self.dev_in[slot].dtype, tuple(self.dev_in[slot].shape)))
         with torch.cuda.stream(self.up):
             if self._in_used[slot]:
                 self.up.wait_event(self.in_free[slot])     # the conversion that read this slot last has run
@@ -515,7 +533,9 @@ class FramePipe(object):
         padded to the coded size when the pipe's size is not codable)"""
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(self.up_done[slot])
-        if self.native:
+        if self.pix_fmt is not None:
+            self.ops.frames_yuv420_to_f32(self.dev_in[slot], self.h, self.w, self.pix_fmt, self.matrix, self.range, self.frames)
+        elif self.native:
             self.ops.frames_u8_to_f32(self.dev_in[slot], self.frames)
         else:
             self.ops.frames_u8_to_f32_erp(self.dev_in[slot], self.frames)
@@ -530,7 +550,10 @@ class FramePipe(object):
         cur = torch.cuda.current_stream(self.device)
         if self._out_used[slot]:
             cur.wait_event(self.down_done[slot])           # the previous download out of this slot has finished
-        if self.native:
+        if self.pix_fmt is not None:
+            self.ops.frames_f32_to_yuv420(rec.contiguous(), self.h, self.w, self.pix_fmt, self.matrix, self.range,
+                                          self.dev_out[slot])
+        elif self.native:
             self.ops.frames_f32_to_u8(rec.contiguous(), self.dev_out[slot])
         else:
             self.ops.frames_f32_to_u8_crop(rec.contiguous(), self.h, self.w, self.dev_out[slot])

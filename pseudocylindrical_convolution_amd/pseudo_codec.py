@@ -10,6 +10,9 @@ Differences from the reference, all additive:
     coded at coded_size(h, w), the decoder crops back (container version 2,
     command line --native-size);
   * --test --ws adds WS-PSNR / WS-SSIM (sphere_metrics.py) beside the viewport figures;
+  * --yuv / --yuv-out code raw YUV 4:2:0 files (yuv.py: yuv420p, nv12, yuv420p10le), one code file per frame, the
+    colour conversion on the GPU; --test --ws then adds WS-PSNR-Y/U/V.  The stream and the container are the RGB ones:
+    the decoder is told the pixel format on the command line;
   * --rd scores images without writing a file: the rate from the CDF rows (rate.py), the distortion from the
     reconstruction of the encoder's own symbols -- no arithmetic coder, no entropy decoder;
   * images are read/written with PIL (cv2 is not required) in the reference's BGR
@@ -35,6 +38,7 @@ from . import container
 from .erp_size import coded_size  # noqa: F401  (re-exported beside latent_shape)
 from . import erp_size
 from . import sphere_metrics
+from . import yuv
 
 psnr_f = lambda xa: 10 * math.log10(1. / xa)
 
@@ -553,6 +557,137 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     return rows
 
 
+def _yuv_rgb(frames, h, w, yuv_opts, dev):
+    """frame buffers (n, frame_elems) -> the codec's input (n, 3, H, W) at the coded size.  yuv.to_rgb gives R, G, B
+    planes; the checkpoints were trained on cv2's B, G, R order (read_image), so the planes are reversed"""
+    return yuv.to_rgb(frames.to(dev), h, w, **yuv_opts).flip(1).contiguous()
+
+
+def _rgb_yuv(rec, h, w, yuv_opts):
+    """the decoder's reconstruction at the coded size -> frame buffers on the CPU (the inverse of _yuv_rgb)"""
+    return yuv.from_rgb(rec.flip(1).contiguous(), h, w, **yuv_opts).cpu()
+
+
+def encoding_yuv(path, out_list, height, width, yuv_opts, start=0, model_idx=0, mse=True, device_id=0, boxed=False):
+    """--enc --yuv: frames start .. start+len(out_list)-1 of a raw .yuv file of height x width, one code file each.
+    Every frame is coded at its own size (converted and padded to the coded size in one pass, yuv.to_rgb);
+    boxed=True (--container) records that size, a headerless file is decoded with --size."""
+    prex, vd, model_dir = _pick(model_idx, mse)
+    dev = backend.device_of(device_id)
+    t1 = PseudoEncoder(vd, device_id=device_id).to(dev)
+    load_models(t1, '{}/{}_encoder.pt'.format(model_dir, prex), '{}/{}_ent.pt'.format(model_dir, prex), dev)
+    header = {"model_idx": model_idx, "ssim": not mse, "size": (height, width)} if boxed else None
+    frames = yuv.read_frames(path, height, width, yuv_opts["fmt"], start, len(out_list))
+    for k, fo in enumerate(out_list):
+        t1(_yuv_rgb(frames[k:k + 1], height, width, yuv_opts, dev), fo, header)
+        print('Encoding {} frame {}, bitrate: {:.3f}bpp'.format(path, start + k, bitrate(fo, height, width)))
+
+
+def _decode_coded(t1, fc, model_idx, mse, height, width, raw):
+    """(reconstruction at the CODED size, height, width) of one code file: the size from its container header when
+    it has one, else from the arguments"""
+    h, w, is_raw = _file_geometry(fc, model_idx, mse, height, width, raw)
+    if h is None or w is None:
+        raise ValueError("%s has no container header: its frame size must be given (--size WxH)" % fc)
+    hc, wc, _ = erp_size.coded_size(h, w)
+    payload = None
+    if not is_raw:
+        head, payload = container.read(fc)
+        if head["valid_dim"] != t1.valid_dim:
+            raise container.ContainerError("file was coded with valid_dim %d, this decoder has %d"
+                                           % (head["valid_dim"], t1.valid_dim))
+    return t1._decode(fc, hc, wc, is_raw, payload), h, w
+
+
+def decoding_yuv(code_list, path, yuv_opts, height=None, width=None, model_idx=0, mse=True, device_id=0, raw=False):
+    """--dec --yuv-out: every code file becomes one frame of the raw .yuv file `path`, in the order of the list"""
+    t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
+    for k, fc in enumerate(code_list):
+        rec, h, w = _decode_coded(t1, fc, model_idx, mse, height, width, raw)
+        yuv.write_frames(path, _rgb_yuv(rec, h, w, yuv_opts), h, w, yuv_opts["fmt"], append=k > 0)
+        print('Decoding {}, output to {} frame {}'.format(fc, path, k))
+
+
+def decoding_and_test_yuv(code_list, path, height, width, yuv_opts, start=0, model_idx=0, mse=True, device_id=0,
+                          raw=False, ws=False):
+    """--test --yuv: decoding_and_test against frames start.. of a raw .yuv file.  The viewport figures (and with
+    ws=True WS-PSNR / WS-SSIM) compare the converted source with the reconstruction, both cropped to the frame's own
+    size; ws=True also prints WS-PSNR-Y/U/V of the frame as --dec --yuv-out would write it against the source frame.
+    Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim, ws_psnr_y, ws_psnr_u, ws_psnr_v])"""
+    t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
+    metrics = ViewportMetrics(device_id)
+    frames = yuv.read_frames(path, height, width, yuv_opts["fmt"], start, len(code_list))
+    rows = []
+    for k, fc in enumerate(code_list):
+        rec, h, w = _decode_coded(t1, fc, model_idx, mse, height, width, raw)
+        if (h, w) != (height, width):
+            raise ValueError("%s holds a %dx%d frame, --size says %dx%d" % (fc, w, h, width, height))
+        src = frames[k:k + 1].to(dev)
+        data, rdata = erp_size.crop(_yuv_rgb(src, h, w, yuv_opts, dev), h, w), erp_size.crop(rec, h, w)
+        pr, vssim = metrics(data, rdata)
+        rt = bitrate(fc, h, w)
+        rows.append((rt, pr, vssim))
+        print('Decoding {}, compare it to {} frame {} \n Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(
+            fc, path, start + k, rt, pr, vssim))
+        if ws:
+            wmse, wssim = sphere_metrics.metrics(data, rdata)[0].tolist()
+            back = _rgb_yuv(rec, h, w, yuv_opts).to(dev)
+            rows[-1] += (sphere_metrics.psnr(wmse), wssim) + tuple(yuv.ws_psnr_yuv(src, back, h, w, yuv_opts["fmt"])[0].tolist())
+            print(' WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*rows[-1][3:5]))
+            print(' WS-PSNR-Y:{:.2f}dB, WS-PSNR-U:{:.2f}dB, WS-PSNR-V:{:.2f}dB'.format(*rows[-1][5:]))
+    print('-' * 53 + '\nAverage Performance\n' + '-' * 53)
+    avg = np.average(np.array(rows), axis=0)
+    print('Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(*avg[:3]))
+    if ws:
+        print('WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*avg[3:5]))
+        print('WS-PSNR-Y:{:.2f}dB, WS-PSNR-U:{:.2f}dB, WS-PSNR-V:{:.2f}dB'.format(*avg[5:]))
+    return rows
+
+
+def _yuv_flags(parser, args):
+    """the checks of --yuv / --yuv-out / --pix-fmt; returns (height, width, options of yuv.to_rgb / from_rgb) or
+    None when the call has nothing to do with YUV.  Contradictions end the run with a message (parser.error)"""
+    if args.yuv is None and args.yuv_out is None:
+        for flag, value in (("--pix-fmt", args.pix_fmt), ("--size", args.size), ("--frames", args.frames),
+                            ("--start", args.start), ("--yuv-matrix", args.yuv_matrix), ("--yuv-range", args.yuv_range)):
+            if value is not None:
+                parser.error("%s needs --yuv or --yuv-out" % flag)
+        return None
+    if args.pix_fmt is None:
+        parser.error("--yuv and --yuv-out need --pix-fmt (one of %s)" % ", ".join(sorted(yuv.FORMATS)))
+    if args.rd:
+        parser.error("--rd takes images (--img-list / --img-file), not --yuv")
+    if args.native_size:
+        parser.error("--native-size is for images: a YUV frame is always coded at its own size")
+    if args.yuv is not None:
+        if args.img_list is not None or args.img_file is not None:
+            parser.error("--yuv and --img-list / --img-file are two sources for the same frames: give one")
+        if not (args.enc or args.test):
+            parser.error("--yuv is the source of --enc or --test; --dec writes to --yuv-out")
+        if args.size is None:
+            parser.error("--yuv needs --size WxH: a raw file does not carry its frame size")
+    if args.yuv_out is not None:
+        if not args.dec:
+            parser.error("--yuv-out needs --dec")
+        if args.out_list is not None or args.out_file is not None:
+            parser.error("--yuv-out and --out-list / --out-file are two destinations for the same frames: give one")
+        if args.start is not None or args.frames is not None:
+            parser.error("--start and --frames select frames of --yuv; --dec writes one frame per code file")
+    height = width = None
+    if args.size is not None:
+        try:
+            width, height = (int(v) for v in args.size.lower().split("x"))
+        except ValueError:
+            parser.error("--size takes WIDTHxHEIGHT, for example 3840x1920; got %r" % args.size)
+        if height < 2 or width < 2 or height % 2 or width % 2:
+            parser.error("--size %s: a 4:2:0 frame needs even sides of at least 2" % args.size)
+    if args.frames is not None and args.code_list is not None and args.frames != len(args.code_list):
+        parser.error("--frames %d but %d code files: one code file per frame" % (args.frames, len(args.code_list)))
+    if (args.start or 0) < 0:
+        parser.error("--start must not be negative")
+    return height, width, dict(fmt=args.pix_fmt, matrix=args.yuv_matrix or "bt709", range=args.yuv_range or "limited")
+
+
 def read_list(fname):
     with open(fname) as f:
         return [line.rstrip('\n') for line in f.readlines()]
@@ -599,7 +734,18 @@ def main(argv=None):
     parser.add_argument('--ws', action='store_true', default=False,
                         help='Testing: also report WS-PSNR / WS-SSIM (rows weighted by their area on the sphere) of '
                              'each decoded image at its own size.  Needs --test or --rd')
+    parser.add_argument('--yuv', help='Encoding / testing: a raw YUV 4:2:0 file as the source instead of images, one '
+                                      'code file per frame (needs --size and --pix-fmt)')
+    parser.add_argument('--yuv-out', help='Decoding: write the decoded frames to this raw YUV 4:2:0 file, in the order '
+                                          'of the code list (needs --pix-fmt; --size for headerless code files)')
+    parser.add_argument('--size', help='WIDTHxHEIGHT of the frames of --yuv (any even size: padded at the poles and the seam)')
+    parser.add_argument('--pix-fmt', choices=sorted(yuv.FORMATS), help='Pixel format of --yuv / --yuv-out')
+    parser.add_argument('--frames', type=int, help='Frames to read from --yuv (default: one per code file)')
+    parser.add_argument('--start', type=int, help='First frame to read from --yuv (default 0)')
+    parser.add_argument('--yuv-matrix', choices=sorted(yuv.MATRICES), help='YCbCr matrix (default bt709)')
+    parser.add_argument('--yuv-range', choices=sorted(yuv.RANGES), help='Code value range (default limited)')
     args = parser.parse_args(argv)
+    yuv_call = _yuv_flags(parser, args)   # contradictory YUV flags end the run here, before anything is loaded
     assert not args.ws or ((args.test or args.rd) and not args.enc and not args.dec), '--ws needs --test or --rd'
     assert not args.rd or not (args.enc or args.dec or args.test), '--rd excludes --enc, --dec and --test'
     check_models()
@@ -614,7 +760,20 @@ def main(argv=None):
     img_list, code_list, out_list = pick(args.img_list, args.img_file), pick(args.code_list, args.code_file), \
         pick(args.out_list, args.out_file)
     size = dict(height=args.height, width=args.width)
-    if args.rd:
+    if yuv_call is not None:
+        height, width, yuv_opts = yuv_call
+        assert code_list is not None, 'No code files'
+        assert args.frames is None or args.frames == len(code_list), 'One code file per frame: --frames differs from the code list'
+        common = dict(model_idx=midx, mse=not args.ssim, device_id=args.gpu_id)
+        if args.enc:
+            encoding_yuv(args.yuv, code_list, height, width, yuv_opts, start=args.start or 0,
+                         boxed=args.container and not args.raw, **common)
+        elif args.dec:
+            decoding_yuv(code_list, args.yuv_out, yuv_opts, height, width, raw=args.raw, **common)
+        else:
+            decoding_and_test_yuv(code_list, args.yuv, height, width, yuv_opts, start=args.start or 0, raw=args.raw,
+                                  ws=args.ws, **common)
+    elif args.rd:
         assert img_list is not None, 'No input images for scoring'
         rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws, **size)
     elif args.enc:
