@@ -257,6 +257,38 @@ int pconv_ws_metrics_f32(const float *x, const float *y, int n, int c, int h, in
 int pconv_ws_metrics_u8(const uint8_t *x, const uint8_t *y, int n, int c, int h, int w, int weighting,
                         void *workspace, double *out, void *stream);
 
+/* Sphere-aware resize of ERP frames (csrc/erp_resample.hip; pseudocylindrical_convolution_amd/erp_resample.py states
+ * the same definition in torch).  Separable Lanczos-3 on float32 (n, C, h, w) -> (n, C, h2, w2); pixel centres sit at
+ * (j + 1/2) / size on both grids; the kernel is stretched by max(1, in / out) when an axis shrinks.
+ * Tap table of one axis, n_in -> n_out (pconv_host_lanczos_taps: host only, in double, the single source of the bits):
+ *   D = 2 * max(n_in, n_out);  N(i, k) = 2*n_out*k - (2*i + 1)*n_in + n_out in exact 64-bit integers: source sample k
+ *   lies N / D kernel units from output sample i.
+ *   raw weight r = 1 if N == 0;  0 if N != 0 and D divides N (the exact zeros of sinc: equal sizes are a bit-exact
+ *   identity);  otherwise, with x = pi * |N| / D,  r = 3 * sin(x) * sin(x / 3) / (x * x).
+ *   The taps of output i are all k with |N| < 3*D; first[i] is the smallest (it may be negative or run past the
+ *   axis).  Weights are divided by their sum (taken in ascending k, in double) and rounded once to float32.  T is
+ *   the largest tap count over i (6 when enlarging, 12 at 2:1, at most 48 at 8:1); shorter rows are padded with
+ *   +0.0f.  weights is (n_out, T) row-major.  The table repeats every n_out / gcd(n_in, n_out) outputs: first advances
+ *   by n_in / gcd and the weights repeat bit for bit.  With first == weights == NULL only *taps is written.
+ * Horizontal pass first:  mid[y][i] = sum_t wx[i][t] * x[y][(first_x[i] + t) mod w]  (the mathematical modulo: the
+ *   seam wraps).
+ * Vertical pass on mid:  source row r = first_y[j] + t goes through the pole rule of pconv_erp_coded_size:
+ *   r < 0 -> -1 - r;  r >= h -> 2*h - 1 - r;  then clamp to [0, h - 1];  a row that crossed a pole is read at column
+ *   (i + floor(w2 / 2)) mod w2, the half turn of longitude applied to the intermediate picture.
+ * Rounding: both sums run t-ascending; every product and every addition is one fp32 rounding, never contracted; the
+ *   first product starts the chain; mid is float32.  clamp != 0: the result is min(max(v, 0), 1) (Lanczos overshoots:
+ *   a unit step gives -0.031 .. 1.031).  Non-finite inputs: unspecified.
+ * pconv_erp_resample_f32: first_x / wx (w2 rows of tx) and first_y / wy (h2 rows of ty) are DEVICE copies of the
+ *   tables; workspace is device memory of pconv_erp_resample_workspace_bytes(...) bytes (mid).  All tensors 4-byte
+ *   aligned (16-byte alignment enables the wide accesses); no allocation, no atomics.  Refused on the host, before
+ *   any launch, with PCONV_EINVAL: null pointers, a side outside 2 .. 2^20, n_in > 8 * n_out on an axis, n * C
+ *   outside 1 .. 65535, tap counts that are not those of the two axes (workspace_bytes: a negative value). */
+int pconv_host_lanczos_taps(int n_in, int n_out, int32_t *first, float *weights, int *taps);
+long long pconv_erp_resample_workspace_bytes(int n, int c, int h, int w, int h2, int w2);
+int pconv_erp_resample_f32(const float *in, float *out, void *workspace, const int32_t *first_x, const float *wx, int tx,
+                           const int32_t *first_y, const float *wy, int ty, int n, int c, int h, int w, int h2, int w2,
+                           int clamp, void *stream);
+
 /* PseudoDQuantOp.forward  (pseudo_dquant_cuda.cu:24-70)
  * weight (wc, levels) raw parameter, level_tab (wc, levels) scratch */
 int pconv_dquant(const float *x, const float *weight, float *level_tab, float *out,

@@ -1457,6 +1457,42 @@ def frames_f32_to_yuv420(x, h, w, fmt, matrix="bt709", range="limited", out=None
     return out
 
 
+_resample_tables = {}   # (device, h, w, h2, w2) -> (first_x, wx, first_y, wy) on the device
+
+
+def erp_resample_f32(x, h2, w2, clamp=False, out=None, workspace=None):
+    """float32 (n, C, h, w) GPU tensor -> (n, C, h2, w2): the sphere-aware Lanczos-3 resize (erp_resample.py,
+    pconv_erp_resample_f32).  The tap tables live on the device, cached per (h, w, h2, w2); workspace: a uint8 GPU
+    tensor of at least pconv_erp_resample_workspace_bytes bytes (allocated when None)"""
+    _require_gpu(x, "erp_resample_f32")
+    if x.dim() != 4:
+        raise PconvError("erp_resample_f32: float32 (n, C, h, w) expected")
+    n, c, h, w = x.shape
+    h2, w2 = int(h2), int(w2)
+    nbytes = call("pconv_erp_resample_workspace_bytes", n, c, h, w, h2, w2)
+    key = (x.device, h, w, h2, w2)
+    if key not in _resample_tables:
+        from .erp_resample import taps
+        fx, wx = taps(w, w2)
+        fy, wy = taps(h, h2)
+        _resample_tables[key] = tuple(t.to(x.device) for t in (fx, wx, fy, wy))
+    fx, wx, fy, wy = _resample_tables[key]
+    if out is None:
+        out = torch.empty((n, c, h2, w2), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, c, h2, w2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise PconvError("erp_resample_f32: out must be contiguous float32 (%d, %d, %d, %d) on the input's device" % (n, c, h2, w2))
+    if workspace is None:
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous() or workspace.device != x.device:
+        raise PconvError("erp_resample_f32: workspace must be a contiguous uint8 tensor of %d bytes on the input's device" % nbytes)
+    # input read + intermediate written and read + output written
+    counted = 4.0 * (x.numel() + 2.0 * n * c * h * w2 + out.numel())
+    with _HbmTimed("erp_resample_kernels", "ErpResample %dx%d->%dx%d n%d" % (w, h, w2, h2, n), counted, x.device):
+        call("pconv_erp_resample_f32", _ptr(x), _ptr(out), _ptr(workspace), _ptr(fx), _ptr(wx), wx.shape[1], _ptr(fy),
+             _ptr(wy), wy.shape[1], n, c, h, w, h2, w2, 1 if clamp else 0, _stream(x.device))
+    return out
+
+
 WS_WEIGHTINGS = {"ws": 0, "uniform": 1}   # PCONV_WS_WEIGHT_SPHERE, PCONV_WS_WEIGHT_UNIFORM
 
 

@@ -49,6 +49,9 @@ _HIP_SIGNATURES = {
     "pconv_ws_metrics_workspace_bytes": [I, I, I],
     "pconv_ws_metrics_f32": [P, P, I, I, I, I, I, P, P, P],
     "pconv_ws_metrics_u8": [P, P, I, I, I, I, I, P, P, P],
+    "pconv_host_lanczos_taps": [I, I, P, P, P],
+    "pconv_erp_resample_workspace_bytes": [I, I, I, I, I, I],
+    "pconv_erp_resample_f32": [P, P, P, P, P, I, P, P, I, I, I, I, I, I, I, I, P],
     "pconv_project": [P, P, P, I, I, I, I, I, I, I, I, P],
     "pconv_context_reshape": [P, P, I, I, I, I, I, P],
     "pconv_mask_constrain": [P, I, I, I, I, I, P],
@@ -167,6 +170,7 @@ def hip_lib():
         lib.pconv_wino_packed_size.restype = c_longlong
         lib.pconv_wino42_packed_size.restype = c_longlong
         lib.pconv_ws_metrics_workspace_bytes.restype = c_longlong
+        lib.pconv_erp_resample_workspace_bytes.restype = c_longlong
         _hip = lib
     return _hip
 

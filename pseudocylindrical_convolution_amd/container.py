@@ -26,9 +26,22 @@ erp_size.coded_size(h, w) under the pole / seam padding rule of erp_size.py, the
     12      4     exact ERP width, little endian
     16      4     payload length in bytes, little endian
 
+Version 3 (28 bytes) carries, beside the size of the coded content, the size of the source the content was resized
+from (erp_resample.py: --code-size); the decoder resizes its picture back to it:
+
+    0       4     magic  b"PCVC"
+    4       1     version (3)
+    5..7          flags, model index, ngroup as in version 1
+    8       4     exact ERP height of the coded content, little endian
+    12      4     exact ERP width of the coded content, little endian
+    16      4     source height, little endian
+    20      4     source width, little endian
+    24      4     payload length in bytes, little endian
+
 `pack` writes version 1 only; `pack_any` writes version 1 (the same bytes as `pack`) for a codable size and
-version 2 otherwise.  `unpack`, `sniff` and `read` take both and return the same dict: height / width are the
-original size.
+version 2 otherwise, and version 3 only when `source=(hs, ws)` is given and differs from (height, width).
+`unpack`, `sniff` and `read` take all three and return the same dict: height / width are the size of the coded
+content before its padding; a version-3 header adds source_height / source_width.
 
 The command line writes the reference's headerless files unless `--container` is given;
 decoding recognises a container by `sniff` (magic, version and a payload length that
@@ -44,6 +57,9 @@ _FMT = "<4sBBBBHHI"
 VERSION_ANY = 2
 HEADER_BYTES_ANY = 20
 _FMT_ANY = "<4sBBBBIII"
+VERSION_SOURCE = 3
+HEADER_BYTES_SOURCE = 28
+_FMT_SOURCE = "<4sBBBBIIIII"
 
 
 class ContainerError(ValueError):
@@ -65,12 +81,17 @@ def pack(payload, height, width, model_idx, ssim, valid_dim):
     return head + bytes(payload)
 
 
-def pack_any(payload, height, width, model_idx, ssim, valid_dim):
+def pack_any(payload, height, width, model_idx, ssim, valid_dim, source=None):
     """header + payload for an ERP of any size: `pack` (version 1) when the codec takes height x width as it
-    is, else version 2 with the exact size (coded at erp_size.coded_size under the padding rule)"""
+    is, else version 2 with the exact size (coded at erp_size.coded_size under the padding rule).
+    source=(hs, ws) != (height, width): version 3, which also records the size the content was resized from"""
     from .erp_size import codable
-    if codable(height, width):
+    if source is not None and (int(source[0]), int(source[1])) == (height, width):
+        source = None
+    if source is None and codable(height, width):
         return pack(payload, height, width, model_idx, ssim, valid_dim)
+    if source is not None and not (2 <= int(source[0]) <= 1 << 20 and 2 <= int(source[1]) <= 1 << 20):
+        raise ContainerError("source size %dx%d does not fit the header (2 .. 2^20 per side)" % (source[1], source[0]))
     if not (2 <= height <= 1 << 20 and 2 <= width <= 1 << 20):
         raise ContainerError("ERP size %dx%d does not fit the header (2 .. 2^20 per side)" % (width, height))
     if valid_dim % 4 or not 0 < valid_dim // 4 < 256:
@@ -79,6 +100,10 @@ def pack_any(payload, height, width, model_idx, ssim, valid_dim):
         raise ContainerError("model index %d does not fit the header" % model_idx)
     if len(payload) >= 1 << 32:
         raise ContainerError("payload too long")
+    if source is not None:
+        head = struct.pack(_FMT_SOURCE, MAGIC, VERSION_SOURCE, 1 if ssim else 0, model_idx, valid_dim // 4, height,
+                           width, int(source[0]), int(source[1]), len(payload))
+        return head + bytes(payload)
     head = struct.pack(_FMT_ANY, MAGIC, VERSION_ANY, 1 if ssim else 0, model_idx, valid_dim // 4, height, width,
                        len(payload))
     return head + bytes(payload)
@@ -91,6 +116,7 @@ def _parse(head, size):
     if head[:4] != MAGIC:
         return "no container magic: a headerless reference-format stream?"
     version = head[4]
+    source = None
     if version == VERSION:
         magic, version, flags, model_idx, ngroup, h16, w16, n = struct.unpack(_FMT, head[:HEADER_BYTES])
         nhead, height, width = HEADER_BYTES, h16 * 16, w16 * 16
@@ -101,19 +127,34 @@ def _parse(head, size):
         nhead = HEADER_BYTES_ANY
         if not (2 <= height <= 1 << 20 and 2 <= width <= 1 << 20):
             return "ERP size %dx%d in the header is out of range" % (width, height)
+    elif version == VERSION_SOURCE:
+        if len(head) < HEADER_BYTES_SOURCE:
+            return "file shorter than the %d-byte version-3 header" % HEADER_BYTES_SOURCE
+        magic, version, flags, model_idx, ngroup, height, width, hs, ws, n = struct.unpack(
+            _FMT_SOURCE, head[:HEADER_BYTES_SOURCE])
+        nhead = HEADER_BYTES_SOURCE
+        if not (2 <= height <= 1 << 20 and 2 <= width <= 1 << 20):
+            return "ERP size %dx%d in the header is out of range" % (width, height)
+        if not (2 <= hs <= 1 << 20 and 2 <= ws <= 1 << 20):
+            return "source size %dx%d in the header is out of range" % (ws, hs)
+        source = (hs, ws)
     else:
-        return "container version %d, this build reads %d and %d" % (version, VERSION, VERSION_ANY)
+        return "container version %d, this build reads %d, %d and %d" % (version, VERSION, VERSION_ANY, VERSION_SOURCE)
     if size - nhead != n:
         return "payload is %d bytes, header says %d" % (size - nhead, n)
     if not (height and width and ngroup):
         return "empty field in the header"
-    return {"height": height, "width": width, "model_idx": model_idx, "ssim": bool(flags & 1),
-            "valid_dim": ngroup * 4}, nhead
+    fields = {"height": height, "width": width, "model_idx": model_idx, "ssim": bool(flags & 1),
+              "valid_dim": ngroup * 4}
+    if source is not None:
+        fields["source_height"], fields["source_width"] = source
+    return fields, nhead
 
 
 def unpack(data):
-    """-> (dict(height, width, model_idx, ssim, valid_dim), payload bytes); version 1 or 2"""
-    got = _parse(bytes(data[:HEADER_BYTES_ANY]), len(data))
+    """-> (dict(height, width, model_idx, ssim, valid_dim[, source_height, source_width]), payload bytes);
+    version 1, 2 or 3"""
+    got = _parse(bytes(data[:HEADER_BYTES_SOURCE]), len(data))
     if isinstance(got, str):
         raise ContainerError(got)
     head, nhead = got
@@ -124,14 +165,14 @@ def _sniff(path):
     try:
         size = os.path.getsize(path)
         with open(path, "rb") as f:
-            head = f.read(HEADER_BYTES_ANY)
+            head = f.read(HEADER_BYTES_SOURCE)
     except OSError:
         return "unreadable"
     return _parse(head, size)
 
 
 def sniff(path):
-    """header dict when the file is a well-formed container (version 1 or 2), else None (a headerless stream).
+    """header dict when the file is a well-formed container (version 1, 2 or 3), else None (a headerless stream).
     A raw arithmetic-coded stream passes for a container only if its first bytes happen to spell the magic,
     a version and its own length: 2^-72 for random bytes."""
     got = _sniff(path)
@@ -139,7 +180,7 @@ def sniff(path):
 
 
 def header_bytes(path):
-    """16 or 20 when `path` is a well-formed container, else 0"""
+    """16, 20 or 28 when `path` is a well-formed container, else 0"""
     got = _sniff(path)
     return 0 if isinstance(got, str) else got[1]
 

@@ -19,6 +19,7 @@ from ._native import PconvError, call
 from .PCONV_operator import backend, set_weight
 from . import pseudo_codec as PC
 from . import erp_size
+from . import erp_resample
 from . import yuv
 
 
@@ -300,13 +301,16 @@ class CodecEngine(object):
     ENCODE_CHUNK = int(os.environ.get("PCONV_ENCODE_CHUNK", "2"))
 
     @torch.no_grad()
-    def encode(self, frames):
+    def encode(self, frames, code_size=None):
         """(n, 3, H, W) frames on the GPU -> n byte strings.  The frames of a chunk go through the
         entropy wavefront in lock-step; the chunks are pipelined: chunk k's CDF tables are coded by
         host threads while the GPU computes the symbols of chunk k+1 (each chunk has its own
         engine: the coder reads the engine's pinned buffers until encode_end).  Frames of a size
         the codec does not take as it is are first padded on the device to their coded size
-        (erp_size.py: poles and seam); decode(streams, h, w) crops back."""
+        (erp_size.py: poles and seam); decode(streams, h, w) crops back.  code_size=(h2, w2): the frames are
+        first resized on the device to h2 x w2 by the sphere-aware rule of erp_resample.py, clamped to [0, 1];
+        decode(streams, h2, w2, out_size=(H, W)) brings the reconstruction back to the source size."""
+        frames = self._at_code_size(frames, code_size)
         if not erp_size.codable(frames.shape[2], frames.shape[3]):
             frames = erp_size.pad(frames)
         n = frames.shape[0]
@@ -347,6 +351,14 @@ class CodecEngine(object):
             self._phase("entropy_encode", t1, self._mark())
         return out
 
+    @staticmethod
+    def _at_code_size(frames, code_size):
+        """frames resized to code_size = (h2, w2) with the clamp (erp_resample.py); None or the frames' own size:
+        the frames as they are"""
+        if code_size is None or tuple(int(v) for v in code_size) == tuple(frames.shape[2:]):
+            return frames
+        return erp_resample.resize(frames, int(code_size[0]), int(code_size[1]), clamp=True)
+
     def _rate_of_symbols(self, sym, n, rate_map):
         """bits (n, npart, ngroup) [, map] of the symbols of n frames, through the chunks -- and the engines --
         encode() takes them through"""
@@ -375,11 +387,14 @@ class CodecEngine(object):
         return self._rate_of_symbols(self.symbols(frames).contiguous(), frames.shape[0], rate_map)
 
     @torch.no_grad()
-    def evaluate(self, frames, rate_map=False):
+    def evaluate(self, frames, rate_map=False, code_size=None):
         """one rate-distortion point without a file: (bits, reconstruction[, map]).  The symbols are computed once;
         bits (and map) are rate()'s, the reconstruction is decode(encode(frames), H, W)'s -- the entropy decoder
         returns exactly the symbols the encoder holds (tests/test_gpu_engine.py), so neither it nor the arithmetic
-        coder has to run."""
+        coder has to run.  code_size=(h2, w2): the frames are coded at h2 x w2 (resized as encode() resizes them) and
+        the reconstruction is returned at the frames' own size, resized back with the clamp: the end-to-end point."""
+        source = tuple(frames.shape[2:])
+        frames = self._at_code_size(frames, code_size)
         height, width = frames.shape[2], frames.shape[3]
         native = erp_size.codable(height, width)
         if not native:
@@ -390,6 +405,7 @@ class CodecEngine(object):
         rec = self.reconstruct(sym, n)
         if not native:
             rec = erp_size.crop(rec, height, width)
+        rec = self._at_code_size(rec, source)
         return (res[0], rec, res[1]) if rate_map else (res, rec)
 
     # frames per pipeline stage of decode(); 0 = decode all frames of a call together, then run the
@@ -397,12 +413,16 @@ class CodecEngine(object):
     DECODE_CHUNK = int(os.environ.get("PCONV_DECODE_CHUNK", "0"))
 
     @torch.no_grad()
-    def decode(self, streams, height, width):
+    def decode(self, streams, height, width, out_size=None):
         """n byte strings -> (n, 3, H, W).  With DECODE_CHUNK = c > 0 and more than c frames the call
         is pipelined: while the synthesis transform of chunk k runs, the entropy decoder of chunk k+1
         (a latency chain that leaves most of the GPU idle) runs beside it on a second stream, driven
         by a host thread; two engines alternate.  A size the codec does not take as it is: the streams
-        of encode() of such frames, decoded at the coded size and cropped to (n, 3, height, width)."""
+        of encode() of such frames, decoded at the coded size and cropped to (n, 3, height, width).
+        out_size=(H, W): the reconstruction is then resized on the device to H x W by the rule of erp_resample.py,
+        clamped to [0, 1] (the way back of encode(frames, code_size=(height, width)))."""
+        if out_size is not None:
+            return self._at_code_size(self.decode(streams, height, width), out_size)
         if not erp_size.codable(height, width):
             hc, wc, _ = erp_size.coded_size(height, width)
             return erp_size.crop(self.decode(streams, hc, wc), height, width)

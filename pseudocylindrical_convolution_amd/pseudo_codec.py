@@ -37,6 +37,7 @@ from .model_zoo_v2 import ClipData, DecoderV2, EncoderV2
 from . import container
 from .erp_size import coded_size  # noqa: F401  (re-exported beside latent_shape)
 from . import erp_size
+from . import erp_resample
 from . import sphere_metrics
 from . import yuv
 
@@ -212,7 +213,9 @@ class PseudoEncoder(nn.Module):
         header: dict(model_idx=, ssim=) -> the file gets the 16-byte container header
         (container.py) in front of the same payload; None = the reference's raw stream.
         header["size"] = (h, w): x is an h x w frame padded to its coded size (erp_size.py); the
-        header records the original size (container version 2 unless h x w is codable)."""
+        header records the original size (container version 2 unless h x w is codable).
+        header["source"] = (hs, ws): the frame was resized from hs x ws (erp_resample.py); the header records both
+        sizes (container version 3) and the decoder resizes its picture back."""
         with torch.no_grad():
             hcode_i = self.symbols(x)
             eng = _native_engine(self, "enc", hcode_i)
@@ -226,12 +229,12 @@ class PseudoEncoder(nn.Module):
             if header is not None:
                 with open(code_name, "rb") as f:
                     payload = f.read()
-                if "size" in header:
-                    h, w = header["size"]
+                if "size" in header or "source" in header:
+                    h, w = header.get("size", tuple(x.shape[2:]))
                     if erp_size.coded_size(h, w)[:2] != tuple(x.shape[2:]):
                         raise ValueError("frame %s is not the coded size of %dx%d" % (tuple(x.shape[2:]), w, h))
                     container.write_any(code_name, payload, height=h, width=w, model_idx=header["model_idx"],
-                                        ssim=header["ssim"], valid_dim=self.valid_dim)
+                                        ssim=header["ssim"], valid_dim=self.valid_dim, source=header.get("source"))
                 else:
                     container.write(code_name, payload, height=x.shape[2], width=x.shape[3],
                                     model_idx=header["model_idx"], ssim=header["ssim"], valid_dim=self.valid_dim)
@@ -277,7 +280,8 @@ class PseudoDecoder(nn.Module):
         width are read from it; raw=None (default): a file that starts with a valid container
         header is read as one, anything else as a raw stream.  A container of a size the codec does not
         take as it is (version 2) is decoded at its coded size and cropped to the original size
-        (erp_size.py)."""
+        (erp_size.py).  A container that records a source size (version 3) is decoded the same way and then
+        resized to the source size, clamped to [0, 1] (erp_resample.py)."""
         with torch.no_grad():
             payload = None
             if raw is None:
@@ -290,7 +294,12 @@ class PseudoDecoder(nn.Module):
                 height, width = head["height"], head["width"]
                 if not erp_size.codable(height, width):
                     hc, wc, _ = erp_size.coded_size(height, width)
-                    return erp_size.crop(self._decode(code_name, hc, wc, raw, payload), height, width)
+                    rec = erp_size.crop(self._decode(code_name, hc, wc, raw, payload), height, width)
+                else:
+                    rec = self._decode(code_name, height, width, raw, payload)
+                if "source_height" in head:
+                    rec = erp_resample.resize(rec.contiguous(), head["source_height"], head["source_width"], clamp=True)
+                return rec
             return self._decode(code_name, height, width, raw, payload)
 
     def _decode(self, code_name, height, width, raw, payload):
@@ -394,22 +403,41 @@ def bitrate(path, height=512, width=1024):
     return nbytes * 8 / float(width) / float(height)
 
 
+def frame_at_code_size(img, code_size, dev):
+    """uint8 (h, w, 3) image -> float32 (1, 3, H2, W2) on `dev`: img2tensor's division on the device, then the
+    sphere-aware resize of erp_resample.py to code_size = (H2, W2), clamped to [0, 1]"""
+    data = (torch.from_numpy(np.ascontiguousarray(img)).to(dev).permute(2, 0, 1).float() / 255.)[None].contiguous()
+    if tuple(code_size) == tuple(data.shape[2:]):
+        return data
+    return erp_resample.resize(data, code_size[0], code_size[1], clamp=True)
+
+
 def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, boxed=False,
-             native=False):
+             native=False, code_size=None):
     """reference: pseudo_codec.py:236-247.  The files are the reference's headerless streams unless
     boxed=True (--container): then the 16-byte header of container.py goes in front of the same
     payload and the file decodes without any size / model argument.  native=True (--native-size,
     needs boxed): every image is coded at its own size, padded by the pole / seam rule of erp_size.py
-    instead of resized; height / width are ignored."""
+    instead of resized; height / width are ignored.  code_size=(H2, W2) (--code-size, needs boxed, excludes native):
+    every image is resized on the device to H2 x W2 by the sphere-aware rule of erp_resample.py (any size of at
+    least 2 x 2, padded by the pole / seam rule where it is not codable); the file records both sizes (container
+    version 3) and the bitrate counts the source's pixels."""
     if native and not boxed:
         raise ValueError("--native-size needs --container: a headerless file cannot carry the image size")
+    if code_size is not None and (native or not boxed):
+        raise ValueError("--code-size needs --container and excludes --native-size")
     prex, vd, model_dir = _pick(model_idx, mse)
     dev = backend.device_of(device_id)
     t1 = PseudoEncoder(vd, device_id=device_id).to(dev)
     load_models(t1, '{}/{}_encoder.pt'.format(model_dir, prex), '{}/{}_ent.pt'.format(model_dir, prex), dev)
     header = {"model_idx": model_idx, "ssim": not mse} if boxed else None
     for fn, fo in zip(img_list, out_list):
-        if native:
+        if code_size is not None:
+            img = read_image(fn)
+            h, w = img.shape[:2]
+            t1(erp_size.pad(frame_at_code_size(img, code_size, dev)), fo,
+               dict(header, size=tuple(code_size), source=(h, w)))
+        elif native:
             img = read_image(fn)
             h, w = img.shape[:2]
             t1(erp_size.pad(img2tensor(img, dev)), fo, dict(header, size=(h, w)))
@@ -432,14 +460,20 @@ def _decoder_for(code_list, model_idx, mse, device_id, raw):
     return t1, dev, model_idx, mse
 
 
-def _file_geometry(fc, model_idx, mse, height, width, raw):
+def _file_geometry(fc, model_idx, mse, height, width, raw, source=False):
     """(height, width, is_raw) of one code file: from its container header when it has one (which
-    must name the model the decoder was built for), else from the arguments"""
+    must name the model the decoder was built for), else from the arguments.  source=True: the size of the
+    picture the decoder returns -- the source size where the header records one (version 3); source=False
+    refuses such a file"""
     head = None if raw else container.sniff(fc)
     if head is None:
         return height, width, True
     if head["model_idx"] != model_idx or head["ssim"] == mse:
         raise container.ContainerError("%s was coded with another model than the first file of the list" % fc)
+    if "source_height" in head:
+        if not source:
+            raise container.ContainerError("%s was coded at a reduced size (--code-size): decode it to images" % fc)
+        return head["source_height"], head["source_width"], False
     return head["height"], head["width"], False
 
 
@@ -447,7 +481,7 @@ def decoding(code_list, decoded_img_list, model_idx=0, mse=True, device_id=0, he
     """reference: pseudo_codec.py:249-260"""
     t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     for fc, fo in zip(code_list, decoded_img_list):
-        h, w, is_raw = _file_geometry(fc, model_idx, mse, height, width, raw)
+        h, w, is_raw = _file_geometry(fc, model_idx, mse, height, width, raw, source=True)
         write_image(fo, tensor2img(t1(fc, h, w, is_raw)))
         print('Decoding {}, output to {}'.format(fc, fo))
 
@@ -492,13 +526,15 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
                       ws=False):
     """reference: pseudo_codec.py:263-290.  ws=True (--ws): each row also carries the WS-PSNR and WS-SSIM of the
     decoded image as written (tensor2img) against the source at the image's own size: (bpp, vpsnr, vssim, ws_psnr,
-    ws_ssim), with a WS line per image and for the average"""
+    ws_ssim), with a WS line per image and for the average.  A file coded at a reduced size (--code-size, container
+    version 3) is scored end to end: the picture resized back to the source size against the source, bpp over the
+    source's pixels"""
     t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
     rows = []
     for fc, fn in zip(code_list, img_list):
-        h, w, is_raw = _file_geometry(fc, model_idx, mse, height, width, raw)
+        h, w, is_raw = _file_geometry(fc, model_idx, mse, height, width, raw, source=True)
         rdata = t1(fc, h, w, is_raw)
         img = check_img(read_image(fn), h, w)
         data = img2tensor(img, dev)
@@ -517,12 +553,15 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
     return rows
 
 
-def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False):
+def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False,
+                    code_size=None):
     """--rd: what encoding() + decoding_and_test() report for the images, without a file in between.  The rate is
     the code length of the CDF rows the coder would get (rate.py: within a few bits of the stream), the
     reconstruction is the synthesis of the encoder's own symbols -- what the entropy decoder would hand back.
     Needs the native engine (GPU).  native=True (--native-size): every image at its own size, padded by the rule of
-    erp_size.py; otherwise resized to height x width as --enc does.  Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim])."""
+    erp_size.py; otherwise resized to height x width as --enc does.  code_size=(H2, W2) (--code-size): every image is
+    coded at H2 x W2 under the rule of erp_resample.py and scored end to end at its own size, bpp over its own pixels.
+    Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim])."""
     from .engine import CodecEngine
     from . import rate
     prex, vd, model_dir = _pick(model_idx, mse)
@@ -537,11 +576,11 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     rows = []
     for fn in img_list:
         img = read_image(fn)
-        if not native:
+        if not native and code_size is None:
             img = check_img(img, height, width)
         h, w = img.shape[:2]
         data = img2tensor(img, dev)
-        bits, rdata = codec.evaluate(data)
+        bits, rdata = codec.evaluate(data, code_size=code_size)
         pr, vssim = metrics(data, rdata)
         rt = rate.bpp(bits, h, w)[0].item()
         rows.append((rt, pr, vssim))
@@ -688,6 +727,27 @@ def _yuv_flags(parser, args):
     return height, width, dict(fmt=args.pix_fmt, matrix=args.yuv_matrix or "bt709", range=args.yuv_range or "limited")
 
 
+def _code_size_flag(parser, args):
+    """(H2, W2) of --code-size WxH, or None; contradictions end the run with a message (parser.error)"""
+    if args.code_size is None:
+        return None
+    try:
+        width, height = (int(v) for v in args.code_size.lower().split("x"))
+    except ValueError:
+        parser.error("--code-size takes WIDTHxHEIGHT, for example 4096x2048; got %r" % args.code_size)
+    if height < 2 or width < 2 or height > 1 << 20 or width > 1 << 20:
+        parser.error("--code-size %s: each side must be in 2 .. 2^20" % args.code_size)
+    if args.yuv is not None or args.yuv_out is not None:
+        parser.error("--code-size is for images: the YUV path at a reduced size is not supported")
+    if not (args.enc or args.rd):
+        parser.error("--code-size goes with --enc or --rd; --dec and --test read the sizes from the file")
+    if args.native_size:
+        parser.error("--code-size and --native-size are two answers to the same question: give one")
+    if args.enc and not (args.container and not args.raw):
+        parser.error("--code-size needs --container: a headerless file cannot carry the two sizes")
+    return height, width
+
+
 def read_list(fname):
     with open(fname) as f:
         return [line.rstrip('\n') for line in f.readlines()]
@@ -729,6 +789,11 @@ def main(argv=None):
                              '--height/--width are ignored): the frame is padded at the poles and the seam to '
                              'the next codable size and the decoder crops back.  Needs --container '
                              '(--rd: needs nothing, no file is written)')
+    parser.add_argument('--code-size', help='Encoding / --rd: WIDTHxHEIGHT to code every image at, whatever its own size: '
+                                            'the picture is resized on the device by the sphere-aware Lanczos-3 rule '
+                                            '(seam wrapped, poles continued), the file records both sizes, --dec and '
+                                            '--test work at the source size and the bitrate counts the source\'s '
+                                            'pixels.  Needs --container (--rd: nothing), excludes --native-size')
     parser.add_argument('--raw', action='store_true', default=False,
                         help='Decoding: never look for a container header (size and model from the flags)')
     parser.add_argument('--ws', action='store_true', default=False,
@@ -745,6 +810,7 @@ def main(argv=None):
     parser.add_argument('--yuv-matrix', choices=sorted(yuv.MATRICES), help='YCbCr matrix (default bt709)')
     parser.add_argument('--yuv-range', choices=sorted(yuv.RANGES), help='Code value range (default limited)')
     args = parser.parse_args(argv)
+    code_size = _code_size_flag(parser, args)
     yuv_call = _yuv_flags(parser, args)   # contradictory YUV flags end the run here, before anything is loaded
     assert not args.ws or ((args.test or args.rd) and not args.enc and not args.dec), '--ws needs --test or --rd'
     assert not args.rd or not (args.enc or args.dec or args.test), '--rd excludes --enc, --dec and --test'
@@ -775,14 +841,15 @@ def main(argv=None):
                                   ws=args.ws, **common)
     elif args.rd:
         assert img_list is not None, 'No input images for scoring'
-        rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws, **size)
+        rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws,
+                        code_size=code_size, **size)
     elif args.enc:
         assert img_list is not None, 'No input images for encoding'
         assert code_list is not None, 'No code files for saving the codes'
         assert len(img_list) == len(code_list), 'The number of images and codes should be the same'
         assert not args.native_size or (args.container and not args.raw), '--native-size needs --container'
         encoding(img_list, code_list, midx, not args.ssim, args.gpu_id, boxed=args.container and not args.raw,
-                 native=args.native_size, **size)
+                 native=args.native_size, code_size=code_size, **size)
     else:
         assert code_list is not None, 'No code files for decoding'
         if args.dec:
