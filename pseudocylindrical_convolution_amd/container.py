@@ -47,38 +47,57 @@ The command line writes the reference's headerless files unless `--container` is
 decoding recognises a container by `sniff` (magic, version and a payload length that
 matches the file), so headerless files produced by the reference decode as before.
 """
+import collections
 import os
 import struct
 
 MAGIC = b"PCVC"
-VERSION = 1
-HEADER_BYTES = 16
-_FMT = "<4sBBBBHHI"
-VERSION_ANY = 2
-HEADER_BYTES_ANY = 20
-_FMT_ANY = "<4sBBBBIII"
-VERSION_SOURCE = 3
-HEADER_BYTES_SOURCE = 28
-_FMT_SOURCE = "<4sBBBBIIIII"
+VERSION, VERSION_ANY, VERSION_SOURCE = 1, 2, 3
+# per version: the struct format (magic, version, flags, model index, ngroup, sizes ..., payload length), what one
+# count of the height / width fields stands for, and whether a source size follows them
+_Layout = collections.namedtuple("_Layout", "fmt unit source")
+_LAYOUT = {VERSION: _Layout("<4sBBBBHHI", 16, False),
+           VERSION_ANY: _Layout("<4sBBBBIII", 1, False),
+           VERSION_SOURCE: _Layout("<4sBBBBIIIII", 1, True)}
+HEADER_BYTES, HEADER_BYTES_ANY, HEADER_BYTES_SOURCE = (struct.calcsize(_LAYOUT[v].fmt) for v in sorted(_LAYOUT))
 
 
 class ContainerError(ValueError):
     pass
 
 
-def pack(payload, height, width, model_idx, ssim, valid_dim):
-    """header + payload"""
-    if height % 16 or width % 16 or not (0 < height // 16 < 65536 and 0 < width // 16 < 65536):
-        raise ContainerError("ERP size %dx%d does not fit the header (multiples of 16, < 2^20)" % (width, height))
+def _misfit(version, height, width, source, model_idx, valid_dim, nbytes):
+    """why the fields do not fit a header of `version`, or None: the one check of pack, pack_any and _parse"""
+    side = lambda v: 2 <= v <= 1 << 20
+    if source is not None and not (side(source[0]) and side(source[1])):
+        return "source size %dx%d does not fit the header (2 .. 2^20 per side)" % (source[1], source[0])
+    if _LAYOUT[version].unit == 16:
+        if height % 16 or width % 16 or not (0 < height // 16 < 65536 and 0 < width // 16 < 65536):
+            return "ERP size %dx%d does not fit the header (multiples of 16, < 2^20)" % (width, height)
+    elif not (side(height) and side(width)):
+        return "ERP size %dx%d does not fit the header (2 .. 2^20 per side)" % (width, height)
     if valid_dim % 4 or not 0 < valid_dim // 4 < 256:
-        raise ContainerError("valid_dim %d does not fit the header" % valid_dim)
+        return "valid_dim %d does not fit the header" % valid_dim
     if not 0 <= model_idx < 256:
-        raise ContainerError("model index %d does not fit the header" % model_idx)
-    if len(payload) >= 1 << 32:
-        raise ContainerError("payload too long")
-    head = struct.pack(_FMT, MAGIC, VERSION, 1 if ssim else 0, model_idx, valid_dim // 4, height // 16, width // 16,
-                       len(payload))
-    return head + bytes(payload)
+        return "model index %d does not fit the header" % model_idx
+    if nbytes >= 1 << 32:
+        return "payload too long"
+    return None
+
+
+def _pack(version, payload, height, width, model_idx, ssim, valid_dim, source=None):
+    why = _misfit(version, height, width, source, model_idx, valid_dim, len(payload))
+    if why:
+        raise ContainerError(why)
+    layout = _LAYOUT[version]
+    sizes = (height // layout.unit, width // layout.unit) + (tuple(source) if layout.source else ())
+    return struct.pack(layout.fmt, MAGIC, version, 1 if ssim else 0, model_idx, valid_dim // 4, *sizes,
+                       len(payload)) + bytes(payload)
+
+
+def pack(payload, height, width, model_idx, ssim, valid_dim):
+    """header + payload, version 1"""
+    return _pack(VERSION, payload, height, width, model_idx, ssim, valid_dim)
 
 
 def pack_any(payload, height, width, model_idx, ssim, valid_dim, source=None):
@@ -86,27 +105,12 @@ def pack_any(payload, height, width, model_idx, ssim, valid_dim, source=None):
     is, else version 2 with the exact size (coded at erp_size.coded_size under the padding rule).
     source=(hs, ws) != (height, width): version 3, which also records the size the content was resized from"""
     from .erp_size import codable
-    if source is not None and (int(source[0]), int(source[1])) == (height, width):
-        source = None
-    if source is None and codable(height, width):
-        return pack(payload, height, width, model_idx, ssim, valid_dim)
-    if source is not None and not (2 <= int(source[0]) <= 1 << 20 and 2 <= int(source[1]) <= 1 << 20):
-        raise ContainerError("source size %dx%d does not fit the header (2 .. 2^20 per side)" % (source[1], source[0]))
-    if not (2 <= height <= 1 << 20 and 2 <= width <= 1 << 20):
-        raise ContainerError("ERP size %dx%d does not fit the header (2 .. 2^20 per side)" % (width, height))
-    if valid_dim % 4 or not 0 < valid_dim // 4 < 256:
-        raise ContainerError("valid_dim %d does not fit the header" % valid_dim)
-    if not 0 <= model_idx < 256:
-        raise ContainerError("model index %d does not fit the header" % model_idx)
-    if len(payload) >= 1 << 32:
-        raise ContainerError("payload too long")
     if source is not None:
-        head = struct.pack(_FMT_SOURCE, MAGIC, VERSION_SOURCE, 1 if ssim else 0, model_idx, valid_dim // 4, height,
-                           width, int(source[0]), int(source[1]), len(payload))
-        return head + bytes(payload)
-    head = struct.pack(_FMT_ANY, MAGIC, VERSION_ANY, 1 if ssim else 0, model_idx, valid_dim // 4, height, width,
-                       len(payload))
-    return head + bytes(payload)
+        source = (int(source[0]), int(source[1]))
+    if source is None or source == (height, width):
+        return _pack(VERSION if codable(height, width) else VERSION_ANY, payload, height, width, model_idx, ssim,
+                     valid_dim)
+    return _pack(VERSION_SOURCE, payload, height, width, model_idx, ssim, valid_dim, source)
 
 
 def _parse(head, size):
@@ -116,37 +120,21 @@ def _parse(head, size):
     if head[:4] != MAGIC:
         return "no container magic: a headerless reference-format stream?"
     version = head[4]
-    source = None
-    if version == VERSION:
-        magic, version, flags, model_idx, ngroup, h16, w16, n = struct.unpack(_FMT, head[:HEADER_BYTES])
-        nhead, height, width = HEADER_BYTES, h16 * 16, w16 * 16
-    elif version == VERSION_ANY:
-        if len(head) < HEADER_BYTES_ANY:
-            return "file shorter than the %d-byte version-2 header" % HEADER_BYTES_ANY
-        magic, version, flags, model_idx, ngroup, height, width, n = struct.unpack(_FMT_ANY, head[:HEADER_BYTES_ANY])
-        nhead = HEADER_BYTES_ANY
-        if not (2 <= height <= 1 << 20 and 2 <= width <= 1 << 20):
-            return "ERP size %dx%d in the header is out of range" % (width, height)
-    elif version == VERSION_SOURCE:
-        if len(head) < HEADER_BYTES_SOURCE:
-            return "file shorter than the %d-byte version-3 header" % HEADER_BYTES_SOURCE
-        magic, version, flags, model_idx, ngroup, height, width, hs, ws, n = struct.unpack(
-            _FMT_SOURCE, head[:HEADER_BYTES_SOURCE])
-        nhead = HEADER_BYTES_SOURCE
-        if not (2 <= height <= 1 << 20 and 2 <= width <= 1 << 20):
-            return "ERP size %dx%d in the header is out of range" % (width, height)
-        if not (2 <= hs <= 1 << 20 and 2 <= ws <= 1 << 20):
-            return "source size %dx%d in the header is out of range" % (ws, hs)
-        source = (hs, ws)
-    else:
+    if version not in _LAYOUT:
         return "container version %d, this build reads %d, %d and %d" % (version, VERSION, VERSION_ANY, VERSION_SOURCE)
+    layout = _LAYOUT[version]
+    nhead = struct.calcsize(layout.fmt)
+    if len(head) < nhead:
+        return "file shorter than the %d-byte version-%d header" % (nhead, version)
+    _, _, flags, model_idx, ngroup, h, w, *source, n = struct.unpack(layout.fmt, head[:nhead])
+    fields = {"height": h * layout.unit, "width": w * layout.unit, "model_idx": model_idx, "ssim": bool(flags & 1),
+              "valid_dim": ngroup * 4}
+    why = _misfit(version, fields["height"], fields["width"], source or None, model_idx, ngroup * 4, size - nhead)
+    if why:
+        return why
     if size - nhead != n:
         return "payload is %d bytes, header says %d" % (size - nhead, n)
-    if not (height and width and ngroup):
-        return "empty field in the header"
-    fields = {"height": height, "width": width, "model_idx": model_idx, "ssim": bool(flags & 1),
-              "valid_dim": ngroup * 4}
-    if source is not None:
+    if source:
         fields["source_height"], fields["source_width"] = source
     return fields, nhead
 

@@ -18,9 +18,8 @@ from . import _native
 from ._native import PconvError, call
 from .PCONV_operator import backend, set_weight
 from . import pseudo_codec as PC
-from . import erp_size
-from . import erp_resample
 from . import yuv
+from .frame_geometry import FrameGeometry
 
 
 class EntropyEngine(object):
@@ -310,9 +309,7 @@ class CodecEngine(object):
         (erp_size.py: poles and seam); decode(streams, h, w) crops back.  code_size=(h2, w2): the frames are
         first resized on the device to h2 x w2 by the sphere-aware rule of erp_resample.py, clamped to [0, 1];
         decode(streams, h2, w2, out_size=(H, W)) brings the reconstruction back to the source size."""
-        frames = self._at_code_size(frames, code_size)
-        if not erp_size.codable(frames.shape[2], frames.shape[3]):
-            frames = erp_size.pad(frames)
+        frames = FrameGeometry(frames.shape[2:], code_size).to_coded(frames)
         n = frames.shape[0]
         chunk = self.ENCODE_CHUNK if n > self.ENCODE_CHUNK else n
         tiles = self.enc.ent.npart
@@ -351,14 +348,6 @@ class CodecEngine(object):
             self._phase("entropy_encode", t1, self._mark())
         return out
 
-    @staticmethod
-    def _at_code_size(frames, code_size):
-        """frames resized to code_size = (h2, w2) with the clamp (erp_resample.py); None or the frames' own size:
-        the frames as they are"""
-        if code_size is None or tuple(int(v) for v in code_size) == tuple(frames.shape[2:]):
-            return frames
-        return erp_resample.resize(frames, int(code_size[0]), int(code_size[1]), clamp=True)
-
     def _rate_of_symbols(self, sym, n, rate_map):
         """bits (n, npart, ngroup) [, map] of the symbols of n frames, through the chunks -- and the engines --
         encode() takes them through"""
@@ -382,8 +371,7 @@ class CodecEngine(object):
         copy to the host, no file.  rate.bpp(bits, H, W) is the frame rate.  rate_map=True: also the bits of every
         latent position, (n, npart*2h, 2w) float32.  Sizes the codec does not take as they are are padded as
         encode() pads them (their bpp still counts their own pixels)."""
-        if not erp_size.codable(frames.shape[2], frames.shape[3]):
-            frames = erp_size.pad(frames)
+        frames = FrameGeometry(frames.shape[2:]).to_coded(frames)
         return self._rate_of_symbols(self.symbols(frames).contiguous(), frames.shape[0], rate_map)
 
     @torch.no_grad()
@@ -393,19 +381,12 @@ class CodecEngine(object):
         returns exactly the symbols the encoder holds (tests/test_gpu_engine.py), so neither it nor the arithmetic
         coder has to run.  code_size=(h2, w2): the frames are coded at h2 x w2 (resized as encode() resizes them) and
         the reconstruction is returned at the frames' own size, resized back with the clamp: the end-to-end point."""
-        source = tuple(frames.shape[2:])
-        frames = self._at_code_size(frames, code_size)
-        height, width = frames.shape[2], frames.shape[3]
-        native = erp_size.codable(height, width)
-        if not native:
-            frames = erp_size.pad(frames)
+        geometry = FrameGeometry(frames.shape[2:], code_size)
+        frames = geometry.to_coded(frames)
         n = frames.shape[0]
         sym = self.symbols(frames).contiguous()
         res = self._rate_of_symbols(sym, n, rate_map)
-        rec = self.reconstruct(sym, n)
-        if not native:
-            rec = erp_size.crop(rec, height, width)
-        rec = self._at_code_size(rec, source)
+        rec = geometry.from_coded(self.reconstruct(sym, n))
         return (res[0], rec, res[1]) if rate_map else (res, rec)
 
     # frames per pipeline stage of decode(); 0 = decode all frames of a call together, then run the
@@ -421,12 +402,8 @@ class CodecEngine(object):
         of encode() of such frames, decoded at the coded size and cropped to (n, 3, height, width).
         out_size=(H, W): the reconstruction is then resized on the device to H x W by the rule of erp_resample.py,
         clamped to [0, 1] (the way back of encode(frames, code_size=(height, width)))."""
-        if out_size is not None:
-            return self._at_code_size(self.decode(streams, height, width), out_size)
-        if not erp_size.codable(height, width):
-            hc, wc, _ = erp_size.coded_size(height, width)
-            return erp_size.crop(self.decode(streams, hc, wc), height, width)
-        h, w = PC.latent_shape(height, width, self.dec.npart)
+        geometry = FrameGeometry((height, width) if out_size is None else out_size, (height, width))
+        h, w = PC.latent_shape(*geometry.coded, self.dec.npart)
         n = len(streams)
         tiles = self.dec.npart
         chunk = self.DECODE_CHUNK
@@ -437,7 +414,7 @@ class CodecEngine(object):
             rec = self.reconstruct(sym, n)
             self._phase("entropy_decode", t0, t1)
             self._phase("synthesis", t1, self._mark())
-            return rec
+            return geometry.from_coded(rec)
         chunks = [streams[i:i + chunk] for i in range(0, n, chunk)]
         side = torch.cuda.Stream(device=self.device)
         box = {}
@@ -465,7 +442,7 @@ class CodecEngine(object):
             out.append(self.reconstruct(sym, len(chunks[k])))
             if worker is not None:
                 worker.join()
-        return torch.cat(out, 0)
+        return geometry.from_coded(torch.cat(out, 0))
 
 
 class FramePipe(object):
@@ -499,8 +476,9 @@ class FramePipe(object):
             pad = True   # the YUV kernels work at the coded size (the identity for a codable one)
         elif pad is None:
             pad = self.w % 4 != 0
-        self.native = pix_fmt is None and (not pad or erp_size.codable(self.h, self.w))
-        self.coded = (self.h, self.w) if self.native else erp_size.coded_size(self.h, self.w)[:2]
+        geometry = FrameGeometry((self.h, self.w))
+        self.native = pix_fmt is None and not (pad and geometry.padded)
+        self.coded = (self.h, self.w) if self.native else geometry.coded
         self.device = torch.device(device)
         self.ops = backend.ops()
         need = "frames_yuv420_to_f32" if pix_fmt is not None else ("frames_u8_to_f32" if self.native else "frames_u8_to_f32_erp")

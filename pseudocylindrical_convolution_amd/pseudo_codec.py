@@ -36,10 +36,9 @@ from .PCONV_operator import (DExtract2, DExtract2Batch, DInput2, Dtow, EntropyAd
 from .model_zoo_v2 import ClipData, DecoderV2, EncoderV2
 from . import container
 from .erp_size import coded_size  # noqa: F401  (re-exported beside latent_shape)
-from . import erp_size
-from . import erp_resample
 from . import sphere_metrics
 from . import yuv
+from .frame_geometry import FrameGeometry
 
 psnr_f = lambda xa: 10 * math.log10(1. / xa)
 
@@ -205,39 +204,40 @@ class PseudoEncoder(nn.Module):
             _, code_i = self.quant(self.encoder(self.slice(x)))
             return self.dtw(self.ext(code_i))
 
-    def forward(self, x, code_name, header=None):
+    def forward(self, x, code_name, header=None, geometry=None):
         """x -> code file.  On the GPU the entropy stage runs on the native engine
         (engine.EntropyEngine: one launch per layer over all wavefront steps); the file is
         byte for byte what the op-by-op loop of `forward_per_op` writes
         (tests/test_gpu_engine.py).  PCONV_ENTROPY=per-op forces the loop.
-        header: dict(model_idx=, ssim=) -> the file gets the 16-byte container header
-        (container.py) in front of the same payload; None = the reference's raw stream.
-        header["size"] = (h, w): x is an h x w frame padded to its coded size (erp_size.py); the
-        header records the original size (container version 2 unless h x w is codable).
-        header["source"] = (hs, ws): the frame was resized from hs x ws (erp_resample.py); the header records both
-        sizes (container version 3) and the decoder resizes its picture back."""
+        header: dict(model_idx=, ssim=) -> the file gets the container header (container.py) in front of
+        the same payload; None = the reference's raw stream.
+        geometry: the FrameGeometry x is the coded frame of (frame_geometry.py) -- x was padded from, or resized
+        and padded from, another size, which the header then records (container version 2 or 3) and the decoder
+        returns to; None = x is the picture itself."""
         with torch.no_grad():
+            if header is not None:
+                if geometry is None:
+                    geometry = FrameGeometry(x.shape[2:])
+                if geometry.coded != tuple(x.shape[2:]):
+                    raise ValueError("frame %s is not the coded size of %dx%d"
+                                     % (tuple(x.shape[2:]), geometry.content[1], geometry.content[0]))
             hcode_i = self.symbols(x)
             eng = _native_engine(self, "enc", hcode_i)
-            if eng is None:
+            if eng is None:   # the coder module writes the file itself: a header goes in front of what it wrote
                 self.ent.start(code_name)
                 self.ent(hcode_i)
-            else:
-                stream = eng.encode(self.ent.fill(hcode_i).contiguous())[0]
-                with open(code_name, "wb") as f:
-                    f.write(stream)
-            if header is not None:
+                if header is None:
+                    return
                 with open(code_name, "rb") as f:
                     payload = f.read()
-                if "size" in header or "source" in header:
-                    h, w = header.get("size", tuple(x.shape[2:]))
-                    if erp_size.coded_size(h, w)[:2] != tuple(x.shape[2:]):
-                        raise ValueError("frame %s is not the coded size of %dx%d" % (tuple(x.shape[2:]), w, h))
-                    container.write_any(code_name, payload, height=h, width=w, model_idx=header["model_idx"],
-                                        ssim=header["ssim"], valid_dim=self.valid_dim, source=header.get("source"))
-                else:
-                    container.write(code_name, payload, height=x.shape[2], width=x.shape[3],
-                                    model_idx=header["model_idx"], ssim=header["ssim"], valid_dim=self.valid_dim)
+            else:
+                payload = eng.encode(self.ent.fill(hcode_i).contiguous())[0]
+            if header is None:
+                with open(code_name, "wb") as f:
+                    f.write(payload)
+            else:
+                container.write_any(code_name, payload, model_idx=header["model_idx"], ssim=header["ssim"],
+                                    valid_dim=self.valid_dim, **geometry.header_fields())
 
     def forward_per_op(self, x, code_name):
         """the reference's loop (pseudo_codec.py:97-114): ~36 op calls per wavefront step"""
@@ -278,29 +278,31 @@ class PseudoDecoder(nn.Module):
         (see PseudoEncoder.forward).  raw=True: the reference's headerless stream, size from the
         arguments; raw=False: the file carries the container header (container.py) and height /
         width are read from it; raw=None (default): a file that starts with a valid container
-        header is read as one, anything else as a raw stream.  A container of a size the codec does not
-        take as it is (version 2) is decoded at its coded size and cropped to the original size
-        (erp_size.py).  A container that records a source size (version 3) is decoded the same way and then
+        header is read as one, anything else as a raw stream.  A size the codec does not take as it is
+        (container version 2) is decoded at its coded size and cropped to the original size (erp_size.py).
+        A container that records a source size (version 3) is decoded the same way and then
         resized to the source size, clamped to [0, 1] (erp_resample.py)."""
-        with torch.no_grad():
-            payload = None
-            if raw is None:
-                raw = container.sniff(code_name) is None
-            if not raw:
-                head, payload = container.read(code_name)
-                if head["valid_dim"] != self.valid_dim:
-                    raise container.ContainerError("file was coded with valid_dim %d, this decoder has %d"
-                                                   % (head["valid_dim"], self.valid_dim))
-                height, width = head["height"], head["width"]
-                if not erp_size.codable(height, width):
-                    hc, wc, _ = erp_size.coded_size(height, width)
-                    rec = erp_size.crop(self._decode(code_name, hc, wc, raw, payload), height, width)
-                else:
-                    rec = self._decode(code_name, height, width, raw, payload)
-                if "source_height" in head:
-                    rec = erp_resample.resize(rec.contiguous(), head["source_height"], head["source_width"], clamp=True)
-                return rec
-            return self._decode(code_name, height, width, raw, payload)
+        rec, geometry = self.decode_coded(code_name, height, width, raw)
+        return geometry.from_coded(rec)
+
+    def decode_coded(self, code_name, height=512, width=1024, raw=None):
+        """(reconstruction at the coded size, FrameGeometry) of a code file, raw as in forward(): the geometry is the
+        header's for a container, FrameGeometry.for_raw(height, width) for a headerless stream;
+        geometry.from_coded(reconstruction) is the picture"""
+        payload = None
+        if raw is None:
+            raw = container.sniff(code_name) is None
+        if raw:
+            if height is None or width is None:
+                raise ValueError("%s has no container header: its frame size must be given (--size WxH)" % code_name)
+            geometry = FrameGeometry.for_raw(height, width)
+        else:
+            head, payload = container.read(code_name)
+            if head["valid_dim"] != self.valid_dim:
+                raise container.ContainerError("file was coded with valid_dim %d, this decoder has %d"
+                                               % (head["valid_dim"], self.valid_dim))
+            geometry = FrameGeometry.from_header(head)
+        return self._decode(code_name, geometry.coded[0], geometry.coded[1], raw, payload), geometry
 
     def _decode(self, code_name, height, width, raw, payload):
         with torch.no_grad():
@@ -390,10 +392,16 @@ def load_models(model, p1, p2, device):
     model.load_state_dict(merged)
 
 
-def _pick(model_idx, mse):
+def _load(kind, model_idx, mse, device_id):
+    """(PseudoEncoder for kind "encoder" or PseudoDecoder for "decoder" of a model of the VMSE / VSSIM list, on its
+    device and with its checkpoint loaded; that device)"""
     prex = model_mse_list[model_idx] if mse else model_ssim_list[model_idx]
     vd = mse_channel_list[model_idx] if mse else ssim_channel_list[model_idx]
-    return prex, vd, (mse_model_dir if mse else ssim_model_dir)
+    model_dir = mse_model_dir if mse else ssim_model_dir
+    dev = backend.device_of(device_id)
+    model = {"encoder": PseudoEncoder, "decoder": PseudoDecoder}[kind](vd, device_id=device_id).to(dev)
+    load_models(model, '{}/{}_{}.pt'.format(model_dir, prex, kind), '{}/{}_ent.pt'.format(model_dir, prex), dev)
+    return model, dev
 
 
 def bitrate(path, height=512, width=1024):
@@ -403,13 +411,11 @@ def bitrate(path, height=512, width=1024):
     return nbytes * 8 / float(width) / float(height)
 
 
-def frame_at_code_size(img, code_size, dev):
-    """uint8 (h, w, 3) image -> float32 (1, 3, H2, W2) on `dev`: img2tensor's division on the device, then the
-    sphere-aware resize of erp_resample.py to code_size = (H2, W2), clamped to [0, 1]"""
-    data = (torch.from_numpy(np.ascontiguousarray(img)).to(dev).permute(2, 0, 1).float() / 255.)[None].contiguous()
-    if tuple(code_size) == tuple(data.shape[2:]):
-        return data
-    return erp_resample.resize(data, code_size[0], code_size[1], clamp=True)
+def img2tensor_on_device(img, device):
+    """img2tensor with the division on `device`: the uint8 pixels cross the bus.  NOT the same bits on a GPU, where
+    torch divides by a scalar as a multiplication by float32(1 / 255.) (126 of the 256 values are one ulp off the
+    host's quotient); --code-size has coded this tensor since its first file, so it keeps it"""
+    return (torch.from_numpy(np.ascontiguousarray(img)).to(device).permute(2, 0, 1).float() / 255.)[None].contiguous()
 
 
 def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, boxed=False,
@@ -426,25 +432,16 @@ def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512,
         raise ValueError("--native-size needs --container: a headerless file cannot carry the image size")
     if code_size is not None and (native or not boxed):
         raise ValueError("--code-size needs --container and excludes --native-size")
-    prex, vd, model_dir = _pick(model_idx, mse)
-    dev = backend.device_of(device_id)
-    t1 = PseudoEncoder(vd, device_id=device_id).to(dev)
-    load_models(t1, '{}/{}_encoder.pt'.format(model_dir, prex), '{}/{}_ent.pt'.format(model_dir, prex), dev)
+    t1, dev = _load("encoder", model_idx, mse, device_id)
     header = {"model_idx": model_idx, "ssim": not mse} if boxed else None
     for fn, fo in zip(img_list, out_list):
-        if code_size is not None:
-            img = read_image(fn)
-            h, w = img.shape[:2]
-            t1(erp_size.pad(frame_at_code_size(img, code_size, dev)), fo,
-               dict(header, size=tuple(code_size), source=(h, w)))
-        elif native:
-            img = read_image(fn)
-            h, w = img.shape[:2]
-            t1(erp_size.pad(img2tensor(img, dev)), fo, dict(header, size=(h, w)))
-        else:
-            h, w = height, width
-            t1(img2tensor(check_img(read_image(fn), height, width), dev), fo, header)
-        print('Encoding {}, bitrate: {:.3f}bpp'.format(fn, bitrate(fo, h, w)))
+        img = read_image(fn)
+        if not native and code_size is None:
+            img = check_img(img, height, width)
+        geometry = FrameGeometry(img.shape[:2], code_size)
+        data = img2tensor(img, dev) if code_size is None else img2tensor_on_device(img, dev)
+        t1(geometry.to_coded(data), fo, header, geometry)
+        print('Encoding {}, bitrate: {:.3f}bpp'.format(fn, bitrate(fo, *geometry.source)))
 
 
 def _decoder_for(code_list, model_idx, mse, device_id, raw):
@@ -453,36 +450,28 @@ def _decoder_for(code_list, model_idx, mse, device_id, raw):
     head = None if raw else container.sniff(code_list[0])
     if head is not None:
         model_idx, mse = head["model_idx"], not head["ssim"]
-    prex, vd, model_dir = _pick(model_idx, mse)
-    dev = backend.device_of(device_id)
-    t1 = PseudoDecoder(vd, device_id=device_id).to(dev)
-    load_models(t1, '{}/{}_decoder.pt'.format(model_dir, prex), '{}/{}_ent.pt'.format(model_dir, prex), dev)
-    return t1, dev, model_idx, mse
+    return _load("decoder", model_idx, mse, device_id) + (model_idx, mse)
 
 
-def _file_geometry(fc, model_idx, mse, height, width, raw, source=False):
-    """(height, width, is_raw) of one code file: from its container header when it has one (which
-    must name the model the decoder was built for), else from the arguments.  source=True: the size of the
-    picture the decoder returns -- the source size where the header records one (version 3); source=False
-    refuses such a file"""
+def _decode_file(t1, fc, model_idx, mse, height, width, raw, to_source=True):
+    """(reconstruction at the coded size, FrameGeometry) of one code file of a list: the sizes from its container
+    header when it has one (which must name the model the decoder was built for), else from the arguments.
+    to_source=False refuses a file whose picture has to be resized back (version 3)"""
     head = None if raw else container.sniff(fc)
-    if head is None:
-        return height, width, True
-    if head["model_idx"] != model_idx or head["ssim"] == mse:
-        raise container.ContainerError("%s was coded with another model than the first file of the list" % fc)
-    if "source_height" in head:
-        if not source:
+    if head is not None:
+        if head["model_idx"] != model_idx or head["ssim"] == mse:
+            raise container.ContainerError("%s was coded with another model than the first file of the list" % fc)
+        if "source_height" in head and not to_source:
             raise container.ContainerError("%s was coded at a reduced size (--code-size): decode it to images" % fc)
-        return head["source_height"], head["source_width"], False
-    return head["height"], head["width"], False
+    return t1.decode_coded(fc, height, width, raw=head is None)
 
 
 def decoding(code_list, decoded_img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False):
     """reference: pseudo_codec.py:249-260"""
-    t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
+    t1, _, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     for fc, fo in zip(code_list, decoded_img_list):
-        h, w, is_raw = _file_geometry(fc, model_idx, mse, height, width, raw, source=True)
-        write_image(fo, tensor2img(t1(fc, h, w, is_raw)))
+        rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw)
+        write_image(fo, tensor2img(geometry.from_coded(rec)))
         print('Decoding {}, output to {}'.format(fc, fo))
 
 
@@ -522,6 +511,23 @@ class SphericalMetrics(object):
         return sphere_metrics.psnr(wmse), wssim
 
 
+_VIEWPORT = 'Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'
+_WS = 'WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'
+_WS_YUV = 'WS-PSNR-Y:{:.2f}dB, WS-PSNR-U:{:.2f}dB, WS-PSNR-V:{:.2f}dB'
+
+
+def _report(rows, lines):
+    """print the 'Average Performance' block of --test / --rd: the column averages of `rows`, each format string of
+    `lines` taking the next columns it has fields for; returns rows"""
+    print('-' * 53 + '\nAverage Performance\n' + '-' * 53)
+    avg = list(np.average(np.array(rows), axis=0))
+    for line in lines:
+        n = line.count('{')
+        print(line.format(*avg[:n]))
+        avg = avg[n:]
+    return rows
+
+
 def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False,
                       ws=False):
     """reference: pseudo_codec.py:263-290.  ws=True (--ws): each row also carries the WS-PSNR and WS-SSIM of the
@@ -534,23 +540,17 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
     spherical = SphericalMetrics(device_id) if ws else None
     rows = []
     for fc, fn in zip(code_list, img_list):
-        h, w, is_raw = _file_geometry(fc, model_idx, mse, height, width, raw, source=True)
-        rdata = t1(fc, h, w, is_raw)
-        img = check_img(read_image(fn), h, w)
-        data = img2tensor(img, dev)
-        pr, vssim = metrics(data, rdata)
-        rt = bitrate(fc, h, w)
+        rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw)
+        rdata = geometry.from_coded(rec)
+        img = check_img(read_image(fn), *geometry.source)
+        pr, vssim = metrics(img2tensor(img, dev), rdata)
+        rt = bitrate(fc, *geometry.source)
         rows.append((rt, pr, vssim))
-        print('Decoding {}, compare it to {} \n Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(fc, fn, rt, pr, vssim))
+        print(('Decoding {}, compare it to {} \n ' + _VIEWPORT).format(fc, fn, rt, pr, vssim))
         if ws:
             rows[-1] += spherical(img, tensor2img(rdata))
-            print(' WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*rows[-1][3:]))
-    print('-' * 53 + '\nAverage Performance\n' + '-' * 53)
-    avg = np.average(np.array(rows), axis=0)
-    print('Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(*avg[:3]))
-    if ws:
-        print('WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*avg[3:]))
-    return rows
+            print(' ' + _WS.format(*rows[-1][3:]))
+    return _report(rows, [_VIEWPORT, _WS] if ws else [_VIEWPORT])
 
 
 def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False,
@@ -564,13 +564,8 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim])."""
     from .engine import CodecEngine
     from . import rate
-    prex, vd, model_dir = _pick(model_idx, mse)
-    dev = backend.device_of(device_id)
-    enc = PseudoEncoder(vd, device_id=device_id).to(dev)
-    load_models(enc, '{}/{}_encoder.pt'.format(model_dir, prex), '{}/{}_ent.pt'.format(model_dir, prex), dev)
-    dec = PseudoDecoder(vd, device_id=device_id).to(dev)
-    load_models(dec, '{}/{}_decoder.pt'.format(model_dir, prex), '{}/{}_ent.pt'.format(model_dir, prex), dev)
-    codec = CodecEngine(vd, device_id, enc, dec)
+    (enc, dev), (dec, _) = _load("encoder", model_idx, mse, device_id), _load("decoder", model_idx, mse, device_id)
+    codec = CodecEngine(enc.valid_dim, device_id, enc, dec)
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
     rows = []
@@ -587,13 +582,8 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
         print('Estimating {} \n Bitrate:{:.3f}bpp (tables), PSNR:{:.2f}dB, SSIM:{:.4f}'.format(fn, rt, pr, vssim))
         if ws:
             rows[-1] += spherical(img, tensor2img(rdata))
-            print(' WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*rows[-1][3:]))
-    print('-' * 53 + '\nAverage Performance\n' + '-' * 53)
-    avg = np.average(np.array(rows), axis=0)
-    print('Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(*avg[:3]))
-    if ws:
-        print('WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*avg[3:]))
-    return rows
+            print(' ' + _WS.format(*rows[-1][3:]))
+    return _report(rows, [_VIEWPORT, _WS] if ws else [_VIEWPORT])
 
 
 def _yuv_rgb(frames, h, w, yuv_opts, dev):
@@ -611,38 +601,21 @@ def encoding_yuv(path, out_list, height, width, yuv_opts, start=0, model_idx=0, 
     """--enc --yuv: frames start .. start+len(out_list)-1 of a raw .yuv file of height x width, one code file each.
     Every frame is coded at its own size (converted and padded to the coded size in one pass, yuv.to_rgb);
     boxed=True (--container) records that size, a headerless file is decoded with --size."""
-    prex, vd, model_dir = _pick(model_idx, mse)
-    dev = backend.device_of(device_id)
-    t1 = PseudoEncoder(vd, device_id=device_id).to(dev)
-    load_models(t1, '{}/{}_encoder.pt'.format(model_dir, prex), '{}/{}_ent.pt'.format(model_dir, prex), dev)
-    header = {"model_idx": model_idx, "ssim": not mse, "size": (height, width)} if boxed else None
+    t1, dev = _load("encoder", model_idx, mse, device_id)
+    header = {"model_idx": model_idx, "ssim": not mse} if boxed else None
+    geometry = FrameGeometry((height, width))
     frames = yuv.read_frames(path, height, width, yuv_opts["fmt"], start, len(out_list))
     for k, fo in enumerate(out_list):
-        t1(_yuv_rgb(frames[k:k + 1], height, width, yuv_opts, dev), fo, header)
-        print('Encoding {} frame {}, bitrate: {:.3f}bpp'.format(path, start + k, bitrate(fo, height, width)))
-
-
-def _decode_coded(t1, fc, model_idx, mse, height, width, raw):
-    """(reconstruction at the CODED size, height, width) of one code file: the size from its container header when
-    it has one, else from the arguments"""
-    h, w, is_raw = _file_geometry(fc, model_idx, mse, height, width, raw)
-    if h is None or w is None:
-        raise ValueError("%s has no container header: its frame size must be given (--size WxH)" % fc)
-    hc, wc, _ = erp_size.coded_size(h, w)
-    payload = None
-    if not is_raw:
-        head, payload = container.read(fc)
-        if head["valid_dim"] != t1.valid_dim:
-            raise container.ContainerError("file was coded with valid_dim %d, this decoder has %d"
-                                           % (head["valid_dim"], t1.valid_dim))
-    return t1._decode(fc, hc, wc, is_raw, payload), h, w
+        t1(_yuv_rgb(frames[k:k + 1], height, width, yuv_opts, dev), fo, header, geometry)
+        print('Encoding {} frame {}, bitrate: {:.3f}bpp'.format(path, start + k, bitrate(fo, *geometry.source)))
 
 
 def decoding_yuv(code_list, path, yuv_opts, height=None, width=None, model_idx=0, mse=True, device_id=0, raw=False):
     """--dec --yuv-out: every code file becomes one frame of the raw .yuv file `path`, in the order of the list"""
-    t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
+    t1, _, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     for k, fc in enumerate(code_list):
-        rec, h, w = _decode_coded(t1, fc, model_idx, mse, height, width, raw)
+        rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw, to_source=False)
+        h, w = geometry.content
         yuv.write_frames(path, _rgb_yuv(rec, h, w, yuv_opts), h, w, yuv_opts["fmt"], append=k > 0)
         print('Decoding {}, output to {} frame {}'.format(fc, path, k))
 
@@ -658,29 +631,32 @@ def decoding_and_test_yuv(code_list, path, height, width, yuv_opts, start=0, mod
     frames = yuv.read_frames(path, height, width, yuv_opts["fmt"], start, len(code_list))
     rows = []
     for k, fc in enumerate(code_list):
-        rec, h, w = _decode_coded(t1, fc, model_idx, mse, height, width, raw)
+        rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw, to_source=False)
+        h, w = geometry.content
         if (h, w) != (height, width):
             raise ValueError("%s holds a %dx%d frame, --size says %dx%d" % (fc, w, h, width, height))
         src = frames[k:k + 1].to(dev)
-        data, rdata = erp_size.crop(_yuv_rgb(src, h, w, yuv_opts, dev), h, w), erp_size.crop(rec, h, w)
+        data, rdata = geometry.from_coded(_yuv_rgb(src, h, w, yuv_opts, dev)), geometry.from_coded(rec)
         pr, vssim = metrics(data, rdata)
-        rt = bitrate(fc, h, w)
+        rt = bitrate(fc, *geometry.source)
         rows.append((rt, pr, vssim))
-        print('Decoding {}, compare it to {} frame {} \n Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(
-            fc, path, start + k, rt, pr, vssim))
+        print(('Decoding {}, compare it to {} frame {} \n ' + _VIEWPORT).format(fc, path, start + k, rt, pr, vssim))
         if ws:
             wmse, wssim = sphere_metrics.metrics(data, rdata)[0].tolist()
             back = _rgb_yuv(rec, h, w, yuv_opts).to(dev)
             rows[-1] += (sphere_metrics.psnr(wmse), wssim) + tuple(yuv.ws_psnr_yuv(src, back, h, w, yuv_opts["fmt"])[0].tolist())
-            print(' WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*rows[-1][3:5]))
-            print(' WS-PSNR-Y:{:.2f}dB, WS-PSNR-U:{:.2f}dB, WS-PSNR-V:{:.2f}dB'.format(*rows[-1][5:]))
-    print('-' * 53 + '\nAverage Performance\n' + '-' * 53)
-    avg = np.average(np.array(rows), axis=0)
-    print('Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'.format(*avg[:3]))
-    if ws:
-        print('WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'.format(*avg[3:5]))
-        print('WS-PSNR-Y:{:.2f}dB, WS-PSNR-U:{:.2f}dB, WS-PSNR-V:{:.2f}dB'.format(*avg[5:]))
-    return rows
+            print(' ' + _WS.format(*rows[-1][3:5]))
+            print(' ' + _WS_YUV.format(*rows[-1][5:]))
+    return _report(rows, [_VIEWPORT, _WS, _WS_YUV] if ws else [_VIEWPORT])
+
+
+def _parse_wxh(parser, flag, text):
+    """(height, width) of a WIDTHxHEIGHT flag value; anything else ends the run with a message (parser.error)"""
+    try:
+        width, height = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        parser.error("%s takes WIDTHxHEIGHT, for example 3840x1920; got %r" % (flag, text))
+    return height, width
 
 
 def _yuv_flags(parser, args):
@@ -714,10 +690,7 @@ def _yuv_flags(parser, args):
             parser.error("--start and --frames select frames of --yuv; --dec writes one frame per code file")
     height = width = None
     if args.size is not None:
-        try:
-            width, height = (int(v) for v in args.size.lower().split("x"))
-        except ValueError:
-            parser.error("--size takes WIDTHxHEIGHT, for example 3840x1920; got %r" % args.size)
+        height, width = _parse_wxh(parser, "--size", args.size)
         if height < 2 or width < 2 or height % 2 or width % 2:
             parser.error("--size %s: a 4:2:0 frame needs even sides of at least 2" % args.size)
     if args.frames is not None and args.code_list is not None and args.frames != len(args.code_list):
@@ -731,10 +704,7 @@ def _code_size_flag(parser, args):
     """(H2, W2) of --code-size WxH, or None; contradictions end the run with a message (parser.error)"""
     if args.code_size is None:
         return None
-    try:
-        width, height = (int(v) for v in args.code_size.lower().split("x"))
-    except ValueError:
-        parser.error("--code-size takes WIDTHxHEIGHT, for example 4096x2048; got %r" % args.code_size)
+    height, width = _parse_wxh(parser, "--code-size", args.code_size)
     if height < 2 or width < 2 or height > 1 << 20 or width > 1 << 20:
         parser.error("--code-size %s: each side must be in 2 .. 2^20" % args.code_size)
     if args.yuv is not None or args.yuv_out is not None:

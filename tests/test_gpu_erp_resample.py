@@ -153,3 +153,22 @@ def test_codec_engine_codes_at_a_reduced_size(hip_backend):
     # None changes nothing
     assert eng.encode(small, code_size=None) == streams
     assert torch.equal(eng.decode(streams, 256, 512, out_size=None), rec_small)
+
+
+def test_codec_engine_resizes_and_pads_together(hip_backend):
+    """code_size = 250 x 500, a size the codec does not take as it is: 300 x 600 frames are resized, then padded to
+    256 x 512, and come back by the crop, then the resize -- each call against the explicit composition"""
+    from pseudocylindrical_convolution_amd import erp_resample, erp_size
+    from pseudocylindrical_convolution_amd.engine import CodecEngine
+    enc, dec = _codec()
+    eng = CodecEngine(56, 0, enc, dec)
+    g = torch.Generator().manual_seed(4)
+    x = (torch.randint(0, 256, (2, 3, 300, 600), generator=g).float() / 255.).cuda()
+    coded = erp_size.pad(erp_resample.resize(x, 250, 500, clamp=True))
+    assert coded.shape == (2, 3, 256, 512)
+    streams = eng.encode(x, code_size=(250, 500))
+    assert streams == eng.encode(coded)
+    want = erp_resample.resize(erp_size.crop(eng.decode(streams, 256, 512), 250, 500), 300, 600, clamp=True)
+    got = eng.decode(streams, 250, 500, out_size=(300, 600))
+    assert got.shape == (2, 3, 300, 600) and torch.equal(got, want)
+    assert torch.equal(eng.evaluate(x, code_size=(250, 500))[1], want)
