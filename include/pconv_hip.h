@@ -289,6 +289,51 @@ int pconv_erp_resample_f32(const float *in, float *out, void *workspace, const i
                            const int32_t *first_y, const float *wy, int ty, int n, int c, int h, int w, int h2, int w2,
                            int clamp, void *stream);
 
+/* Sphere rotation of ERP frames (csrc/erp_rotate.hip; pseudocylindrical_convolution_amd/erp_rotate.py states the same
+ * definition in torch and numpy): float32 (n, C, h, w) -> (n, C, h, w), the picture of the same sphere in a rotated
+ * orientation.  A map says where on the source each output pixel lies; a sampler reads the source there.
+ * Angles (the units and ranges of the sphere-rotation SEI of HEVC / VVC): int32 in units of 2^-16 degree,
+ *   yaw in [-180*2^16, 180*2^16 - 1], pitch in [-90*2^16, 90*2^16], roll in [-180*2^16, 180*2^16 - 1].
+ * Directions: pixel (row j, column i) of an h x w frame has longitude t = ((i + 1/2)/w - 1/2)*2*pi and latitude
+ *   p = (1/2 - (j + 1/2)/h)*pi; its direction is d = (cos p cos t, cos p sin t, sin p).
+ * Matrix (pconv_host_erp_rotation_matrix: host, in double, row-major m[9]): M = Rz(yaw) * Ry(-pitch) * Rx(roll), the
+ *   right-handed axis rotations Rz(a) = [c -s 0; s c 0; 0 0 1], Ry(a) = [c 0 s; 0 1 0; -s 0 c], Rx(a) = [1 0 0; 0 c -s;
+ *   0 s c].  Output pixel d reads the source at s = M * d: the source point at longitude yaw, latitude pitch lands in
+ *   the centre of the rotated picture and roll turns the picture about that centre.  inverse != 0 gives the transpose
+ *   of M, entry for entry: the way back.
+ * Source coordinates, all in fp64:  u = (atan2(s_y, s_x)/(2*pi) + 1/2)*w - 1/2,
+ *   v = (1/2 - atan2(s_z, hypot(s_x, s_y))/pi)*h - 1/2.
+ * Map record (pconv_erp_rotation_map: (h, w, 2) int32 on the device), P = PCONV_ERP_ROTATE_PHASES = 256 phases per pixel:
+ *   map[j][i][0] = qu = rint(u*P) reduced modulo w*P (the mathematical modulo, 0 <= qu < w*P);  map[j][i][1] = qv =
+ *   rint(v*P) (it may be negative).  rint rounds halves to even.  Column and phase: floor(qu / P), qu mod P; row and
+ *   phase: floor(qv / P), qv mod P (floor division, the phase never negative).  A position is thus quantised to 1/256
+ *   pixel.  The trigonometry runs in fp64 on the device: the map equals a float64 evaluation on the host except where
+ *   u*P or v*P lies within the evaluation error (about 1e-10) of a rounding boundary.
+ * Phase table (pconv_host_lanczos_phases: host, in double; weights is P rows of PCONV_ERP_ROTATE_TAPS = 6 floats): row p,
+ *   f = p / P, weighs the source samples base - 2 .. base + 3 with L(f - k), k = -2 .. 3, L(x) = 3 sin(pi x) sin(pi x/3)
+ *   / (pi x)^2, L(0) = 1; each row is divided by its sum (ascending k, in double) and rounded once to float32.  Row 0 is
+ *   exactly (0, 0, 1, 0, 0, 0): the zeros of L at the integers are set, not evaluated.
+ * Sampler (pconv_erp_remap_f32), with (column, fx) and (row, fy) of the pixel's record, wx = row fx and wy = row fy of
+ *   the table:  tap row r_a = row - 2 + a goes through the pole rule of pconv_erp_coded_size: r < 0 -> -1 - r;
+ *   r >= h -> 2*h - 1 - r; then clamp to [0, h - 1].  Tap column c_b = (column - 2 + b) mod w; in a tap row that
+ *   crossed a pole, (c_b + floor(w / 2)) mod w.
+ *   out = sum_a wy[a] * (sum_b wx[b] * x[r_a][c_b]): both sums ascending, every product and every addition one fp32
+ *   rounding, never contracted; the first product starts each chain; the inner sum of a row is finished before the
+ *   outer sum takes it.  clamp != 0: min(max(v, 0), 1).  Non-finite inputs: unspecified.  The sampler reduces whatever
+ *   the map holds to a position inside the frame (columns modulo w, rows by the pole rule), so no map content makes it
+ *   read outside `in`.
+ * pconv_erp_remap_f32: in / out (n, C, h, w), distinct; map (h, w, 2) int32 and phases (P x 6 float32) on the device.
+ *   Tensors 4-byte aligned, the map 8-byte aligned; no allocation, no atomics, no workspace.  Refused on the host, before
+ *   any launch, with PCONV_EINVAL: null pointers, a side outside 2 .. 2^20, a plane of 2^31 bytes or more, n * C
+ *   outside 1 .. 65535, angles out of range, misaligned tensors, in == out. */
+#define PCONV_ERP_ROTATE_PHASES 256
+#define PCONV_ERP_ROTATE_TAPS 6
+int pconv_host_erp_rotation_matrix(int yaw, int pitch, int roll, int inverse, double *m);
+int pconv_host_lanczos_phases(float *weights);
+int pconv_erp_rotation_map(int32_t *map, int h, int w, int yaw, int pitch, int roll, int inverse, void *stream);
+int pconv_erp_remap_f32(const float *in, float *out, const int32_t *map, const float *phases, int n, int c, int h, int w,
+                        int clamp, void *stream);
+
 /* PseudoDQuantOp.forward  (pseudo_dquant_cuda.cu:24-70)
  * weight (wc, levels) raw parameter, level_tab (wc, levels) scratch */
 int pconv_dquant(const float *x, const float *weight, float *level_tab, float *out,

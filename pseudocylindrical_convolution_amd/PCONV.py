@@ -1493,6 +1493,60 @@ def erp_resample_f32(x, h2, w2, clamp=False, out=None, workspace=None):
     return out
 
 
+_rotate_phases = {}   # device -> the phase table of erp_rotate.phases() on the device
+
+
+def erp_rotation_map(h, w, rotation, inverse=False, device=None, out=None):
+    """int32 (h, w, 2) GPU tensor: where on the source each pixel of the rotated h x w frame lies, in 1/256 pixel
+    (erp_rotate.py, pconv_erp_rotation_map).  rotation: (yaw, pitch, roll) in units of 2^-16 degree; inverse: the map
+    of the way back.  One launch; the trigonometry runs in fp64 on the device"""
+    h, w = int(h), int(w)
+    try:
+        yaw, pitch, roll = (int(v) for v in rotation)
+    except (TypeError, ValueError):
+        raise PconvError("erp_rotation_map: a rotation is three integers in units of 2^-16 degree, got %r" % (rotation,))
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise PconvError("erp_rotation_map: expected a GPU device (this build has no CPU path), got %s" % device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if not (2 <= h <= 1 << 20 and 2 <= w <= 1 << 20) or 4 * h * w >= 1 << 31:
+        raise PconvError("erp_rotation_map: %dx%d: sides of 2 .. 2^20 and a plane below 2^31 bytes expected" % (w, h))
+    if out is None:
+        out = torch.empty((h, w, 2), dtype=torch.int32, device=device)
+    elif tuple(out.shape) != (h, w, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != device:
+        raise PconvError("erp_rotation_map: out must be contiguous int32 (%d, %d, 2) on %s" % (h, w, device))
+    with torch.cuda.device(device), _HbmTimed("erp_rotation_map_kernel", "ErpRotationMap %dx%d" % (w, h), 8.0 * h * w, device):
+        call("pconv_erp_rotation_map", _ptr(out), h, w, yaw, pitch, roll, 1 if inverse else 0, _stream(device))
+    return out
+
+
+def erp_remap_f32(x, map, clamp=False, out=None):
+    """float32 (n, C, h, w) GPU tensor -> (n, C, h, w) read through `map` (int32 (h, w, 2) on the same device, from
+    erp_rotation_map) with the 6 x 6 Lanczos-3 footprint of erp_rotate.py (pconv_erp_remap_f32).  The phase table lives
+    on the device, cached per device; out must not be x"""
+    _require_gpu(x, "erp_remap_f32")
+    if x.dim() != 4:
+        raise PconvError("erp_remap_f32: float32 (n, C, h, w) expected")
+    n, c, h, w = x.shape
+    if map.dtype != torch.int32 or tuple(map.shape) != (h, w, 2) or not map.is_contiguous() or map.device != x.device:
+        raise PconvError("erp_remap_f32: the map must be contiguous int32 (%d, %d, 2) on the input's device" % (h, w))
+    if x.device not in _rotate_phases:
+        from .erp_rotate import phases
+        _rotate_phases[x.device] = phases().to(x.device)
+    table = _rotate_phases[x.device]
+    if out is None:
+        out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, c, h, w) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise PconvError("erp_remap_f32: out must be contiguous float32 (%d, %d, %d, %d) on the input's device" % (n, c, h, w))
+    # input read + output written + the map read once per frame
+    counted = 4.0 * (x.numel() + out.numel()) + 8.0 * n * h * w
+    with _HbmTimed("erp_remap_f32_kernel", "ErpRemap %dx%d n%d" % (w, h, n), counted, x.device):
+        call("pconv_erp_remap_f32", _ptr(x), _ptr(out), _ptr(map), _ptr(table), n, c, h, w, 1 if clamp else 0,
+             _stream(x.device))
+    return out
+
+
 WS_WEIGHTINGS = {"ws": 0, "uniform": 1}   # PCONV_WS_WEIGHT_SPHERE, PCONV_WS_WEIGHT_UNIFORM
 
 

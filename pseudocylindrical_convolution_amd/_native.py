@@ -52,6 +52,10 @@ _HIP_SIGNATURES = {
     "pconv_host_lanczos_taps": [I, I, P, P, P],
     "pconv_erp_resample_workspace_bytes": [I, I, I, I, I, I],
     "pconv_erp_resample_f32": [P, P, P, P, P, I, P, P, I, I, I, I, I, I, I, I, P],
+    "pconv_host_erp_rotation_matrix": [I, I, I, I, P],
+    "pconv_host_lanczos_phases": [P],
+    "pconv_erp_rotation_map": [P, I, I, I, I, I, I, P],
+    "pconv_erp_remap_f32": [P, P, P, P, I, I, I, I, I, P],
     "pconv_project": [P, P, P, I, I, I, I, I, I, I, I, P],
     "pconv_context_reshape": [P, P, I, I, I, I, I, P],
     "pconv_mask_constrain": [P, I, I, I, I, I, P],

@@ -27,6 +27,7 @@ HIP_SOURCES = [
     "erp_size.hip",    # pole / seam padding of ERP frames of any size, and the crop back
     "yuv.hip",         # YUV 4:2:0 frames: colour conversion fused with the pad / the crop
     "erp_resample.hip",  # sphere-aware Lanczos-3 resize of ERP frames (seam wrapped, poles continued)
+    "erp_rotate.hip",  # sphere rotation of ERP frames: the source map and the 6 x 6 Lanczos-3 sampler
     "sphere_metrics.hip",  # WS-PSNR / WS-SSIM of ERP frames
     "entropy.hip",
     "entropy_engine.hip",

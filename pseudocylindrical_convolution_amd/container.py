@@ -38,10 +38,29 @@ from (erp_resample.py: --code-size); the decoder resizes its picture back to it:
     20      4     source width, little endian
     24      4     payload length in bytes, little endian
 
+Version 4 (40 bytes) carries, beside the two sizes, the orientation the picture was coded in (erp_rotate.py: --rotate):
+yaw, pitch and roll in units of 2^-16 degree, in the ranges of the sphere-rotation SEI of HEVC / VVC (yaw and roll
+-180*2^16 .. 180*2^16 - 1, pitch -90*2^16 .. 90*2^16); the decoder rotates its picture back last.  The source size is
+always present and equals the size of the coded content when nothing was resized:
+
+    0       4     magic  b"PCVC"
+    4       1     version (4)
+    5..7          flags, model index, ngroup as in version 1
+    8       4     exact ERP height of the coded content, little endian
+    12      4     exact ERP width of the coded content, little endian
+    16      4     source height, little endian
+    20      4     source width, little endian
+    24      4     yaw, signed, little endian
+    28      4     pitch, signed, little endian
+    32      4     roll, signed, little endian
+    36      4     payload length in bytes, little endian
+
 `pack` writes version 1 only; `pack_any` writes version 1 (the same bytes as `pack`) for a codable size and
-version 2 otherwise, and version 3 only when `source=(hs, ws)` is given and differs from (height, width).
-`unpack`, `sniff` and `read` take all three and return the same dict: height / width are the size of the coded
-content before its padding; a version-3 header adds source_height / source_width.
+version 2 otherwise, version 3 only when `source=(hs, ws)` is given and differs from (height, width), and version 4
+only when `rotation=(yaw, pitch, roll)` is given and not all zeros.
+`unpack`, `sniff` and `read` take all four and return the same dict: height / width are the size of the coded
+content before its padding; a version-3 header adds source_height / source_width, a version-4 header adds them only
+where they differ from height / width, and `rotation`, the integer triple.
 
 The command line writes the reference's headerless files unless `--container` is given;
 decoding recognises a container by `sniff` (magic, version and a payload length that
@@ -52,23 +71,32 @@ import os
 import struct
 
 MAGIC = b"PCVC"
-VERSION, VERSION_ANY, VERSION_SOURCE = 1, 2, 3
-# per version: the struct format (magic, version, flags, model index, ngroup, sizes ..., payload length), what one
-# count of the height / width fields stands for, and whether a source size follows them
-_Layout = collections.namedtuple("_Layout", "fmt unit source")
-_LAYOUT = {VERSION: _Layout("<4sBBBBHHI", 16, False),
-           VERSION_ANY: _Layout("<4sBBBBIII", 1, False),
-           VERSION_SOURCE: _Layout("<4sBBBBIIIII", 1, True)}
-HEADER_BYTES, HEADER_BYTES_ANY, HEADER_BYTES_SOURCE = (struct.calcsize(_LAYOUT[v].fmt) for v in sorted(_LAYOUT))
+VERSION, VERSION_ANY, VERSION_SOURCE, VERSION_ROTATED = 1, 2, 3, 4
+# per version: the struct format (magic, version, flags, model index, ngroup, sizes ..., [angles,] payload length), what
+# one count of the height / width fields stands for, whether a source size follows them, and whether three angles
+# follow that
+_Layout = collections.namedtuple("_Layout", "fmt unit source rotation")
+_LAYOUT = {VERSION: _Layout("<4sBBBBHHI", 16, False, False),
+           VERSION_ANY: _Layout("<4sBBBBIII", 1, False, False),
+           VERSION_SOURCE: _Layout("<4sBBBBIIIII", 1, True, False),
+           VERSION_ROTATED: _Layout("<4sBBBBIIIIiiiI", 1, True, True)}
+HEADER_BYTES, HEADER_BYTES_ANY, HEADER_BYTES_SOURCE, HEADER_BYTES_ROTATED = \
+    (struct.calcsize(_LAYOUT[v].fmt) for v in sorted(_LAYOUT))
+HEADER_BYTES_MAX = max(struct.calcsize(layout.fmt) for layout in _LAYOUT.values())   # what sniff has to read
+_ANGLES = (("yaw", -180 << 16, (180 << 16) - 1), ("pitch", -90 << 16, 90 << 16), ("roll", -180 << 16, (180 << 16) - 1))
 
 
 class ContainerError(ValueError):
     pass
 
 
-def _misfit(version, height, width, source, model_idx, valid_dim, nbytes):
+def _misfit(version, height, width, source, model_idx, valid_dim, nbytes, rotation=None):
     """why the fields do not fit a header of `version`, or None: the one check of pack, pack_any and _parse"""
     side = lambda v: 2 <= v <= 1 << 20
+    if rotation is not None:
+        for (name, lo, hi), v in zip(_ANGLES, rotation):
+            if not lo <= v <= hi:
+                return "%s %d does not fit the header (%d .. %d, units of 2^-16 degree)" % (name, v, lo, hi)
     if source is not None and not (side(source[0]) and side(source[1])):
         return "source size %dx%d does not fit the header (2 .. 2^20 per side)" % (source[1], source[0])
     if _LAYOUT[version].unit == 16:
@@ -85,12 +113,13 @@ def _misfit(version, height, width, source, model_idx, valid_dim, nbytes):
     return None
 
 
-def _pack(version, payload, height, width, model_idx, ssim, valid_dim, source=None):
-    why = _misfit(version, height, width, source, model_idx, valid_dim, len(payload))
+def _pack(version, payload, height, width, model_idx, ssim, valid_dim, source=None, rotation=None):
+    why = _misfit(version, height, width, source, model_idx, valid_dim, len(payload), rotation)
     if why:
         raise ContainerError(why)
     layout = _LAYOUT[version]
-    sizes = (height // layout.unit, width // layout.unit) + (tuple(source) if layout.source else ())
+    sizes = (height // layout.unit, width // layout.unit) + (tuple(source) if layout.source else ()) + \
+        (tuple(rotation) if layout.rotation else ())
     return struct.pack(layout.fmt, MAGIC, version, 1 if ssim else 0, model_idx, valid_dim // 4, *sizes,
                        len(payload)) + bytes(payload)
 
@@ -100,13 +129,25 @@ def pack(payload, height, width, model_idx, ssim, valid_dim):
     return _pack(VERSION, payload, height, width, model_idx, ssim, valid_dim)
 
 
-def pack_any(payload, height, width, model_idx, ssim, valid_dim, source=None):
+def pack_any(payload, height, width, model_idx, ssim, valid_dim, source=None, rotation=None):
     """header + payload for an ERP of any size: `pack` (version 1) when the codec takes height x width as it
     is, else version 2 with the exact size (coded at erp_size.coded_size under the padding rule).
-    source=(hs, ws) != (height, width): version 3, which also records the size the content was resized from"""
+    source=(hs, ws) != (height, width): version 3, which also records the size the content was resized from.
+    rotation=(yaw, pitch, roll) in units of 2^-16 degree, not all zeros: version 4, which records the orientation
+    as well (and always a source size); None or zeros: the bytes of versions 1 to 3"""
     from .erp_size import codable
     if source is not None:
         source = (int(source[0]), int(source[1]))
+    if rotation is not None:
+        try:
+            rotation = tuple(int(v) for v in rotation)
+            if len(rotation) != 3:
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ContainerError("rotation must be three integers (yaw, pitch, roll) in units of 2^-16 degree")
+        if any(rotation):
+            return _pack(VERSION_ROTATED, payload, height, width, model_idx, ssim, valid_dim,
+                         (height, width) if source is None else source, rotation)
     if source is None or source == (height, width):
         return _pack(VERSION if codable(height, width) else VERSION_ANY, payload, height, width, model_idx, ssim,
                      valid_dim)
@@ -121,28 +162,32 @@ def _parse(head, size):
         return "no container magic: a headerless reference-format stream?"
     version = head[4]
     if version not in _LAYOUT:
-        return "container version %d, this build reads %d, %d and %d" % (version, VERSION, VERSION_ANY, VERSION_SOURCE)
+        return "container version %d, this build reads %s" % (version, ", ".join(str(v) for v in sorted(_LAYOUT)))
     layout = _LAYOUT[version]
     nhead = struct.calcsize(layout.fmt)
     if len(head) < nhead:
         return "file shorter than the %d-byte version-%d header" % (nhead, version)
-    _, _, flags, model_idx, ngroup, h, w, *source, n = struct.unpack(layout.fmt, head[:nhead])
+    _, _, flags, model_idx, ngroup, h, w, *more, n = struct.unpack(layout.fmt, head[:nhead])
+    source, rotation = tuple(more[:2]), tuple(more[2:])
     fields = {"height": h * layout.unit, "width": w * layout.unit, "model_idx": model_idx, "ssim": bool(flags & 1),
               "valid_dim": ngroup * 4}
-    why = _misfit(version, fields["height"], fields["width"], source or None, model_idx, ngroup * 4, size - nhead)
+    why = _misfit(version, fields["height"], fields["width"], source or None, model_idx, ngroup * 4, size - nhead,
+                  rotation or None)
     if why:
         return why
     if size - nhead != n:
         return "payload is %d bytes, header says %d" % (size - nhead, n)
-    if source:
+    if source and (not layout.rotation or source != (fields["height"], fields["width"])):
         fields["source_height"], fields["source_width"] = source
+    if rotation:
+        fields["rotation"] = rotation
     return fields, nhead
 
 
 def unpack(data):
-    """-> (dict(height, width, model_idx, ssim, valid_dim[, source_height, source_width]), payload bytes);
-    version 1, 2 or 3"""
-    got = _parse(bytes(data[:HEADER_BYTES_SOURCE]), len(data))
+    """-> (dict(height, width, model_idx, ssim, valid_dim[, source_height, source_width][, rotation]), payload bytes);
+    version 1, 2, 3 or 4"""
+    got = _parse(bytes(data[:HEADER_BYTES_MAX]), len(data))
     if isinstance(got, str):
         raise ContainerError(got)
     head, nhead = got
@@ -153,14 +198,14 @@ def _sniff(path):
     try:
         size = os.path.getsize(path)
         with open(path, "rb") as f:
-            head = f.read(HEADER_BYTES_SOURCE)
+            head = f.read(HEADER_BYTES_MAX)
     except OSError:
         return "unreadable"
     return _parse(head, size)
 
 
 def sniff(path):
-    """header dict when the file is a well-formed container (version 1, 2 or 3), else None (a headerless stream).
+    """header dict when the file is a well-formed container (version 1, 2, 3 or 4), else None (a headerless stream).
     A raw arithmetic-coded stream passes for a container only if its first bytes happen to spell the magic,
     a version and its own length: 2^-72 for random bytes."""
     got = _sniff(path)
@@ -168,7 +213,7 @@ def sniff(path):
 
 
 def header_bytes(path):
-    """16, 20 or 28 when `path` is a well-formed container, else 0"""
+    """16, 20, 28 or 40 when `path` is a well-formed container, else 0"""
     got = _sniff(path)
     return 0 if isinstance(got, str) else got[1]
 

@@ -300,7 +300,7 @@ class CodecEngine(object):
     ENCODE_CHUNK = int(os.environ.get("PCONV_ENCODE_CHUNK", "2"))
 
     @torch.no_grad()
-    def encode(self, frames, code_size=None):
+    def encode(self, frames, code_size=None, rotation=None):
         """(n, 3, H, W) frames on the GPU -> n byte strings.  The frames of a chunk go through the
         entropy wavefront in lock-step; the chunks are pipelined: chunk k's CDF tables are coded by
         host threads while the GPU computes the symbols of chunk k+1 (each chunk has its own
@@ -308,8 +308,11 @@ class CodecEngine(object):
         the codec does not take as it is are first padded on the device to their coded size
         (erp_size.py: poles and seam); decode(streams, h, w) crops back.  code_size=(h2, w2): the frames are
         first resized on the device to h2 x w2 by the sphere-aware rule of erp_resample.py, clamped to [0, 1];
-        decode(streams, h2, w2, out_size=(H, W)) brings the reconstruction back to the source size."""
-        frames = FrameGeometry(frames.shape[2:], code_size).to_coded(frames)
+        decode(streams, h2, w2, out_size=(H, W)) brings the reconstruction back to the source size.
+        rotation=(yaw, pitch, roll) in units of 2^-16 degree (erp_rotate.units): the frames are first of all turned
+        on the device into that orientation (erp_rotate.py, clamped to [0, 1]), so that the point at longitude yaw,
+        latitude pitch is coded on the equator; decode(..., rotation=the same triple) turns the reconstruction back."""
+        frames = FrameGeometry(frames.shape[2:], code_size, rotation).to_coded(frames)
         n = frames.shape[0]
         chunk = self.ENCODE_CHUNK if n > self.ENCODE_CHUNK else n
         tiles = self.enc.ent.npart
@@ -365,23 +368,26 @@ class CodecEngine(object):
         return (cat(bits), cat(maps)) if rate_map else cat(bits)
 
     @torch.no_grad()
-    def rate(self, frames, rate_map=False):
+    def rate(self, frames, rate_map=False, rotation=None):
         """(n, 3, H, W) frames on the GPU -> bits (n, npart, ngroup) float64 on the GPU: what encode() would spend
         per frame, latitude tile and channel group, from the CDF rows alone (rate.py) -- no arithmetic coder, no
         copy to the host, no file.  rate.bpp(bits, H, W) is the frame rate.  rate_map=True: also the bits of every
         latent position, (n, npart*2h, 2w) float32.  Sizes the codec does not take as they are are padded as
-        encode() pads them (their bpp still counts their own pixels)."""
-        frames = FrameGeometry(frames.shape[2:]).to_coded(frames)
+        encode() pads them (their bpp still counts their own pixels).  rotation: the frames are turned as encode()
+        turns them (rate_map is then in the coded orientation): what an orientation costs, without a file."""
+        frames = FrameGeometry(frames.shape[2:], None, rotation).to_coded(frames)
         return self._rate_of_symbols(self.symbols(frames).contiguous(), frames.shape[0], rate_map)
 
     @torch.no_grad()
-    def evaluate(self, frames, rate_map=False, code_size=None):
+    def evaluate(self, frames, rate_map=False, code_size=None, rotation=None):
         """one rate-distortion point without a file: (bits, reconstruction[, map]).  The symbols are computed once;
         bits (and map) are rate()'s, the reconstruction is decode(encode(frames), H, W)'s -- the entropy decoder
         returns exactly the symbols the encoder holds (tests/test_gpu_engine.py), so neither it nor the arithmetic
         coder has to run.  code_size=(h2, w2): the frames are coded at h2 x w2 (resized as encode() resizes them) and
-        the reconstruction is returned at the frames' own size, resized back with the clamp: the end-to-end point."""
-        geometry = FrameGeometry(frames.shape[2:], code_size)
+        the reconstruction is returned at the frames' own size, resized back with the clamp: the end-to-end point.
+        rotation: the frames are coded in that orientation (as encode() turns them) and the reconstruction is returned
+        in the frames' own orientation, turned back last."""
+        geometry = FrameGeometry(frames.shape[2:], code_size, rotation)
         frames = geometry.to_coded(frames)
         n = frames.shape[0]
         sym = self.symbols(frames).contiguous()
@@ -394,15 +400,16 @@ class CodecEngine(object):
     DECODE_CHUNK = int(os.environ.get("PCONV_DECODE_CHUNK", "0"))
 
     @torch.no_grad()
-    def decode(self, streams, height, width, out_size=None):
+    def decode(self, streams, height, width, out_size=None, rotation=None):
         """n byte strings -> (n, 3, H, W).  With DECODE_CHUNK = c > 0 and more than c frames the call
         is pipelined: while the synthesis transform of chunk k runs, the entropy decoder of chunk k+1
         (a latency chain that leaves most of the GPU idle) runs beside it on a second stream, driven
         by a host thread; two engines alternate.  A size the codec does not take as it is: the streams
         of encode() of such frames, decoded at the coded size and cropped to (n, 3, height, width).
         out_size=(H, W): the reconstruction is then resized on the device to H x W by the rule of erp_resample.py,
-        clamped to [0, 1] (the way back of encode(frames, code_size=(height, width)))."""
-        geometry = FrameGeometry((height, width) if out_size is None else out_size, (height, width))
+        clamped to [0, 1] (the way back of encode(frames, code_size=(height, width))).
+        rotation: the triple encode() was given; the inverse rotation is applied last (erp_rotate.py, clamped)."""
+        geometry = FrameGeometry((height, width) if out_size is None else out_size, (height, width), rotation)
         h, w = PC.latent_shape(*geometry.coded, self.dec.npart)
         n = len(streams)
         tiles = self.dec.npart

@@ -211,10 +211,12 @@ class PseudoEncoder(nn.Module):
         (tests/test_gpu_engine.py).  PCONV_ENTROPY=per-op forces the loop.
         header: dict(model_idx=, ssim=) -> the file gets the container header (container.py) in front of
         the same payload; None = the reference's raw stream.
-        geometry: the FrameGeometry x is the coded frame of (frame_geometry.py) -- x was padded from, or resized
-        and padded from, another size, which the header then records (container version 2 or 3) and the decoder
-        returns to; None = x is the picture itself."""
+        geometry: the FrameGeometry x is the coded frame of (frame_geometry.py) -- x was padded from, or rotated,
+        resized and padded from, another picture, which the header then records (container version 2, 3 or 4) and the
+        decoder returns to; None = x is the picture itself."""
         with torch.no_grad():
+            if header is None and geometry is not None and geometry.rotated:
+                raise ValueError("a headerless stream cannot carry the rotation: give a header")
             if header is not None:
                 if geometry is None:
                     geometry = FrameGeometry(x.shape[2:])
@@ -281,7 +283,8 @@ class PseudoDecoder(nn.Module):
         header is read as one, anything else as a raw stream.  A size the codec does not take as it is
         (container version 2) is decoded at its coded size and cropped to the original size (erp_size.py).
         A container that records a source size (version 3) is decoded the same way and then
-        resized to the source size, clamped to [0, 1] (erp_resample.py)."""
+        resized to the source size, clamped to [0, 1] (erp_resample.py); one that records a rotation (version 4) is
+        last of all turned back to the source's orientation (erp_rotate.py)."""
         rec, geometry = self.decode_coded(code_name, height, width, raw)
         return geometry.from_coded(rec)
 
@@ -419,7 +422,7 @@ def img2tensor_on_device(img, device):
 
 
 def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, boxed=False,
-             native=False, code_size=None):
+             native=False, code_size=None, rotation=None):
     """reference: pseudo_codec.py:236-247.  The files are the reference's headerless streams unless
     boxed=True (--container): then the 16-byte header of container.py goes in front of the same
     payload and the file decodes without any size / model argument.  native=True (--native-size,
@@ -427,7 +430,11 @@ def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512,
     instead of resized; height / width are ignored.  code_size=(H2, W2) (--code-size, needs boxed, excludes native):
     every image is resized on the device to H2 x W2 by the sphere-aware rule of erp_resample.py (any size of at
     least 2 x 2, padded by the pole / seam rule where it is not codable); the file records both sizes (container
-    version 3) and the bitrate counts the source's pixels."""
+    version 3) and the bitrate counts the source's pixels.  rotation (--rotate, needs boxed): the triple of
+    erp_rotate.units; every image is first turned into that orientation on the device (erp_rotate.py) and the file
+    records it (container version 4)."""
+    if rotation is not None and not boxed:
+        raise ValueError("--rotate needs --container: a headerless file cannot carry the rotation")
     if native and not boxed:
         raise ValueError("--native-size needs --container: a headerless file cannot carry the image size")
     if code_size is not None and (native or not boxed):
@@ -438,7 +445,7 @@ def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512,
         img = read_image(fn)
         if not native and code_size is None:
             img = check_img(img, height, width)
-        geometry = FrameGeometry(img.shape[:2], code_size)
+        geometry = FrameGeometry(img.shape[:2], code_size, rotation)
         data = img2tensor(img, dev) if code_size is None else img2tensor_on_device(img, dev)
         t1(geometry.to_coded(data), fo, header, geometry)
         print('Encoding {}, bitrate: {:.3f}bpp'.format(fn, bitrate(fo, *geometry.source)))
@@ -456,13 +463,15 @@ def _decoder_for(code_list, model_idx, mse, device_id, raw):
 def _decode_file(t1, fc, model_idx, mse, height, width, raw, to_source=True):
     """(reconstruction at the coded size, FrameGeometry) of one code file of a list: the sizes from its container
     header when it has one (which must name the model the decoder was built for), else from the arguments.
-    to_source=False refuses a file whose picture has to be resized back (version 3)"""
+    to_source=False refuses a file whose picture has to be resized or rotated back (version 3, 4)"""
     head = None if raw else container.sniff(fc)
     if head is not None:
         if head["model_idx"] != model_idx or head["ssim"] == mse:
             raise container.ContainerError("%s was coded with another model than the first file of the list" % fc)
         if "source_height" in head and not to_source:
             raise container.ContainerError("%s was coded at a reduced size (--code-size): decode it to images" % fc)
+        if "rotation" in head and not to_source:
+            raise container.ContainerError("%s was coded in a rotated orientation (--rotate): decode it to images" % fc)
     return t1.decode_coded(fc, height, width, raw=head is None)
 
 
@@ -529,18 +538,21 @@ def _report(rows, lines):
 
 
 def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False,
-                      ws=False):
+                      ws=False, rotation=None):
     """reference: pseudo_codec.py:263-290.  ws=True (--ws): each row also carries the WS-PSNR and WS-SSIM of the
     decoded image as written (tensor2img) against the source at the image's own size: (bpp, vpsnr, vssim, ws_psnr,
     ws_ssim), with a WS line per image and for the average.  A file coded at a reduced size (--code-size, container
     version 3) is scored end to end: the picture resized back to the source size against the source, bpp over the
-    source's pixels"""
+    source's pixels; so is a file coded in a rotated orientation (--rotate, version 4): the picture turned back against
+    the unrotated source.  rotation (--test --rotate): the triple every file must record, a ContainerError otherwise"""
     t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
     rows = []
     for fc, fn in zip(code_list, img_list):
         rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw)
+        if rotation is not None and geometry.rotation != tuple(rotation):
+            raise container.ContainerError("%s records the rotation %s, --rotate says %s" % (fc, geometry.rotation, tuple(rotation)))
         rdata = geometry.from_coded(rec)
         img = check_img(read_image(fn), *geometry.source)
         pr, vssim = metrics(img2tensor(img, dev), rdata)
@@ -554,13 +566,15 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
 
 
 def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False,
-                    code_size=None):
+                    code_size=None, rotation=None):
     """--rd: what encoding() + decoding_and_test() report for the images, without a file in between.  The rate is
     the code length of the CDF rows the coder would get (rate.py: within a few bits of the stream), the
     reconstruction is the synthesis of the encoder's own symbols -- what the entropy decoder would hand back.
     Needs the native engine (GPU).  native=True (--native-size): every image at its own size, padded by the rule of
     erp_size.py; otherwise resized to height x width as --enc does.  code_size=(H2, W2) (--code-size): every image is
     coded at H2 x W2 under the rule of erp_resample.py and scored end to end at its own size, bpp over its own pixels.
+    rotation (--rotate): every image is coded in that orientation (erp_rotate.py) and scored, turned back, against the
+    unrotated source.
     Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim])."""
     from .engine import CodecEngine
     from . import rate
@@ -575,7 +589,7 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
             img = check_img(img, height, width)
         h, w = img.shape[:2]
         data = img2tensor(img, dev)
-        bits, rdata = codec.evaluate(data, code_size=code_size)
+        bits, rdata = codec.evaluate(data, code_size=code_size, rotation=rotation)
         pr, vssim = metrics(data, rdata)
         rt = rate.bpp(bits, h, w)[0].item()
         rows.append((rt, pr, vssim))
@@ -718,6 +732,29 @@ def _code_size_flag(parser, args):
     return height, width
 
 
+def _rotate_flag(parser, args):
+    """the integer triple of --rotate YAW,PITCH,ROLL (degrees), or None; contradictions end the run with a message
+    (parser.error)"""
+    if args.rotate is None:
+        return None
+    from . import erp_rotate
+    try:
+        yaw, pitch, roll = (float(v) for v in args.rotate.split(","))
+    except ValueError:
+        parser.error("--rotate takes YAW,PITCH,ROLL in degrees, for example 30,-45,0; got %r" % args.rotate)
+    try:
+        rotation = erp_rotate.units(yaw, pitch, roll)
+    except erp_rotate.PconvError as exc:
+        parser.error("--rotate %s: %s (yaw and roll in [-180, 180), pitch in [-90, 90])" % (args.rotate, exc))
+    if args.yuv is not None or args.yuv_out is not None:
+        parser.error("--rotate is for images: the YUV path converts and pads in one kernel and does not rotate")
+    if not (args.enc or args.rd or args.test):
+        parser.error("--rotate goes with --enc, --rd or --test; --dec reads the rotation from the file")
+    if args.enc and not (args.container and not args.raw):
+        parser.error("--rotate needs --container: a headerless file cannot carry the rotation")
+    return rotation
+
+
 def read_list(fname):
     with open(fname) as f:
         return [line.rstrip('\n') for line in f.readlines()]
@@ -764,6 +801,12 @@ def main(argv=None):
                                             '(seam wrapped, poles continued), the file records both sizes, --dec and '
                                             '--test work at the source size and the bitrate counts the source\'s '
                                             'pixels.  Needs --container (--rd: nothing), excludes --native-size')
+    parser.add_argument('--rotate', help='Encoding / --rd / --test: YAW,PITCH,ROLL in degrees (yaw and roll in [-180, 180), '
+                                         'pitch in [-90, 90]): code every image in the orientation that puts the point at '
+                                         'longitude YAW, latitude PITCH in the centre of the picture, where the codec '
+                                         'spends the most samples; the file records the angles, --dec turns the picture '
+                                         'back and --test / --rd score against the unrotated source.  Needs --container '
+                                         '(--rd: nothing; --test: checks that the files record these angles)')
     parser.add_argument('--raw', action='store_true', default=False,
                         help='Decoding: never look for a container header (size and model from the flags)')
     parser.add_argument('--ws', action='store_true', default=False,
@@ -781,6 +824,7 @@ def main(argv=None):
     parser.add_argument('--yuv-range', choices=sorted(yuv.RANGES), help='Code value range (default limited)')
     args = parser.parse_args(argv)
     code_size = _code_size_flag(parser, args)
+    rotation = _rotate_flag(parser, args)
     yuv_call = _yuv_flags(parser, args)   # contradictory YUV flags end the run here, before anything is loaded
     assert not args.ws or ((args.test or args.rd) and not args.enc and not args.dec), '--ws needs --test or --rd'
     assert not args.rd or not (args.enc or args.dec or args.test), '--rd excludes --enc, --dec and --test'
@@ -812,14 +856,14 @@ def main(argv=None):
     elif args.rd:
         assert img_list is not None, 'No input images for scoring'
         rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws,
-                        code_size=code_size, **size)
+                        code_size=code_size, rotation=rotation, **size)
     elif args.enc:
         assert img_list is not None, 'No input images for encoding'
         assert code_list is not None, 'No code files for saving the codes'
         assert len(img_list) == len(code_list), 'The number of images and codes should be the same'
         assert not args.native_size or (args.container and not args.raw), '--native-size needs --container'
         encoding(img_list, code_list, midx, not args.ssim, args.gpu_id, boxed=args.container and not args.raw,
-                 native=args.native_size, code_size=code_size, **size)
+                 native=args.native_size, code_size=code_size, rotation=rotation, **size)
     else:
         assert code_list is not None, 'No code files for decoding'
         if args.dec:
@@ -829,7 +873,8 @@ def main(argv=None):
         else:
             assert img_list is not None, 'No source images for evaluation.'
             assert len(code_list) == len(img_list), 'The number of codes and corresponding source images should be the same'
-            decoding_and_test(code_list, img_list, midx, not args.ssim, args.gpu_id, raw=args.raw, ws=args.ws, **size)
+            decoding_and_test(code_list, img_list, midx, not args.ssim, args.gpu_id, raw=args.raw, ws=args.ws,
+                              rotation=rotation, **size)
 
 
 if __name__ == '__main__':
