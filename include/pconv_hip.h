@@ -257,6 +257,30 @@ int pconv_ws_metrics_f32(const float *x, const float *y, int n, int c, int h, in
 int pconv_ws_metrics_u8(const uint8_t *x, const uint8_t *y, int n, int c, int h, int w, int weighting,
                         void *workspace, double *out, void *stream);
 
+/* Backward of the two sphere metrics (csrc/sphere_metrics.hip; sphere_metrics.backward_torch states the same in torch).
+ * For one frame and channel of x (the other picture) and y (the picture that receives the gradient), with blur the
+ * window g⊗g above (symmetric, and with its zero padding its own transpose on the h x w grid), per pixel:
+ *   mux = blur(x)  muy = blur(y)  sx2 = blur(x·x) - mux²  sy2 = blur(y·y) - muy²  sxy = blur(x·y) - mux·muy
+ *   A1 = 2·mux·muy + C1   A2 = 2·sxy + C2   B1 = mux² + muy² + C1   B2 = sx2 + sy2 + C2   D = B1·B2   S = A1·A2 / D
+ *   b = -S / B2                                                  (dS/dblur(y²))
+ *   c = 2·A1 / D                                                 (dS/dblur(xy))
+ *   a = 2·mux·A2 / D - 2·muy·S / B1 - mux·c - 2·muy·b            (dS/dmuy, the sigma terms included)
+ * gout holds the upstream gradients (gm of the frame's WS-MSE, gs of its WS-SSIM) as n fp64 pairs ON THE DEVICE:
+ *   ks_j = gs·w_j / N   km_j = 2·gm·w_j / N   (N = c·w·Σ_j w_j, the sum j-ascending; fp64, rounded once to fp32)
+ *   grad_y = blur(ks·a) + 2·y·blur(ks·b) + x·blur(ks·c) + km·(y - x)      (ks·a, ks·b, ks·c are zero outside the frame)
+ * Both metrics are symmetric in their arguments: the gradient with respect to x is the same call with x and y swapped.
+ * Arithmetic: fp32 without contraction apart from ks and km.  Every 11-tap sum runs k-ascending as
+ * acc = fmaf(g[k], v, acc) from acc = 0, the horizontal pass before the vertical one; x·x, y·y and x·y are rounded
+ * before they are filtered; a = (((2·mux)·A2 / D - (2·muy)·S / B1) - mux·c) - (2·muy)·b; the final sum is
+ * ((blur(ks·a) + (2·y)·blur(ks·b)) + x·blur(ks·c)) + km·(y - x).  A pixel's result depends on nothing but its frame
+ * and the frame's pair: the same bits alone, inside any batch and on every run.
+ * One launch, a gather: every element of grad_y (float32 (n, c, h, w)) is stored exactly once.  No atomics, no
+ * workspace, no allocation, no copy to or from the host.  Any h, w >= 1.  Refused on the host, before any launch,
+ * with PCONV_EINVAL: null pointers, n, c, h or w outside pconv_ws_metrics_f32's ranges (n <= 65535, c <= 4096), an
+ * unknown weighting, a plane of 2^31 bytes or more. */
+int pconv_ws_metrics_backward_f32(const float *x, const float *y, const double *gout, int n, int c, int h, int w,
+                                  int weighting, float *grad_y, void *stream);
+
 /* Sphere-aware resize of ERP frames (csrc/erp_resample.hip; pseudocylindrical_convolution_amd/erp_resample.py states
  * the same definition in torch).  Separable Lanczos-3 on float32 (n, C, h, w) -> (n, C, h2, w2); pixel centres sit at
  * (j + 1/2) / size on both grids; the kernel is stretched by max(1, in / out) when an axis shrinks.

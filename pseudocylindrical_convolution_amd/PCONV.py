@@ -1554,6 +1554,11 @@ def ws_metrics(x, y, weighting="ws"):
     """WS-MSE and WS-SSIM of each frame (pconv_ws_metrics_f32 / _u8, sphere_metrics.py): x, y GPU tensors of the
     same shape, both contiguous float32 (n, C, h, w) or both uint8 (n, h, w, 3) (read as float(u8) / 255).
     Returns a float64 CPU tensor (n, 2): [:, 0] the weighted MSE, [:, 1] the weighted SSIM"""
+    return ws_metrics_device(x, y, weighting).cpu()
+
+
+def ws_metrics_device(x, y, weighting="ws"):
+    """ws_metrics with the float64 (n, 2) result left on the inputs' device: nothing waits for the kernel"""
     if weighting not in WS_WEIGHTINGS:
         raise PconvError("ws_metrics: weighting must be one of %s, got %r" % (sorted(WS_WEIGHTINGS), weighting))
     if not (x.is_cuda and y.is_cuda):
@@ -1578,7 +1583,34 @@ def ws_metrics(x, y, weighting="ws"):
     out = torch.empty((n, 2), dtype=torch.float64, device=x.device)
     with _HbmTimed("ws_metrics_kernel", "WsMetrics n%d" % n, 2.0 * x.numel() * x.element_size(), x.device):
         call(fn, _ptr(x), _ptr(y), n, c, h, w, WS_WEIGHTINGS[weighting], _ptr(workspace), _ptr(out), _stream(x.device))
-    return out.cpu()
+    return out
+
+
+def ws_metrics_backward(x, y, gout, weighting="ws"):
+    """Gradient of Σ_f gout[f, 0]·WS-MSE_f + gout[f, 1]·WS-SSIM_f with respect to y (pconv_ws_metrics_backward_f32):
+    x, y contiguous float32 (n, C, h, w) GPU tensors of the same shape, gout contiguous float64 (n, 2) on the same
+    device (read by the kernel: no host copy).  Returns float32 (n, C, h, w).  For the gradient with respect to x
+    swap x and y"""
+    if weighting not in WS_WEIGHTINGS:
+        raise PconvError("ws_metrics_backward: weighting must be one of %s, got %r" % (sorted(WS_WEIGHTINGS), weighting))
+    if not (x.is_cuda and y.is_cuda and gout.is_cuda):
+        raise PconvError("ws_metrics_backward: expected GPU tensors (this build has no CPU path), got %s, %s and %s"
+                         % (x.device, y.device, gout.device))
+    if x.device != y.device or x.dtype != y.dtype or x.shape != y.shape:
+        raise PconvError("ws_metrics_backward: the two batches differ: %s %s %s vs %s %s %s"
+                         % (x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
+    if x.dtype != torch.float32 or x.dim() != 4 or not (x.is_contiguous() and y.is_contiguous()):
+        raise PconvError("ws_metrics_backward: contiguous float32 (n, C, h, w) expected, got %s %s"
+                         % (x.dtype, tuple(x.shape)))
+    n, c, h, w = x.shape
+    if gout.device != x.device or gout.dtype != torch.float64 or tuple(gout.shape) != (n, 2) or not gout.is_contiguous():
+        raise PconvError("ws_metrics_backward: gout must be contiguous float64 (%d, 2) on the inputs' device, got %s %s %s"
+                         % (n, gout.device, gout.dtype, tuple(gout.shape)))
+    out = torch.empty_like(x)
+    with _HbmTimed("ws_metrics_backward_kernel", "WsMetricsBackward n%d" % n, 12.0 * x.numel(), x.device):
+        call("pconv_ws_metrics_backward_f32", _ptr(x), _ptr(y), _ptr(gout), n, c, h, w, WS_WEIGHTINGS[weighting],
+             _ptr(out), _stream(x.device))
+    return out
 
 
 def tile_gdn(owner, x, gamma, beta, inverse, col_limit=None, npart=0, residual=None, ring=0):

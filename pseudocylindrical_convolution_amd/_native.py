@@ -49,6 +49,7 @@ _HIP_SIGNATURES = {
     "pconv_ws_metrics_workspace_bytes": [I, I, I],
     "pconv_ws_metrics_f32": [P, P, I, I, I, I, I, P, P, P],
     "pconv_ws_metrics_u8": [P, P, I, I, I, I, I, P, P, P],
+    "pconv_ws_metrics_backward_f32": [P, P, P, I, I, I, I, I, P, P],
     "pconv_host_lanczos_taps": [I, I, P, P, P],
     "pconv_erp_resample_workspace_bytes": [I, I, I, I, I, I],
     "pconv_erp_resample_f32": [P, P, P, P, P, I, P, P, I, I, I, I, I, I, I, I, P],

@@ -12,11 +12,24 @@ Inputs are two batches of the same shape: float32 (n, C, h, w) as the codec hold
 GPU tensors go to the HIP kernel of csrc/sphere_metrics.hip (PCONV.ws_metrics: one fused pass over the frames,
 fp32 map, fp64 sums, no atomics).  CPU tensors go to the float64 torch implementation below, which the oracle
 backend and the CPU tests use; like erp_size's torch gather it is not a fallback for GPU tensors.
+
+As a training loss: loss_terms(x, y) gives the same [WS-MSE, WS-SSIM] per frame on the inputs' device and attached
+to autograd.  For GPU tensors its backward is one more HIP kernel (PCONV.ws_metrics_backward: a gather, no atomics,
+the upstream gradients read on the device).  include/pconv_hip.h states the gradient; backward_torch is the same
+statement in torch.  With blur the zero-padded g⊗g filter (its own transpose), x the other picture, y the picture
+that receives the gradient, and gm, gs the frame's upstream gradients:
+  mux = blur(x)  muy = blur(y)  sx2 = blur(x²) - mux²  sy2 = blur(y²) - muy²  sxy = blur(xy) - mux·muy
+  A1 = 2·mux·muy + C1   A2 = 2·sxy + C2   B1 = mux² + muy² + C1   B2 = sx2 + sy2 + C2   S = A1·A2 / (B1·B2)
+  b = -S / B2      c = 2·A1 / (B1·B2)      a = 2·mux·A2 / (B1·B2) - 2·muy·S / B1 - mux·c - 2·muy·b
+  ks_j = gs·w_j / N      km_j = 2·gm·w_j / N
+  dL/dy = blur(ks·a) + 2·y·blur(ks·b) + x·blur(ks·c) + km·(y - x)
+Both metrics are symmetric: the gradient with respect to x is the same with x and y swapped.
 """
 import math
 
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from ._native import PconvError
 from .PCONV_operator import backend
@@ -113,3 +126,91 @@ def ws_psnr(x, y, weighting="ws"):
 def ws_ssim(x, y, weighting="ws"):
     """float64 (n,) WS-SSIM of each frame"""
     return metrics(x, y, weighting)[:, 1]
+
+
+def _terms_torch(a, b, weighting):
+    """float64 (n, 2) [WS-MSE, WS-SSIM] of float32 (n, C, h, w) batches on their device: metrics_torch's arithmetic,
+    differentiable"""
+    n, c, h, w = a.shape
+    wr = weights(h, weighting).to(a.device)
+    norm = c * w * float(wr.sum())
+    wr = wr.view(1, 1, h, 1)
+    e2 = ((a - b) * (a - b)).double()
+    a, b = a.double(), b.double()
+    g = gaussian()
+    mu1, mu2 = _blur(a, g), _blur(b, g)
+    mu1_sq, mu2_sq, mu1_mu2 = mu1 * mu1, mu2 * mu2, mu1 * mu2
+    s1, s2, s12 = _blur(a * a, g) - mu1_sq, _blur(b * b, g) - mu2_sq, _blur(a * b, g) - mu1_mu2
+    ssim_map = ((2 * mu1_mu2 + C1) * (2 * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2))
+    return torch.stack([(e2 * wr).sum(dim=(1, 2, 3)) / norm, (ssim_map * wr).sum(dim=(1, 2, 3)) / norm], dim=1)
+
+
+class _WsTerms(torch.autograd.Function):
+    """[WS-MSE, WS-SSIM] per frame of GPU tensors: the forward kernel, and its backward kernel once per input that
+    needs a gradient"""
+
+    @staticmethod
+    def forward(ctx, x, y, weighting, ops):
+        ctx.save_for_backward(x, y)
+        ctx.weighting, ctx.ops = weighting, ops
+        return ops.ws_metrics_device(x, y, weighting)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        x, y = ctx.saved_tensors
+        gout = gout.contiguous()
+        gx = ctx.ops.ws_metrics_backward(y, x, gout, ctx.weighting) if ctx.needs_input_grad[0] else None
+        gy = ctx.ops.ws_metrics_backward(x, y, gout, ctx.weighting) if ctx.needs_input_grad[1] else None
+        return gx, gy, None, None
+
+
+def loss_terms(x, y, weighting="ws"):
+    """float64 (n, 2) [WS-MSE, WS-SSIM] of each frame, on the inputs' device and attached to autograd: the values
+    of `metrics`, as a loss.  x, y: float (n, C, h, w) batches of one shape (uint8 carries no gradient and is
+    refused).  GPU tensors (float32, contiguous or made so): the HIP kernel forward, the HIP kernel backward.  CPU
+    tensors: the float64 torch statement, differentiated by torch"""
+    if weighting not in WEIGHTINGS:
+        raise ValueError("weighting must be one of %s, got %r" % (WEIGHTINGS, weighting))
+    if x.dtype != y.dtype or x.shape != y.shape or x.device != y.device:
+        raise PconvError("sphere loss: the two batches differ: %s %s %s vs %s %s %s"
+                         % (x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
+    if x.dim() != 4 or not x.is_floating_point():
+        raise PconvError("sphere loss: float (n, C, h, w) batches expected (uint8 frames carry no gradient), got %s %s"
+                         % (x.dtype, tuple(x.shape)))
+    if x.is_cuda:
+        if x.dtype != torch.float32:
+            raise PconvError("sphere loss: float32 GPU tensors expected, got %s" % x.dtype)
+        ops = backend.ops()
+        if not (hasattr(ops, "ws_metrics_device") and hasattr(ops, "ws_metrics_backward")):
+            raise PconvError("sphere loss: the active backend has no ws_metrics kernels for a GPU tensor")
+        return _WsTerms.apply(x.contiguous(), y.contiguous(), weighting, ops)
+    return _terms_torch(x, y, weighting)
+
+
+def backward_torch(x, y, gout, weighting="ws", dt=torch.float64):
+    """the gradient of Σ_f gout[f, 0]·WS-MSE_f + gout[f, 1]·WS-SSIM_f with respect to y, by the explicit formula of
+    the module's head, in torch: the statement the HIP kernel is held to.  x, y (n, C, h, w); gout (n, 2).  ks and km
+    are formed in float64 and rounded once to dt; everything else runs in dt, operation by operation in the kernel's
+    order (the 11-tap sums as shifted sums, k-ascending, horizontal pass first).  Returns dt (n, C, h, w)"""
+    if x.shape != y.shape or x.dim() != 4 or tuple(gout.shape) != (x.shape[0], 2):
+        raise PconvError("sphere loss: (n, C, h, w) batches of one shape and gout (n, 2) expected, got %s %s %s"
+                         % (tuple(x.shape), tuple(y.shape), tuple(gout.shape)))
+    n, c, h, w = x.shape
+    wr = weights(h, weighting).to(x.device)
+    norm = c * w * float(wr.sum())
+    gout = gout.detach().double().to(x.device)
+    ks = (gout[:, 1].view(n, 1, 1, 1) * wr.view(1, 1, h, 1) / norm).to(dt)
+    km = (2.0 * gout[:, 0].view(n, 1, 1, 1) * wr.view(1, 1, h, 1) / norm).to(dt)
+    x, y = x.detach().to(dt), y.detach().to(dt)
+    g = gaussian()
+    mux, muy = _blur(x, g), _blur(y, g)
+    mux_sq, muy_sq, mux_muy = mux * mux, muy * muy, mux * muy
+    s1, s2, s12 = _blur(x * x, g) - mux_sq, _blur(y * y, g) - muy_sq, _blur(x * y, g) - mux_muy
+    A1, A2, B1, B2 = 2 * mux_muy + C1, 2 * s12 + C2, mux_sq + muy_sq + C1, s1 + s2 + C2
+    D = B1 * B2
+    S = (A1 * A2) / D
+    b = -S / B2
+    c_ = (2 * A1) / D
+    a = (2 * mux) * A2 / D - (2 * muy) * S / B1 - mux * c_ - (2 * muy) * b
+    return ((_blur(ks * a, g) + (2 * y) * _blur(ks * b, g)) + x * _blur(ks * c_, g)) + km * (y - x)

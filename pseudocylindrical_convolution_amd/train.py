@@ -4,7 +4,8 @@
     python -m pseudocylindrical_convolution_amd.train --gpus 8 --data-dir ... --train-list ... --test-list ...
     python -m torch.distributed.run --nproc-per-node 8 -m pseudocylindrical_convolution_amd.train ...
 
-The loop, the loss (gamma*viewport MSE + beta*(1 - viewport SSIM) + alpha*rate), the alternating
+The loop, the loss (gamma*viewport MSE + beta*(1 - viewport SSIM) + alpha*rate; with `--loss ws` the two
+viewport terms become the sphere-weighted WS-MSE and WS-SSIM of sphere_metrics.loss_terms), the alternating
 optimisers (entropy model / transforms + quantiser levels, the histogram "gradient" of `quant.count`
 applied by its own SGD), gradient accumulation over `acc_batch` steps with clipping, and the
 checkpoint naming follow the reference.  What differs: ranks come from the launcher's environment
@@ -24,7 +25,7 @@ import torch
 import torch.distributed as dist
 from torch.nn.parallel import DistributedDataParallel as DDP
 
-from . import model_zoo_v2
+from . import model_zoo_v2, sphere_metrics
 from .PCONV_operator import Logger, ModuleSaver, MultiProject, SSIM
 from .RDMetric import mse_tb
 from .SphereDataset import (ProceduralSphereDataSet, SphereDataSet, SyntheticSphereDataSet,
@@ -40,12 +41,18 @@ def get_params(model, ent):
 
 
 def forward_losses(args, model, data, pr1, pr2, sim_func):
-    """(mse, ssim, rate) of one batch; rate is None for the base model"""
+    """(mse, ssim, rate) of one batch; rate is None for the base model.  --loss viewport: MSE and SSIM over the 14
+    projected views; --loss ws: the batch means of WS-MSE and WS-SSIM over the ERP frames themselves (pr1, pr2 and
+    sim_func are None)"""
     out = model(data)
     y, ent_vec, mask = out if isinstance(out, tuple) else (out, None, None)
-    py, px = pr1(y), pr2(data)
-    mse = torch.mean((px - py) * (px - py))
-    ssim = sim_func(px, py)
+    if args.loss == 'ws':
+        terms = sphere_metrics.loss_terms(data, y)
+        mse, ssim = terms[:, 0].mean(), terms[:, 1].mean()
+    else:
+        py, px = pr1(y), pr2(data)
+        mse = torch.mean((px - py) * (px - py))
+        ssim = sim_func(px, py)
     rate = None if ent_vec is None else torch.sum(ent_vec) / torch.sum(mask).item()
     return mse, ssim, rate
 
@@ -55,7 +62,7 @@ def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, 
     model.train()
     train_loader.sampler.set_epoch(epoch)
     acc_grad = AccGrad(get_params(model, ent))
-    sim_func = SSIM(11, 3).to(device)
+    sim_func = None if args.loss == 'ws' else SSIM(11, 3).to(device)
     gamma, beta, alpha, clip = args.gamma, args.beta, args.alpha, args.clip
     log.log('clip:{}'.format(clip))
     acc_batch = args.acc_batch
@@ -93,9 +100,10 @@ def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, 
 
 def test(args, model, device, test_loader, log, pr1, pr2):
     """viewport MSE / SSIM / rate over the test set, scored against the anchor curve
-    (reference: trainDDP_Full.py:58-86)"""
+    (reference: trainDDP_Full.py:58-86).  --loss ws: WS-MSE / WS-SSIM / rate, scored by the training loss itself
+    (the anchor curve is one of viewport MSE)"""
     model.eval()
-    sim_func = SSIM(11, 3).to(device)
+    sim_func = None if args.loss == 'ws' else SSIM(11, 3).to(device)
     test_mse, test_ssim, test_ent, n = 0., 0., 0., 0
     vd = args.valid_dim / 256. * .815
     for data in test_loader:
@@ -113,7 +121,10 @@ def test(args, model, device, test_loader, log, pr1, pr2):
         real_rt = vd * test_ent / 0.693
         log.log('\nTest set: MSE loss: {:.6f}  ssim loss: {:.4f} Ent: {:.3f} rt: {:.3f}bpp'.format(
             test_mse, test_ssim, test_ent, real_rt))
-        rt_loss = [float(test_mse - mse_tb(real_rt))]
+        if args.loss == 'ws':
+            rt_loss = [args.gamma * test_mse + args.beta * (1 - test_ssim) + args.alpha * test_ent]
+        else:
+            rt_loss = [float(test_mse - mse_tb(real_rt))]
     log.log(('tloss: ' + '{}\t' * len(rt_loss)).format(*rt_loss))
     return rt_loss
 
@@ -172,9 +183,12 @@ def Job(rank, world_size, args):
                                    args.valid_dim, args.npart)
     prex = '{}_init'.format(prex) if args.init else prex
     log = Logger('{}/{:s}_logs_{}.txt'.format(save_dir, prex, cid), screen=args.verbose and rank == 0, file=(rank == 0))
-    vs = args.viewport_size
-    pr1 = MultiProject(vs, int(vs * 1.5), 0.5, False, cid).to(device)
-    pr2 = MultiProject(vs, int(vs * 1.5), 0.5, False, cid).to(device)
+    if args.loss == 'ws':
+        pr1 = pr2 = None  # the sphere-weighted loss reads the ERP frames themselves
+    else:
+        vs = args.viewport_size
+        pr1 = MultiProject(vs, int(vs * 1.5), 0.5, False, cid).to(device)
+        pr2 = MultiProject(vs, int(vs * 1.5), 0.5, False, cid).to(device)
     net_class = model_zoo_v2.CMPNetV2M if args.base else model_zoo_v2.CMPNetV2MF
     model = net_class(args.valid_dim, args.channels, args.code_dim, args.npart, opt=args.opt, init=args.init,
                       device_id=cid)
@@ -222,6 +236,8 @@ def Job(rank, world_size, args):
                                         {'params': [model.module.quant.weight]}], lr=args.lr)
     optimizer_ent = None if args.base else torch.optim.Adam(model.module.ent.parameters(), lr=args.lr * 10)
     log.log('lr:{}'.format(args.lr))
+    if args.loss == 'ws':
+        log.log('loss: WS-MSE / WS-SSIM over the ERP frames (--viewport_size is ignored)')
     log.log('valid dims:{} \t alpha:{}'.format(args.valid_dim, args.alpha))
     history = []
     args.deadline = time.monotonic() + args.time_budget if args.time_budget > 0 else None
@@ -278,7 +294,13 @@ def build_parser():
                         help='the transforms only, no entropy model (trainDDP_Base.py)')
     parser.add_argument('--latest', action='store_true', default=False)
     parser.add_argument('--restart', action='store_true', default=False)
-    parser.add_argument('--viewport_size', type=int, default=171, metavar='viewport')
+    parser.add_argument('--loss', default='viewport', choices=['viewport', 'ws'],
+                        help='distortion terms: viewport = MSE and SSIM over 14 rectilinear views (the paper\'s loss); '
+                             'ws = WS-MSE and WS-SSIM over the ERP frame (sphere_metrics.loss_terms: what --test --ws '
+                             'reports).  gamma, beta and alpha weigh the terms alike; with ws the best checkpoint is the '
+                             'one with the lowest gamma*mse + beta*(1 - ssim) + alpha*rate on the test set')
+    parser.add_argument('--viewport_size', type=int, default=171, metavar='viewport',
+                        help='side of a projected view (ignored with --loss ws)')
     parser.add_argument('--channels', type=int, default=192)
     parser.add_argument('--code-dim', type=int, default=192)
     parser.add_argument('--npart', type=int, default=16)
