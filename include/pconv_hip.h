@@ -281,6 +281,53 @@ int pconv_ws_metrics_u8(const uint8_t *x, const uint8_t *y, int n, int c, int h,
 int pconv_ws_metrics_backward_f32(const float *x, const float *y, const double *gout, int n, int c, int h, int w,
                                   int weighting, float *grad_y, void *stream);
 
+/* WS-MS-SSIM of ERP frames, forward and backward (csrc/ws_msssim.hip; sphere_metrics.ms_scales_torch and
+ * ms_backward_torch state the same in torch).  Frames as for pconv_ws_metrics_f32 / _u8, with h >= 16 and w >= 16 (the
+ * fifth scale of a smaller frame would have no pixel).  x_0 = x, y_0 = y.
+ * Pyramid.  Scale s = 0..4 has h_s = h >> s rows and w_s = w >> s columns;
+ *   x_{s+1}[j][i] = ((x_s[2j][2i] + x_s[2j][2i+1]) + (x_s[2j+1][2i] + x_s[2j+1][2i+1])) · 0.25f   in fp32, in this order,
+ * and y_{s+1} likewise.  An odd last row or column of a scale belongs to no 2x2 block and is dropped; it still counts in
+ * that scale's own mean.
+ * Per scale.  Window, zero padding of 5, C1, C2 and the moments are those of the WS-SSIM above, applied to (x_s, y_s) on
+ * the h_s x w_s grid:  cs = (2·sxy + C2) / (sx2 + sy2 + C2),  l = (2·mux·muy + C1) / (mux² + muy² + C1).  The row weights
+ * are those of an h_s-row frame, w_j = cos(((j + 0.5)/h_s - 0.5)·pi) or 1, and N_s = c · w_s · Σ_j w_j.  Every map is fp32,
+ * every sum over pixels fp64:
+ *   v_s = Σ w_j·cs / N_s  for s = 0..3,     v_4 = Σ w_j·(l·cs) / N_4  (the full SSIM map, evaluated as pconv_ws_metrics
+ *   evaluates it: ((2·mux·muy + C1)·(2·sxy + C2)) / ((mux² + muy² + C1)·(sx2 + sy2 + C2))).
+ * WS-MS-SSIM = Π_s max(v_s, 0)^β_s,  β = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) (Wang, Simoncelli, Bovik 2003), the
+ * product in fp64 for s = 0..4 ascending.  Identical frames give 1; a frame with any v_s <= 0 gives 0.
+ *   out[7f + s] = v_s (s = 0..4)   out[7f + 5] = WS-MSE, with the bits of pconv_ws_metrics   out[7f + 6] = WS-MS-SSIM
+ * Forward: one launch per scale (one workgroup per 32 x 64 tile and frame, fp64 partials per tile, no atomics), each of
+ * which also writes its tile's 16 x 32 block of the next scale from the tile it has staged, and one closing launch.
+ * workspace: pconv_ws_msssim_workspace_bytes(n, c, h, w) bytes of device memory, 8-byte aligned: x_1, y_1, ..., x_4, y_4 as
+ * float32 (n, c, h_s, w_s) each (one third of the two inputs), then the partials.  It is kept for the backward.
+ * Gradient, with respect to y (x the other picture), gout = n fp64 pairs (gm of WS-MSE, gs of WS-MS-SSIM) and values = the
+ * forward's out, both ON THE DEVICE:
+ *   u_s = gs·β_s·MS / v_s when every v_t > 0, else u_s = 0 for all s (never a NaN or inf): fp64, on the device
+ *   k_j = u_s·w_j / N_s   (fp64, rounded once to fp32; N_s with the sum j-ascending)
+ *   own_s = (blur(k·a) + (2·y_s)·blur(k·b)) + x_s·blur(k·c)
+ *   s = 4: a, b, c exactly those of pconv_ws_metrics_backward_f32, in the same operation order
+ *   s < 4: B2 = sx2 + sy2 + C2,  S = A2 / B2,  b = -S / B2,  c = 2 / B2,  a = (-mux·c) - (2·muy)·b
+ *   g_4 = own_4;  for s = 3..0:  g_s[r][q] = own_s[r][q] + 0.25f·g_{s+1}[r >> 1][q >> 1] where (r >> 1, q >> 1) lies
+ *   inside scale s+1, else own_s[r][q];   grad_y = g_0 + km·(y - x),  km as in pconv_ws_metrics_backward_f32.
+ * Rounding as there: 11-tap sums k-ascending with fmaf from 0, horizontal pass first, products rounded before they are
+ * filtered, no contraction.  Everything is symmetric in x and y: the gradient of x is the same call with x and y
+ * exchanged and swapped = 1, which says that the workspace was filled by the forward of (y, x).
+ * Backward: one gather launch per scale, coarse to fine, every element stored once, no atomics.  backward_workspace:
+ * pconv_ws_msssim_backward_workspace_bytes(n, c, h, w) bytes, 4-byte aligned: g_1..g_4 (one third of one input).
+ * No entry point allocates, synchronises or copies to the host.  Refused on the host, before any launch, with
+ * PCONV_EINVAL (the _bytes queries: a negative value): null or misaligned pointers, n, c, h, w or the weighting outside
+ * pconv_ws_metrics_backward_f32's ranges, "h and w must be at least 16". */
+long long pconv_ws_msssim_workspace_bytes(int n, int c, int h, int w);
+int pconv_ws_msssim_f32(const float *x, const float *y, int n, int c, int h, int w, int weighting, void *workspace,
+                        double *out, void *stream);
+int pconv_ws_msssim_u8(const uint8_t *x, const uint8_t *y, int n, int c, int h, int w, int weighting, void *workspace,
+                       double *out, void *stream);
+long long pconv_ws_msssim_backward_workspace_bytes(int n, int c, int h, int w);
+int pconv_ws_msssim_backward_f32(const float *x, const float *y, const void *workspace, const double *values,
+                                 const double *gout, int n, int c, int h, int w, int weighting, int swapped,
+                                 void *backward_workspace, float *grad_y, void *stream);
+
 /* Sphere-aware resize of ERP frames (csrc/erp_resample.hip; pseudocylindrical_convolution_amd/erp_resample.py states
  * the same definition in torch).  Separable Lanczos-3 on float32 (n, C, h, w) -> (n, C, h2, w2); pixel centres sit at
  * (j + 1/2) / size on both grids; the kernel is stretched by max(1, in / out) when an axis shrinks.

@@ -1613,6 +1613,98 @@ def ws_metrics_backward(x, y, gout, weighting="ws"):
     return out
 
 
+WS_MS_SCALES, WS_MS_MIN_SIDE = 5, 16
+
+
+def _ws_msssim_frames(what, x, y, weighting, float_only):
+    """the checks shared by the WS-MS-SSIM entries; returns (n, c, h, w) and the forward entry's name"""
+    if weighting not in WS_WEIGHTINGS:
+        raise PconvError("%s: weighting must be one of %s, got %r" % (what, sorted(WS_WEIGHTINGS), weighting))
+    if not (x.is_cuda and y.is_cuda):
+        raise PconvError("%s: expected GPU tensors (this build has no CPU path), got %s and %s" % (what, x.device, y.device))
+    if x.device != y.device or x.dtype != y.dtype or x.shape != y.shape:
+        raise PconvError("%s: the two batches differ: %s %s %s vs %s %s %s"
+                         % (what, x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
+    if not (x.is_contiguous() and y.is_contiguous()) or x.dim() != 4:
+        raise PconvError("%s: contiguous 4-D tensors expected" % what)
+    if x.dtype == torch.float32:
+        n, c, h, w = x.shape
+        fn = "pconv_ws_msssim_f32"
+    elif x.dtype == torch.uint8 and x.shape[3] == 3 and not float_only:
+        n, h, w, c = x.shape
+        fn = "pconv_ws_msssim_u8"
+    else:
+        raise PconvError("%s: float32 (n, C, h, w)%s expected, got %s %s"
+                         % (what, "" if float_only else " or uint8 (n, h, w, 3)", x.dtype, tuple(x.shape)))
+    if h < WS_MS_MIN_SIDE or w < WS_MS_MIN_SIDE:
+        raise PconvError("%s: h and w must be at least %d, got %dx%d" % (what, WS_MS_MIN_SIDE, w, h))
+    return (n, c, h, w), fn
+
+
+def ws_msssim_device(x, y, weighting="ws"):
+    """WS-MS-SSIM of each frame (pconv_ws_msssim_f32 / _u8, include/pconv_hip.h states the definition): x, y GPU
+    tensors of the same shape, both contiguous float32 (n, C, h, w) or both uint8 (n, h, w, 3), h, w >= 16.  Returns
+    (values, workspace): values float64 (n, 7) on the device, columns 0-4 the per-scale v_0..v_4, column 5 WS-MSE,
+    column 6 WS-MS-SSIM; workspace the uint8 tensor that holds the pyramid x_1, y_1, ..., x_4, y_4 (ws_msssim_levels)
+    and that ws_msssim_backward reads.  Nothing waits for the kernels"""
+    (n, c, h, w), fn = _ws_msssim_frames("ws_msssim", x, y, weighting, False)
+    nbytes = call("pconv_ws_msssim_workspace_bytes", n, c, h, w)
+    workspace = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    out = torch.empty((n, 7), dtype=torch.float64, device=x.device)
+    # the frames read once, the pyramid (one third of them as float32) written once and read once
+    counted = 2.0 * x.numel() * x.element_size() + 2.0 * (2.0 * n * c * h * w * 4 / 3)
+    with _HbmTimed("ms_forward_kernel", "WsMsSsim n%d" % n, counted, x.device):
+        call(fn, _ptr(x), _ptr(y), n, c, h, w, WS_WEIGHTINGS[weighting], _ptr(workspace), _ptr(out), _stream(x.device))
+    return out, workspace
+
+
+def ws_msssim(x, y, weighting="ws"):
+    """ws_msssim_device with the float64 (n, 7) values copied to the host; also returns the workspace"""
+    out, workspace = ws_msssim_device(x, y, weighting)
+    return out.cpu(), workspace
+
+
+def ws_msssim_levels(workspace, n, c, h, w):
+    """the pyramid inside a workspace of ws_msssim_device: [(x_1, y_1), ..., (x_4, y_4)] as float32 (n, c, h >> s,
+    w >> s) views"""
+    levels, at = [], 0
+    for s in range(1, WS_MS_SCALES):
+        hs, ws = h >> s, w >> s
+        size = n * c * hs * ws
+        pair = workspace[4 * at:4 * (at + 2 * size)].view(torch.float32)
+        levels.append((pair[:size].view(n, c, hs, ws), pair[size:].view(n, c, hs, ws)))
+        at += 2 * size
+    return levels
+
+
+def ws_msssim_backward(x, y, workspace, values, gout, weighting="ws", swapped=False):
+    """Gradient of Σ_f gout[f, 0]·WS-MSE_f + gout[f, 1]·WS-MS-SSIM_f with respect to y (pconv_ws_msssim_backward_f32):
+    x, y contiguous float32 (n, C, h, w) GPU tensors, (values, workspace) what ws_msssim_device returned for them,
+    gout contiguous float64 (n, 2) on the same device (read by the kernels: no host copy).  Returns float32
+    (n, C, h, w).  For the gradient with respect to x exchange x and y and pass swapped=True: the workspace then is
+    that of the forward of (y, x)"""
+    (n, c, h, w), _ = _ws_msssim_frames("ws_msssim_backward", x, y, weighting, True)
+    if not gout.is_cuda or gout.device != x.device or gout.dtype != torch.float64 or tuple(gout.shape) != (n, 2) \
+            or not gout.is_contiguous():
+        raise PconvError("ws_msssim_backward: gout must be contiguous float64 (%d, 2) on the inputs' device, got %s %s %s"
+                         % (n, gout.device, gout.dtype, tuple(gout.shape)))
+    if values.device != x.device or values.dtype != torch.float64 or tuple(values.shape) != (n, 7) \
+            or not values.is_contiguous():
+        raise PconvError("ws_msssim_backward: values must be contiguous float64 (%d, 7) on the inputs' device, got %s %s %s"
+                         % (n, values.device, values.dtype, tuple(values.shape)))
+    nbytes = call("pconv_ws_msssim_workspace_bytes", n, c, h, w)
+    if workspace.device != x.device or workspace.dtype != torch.uint8 or workspace.numel() != nbytes \
+            or not workspace.is_contiguous():
+        raise PconvError("ws_msssim_backward: the workspace must be the %d bytes ws_msssim_device returned, got %s %s %s"
+                         % (nbytes, workspace.device, workspace.dtype, tuple(workspace.shape)))
+    coarse = torch.empty((call("pconv_ws_msssim_backward_workspace_bytes", n, c, h, w),), dtype=torch.uint8, device=x.device)
+    out = torch.empty_like(x)
+    with _HbmTimed("ms_backward_kernel", "WsMsSsimBackward n%d" % n, 16.0 * x.numel(), x.device):
+        call("pconv_ws_msssim_backward_f32", _ptr(x), _ptr(y), _ptr(workspace), _ptr(values), _ptr(gout), n, c, h, w,
+             WS_WEIGHTINGS[weighting], 1 if swapped else 0, _ptr(coarse), _ptr(out), _stream(x.device))
+    return out
+
+
 def tile_gdn(owner, x, gamma, beta, inverse, col_limit=None, npart=0, residual=None, ring=0):
     """PseudoGDNV2.forward in one launch: x / sqrt(beta + gamma x^2) (inverse: x * sqrt)
     (+ residual), zeros from each tile's col_limit on.  gamma (ch, ch), beta (ch):

@@ -50,6 +50,11 @@ _HIP_SIGNATURES = {
     "pconv_ws_metrics_f32": [P, P, I, I, I, I, I, P, P, P],
     "pconv_ws_metrics_u8": [P, P, I, I, I, I, I, P, P, P],
     "pconv_ws_metrics_backward_f32": [P, P, P, I, I, I, I, I, P, P],
+    "pconv_ws_msssim_workspace_bytes": [I, I, I, I],
+    "pconv_ws_msssim_f32": [P, P, I, I, I, I, I, P, P, P],
+    "pconv_ws_msssim_u8": [P, P, I, I, I, I, I, P, P, P],
+    "pconv_ws_msssim_backward_workspace_bytes": [I, I, I, I],
+    "pconv_ws_msssim_backward_f32": [P, P, P, P, P, I, I, I, I, I, I, P, P, P],
     "pconv_host_lanczos_taps": [I, I, P, P, P],
     "pconv_erp_resample_workspace_bytes": [I, I, I, I, I, I],
     "pconv_erp_resample_f32": [P, P, P, P, P, I, P, P, I, I, I, I, I, I, I, I, P],
@@ -175,6 +180,8 @@ def hip_lib():
         lib.pconv_wino_packed_size.restype = c_longlong
         lib.pconv_wino42_packed_size.restype = c_longlong
         lib.pconv_ws_metrics_workspace_bytes.restype = c_longlong
+        lib.pconv_ws_msssim_workspace_bytes.restype = c_longlong
+        lib.pconv_ws_msssim_backward_workspace_bytes.restype = c_longlong
         lib.pconv_erp_resample_workspace_bytes.restype = c_longlong
         _hip = lib
     return _hip

@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "erp_resample.hip",  # sphere-aware Lanczos-3 resize of ERP frames (seam wrapped, poles continued)
     "erp_rotate.hip",  # sphere rotation of ERP frames: the source map and the 6 x 6 Lanczos-3 sampler
     "sphere_metrics.hip",  # WS-PSNR / WS-SSIM of ERP frames
+    "ws_msssim.hip",   # WS-MS-SSIM of ERP frames: five fused scales, forward and backward
     "entropy.hip",
     "entropy_engine.hip",
     "entropy_mfma.hip",

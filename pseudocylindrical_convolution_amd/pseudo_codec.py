@@ -9,7 +9,7 @@ Differences from the reference, all additive:
   * any other ERP size h x w through the pole / seam padding rule of erp_size.py:
     coded at coded_size(h, w), the decoder crops back (container version 2,
     command line --native-size);
-  * --test --ws adds WS-PSNR / WS-SSIM (sphere_metrics.py) beside the viewport figures;
+  * --test --ws adds WS-PSNR / WS-SSIM (sphere_metrics.py) beside the viewport figures, --ms-ssim with it WS-MS-SSIM;
   * --yuv / --yuv-out code raw YUV 4:2:0 files (yuv.py: yuv420p, nv12, yuv420p10le), one code file per frame, the
     colour conversion on the GPU; --test --ws then adds WS-PSNR-Y/U/V.  The stream and the container are the RGB ones:
     the decoder is told the pixel format on the command line;
@@ -519,10 +519,15 @@ class SphericalMetrics(object):
         wmse, wssim = sphere_metrics.metrics(self._frames(original), self._frames(decoded), self.weighting)[0].tolist()
         return sphere_metrics.psnr(wmse), wssim
 
+    def ms_ssim(self, original, decoded):
+        """WS-MS-SSIM of the pair (--ms-ssim): five scales, images of at least 16 x 16"""
+        return sphere_metrics.ws_ms_ssim(self._frames(original), self._frames(decoded), self.weighting)[0].item()
+
 
 _VIEWPORT = 'Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'
 _WS = 'WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'
 _WS_YUV = 'WS-PSNR-Y:{:.2f}dB, WS-PSNR-U:{:.2f}dB, WS-PSNR-V:{:.2f}dB'
+_WS_MS = 'WS-MS-SSIM:{:.4f}'
 
 
 def _report(rows, lines):
@@ -538,13 +543,14 @@ def _report(rows, lines):
 
 
 def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False,
-                      ws=False, rotation=None):
+                      ws=False, rotation=None, ms_ssim=False):
     """reference: pseudo_codec.py:263-290.  ws=True (--ws): each row also carries the WS-PSNR and WS-SSIM of the
     decoded image as written (tensor2img) against the source at the image's own size: (bpp, vpsnr, vssim, ws_psnr,
     ws_ssim), with a WS line per image and for the average.  A file coded at a reduced size (--code-size, container
     version 3) is scored end to end: the picture resized back to the source size against the source, bpp over the
     source's pixels; so is a file coded in a rotated orientation (--rotate, version 4): the picture turned back against
-    the unrotated source.  rotation (--test --rotate): the triple every file must record, a ContainerError otherwise"""
+    the unrotated source.  rotation (--test --rotate): the triple every file must record, a ContainerError otherwise.
+    ms_ssim=True (--ms-ssim, with ws): one more line and a last column, the WS-MS-SSIM of the same pair"""
     t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
@@ -562,11 +568,14 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
         if ws:
             rows[-1] += spherical(img, tensor2img(rdata))
             print(' ' + _WS.format(*rows[-1][3:]))
-    return _report(rows, [_VIEWPORT, _WS] if ws else [_VIEWPORT])
+            if ms_ssim:
+                rows[-1] += (spherical.ms_ssim(img, tensor2img(rdata)),)
+                print(' ' + _WS_MS.format(rows[-1][-1]))
+    return _report(rows, ([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT])
 
 
 def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False,
-                    code_size=None, rotation=None):
+                    code_size=None, rotation=None, ms_ssim=False):
     """--rd: what encoding() + decoding_and_test() report for the images, without a file in between.  The rate is
     the code length of the CDF rows the coder would get (rate.py: within a few bits of the stream), the
     reconstruction is the synthesis of the encoder's own symbols -- what the entropy decoder would hand back.
@@ -575,7 +584,7 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     coded at H2 x W2 under the rule of erp_resample.py and scored end to end at its own size, bpp over its own pixels.
     rotation (--rotate): every image is coded in that orientation (erp_rotate.py) and scored, turned back, against the
     unrotated source.
-    Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim])."""
+    Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim[, ws_ms_ssim]]): the last with ms_ssim=True (--ms-ssim)."""
     from .engine import CodecEngine
     from . import rate
     (enc, dev), (dec, _) = _load("encoder", model_idx, mse, device_id), _load("decoder", model_idx, mse, device_id)
@@ -597,7 +606,10 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
         if ws:
             rows[-1] += spherical(img, tensor2img(rdata))
             print(' ' + _WS.format(*rows[-1][3:]))
-    return _report(rows, [_VIEWPORT, _WS] if ws else [_VIEWPORT])
+            if ms_ssim:
+                rows[-1] += (spherical.ms_ssim(img, tensor2img(rdata)),)
+                print(' ' + _WS_MS.format(rows[-1][-1]))
+    return _report(rows, ([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT])
 
 
 def _yuv_rgb(frames, h, w, yuv_opts, dev):
@@ -635,11 +647,12 @@ def decoding_yuv(code_list, path, yuv_opts, height=None, width=None, model_idx=0
 
 
 def decoding_and_test_yuv(code_list, path, height, width, yuv_opts, start=0, model_idx=0, mse=True, device_id=0,
-                          raw=False, ws=False):
+                          raw=False, ws=False, ms_ssim=False):
     """--test --yuv: decoding_and_test against frames start.. of a raw .yuv file.  The viewport figures (and with
     ws=True WS-PSNR / WS-SSIM) compare the converted source with the reconstruction, both cropped to the frame's own
     size; ws=True also prints WS-PSNR-Y/U/V of the frame as --dec --yuv-out would write it against the source frame.
-    Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim, ws_psnr_y, ws_psnr_u, ws_psnr_v])"""
+    Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim, ws_psnr_y, ws_psnr_u, ws_psnr_v[, ws_ms_ssim]]): the last with
+    ms_ssim=True (--ms-ssim), the WS-MS-SSIM of the pair WS-SSIM is taken of"""
     t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     metrics = ViewportMetrics(device_id)
     frames = yuv.read_frames(path, height, width, yuv_opts["fmt"], start, len(code_list))
@@ -661,7 +674,10 @@ def decoding_and_test_yuv(code_list, path, height, width, yuv_opts, start=0, mod
             rows[-1] += (sphere_metrics.psnr(wmse), wssim) + tuple(yuv.ws_psnr_yuv(src, back, h, w, yuv_opts["fmt"])[0].tolist())
             print(' ' + _WS.format(*rows[-1][3:5]))
             print(' ' + _WS_YUV.format(*rows[-1][5:]))
-    return _report(rows, [_VIEWPORT, _WS, _WS_YUV] if ws else [_VIEWPORT])
+            if ms_ssim:
+                rows[-1] += (sphere_metrics.ws_ms_ssim(data, rdata)[0].item(),)
+                print(' ' + _WS_MS.format(rows[-1][-1]))
+    return _report(rows, ([_VIEWPORT, _WS, _WS_YUV] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT])
 
 
 def _parse_wxh(parser, flag, text):
@@ -812,6 +828,9 @@ def main(argv=None):
     parser.add_argument('--ws', action='store_true', default=False,
                         help='Testing: also report WS-PSNR / WS-SSIM (rows weighted by their area on the sphere) of '
                              'each decoded image at its own size.  Needs --test or --rd')
+    parser.add_argument('--ms-ssim', action='store_true', default=False,
+                        help='Testing: with --ws, also report WS-MS-SSIM (five scales of 2x2 means, sphere-weighted '
+                             'per scale) of each decoded image; images of at least 16 x 16')
     parser.add_argument('--yuv', help='Encoding / testing: a raw YUV 4:2:0 file as the source instead of images, one '
                                       'code file per frame (needs --size and --pix-fmt)')
     parser.add_argument('--yuv-out', help='Decoding: write the decoded frames to this raw YUV 4:2:0 file, in the order '
@@ -827,6 +846,7 @@ def main(argv=None):
     rotation = _rotate_flag(parser, args)
     yuv_call = _yuv_flags(parser, args)   # contradictory YUV flags end the run here, before anything is loaded
     assert not args.ws or ((args.test or args.rd) and not args.enc and not args.dec), '--ws needs --test or --rd'
+    assert not args.ms_ssim or args.ws, '--ms-ssim needs --ws'
     assert not args.rd or not (args.enc or args.dec or args.test), '--rd excludes --enc, --dec and --test'
     check_models()
     midx = args.model_idx
@@ -852,11 +872,11 @@ def main(argv=None):
             decoding_yuv(code_list, args.yuv_out, yuv_opts, height, width, raw=args.raw, **common)
         else:
             decoding_and_test_yuv(code_list, args.yuv, height, width, yuv_opts, start=args.start or 0, raw=args.raw,
-                                  ws=args.ws, **common)
+                                  ws=args.ws, ms_ssim=args.ms_ssim, **common)
     elif args.rd:
         assert img_list is not None, 'No input images for scoring'
         rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws,
-                        code_size=code_size, rotation=rotation, **size)
+                        code_size=code_size, rotation=rotation, ms_ssim=args.ms_ssim, **size)
     elif args.enc:
         assert img_list is not None, 'No input images for encoding'
         assert code_list is not None, 'No code files for saving the codes'
@@ -874,7 +894,7 @@ def main(argv=None):
             assert img_list is not None, 'No source images for evaluation.'
             assert len(code_list) == len(img_list), 'The number of codes and corresponding source images should be the same'
             decoding_and_test(code_list, img_list, midx, not args.ssim, args.gpu_id, raw=args.raw, ws=args.ws,
-                              rotation=rotation, **size)
+                              rotation=rotation, ms_ssim=args.ms_ssim, **size)
 
 
 if __name__ == '__main__':

@@ -24,6 +24,12 @@ that receives the gradient, and gm, gs the frame's upstream gradients:
   ks_j = gs·w_j / N      km_j = 2·gm·w_j / N
   dL/dy = blur(ks·a) + 2·y·blur(ks·b) + x·blur(ks·c) + km·(y - x)
 Both metrics are symmetric: the gradient with respect to x is the same with x and y swapped.
+
+WS-MS-SSIM (the second half of this module; include/pconv_hip.h states it in full): five scales of 2x2 means (`pool`),
+v_s the weighted mean of cs = A2 / B2 at scales 0-3 and of the full map at scale 4, each with the row weights of a frame
+of that scale's height, and WS-MS-SSIM = Π max(v_s, 0)^β_s (`BETAS`).  ms_metrics / ws_ms_ssim score, ms_loss_terms is
+the autograd entry, ms_scales_torch and ms_backward_torch are the torch statements the kernels of csrc/ws_msssim.hip
+are held to.  Frames of at least 16 x 16.
 """
 import math
 
@@ -214,3 +220,192 @@ def backward_torch(x, y, gout, weighting="ws", dt=torch.float64):
     c_ = (2 * A1) / D
     a = (2 * mux) * A2 / D - (2 * muy) * S / B1 - mux * c_ - (2 * muy) * b
     return ((_blur(ks * a, g) + (2 * y) * _blur(ks * b, g)) + x * _blur(ks * c_, g)) + km * (y - x)
+
+
+# ---- WS-MS-SSIM: five scales of 2x2 means, cs at scales 0-3 and the full map at scale 4 (include/pconv_hip.h) ----
+BETAS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)   # Wang, Simoncelli, Bovik 2003
+SCALES, MIN_SIDE = len(BETAS), 1 << (len(BETAS) - 1)
+
+
+def pool(t):
+    """the next scale of t (..., h, w): ((p00 + p01) + (p10 + p11))·0.25 over 2x2 blocks in t's dtype, in this order;
+    an odd last row or column belongs to no block and is dropped"""
+    h, w = t.shape[-2] // 2 * 2, t.shape[-1] // 2 * 2
+    t = t[..., :h, :w]
+    return ((t[..., 0::2, 0::2] + t[..., 0::2, 1::2]) + (t[..., 1::2, 0::2] + t[..., 1::2, 1::2])) * 0.25
+
+
+def _ms_check(x, y, weighting, what="sphere metrics"):
+    if weighting not in WEIGHTINGS:
+        raise ValueError("weighting must be one of %s, got %r" % (WEIGHTINGS, weighting))
+    if x.dtype != y.dtype or x.shape != y.shape or x.device != y.device:
+        raise PconvError("%s: the two batches differ: %s %s %s vs %s %s %s"
+                         % (what, x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
+    if x.dim() != 4:
+        raise PconvError("%s: 4-D batches expected, got %s" % (what, tuple(x.shape)))
+    h, w = (x.shape[1:3] if x.dtype == torch.uint8 else x.shape[2:])
+    if h < MIN_SIDE or w < MIN_SIDE:
+        raise PconvError("%s: h and w must be at least %d, got %dx%d" % (what, MIN_SIDE, w, h))
+
+
+def _moments(x, y, g):
+    """mux, muy, A2 = 2·sxy + C2, B2 = sx2 + sy2 + C2 and the squares they are made of, in x's dtype"""
+    mux, muy = _blur(x, g), _blur(y, g)
+    mux_sq, muy_sq, mux_muy = mux * mux, muy * muy, mux * muy
+    s1, s2, s12 = _blur(x * x, g) - mux_sq, _blur(y * y, g) - muy_sq, _blur(x * y, g) - mux_muy
+    return mux, muy, mux_sq, muy_sq, mux_muy, 2 * s12 + C2, s1 + s2 + C2
+
+
+def ms_scales_torch(x, y, weighting="ws", dt=torch.float64):
+    """(n, 5) [v_0..v_4] in dtype dt on the batches' device, differentiable: v_s the weighted mean of cs (s < 4) or
+    of the full SSIM map (s = 4) of the s-th scale, with the row weights of an (h >> s)-row frame.  x, y: float
+    (n, C, h, w) or uint8 (n, h, w, 3), h, w >= 16"""
+    _ms_check(x, y, weighting)
+    a, b = (_as_planes(t) if t.dtype == torch.uint8 else t for t in (x, y))
+    a, b = a.to(dt), b.to(dt)
+    g, vs = gaussian(), []
+    for s in range(SCALES):
+        n, c, h, w = a.shape
+        wr = weights(h, weighting).to(a.device)
+        norm = c * w * float(wr.sum())
+        mux, muy, mux_sq, muy_sq, mux_muy, A2, B2 = _moments(a, b, g)
+        if s == SCALES - 1:
+            m = ((2 * mux_muy + C1) * A2) / ((mux_sq + muy_sq + C1) * B2)
+        else:
+            m = A2 / B2
+        vs.append(((m.double() * wr.view(1, 1, h, 1)).sum(dim=(1, 2, 3)) / norm).to(dt))
+        if s < SCALES - 1:
+            a, b = pool(a), pool(b)
+    return torch.stack(vs, dim=1)
+
+
+def ms_product(v):
+    """WS-MS-SSIM (n,) of float64 (n, 5) scale values: Π max(v_s, 0)^β_s for s ascending; 0 for a frame with any
+    v_s <= 0, with a zero (not a NaN) gradient there"""
+    positive = v > 0
+    p = torch.where(positive, v, torch.ones_like(v))
+    ms = p[:, 0] ** BETAS[0]
+    for s in range(1, SCALES):
+        ms = ms * p[:, s] ** BETAS[s]
+    return torch.where(positive.all(dim=1), ms, torch.zeros_like(ms))
+
+
+def _ms_terms_torch(a, b, weighting):
+    """float64 (n, 2) [WS-MSE, WS-MS-SSIM] of float (n, C, h, w) batches on their device, differentiable"""
+    n, c, h, w = a.shape
+    wr = weights(h, weighting).to(a.device)
+    norm = c * w * float(wr.sum())
+    e2 = ((a - b) * (a - b)).double()
+    mse = (e2 * wr.view(1, 1, h, 1)).sum(dim=(1, 2, 3)) / norm
+    return torch.stack([mse, ms_product(ms_scales_torch(a, b, weighting, torch.float64))], dim=1)
+
+
+def ms_metrics(x, y, weighting="ws"):
+    """float64 CPU tensor (n, 2): [:, 0] WS-MSE, [:, 1] WS-MS-SSIM of each frame; the HIP kernels for GPU tensors,
+    the float64 torch path for CPU tensors"""
+    _ms_check(x, y, weighting)
+    if x.is_cuda:
+        ops = backend.ops()
+        if not hasattr(ops, "ws_msssim"):
+            raise PconvError("sphere metrics: the active backend has no ws_msssim kernel for a GPU tensor")
+        return ops.ws_msssim(x, y, weighting)[0][:, SCALES:].contiguous()
+    with torch.no_grad():
+        return _ms_terms_torch(_as_planes(x), _as_planes(y), weighting)
+
+
+def ws_ms_ssim(x, y, weighting="ws"):
+    """float64 (n,) WS-MS-SSIM of each frame"""
+    return ms_metrics(x, y, weighting)[:, 1]
+
+
+class _WsMsTerms(torch.autograd.Function):
+    """[WS-MSE, WS-MS-SSIM] per frame of GPU tensors: the forward kernels, whose pyramid and values are kept, and the
+    backward kernels once per input that needs a gradient"""
+
+    @staticmethod
+    def forward(ctx, x, y, weighting, ops):
+        values, workspace = ops.ws_msssim_device(x, y, weighting)
+        ctx.save_for_backward(x, y)
+        ctx.weighting, ctx.ops, ctx.values, ctx.workspace = weighting, ops, values, workspace
+        return values[:, SCALES:].contiguous()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        x, y = ctx.saved_tensors
+        gout = gout.contiguous()
+        back = ctx.ops.ws_msssim_backward
+        gx = back(y, x, ctx.workspace, ctx.values, gout, ctx.weighting, swapped=True) if ctx.needs_input_grad[0] else None
+        gy = back(x, y, ctx.workspace, ctx.values, gout, ctx.weighting) if ctx.needs_input_grad[1] else None
+        return gx, gy, None, None
+
+
+def ms_loss_terms(x, y, weighting="ws"):
+    """float64 (n, 2) [WS-MSE, WS-MS-SSIM] of each frame, on the inputs' device and attached to autograd: the values
+    of `ms_metrics`, as a loss, with the contract of `loss_terms`.  A frame with any v_s <= 0 has WS-MS-SSIM 0 and a
+    zero gradient of it"""
+    _ms_check(x, y, weighting, "sphere loss")
+    if not x.is_floating_point():
+        raise PconvError("sphere loss: float (n, C, h, w) batches expected (uint8 frames carry no gradient), got %s %s"
+                         % (x.dtype, tuple(x.shape)))
+    if x.is_cuda:
+        if x.dtype != torch.float32:
+            raise PconvError("sphere loss: float32 GPU tensors expected, got %s" % x.dtype)
+        ops = backend.ops()
+        if not (hasattr(ops, "ws_msssim_device") and hasattr(ops, "ws_msssim_backward")):
+            raise PconvError("sphere loss: the active backend has no ws_msssim kernels for a GPU tensor")
+        return _WsMsTerms.apply(x.contiguous(), y.contiguous(), weighting, ops)
+    return _ms_terms_torch(x, y, weighting)
+
+
+def ms_backward_torch(x, y, gout, weighting="ws", dt=torch.float64):
+    """the gradient of Σ_f gout[f, 0]·WS-MSE_f + gout[f, 1]·WS-MS-SSIM_f with respect to y, by the explicit chain of
+    include/pconv_hip.h, in torch: the statement the HIP kernels are held to.  x, y (n, C, h, w); gout (n, 2).  The
+    factors u_s, k and km are formed in float64 and rounded once to dt; everything else runs in dt, operation by
+    operation in the kernels' order.  Returns dt (n, C, h, w)"""
+    _ms_check(x, y, weighting, "sphere loss")
+    if tuple(gout.shape) != (x.shape[0], 2):
+        raise PconvError("sphere loss: gout (n, 2) expected, got %s for %s" % (tuple(gout.shape), tuple(x.shape)))
+    n = x.shape[0]
+    gout = gout.detach().double().to(x.device)
+    gm, gs = gout[:, 0], gout[:, 1]
+    x, y = x.detach().to(dt), y.detach().to(dt)
+    v = ms_scales_torch(x, y, weighting, dt).double()
+    ms = ms_product(v)
+    positive = (v > 0).all(dim=1)
+    safe = torch.where(v > 0, v, torch.ones_like(v))
+    g, xs, ys, own = gaussian(), [x], [y], []
+    for s in range(1, SCALES):
+        xs.append(pool(xs[-1]))
+        ys.append(pool(ys[-1]))
+    for s in range(SCALES):
+        a, b = xs[s], ys[s]
+        _, c, h, w = a.shape
+        wr = weights(h, weighting).to(a.device)
+        norm = c * w * float(wr.sum())
+        u = torch.where(positive, gs * BETAS[s] * ms / safe[:, s], torch.zeros_like(gs))
+        k = (u.view(n, 1, 1, 1) * wr.view(1, 1, h, 1) / norm).to(dt)
+        mux, muy, mux_sq, muy_sq, mux_muy, A2, B2 = _moments(a, b, g)
+        if s == SCALES - 1:
+            A1, B1 = 2 * mux_muy + C1, mux_sq + muy_sq + C1
+            D = B1 * B2
+            S = (A1 * A2) / D
+            db = -S / B2
+            dc = (2 * A1) / D
+            da = (2 * mux) * A2 / D - (2 * muy) * S / B1 - mux * dc - (2 * muy) * db
+        else:
+            S = A2 / B2
+            db = -S / B2
+            dc = 2 / B2
+            da = (-mux * dc) - (2 * muy) * db
+        own.append((_blur(k * da, g) + (2 * b) * _blur(k * db, g)) + a * _blur(k * dc, g))
+    grad = own[SCALES - 1]
+    for s in range(SCALES - 2, -1, -1):
+        up = torch.zeros_like(own[s])
+        h2, w2 = grad.shape[-2:]
+        up[..., :2 * h2, :2 * w2] = (0.25 * grad).repeat_interleave(2, dim=-2).repeat_interleave(2, dim=-1)
+        grad = own[s] + up
+    h = x.shape[2]
+    wr = weights(h, weighting).to(x.device)
+    km = (2.0 * gm.view(n, 1, 1, 1) * wr.view(1, 1, h, 1) / (x.shape[1] * x.shape[3] * float(wr.sum()))).to(dt)
+    return grad + km * (y - x)

@@ -5,7 +5,8 @@
     python -m torch.distributed.run --nproc-per-node 8 -m pseudocylindrical_convolution_amd.train ...
 
 The loop, the loss (gamma*viewport MSE + beta*(1 - viewport SSIM) + alpha*rate; with `--loss ws` the two
-viewport terms become the sphere-weighted WS-MSE and WS-SSIM of sphere_metrics.loss_terms), the alternating
+viewport terms become the sphere-weighted WS-MSE and WS-SSIM of sphere_metrics.loss_terms, with `--loss ws-ms`
+WS-MSE and WS-MS-SSIM of sphere_metrics.ms_loss_terms), the alternating
 optimisers (entropy model / transforms + quantiser levels, the histogram "gradient" of `quant.count`
 applied by its own SGD), gradient accumulation over `acc_batch` steps with clipping, and the
 checkpoint naming follow the reference.  What differs: ranks come from the launcher's environment
@@ -32,6 +33,7 @@ from .SphereDataset import (ProceduralSphereDataSet, SphereDataSet, SyntheticSph
                             load_train_test_distribute)
 from .model_zoo_v2 import AccGrad
 
+SPHERE_LOSSES = {'ws': sphere_metrics.loss_terms, 'ws-ms': sphere_metrics.ms_loss_terms}   # --loss: read the ERP frames
 
 def get_params(model, ent):
     m = model.module
@@ -43,11 +45,11 @@ def get_params(model, ent):
 def forward_losses(args, model, data, pr1, pr2, sim_func):
     """(mse, ssim, rate) of one batch; rate is None for the base model.  --loss viewport: MSE and SSIM over the 14
     projected views; --loss ws: the batch means of WS-MSE and WS-SSIM over the ERP frames themselves (pr1, pr2 and
-    sim_func are None)"""
+    sim_func are None); --loss ws-ms: the same with WS-MS-SSIM in the place of WS-SSIM"""
     out = model(data)
     y, ent_vec, mask = out if isinstance(out, tuple) else (out, None, None)
-    if args.loss == 'ws':
-        terms = sphere_metrics.loss_terms(data, y)
+    if args.loss in SPHERE_LOSSES:
+        terms = SPHERE_LOSSES[args.loss](data, y)
         mse, ssim = terms[:, 0].mean(), terms[:, 1].mean()
     else:
         py, px = pr1(y), pr2(data)
@@ -62,7 +64,7 @@ def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, 
     model.train()
     train_loader.sampler.set_epoch(epoch)
     acc_grad = AccGrad(get_params(model, ent))
-    sim_func = None if args.loss == 'ws' else SSIM(11, 3).to(device)
+    sim_func = None if args.loss in SPHERE_LOSSES else SSIM(11, 3).to(device)
     gamma, beta, alpha, clip = args.gamma, args.beta, args.alpha, args.clip
     log.log('clip:{}'.format(clip))
     acc_batch = args.acc_batch
@@ -100,10 +102,10 @@ def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, 
 
 def test(args, model, device, test_loader, log, pr1, pr2):
     """viewport MSE / SSIM / rate over the test set, scored against the anchor curve
-    (reference: trainDDP_Full.py:58-86).  --loss ws: WS-MSE / WS-SSIM / rate, scored by the training loss itself
+    (reference: trainDDP_Full.py:58-86).  --loss ws / ws-ms: WS-MSE / WS-SSIM / rate, scored by the training loss itself
     (the anchor curve is one of viewport MSE)"""
     model.eval()
-    sim_func = None if args.loss == 'ws' else SSIM(11, 3).to(device)
+    sim_func = None if args.loss in SPHERE_LOSSES else SSIM(11, 3).to(device)
     test_mse, test_ssim, test_ent, n = 0., 0., 0., 0
     vd = args.valid_dim / 256. * .815
     for data in test_loader:
@@ -121,7 +123,7 @@ def test(args, model, device, test_loader, log, pr1, pr2):
         real_rt = vd * test_ent / 0.693
         log.log('\nTest set: MSE loss: {:.6f}  ssim loss: {:.4f} Ent: {:.3f} rt: {:.3f}bpp'.format(
             test_mse, test_ssim, test_ent, real_rt))
-        if args.loss == 'ws':
+        if args.loss in SPHERE_LOSSES:
             rt_loss = [args.gamma * test_mse + args.beta * (1 - test_ssim) + args.alpha * test_ent]
         else:
             rt_loss = [float(test_mse - mse_tb(real_rt))]
@@ -183,7 +185,7 @@ def Job(rank, world_size, args):
                                    args.valid_dim, args.npart)
     prex = '{}_init'.format(prex) if args.init else prex
     log = Logger('{}/{:s}_logs_{}.txt'.format(save_dir, prex, cid), screen=args.verbose and rank == 0, file=(rank == 0))
-    if args.loss == 'ws':
+    if args.loss in SPHERE_LOSSES:
         pr1 = pr2 = None  # the sphere-weighted loss reads the ERP frames themselves
     else:
         vs = args.viewport_size
@@ -236,8 +238,9 @@ def Job(rank, world_size, args):
                                         {'params': [model.module.quant.weight]}], lr=args.lr)
     optimizer_ent = None if args.base else torch.optim.Adam(model.module.ent.parameters(), lr=args.lr * 10)
     log.log('lr:{}'.format(args.lr))
-    if args.loss == 'ws':
-        log.log('loss: WS-MSE / WS-SSIM over the ERP frames (--viewport_size is ignored)')
+    if args.loss in SPHERE_LOSSES:
+        log.log('loss: WS-MSE / {} over the ERP frames (--viewport_size is ignored)'.format(
+            'WS-SSIM' if args.loss == 'ws' else 'WS-MS-SSIM'))
     log.log('valid dims:{} \t alpha:{}'.format(args.valid_dim, args.alpha))
     history = []
     args.deadline = time.monotonic() + args.time_budget if args.time_budget > 0 else None
@@ -294,13 +297,14 @@ def build_parser():
                         help='the transforms only, no entropy model (trainDDP_Base.py)')
     parser.add_argument('--latest', action='store_true', default=False)
     parser.add_argument('--restart', action='store_true', default=False)
-    parser.add_argument('--loss', default='viewport', choices=['viewport', 'ws'],
+    parser.add_argument('--loss', default='viewport', choices=['viewport', 'ws', 'ws-ms'],
                         help='distortion terms: viewport = MSE and SSIM over 14 rectilinear views (the paper\'s loss); '
                              'ws = WS-MSE and WS-SSIM over the ERP frame (sphere_metrics.loss_terms: what --test --ws '
-                             'reports).  gamma, beta and alpha weigh the terms alike; with ws the best checkpoint is the '
+                             'reports); ws-ms = WS-MSE and WS-MS-SSIM (sphere_metrics.ms_loss_terms: --test --ws --ms-ssim).  '
+                             'gamma, beta and alpha weigh the terms alike; with ws and ws-ms the best checkpoint is the '
                              'one with the lowest gamma*mse + beta*(1 - ssim) + alpha*rate on the test set')
     parser.add_argument('--viewport_size', type=int, default=171, metavar='viewport',
-                        help='side of a projected view (ignored with --loss ws)')
+                        help='side of a projected view (ignored with --loss ws and ws-ms)')
     parser.add_argument('--channels', type=int, default=192)
     parser.add_argument('--code-dim', type=int, default=192)
     parser.add_argument('--npart', type=int, default=16)
