@@ -50,6 +50,10 @@ int pconv_device_count(void);
  * sphere_cal_npart_hw_v2 (math_cuda.cu:177-221).  widths[npart]. */
 int pconv_host_tile_widths(const float *weight, int npart, int height, int width,
                            int32_t *widths);
+/* The same for SphereSlice, by sphere_cal_npart_hw_v2's rule: the fixed widths apply from a weight total of
+ * 3 * npart on, where the function above (_v3) switches only above it.  widths[npart]. */
+int pconv_host_slice_widths(const float *weight, int npart, int height, int width,
+                            int32_t *widths);
 
 /* Catmull-Rom tap table of SphereSlice: for tile t, output column i < widths[t]
  * the first source column tap_col[t*width+i] and 4 coefficients.

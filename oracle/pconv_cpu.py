@@ -7,9 +7,9 @@ counters / buffer reuse), not the product's shim.  Only tests/, smoke() and
 bench.py's cpu_baseline leg may import it; they plug it under the operator layer
 with `PCONV_operator.backend.use(oracle.pconv_cpu, oracle.coder_cpu)`.
 
-Parity status: "parity unpinned" by reference data for these kernels (the
-reference has no vectors and its CUDA build cannot run here); pinned by the
-invariants of tests/test_oracle_properties.py.
+Parity status: pinned to the reference's own kernels compiled for the CPU (oracle/ref_ops.py,
+tests/test_reference_ops_cpu.py, bit for bit with libm on both sides) -- every op but EntropyConv2Op, which
+stays on the invariants of tests/test_oracle_properties.py.
 """
 import ctypes
 import os
@@ -392,9 +392,6 @@ class PseudoPadOp(_Base):
         p = self.pad_
         hidx, h2, dst, src, pcol, pt = self.ctx_.produce_param(c, h, w, p)
         out = self._top(0, (num, c, h + 2 * p, w + 2 * p))
-        if p == 0:
-            out.copy_(x)
-            return [out]
         lib().orc_pseudo_pad(_p(x), _p(out), _p(hidx), _p(h2), _p(dst), _p(src), _p(pcol), _p(pt), I(num), I(c),
                              I(h), I(w), I(self.npart_), I(p))
         return [out]
@@ -473,22 +470,9 @@ class PseudoQuantOp(_Base):
         # pseudo_quant_cuda.cu:97-143 (pseudo_quant_check_weight + pseudo_quant_scale)
         if self.iter_ % self.mod_ != 0 or self.iter_ == 0:
             return
-        levels = self.bin_num_
         w, cnt = weight.data, ncount.data
-        for i in range(self.channel_):
-            j = levels - 1
-            while j > 1:
-                if cnt[i, j] >= 1e-3:
-                    break
-                j -= 1
-            tmp = w[i, j] - np.float32(np.log(np.float32(levels - j)))
-            w[i, j:] = tmp
-            if cnt[i, 0] < 1e-3:
-                w[i, 0] = w[i, 0] + torch.exp(w[i, 1])
-                tmp = torch.log((torch.exp(w[i, 1]) + torch.exp(w[i, 2])) / 2)
-                w[i, 1] = tmp
-                w[i, 2] = tmp
-        cnt.mul_(self.weight_decay_)
+        assert w.is_contiguous() and cnt.is_contiguous() and w.dtype == cnt.dtype == torch.float32
+        lib().orc_quant_check_weight(_p(w), _p(cnt), I(self.channel_), I(self.bin_num_), F(self.weight_decay_))
 
     def forward(self, x, weight, count, train):
         if train:

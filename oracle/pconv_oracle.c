@@ -398,6 +398,27 @@ void orc_dtow(const float *bottom_data, float *top_data, int num, int channels, 
   }
 }
 
+/* pseudo_quant_check_weight + pseudo_quant_scale (pseudo_quant_cuda.cu:97-143): merge the levels the running
+ * histogram says are unused, split an unused level 0, decay the histogram.  float exp / log of libm, as the
+ * reference's float instantiation calls them. */
+void orc_quant_check_weight(float *weight, float *count, int channel, int levels, float decay) {
+  for (int i = 0; i < channel; i++) {
+    int j = levels - 1;
+    for (; j > 1; j--) {
+      if (count[i * levels + j] >= 1e-3) break;
+    }
+    float tmp = weight[i * levels + j] - logf((float)(levels - j));
+    for (; j < levels; j++) weight[i * levels + j] = tmp;
+    if (count[i * levels] < 1e-3) {
+      weight[i * levels] = weight[i * levels] + expf(weight[i * levels + 1]);
+      tmp = logf((expf(weight[i * levels + 1]) + expf(weight[i * levels + 2])) / 2);
+      weight[i * levels + 1] = tmp;
+      weight[i * levels + 2] = tmp;
+    }
+  }
+  for (int i = 0; i < channel * levels; i++) count[i] = count[i] * decay;
+}
+
 /* ---- pseudo_quant_cuda.cu:37-94 ------------------------------------------------ */
 void orc_quant_forward(const float *bottom, const float *weight_b, float *weight, int *quant, float *top,
                        float *top_idx, float *count, const int *hindex, int num, int channels, int height,
@@ -671,8 +692,10 @@ void orc_gmm_loss(const float *bottom_weight, const float *bottom_delta, const f
       float fb = 0.5 + 0.5 * o_erff(xb * id * s2);
       float p = fb - fa;
       sum_p = sum_p + bottom_weight[index * ng + i] * p;
-      float ga = sp2 * id * o_expf(-0.5 * xa * xa * id * id);
-      float gb = sp2 * id * o_expf(-0.5 * xb * xb * id * id);
+      /* the reference's argument is a double (the -0.5 literal), so its exp is the double one and the product
+       * is rounded to float once; the product's polynomial (detmath) is a float function */
+      float ga = g_detmath ? sp2 * id * pconv_expf(-0.5 * xa * xa * id * id) : sp2 * id * exp(-0.5 * xa * xa * id * id);
+      float gb = g_detmath ? sp2 * id * pconv_expf(-0.5 * xb * xb * id * id) : sp2 * id * exp(-0.5 * xb * xb * id * id);
       label_diff[index] += (gb - ga) * bottom_weight[index * ng + i];
       delta_diff[index * ng + i] = id * (-xb * gb + xa * ga) * bottom_weight[index * ng + i];
       mean_diff[index * ng + i] = (ga - gb) * bottom_weight[index * ng + i];
@@ -1365,16 +1388,20 @@ void orc_projects_backward(float *input, float *count, const float *tf, const fl
   for (i64 i = 0; i < nin; i++) input[i] = count[i] = 0.f;
   const i64 nthreads = (i64)out_shape * inner_shape * nv;
   for (i64 index = 0; index < nthreads; index++) {
-    /* index = (view * out_shape + plane) * inner_shape + pixel, as the forward kernel reads it */
-    int ps = index % inner_shape;
-    int tn = (index / inner_shape) % out_shape;
-    int tb = index / inner_shape / out_shape;
+    /* the reference's thread index is pixel-major (projects_cuda.cu:259-264): thread = (pixel * views + view) *
+     * planes + plane reads element (view * planes + plane) * inner_shape + pixel.  One thread after the other, as
+     * here, that is the order of the sums. */
+    const int mod = out_shape * nv;
+    int ps = index / mod;
+    int tn = (index % mod) % out_shape;
+    int tb = (index % mod) / out_shape;
     int base = tb * 2 * inner_shape;
+    const i64 pidx = (i64)(index % mod) * inner_shape + ps;
     if (nearest) {
       int tw = (int)(floor(tf[base + 2 * ps] + 0.5)) % ws;
       int th = (int)(floor(tf[base + 2 * ps + 1] + 0.5));
       th = th >= hs ? hs - 1 : th;
-      input[((i64)tn * hs + th) * ws + tw] += output[index];
+      input[((i64)tn * hs + th) * ws + tw] += output[pidx];
       count[((i64)tn * hs + th) * ws + tw] += 1.f;
     } else {
       int tw = (int)(floor(tf[base + 2 * ps]));
@@ -1385,13 +1412,13 @@ void orc_projects_backward(float *input, float *count, const float *tf, const fl
       float ty = tf[base + 2 * ps + 1] - th;
       float ntx = 1. - tx;
       float nty = 1. - ty;
-      input[((i64)tn * hs + th) * ws + tw] += ntx * nty * output[index];
+      input[((i64)tn * hs + th) * ws + tw] += ntx * nty * output[pidx];
       count[((i64)tn * hs + th) * ws + tw] += ntx * nty;
-      input[((i64)tn * hs + th) * ws + pw] += tx * nty * output[index];
+      input[((i64)tn * hs + th) * ws + pw] += tx * nty * output[pidx];
       count[((i64)tn * hs + th) * ws + pw] += tx * nty;
-      input[((i64)tn * hs + ph) * ws + tw] += ntx * ty * output[index];
+      input[((i64)tn * hs + ph) * ws + tw] += ntx * ty * output[pidx];
       count[((i64)tn * hs + ph) * ws + tw] += ntx * ty;
-      input[((i64)tn * hs + ph) * ws + pw] += tx * ty * output[index];
+      input[((i64)tn * hs + ph) * ws + pw] += tx * ty * output[pidx];
       count[((i64)tn * hs + ph) * ws + pw] += tx * ty;
     }
   }

@@ -62,11 +62,11 @@ def _require_gpu(x, what):
         raise PconvError("%s: input must be contiguous" % what)
 
 
-def tile_widths(weight, npart, height, width):
-    """Valid width of each latitude tile (math_cuda.cu:223-253)."""
+def tile_widths(weight, npart, height, width, rule="pconv_host_tile_widths"):
+    """Valid width of each latitude tile (math_cuda.cu:223-253; `rule`: the slice's variant, :177-221)."""
     w = np.ascontiguousarray(weight, dtype=np.float32)
     out = np.zeros(npart, dtype=np.int32)
-    call("pconv_host_tile_widths", _np_ptr(w), npart, height, width, _np_ptr(out))
+    call(rule, _np_ptr(w), npart, height, width, _np_ptr(out))
     return out
 
 
@@ -247,7 +247,7 @@ class PseudoContextOp(_TileContext):
         if key not in self._cache:
             wh = self.widths_host(height, width)
             start = np.zeros(self.npart_ * height * width + 1, np.int32)
-            cap = 4 * self.npart_ * pad * width
+            cap = max(4 * self.npart_ * pad * width, 1)   # (pad 0: no records, but no empty buffers either)
             dst = np.zeros(cap, np.int32)
             wgt = np.zeros(cap, np.float32)
             call("pconv_host_pad_reverse", _np_ptr(wh), self.npart_, height, width, pad, _np_ptr(start), _np_ptr(dst),
@@ -274,9 +274,10 @@ class PseudoEntropyContextOp(_TileContext):
         if key not in self._cache:
             wh = self.widths_host(height, width)
             n = self.npart_ * 2 * pad * width
-            col, wgt = np.zeros(n, np.int32), np.zeros(n, np.float32)
-            call("pconv_host_entropy_pad_table", _np_ptr(wh), self.npart_, height, width, pad,
-                 self.context_version_, _np_ptr(col), _np_ptr(wgt))
+            col, wgt = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
+            if pad > 0:    # (pad 0: no halo rows, the kernel copies the valid columns and zeroes the rest)
+                call("pconv_host_entropy_pad_table", _np_ptr(wh), self.npart_, height, width, pad,
+                     self.context_version_, _np_ptr(col), _np_ptr(wgt))
             self._cache[key] = tuple(self._upload(a, like) for a in (col, wgt))
         return self._cache[key]
 
@@ -286,7 +287,7 @@ class PseudoEntropyContextOp(_TileContext):
         if key not in self._cache:
             wh = self.widths_host(height, width)
             start = np.zeros(self.npart_ * height * width + 1, np.int32)
-            cap = 4 * self.npart_ * pad * width
+            cap = max(4 * self.npart_ * pad * width, 1)   # (pad 0: no records, but no empty buffers either)
             dst, wgt = np.zeros(cap, np.int32), np.zeros(cap, np.float32)
             call("pconv_host_causal_reverse", _np_ptr(wh), self.npart_, height, width, pad,
                  self.context_version_, _np_ptr(start), _np_ptr(dst), _np_ptr(wgt))
@@ -451,10 +452,13 @@ class _SphereResample(_Op):
     def _moved(self):
         self._tabs = {}
 
+    def _widths(self, height, width):
+        return tile_widths(self.weight_, self.npart_, height, width)
+
     def _tables(self, builder, height, width, like):
         key = (int(height), int(width), like.device)
         if key not in self._tabs:
-            wh = tile_widths(self.weight_, self.npart_, height, width)
+            wh = self._widths(height, width)
             col = np.zeros(self.npart_ * width, np.int32)
             coef = np.zeros(self.npart_ * width * 4, np.float32)
             call(builder, _np_ptr(wh), self.npart_, width, _np_ptr(col), _np_ptr(coef))
@@ -465,6 +469,11 @@ class _SphereResample(_Op):
 class SphereSliceOp(_SphereResample):
     """PCONV.SphereSliceOp(npart, interp, pad, weight, device, timeit)
     (main.cpp:37-41, sphere_slice_cuda.cu:55-146)."""
+
+    def _widths(self, height, width):
+        """sphere_cal_npart_hw_v2's rule (math_cuda.cu:177-221), which differs from every other op's at a weight
+        total of exactly 3 * npart"""
+        return tile_widths(self.weight_, self.npart_, height, width, "pconv_host_slice_widths")
 
     def forward(self, x):
         _require_gpu(x, "SphereSliceOp")

@@ -22,6 +22,7 @@ LL = c_longlong
 _HIP_SIGNATURES = {
     # host geometry
     "pconv_host_tile_widths": [P, I, I, I, P],
+    "pconv_host_slice_widths": [P, I, I, I, P],
     "pconv_host_slice_taps": [P, I, I, P, P],
     "pconv_host_uslice_taps": [P, I, I, P, P],
     "pconv_host_pad_table": [P, I, I, I, I, P, P, P, P],

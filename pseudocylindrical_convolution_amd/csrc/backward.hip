@@ -275,7 +275,7 @@ extern "C" int pconv_pseudo_pad_backward(const float *gout, float *gin, const in
                                          const int32_t *rev_start, const int32_t *rev_dst, const float *rev_wgt,
                                          int tn, int c, int h, int w, int pad, int npart, void *stream) {
   PCONV_REQUIRE(gout && gin && widths && rev_start && rev_dst && rev_wgt, "pseudo_pad_backward: null pointer");
-  PCONV_REQUIRE(tn > 0 && tn % npart == 0 && c > 0 && h > 0 && w > 0 && pad > 0, "pseudo_pad_backward: bad shape");
+  PCONV_REQUIRE(tn > 0 && tn % npart == 0 && c > 0 && h > 0 && w > 0 && pad >= 0, "pseudo_pad_backward: bad shape");
   PCONV_REQUIRE((long long)(h + 2 * pad) * w < (1 << 24) && npart <= 128, "pseudo_pad_backward: tile too large for the packed table");
   const long long total = (long long)tn * c * h * w;
   hipLaunchKernelGGL(pad_backward_kernel<false>, dim3(pconv_grid(total)), dim3(kBlock), 0, as_stream(stream), gout,
@@ -297,7 +297,7 @@ extern "C" int pconv_context_reshape_backward(const float *top, float *bottom, i
 extern "C" int pconv_entropy_pad(const float *in, float *out, const int32_t *widths, const int32_t *col,
                                  const float *wgt, int tn, int c, int h, int w, int pad, int npart, void *stream) {
   PCONV_REQUIRE(in && out && widths && col && wgt, "entropy_pad: null pointer");
-  PCONV_REQUIRE(tn > 0 && tn % npart == 0 && c > 0 && h > 0 && w > 0 && pad > 0, "entropy_pad: bad shape");
+  PCONV_REQUIRE(tn > 0 && tn % npart == 0 && c > 0 && h > 0 && w > 0 && pad >= 0, "entropy_pad: bad shape");
   const long long nrows = (long long)tn * c * (h + 2 * pad);
   const unsigned grid = (unsigned)(nrows < 256 * 32 ? nrows : 256 * 32);
   hipLaunchKernelGGL(entropy_pad_kernel, dim3(grid), dim3(kBlock), 0, as_stream(stream), in, out, widths, col, wgt, c,
@@ -310,7 +310,7 @@ extern "C" int pconv_entropy_pad_backward(const float *gout, float *gin, const i
                                           const int32_t *rev_start, const int32_t *rev_dst, const float *rev_wgt,
                                           int tn, int c, int h, int w, int pad, int npart, void *stream) {
   PCONV_REQUIRE(gout && gin && widths && rev_start && rev_dst && rev_wgt, "entropy_pad_backward: null pointer");
-  PCONV_REQUIRE(tn > 0 && tn % npart == 0 && c > 0 && h > 0 && w > 0 && pad > 0, "entropy_pad_backward: bad shape");
+  PCONV_REQUIRE(tn > 0 && tn % npart == 0 && c > 0 && h > 0 && w > 0 && pad >= 0, "entropy_pad_backward: bad shape");
   PCONV_REQUIRE((long long)(h + 2 * pad) * w < (1 << 24) && npart <= 128, "entropy_pad_backward: tile too large for the packed table");
   const long long total = (long long)tn * c * h * w;
   hipLaunchKernelGGL(pad_backward_kernel<true>, dim3(pconv_grid(total)), dim3(kBlock), 0, as_stream(stream), gout,

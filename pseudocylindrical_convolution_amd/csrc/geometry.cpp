@@ -38,14 +38,16 @@ extern "C" int pconv_device_count(void) {
   return n;
 }
 
-extern "C" int pconv_host_tile_widths(const float *weight, int npart, int height, int width,
-                                      int32_t *widths) {
+// from_total_on: the fixed widths apply from a weight total of 3 * npart ON (sphere_cal_npart_hw_v2, the slice's
+// rule: `total < 3 * npart` keeps the cosine rule), not only ABOVE it (sphere_cal_npart_hw_v3, every other op's)
+static int tile_widths_rule(const float *weight, int npart, int height, int width, int32_t *widths,
+                            bool from_total_on) {
   PCONV_REQUIRE(weight && widths && npart > 0 && width > 0, "tile_widths: bad argument");
   PCONV_REQUIRE(height % npart == 0, "tile_widths: height %d is not a multiple of npart %d",
                 height, npart);
   float total = 0;
   for (int i = 0; i < npart; i++) total += weight[i];
-  if (total > 3 * npart) {
+  if (from_total_on ? !(total < 3 * npart) : (total > 3 * npart)) {
     // weights given in 1/64 units of the full width (base.py:set_weight)
     for (int i = 0; i < npart; i++) {
       float scaled = weight[i] / 64 * width;
@@ -69,6 +71,16 @@ extern "C" int pconv_host_tile_widths(const float *weight, int npart, int height
     widths[i] = static_cast<int>(ww * cos((edge / height - 0.5) * pi) + 0.5);
   }
   return PCONV_OK;
+}
+
+extern "C" int pconv_host_tile_widths(const float *weight, int npart, int height, int width,
+                                      int32_t *widths) {
+  return tile_widths_rule(weight, npart, height, width, widths, false);
+}
+
+extern "C" int pconv_host_slice_widths(const float *weight, int npart, int height, int width,
+                                       int32_t *widths) {
+  return tile_widths_rule(weight, npart, height, width, widths, true);
 }
 
 // Catmull-Rom coefficients for fractional offset t, in the reference's float
@@ -182,8 +194,12 @@ extern "C" int pconv_host_pad_table(const int32_t *widths, int npart, int height
 extern "C" int pconv_host_pad_reverse(const int32_t *widths, int npart, int height, int width, int pad,
                                       int32_t *rev_start, int32_t *rev_dst, float *rev_wgt) {
   PCONV_REQUIRE(widths && rev_start && rev_dst && rev_wgt, "pad_reverse: null pointer");
-  PCONV_REQUIRE(pad > 0 && height > 0 && (long long)(height + 2 * pad) * width < (1 << 24) && npart <= 128,
+  PCONV_REQUIRE(pad >= 0 && height > 0 && (long long)(height + 2 * pad) * width < (1 << 24) && npart <= 128,
                 "pad_reverse: bad pad/height");
+  if (pad == 0) {  // no halo: nothing reads an element but its own copy (the reference pads by 0 too, pseudo_pad.cu)
+    for (size_t k = 0; k <= (size_t)npart * height * width; k++) rev_start[k] = 0;
+    return 0;
+  }
   const size_t n = (size_t)npart * 2 * pad * width;
   std::vector<int32_t> st(npart * 2 * pad), sr(npart * 2 * pad), col(n);
   std::vector<float> wgt(n);
@@ -227,8 +243,12 @@ extern "C" int pconv_host_entropy_pad_table(const int32_t *widths, int npart, in
 extern "C" int pconv_host_causal_reverse(const int32_t *widths, int npart, int height, int width, int pad,
                                          int version, int32_t *rev_start, int32_t *rev_dst, float *rev_wgt) {
   PCONV_REQUIRE(widths && rev_start && rev_dst && rev_wgt, "causal_reverse: null pointer");
-  PCONV_REQUIRE(pad > 0 && height > 0 && (long long)(height + 2 * pad) * width < (1 << 24) && npart <= 128,
+  PCONV_REQUIRE(pad >= 0 && height > 0 && (long long)(height + 2 * pad) * width < (1 << 24) && npart <= 128,
                 "causal_reverse: bad pad/height");
+  if (pad == 0) {  // no halo: no records (the reference pads by 0 too, pseudo_entropy_pad_cuda.cu)
+    for (size_t k = 0; k <= (size_t)npart * height * width; k++) rev_start[k] = 0;
+    return 0;
+  }
   const size_t n = (size_t)npart * 2 * pad * width;
   std::vector<int32_t> col(n);
   std::vector<float> wgt(n);

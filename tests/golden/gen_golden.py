@@ -16,6 +16,12 @@ authoring container:
                   modules with the CPU oracle underneath: state_dict key -> shape maps,
                   a checksum per seeded parameter, and the outputs on seeded inputs
 
+  ref_ops_*.npz   the reference's extension ops, compiled from its own sources for the CPU
+                  (oracle/ref_ops.py: one thread per kernel grid), on a subset of the cases
+                  of tests/ref_ops_cases.py: arguments, inputs, results and the masks of the
+                  elements the reference never writes (found by running twice in fresh
+                  processes with different allocator fills)
+
 The fixtures are data (inputs + expected outputs); no reference source is copied.
 Run from the repo root:  python tests/golden/gen_golden.py
 """
@@ -206,9 +212,28 @@ def graph_fixtures():
     np.savez_compressed(os.path.join(OUT, "reference_graph.npz"), **out)
 
 
+def ref_ops_fixtures():
+    """the reference's own ops on the CPU (oracle/ref_ops.py) on FIXTURE_CASES of tests/ref_ops_cases.py"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_ops_cases as cases
+    from oracle.ref_ops import ref_ops
+    assert ref_ops() is not None, "the reference tree is needed: python oracle/ref_ops.py"
+    results, masks = cases.reference_results(tempfile.mkdtemp(), cases.FIXTURE_CASES)   # asserts the mask condition
+    sizes = cases.write_fixtures(OUT, results, masks)
+    largest = os.path.getsize(os.path.join(OUT, "reference_graph.npz"))
+    for name, size in sizes.items():
+        print("wrote %s (%d bytes)" % (name, size))
+        assert size <= largest, name
+    assert sum(sizes.values()) <= 1100000
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
+    if "--ref-ops-only" in sys.argv:
+        ref_ops_fixtures()
+        sys.exit(0)
     if "--graph-only" not in sys.argv:
+        ref_ops_fixtures()
         coder_fixtures()
         coder_live_fixture()
         weight_fixtures()
