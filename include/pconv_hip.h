@@ -285,9 +285,10 @@ int pconv_ws_metrics_u8(const uint8_t *x, const uint8_t *y, int n, int c, int h,
 int pconv_ws_metrics_backward_f32(const float *x, const float *y, const double *gout, int n, int c, int h, int w,
                                   int weighting, float *grad_y, void *stream);
 
-/* WS-MS-SSIM of ERP frames, forward and backward (csrc/ws_msssim.hip; sphere_metrics.ms_scales_torch and
- * ms_backward_torch state the same in torch).  Frames as for pconv_ws_metrics_f32 / _u8, with h >= 16 and w >= 16 (the
- * fifth scale of a smaller frame would have no pixel).  x_0 = x, y_0 = y.
+/* WS-MS-SSIM of ERP frames, forward and backward (csrc/sphere_metrics.hip: the kernels of the entries above, launched
+ * once per scale; sphere_metrics.ms_scales_torch and ms_backward_torch state the same in torch).  Frames as for
+ * pconv_ws_metrics_f32 / _u8, with h >= 16 and w >= 16 (the fifth scale of a smaller frame would have no pixel).
+ * x_0 = x, y_0 = y.
  * Pyramid.  Scale s = 0..4 has h_s = h >> s rows and w_s = w >> s columns;
  *   x_{s+1}[j][i] = ((x_s[2j][2i] + x_s[2j][2i+1]) + (x_s[2j+1][2i] + x_s[2j+1][2i+1])) · 0.25f   in fp32, in this order,
  * and y_{s+1} likewise.  An odd last row or column of a scale belongs to no 2x2 block and is dropped; it still counts in

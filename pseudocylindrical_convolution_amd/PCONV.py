@@ -1566,67 +1566,9 @@ def ws_metrics(x, y, weighting="ws"):
     return ws_metrics_device(x, y, weighting).cpu()
 
 
-def ws_metrics_device(x, y, weighting="ws"):
-    """ws_metrics with the float64 (n, 2) result left on the inputs' device: nothing waits for the kernel"""
-    if weighting not in WS_WEIGHTINGS:
-        raise PconvError("ws_metrics: weighting must be one of %s, got %r" % (sorted(WS_WEIGHTINGS), weighting))
-    if not (x.is_cuda and y.is_cuda):
-        raise PconvError("ws_metrics: expected GPU tensors (this build has no CPU path), got %s and %s"
-                         % (x.device, y.device))
-    if x.device != y.device or x.dtype != y.dtype or x.shape != y.shape:
-        raise PconvError("ws_metrics: the two batches differ: %s %s %s vs %s %s %s"
-                         % (x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
-    if not (x.is_contiguous() and y.is_contiguous()) or x.dim() != 4:
-        raise PconvError("ws_metrics: contiguous 4-D tensors expected")
-    if x.dtype == torch.float32:
-        n, c, h, w = x.shape
-        fn = "pconv_ws_metrics_f32"
-    elif x.dtype == torch.uint8 and x.shape[3] == 3:
-        n, h, w, c = x.shape
-        fn = "pconv_ws_metrics_u8"
-    else:
-        raise PconvError("ws_metrics: float32 (n, C, h, w) or uint8 (n, h, w, 3) expected, got %s %s"
-                         % (x.dtype, tuple(x.shape)))
-    nbytes = call("pconv_ws_metrics_workspace_bytes", n, h, w)
-    workspace = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    out = torch.empty((n, 2), dtype=torch.float64, device=x.device)
-    with _HbmTimed("ws_metrics_kernel", "WsMetrics n%d" % n, 2.0 * x.numel() * x.element_size(), x.device):
-        call(fn, _ptr(x), _ptr(y), n, c, h, w, WS_WEIGHTINGS[weighting], _ptr(workspace), _ptr(out), _stream(x.device))
-    return out
-
-
-def ws_metrics_backward(x, y, gout, weighting="ws"):
-    """Gradient of Σ_f gout[f, 0]·WS-MSE_f + gout[f, 1]·WS-SSIM_f with respect to y (pconv_ws_metrics_backward_f32):
-    x, y contiguous float32 (n, C, h, w) GPU tensors of the same shape, gout contiguous float64 (n, 2) on the same
-    device (read by the kernel: no host copy).  Returns float32 (n, C, h, w).  For the gradient with respect to x
-    swap x and y"""
-    if weighting not in WS_WEIGHTINGS:
-        raise PconvError("ws_metrics_backward: weighting must be one of %s, got %r" % (sorted(WS_WEIGHTINGS), weighting))
-    if not (x.is_cuda and y.is_cuda and gout.is_cuda):
-        raise PconvError("ws_metrics_backward: expected GPU tensors (this build has no CPU path), got %s, %s and %s"
-                         % (x.device, y.device, gout.device))
-    if x.device != y.device or x.dtype != y.dtype or x.shape != y.shape:
-        raise PconvError("ws_metrics_backward: the two batches differ: %s %s %s vs %s %s %s"
-                         % (x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
-    if x.dtype != torch.float32 or x.dim() != 4 or not (x.is_contiguous() and y.is_contiguous()):
-        raise PconvError("ws_metrics_backward: contiguous float32 (n, C, h, w) expected, got %s %s"
-                         % (x.dtype, tuple(x.shape)))
-    n, c, h, w = x.shape
-    if gout.device != x.device or gout.dtype != torch.float64 or tuple(gout.shape) != (n, 2) or not gout.is_contiguous():
-        raise PconvError("ws_metrics_backward: gout must be contiguous float64 (%d, 2) on the inputs' device, got %s %s %s"
-                         % (n, gout.device, gout.dtype, tuple(gout.shape)))
-    out = torch.empty_like(x)
-    with _HbmTimed("ws_metrics_backward_kernel", "WsMetricsBackward n%d" % n, 12.0 * x.numel(), x.device):
-        call("pconv_ws_metrics_backward_f32", _ptr(x), _ptr(y), _ptr(gout), n, c, h, w, WS_WEIGHTINGS[weighting],
-             _ptr(out), _stream(x.device))
-    return out
-
-
-WS_MS_SCALES, WS_MS_MIN_SIDE = 5, 16
-
-
-def _ws_msssim_frames(what, x, y, weighting, float_only):
-    """the checks shared by the WS-MS-SSIM entries; returns (n, c, h, w) and the forward entry's name"""
+def _ws_frames(what, x, y, weighting, float_only, min_side, entry):
+    """the checks shared by the sphere-metric entries; returns (n, c, h, w) and the forward entry's name, entry + "_f32"
+    or "_u8" """
     if weighting not in WS_WEIGHTINGS:
         raise PconvError("%s: weighting must be one of %s, got %r" % (what, sorted(WS_WEIGHTINGS), weighting))
     if not (x.is_cuda and y.is_cuda):
@@ -1638,16 +1580,53 @@ def _ws_msssim_frames(what, x, y, weighting, float_only):
         raise PconvError("%s: contiguous 4-D tensors expected" % what)
     if x.dtype == torch.float32:
         n, c, h, w = x.shape
-        fn = "pconv_ws_msssim_f32"
+        fn = entry + "_f32"
     elif x.dtype == torch.uint8 and x.shape[3] == 3 and not float_only:
         n, h, w, c = x.shape
-        fn = "pconv_ws_msssim_u8"
+        fn = entry + "_u8"
     else:
         raise PconvError("%s: float32 (n, C, h, w)%s expected, got %s %s"
                          % (what, "" if float_only else " or uint8 (n, h, w, 3)", x.dtype, tuple(x.shape)))
-    if h < WS_MS_MIN_SIDE or w < WS_MS_MIN_SIDE:
-        raise PconvError("%s: h and w must be at least %d, got %dx%d" % (what, WS_MS_MIN_SIDE, w, h))
+    if h < min_side or w < min_side:
+        raise PconvError("%s: h and w must be at least %d, got %dx%d" % (what, min_side, w, h))
     return (n, c, h, w), fn
+
+
+def _ws_gout(what, gout, x):
+    """the upstream gradients of a sphere-metric backward entry: contiguous float64 (n, 2) next to the frames"""
+    n = x.shape[0]
+    if not gout.is_cuda or gout.device != x.device or gout.dtype != torch.float64 or tuple(gout.shape) != (n, 2) \
+            or not gout.is_contiguous():
+        raise PconvError("%s: gout must be contiguous float64 (%d, 2) on the inputs' device, got %s %s %s"
+                         % (what, n, gout.device, gout.dtype, tuple(gout.shape)))
+
+
+def ws_metrics_device(x, y, weighting="ws"):
+    """ws_metrics with the float64 (n, 2) result left on the inputs' device: nothing waits for the kernel"""
+    (n, c, h, w), fn = _ws_frames("ws_metrics", x, y, weighting, False, 1, "pconv_ws_metrics")
+    nbytes = call("pconv_ws_metrics_workspace_bytes", n, h, w)
+    workspace = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    out = torch.empty((n, 2), dtype=torch.float64, device=x.device)
+    with _HbmTimed("ms_forward_kernel", "WsMetrics n%d" % n, 2.0 * x.numel() * x.element_size(), x.device):
+        call(fn, _ptr(x), _ptr(y), n, c, h, w, WS_WEIGHTINGS[weighting], _ptr(workspace), _ptr(out), _stream(x.device))
+    return out
+
+
+def ws_metrics_backward(x, y, gout, weighting="ws"):
+    """Gradient of Σ_f gout[f, 0]·WS-MSE_f + gout[f, 1]·WS-SSIM_f with respect to y (pconv_ws_metrics_backward_f32):
+    x, y contiguous float32 (n, C, h, w) GPU tensors of the same shape, gout contiguous float64 (n, 2) on the same
+    device (read by the kernel: no host copy).  Returns float32 (n, C, h, w).  For the gradient with respect to x
+    swap x and y"""
+    (n, c, h, w), _ = _ws_frames("ws_metrics_backward", x, y, weighting, True, 1, "pconv_ws_metrics")
+    _ws_gout("ws_metrics_backward", gout, x)
+    out = torch.empty_like(x)
+    with _HbmTimed("ms_backward_kernel", "WsMetricsBackward n%d" % n, 12.0 * x.numel(), x.device):
+        call("pconv_ws_metrics_backward_f32", _ptr(x), _ptr(y), _ptr(gout), n, c, h, w, WS_WEIGHTINGS[weighting],
+             _ptr(out), _stream(x.device))
+    return out
+
+
+WS_MS_SCALES, WS_MS_MIN_SIDE = 5, 16
 
 
 def ws_msssim_device(x, y, weighting="ws"):
@@ -1656,7 +1635,7 @@ def ws_msssim_device(x, y, weighting="ws"):
     (values, workspace): values float64 (n, 7) on the device, columns 0-4 the per-scale v_0..v_4, column 5 WS-MSE,
     column 6 WS-MS-SSIM; workspace the uint8 tensor that holds the pyramid x_1, y_1, ..., x_4, y_4 (ws_msssim_levels)
     and that ws_msssim_backward reads.  Nothing waits for the kernels"""
-    (n, c, h, w), fn = _ws_msssim_frames("ws_msssim", x, y, weighting, False)
+    (n, c, h, w), fn = _ws_frames("ws_msssim", x, y, weighting, False, WS_MS_MIN_SIDE, "pconv_ws_msssim")
     nbytes = call("pconv_ws_msssim_workspace_bytes", n, c, h, w)
     workspace = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
     out = torch.empty((n, 7), dtype=torch.float64, device=x.device)
@@ -1692,11 +1671,8 @@ def ws_msssim_backward(x, y, workspace, values, gout, weighting="ws", swapped=Fa
     gout contiguous float64 (n, 2) on the same device (read by the kernels: no host copy).  Returns float32
     (n, C, h, w).  For the gradient with respect to x exchange x and y and pass swapped=True: the workspace then is
     that of the forward of (y, x)"""
-    (n, c, h, w), _ = _ws_msssim_frames("ws_msssim_backward", x, y, weighting, True)
-    if not gout.is_cuda or gout.device != x.device or gout.dtype != torch.float64 or tuple(gout.shape) != (n, 2) \
-            or not gout.is_contiguous():
-        raise PconvError("ws_msssim_backward: gout must be contiguous float64 (%d, 2) on the inputs' device, got %s %s %s"
-                         % (n, gout.device, gout.dtype, tuple(gout.shape)))
+    (n, c, h, w), _ = _ws_frames("ws_msssim_backward", x, y, weighting, True, WS_MS_MIN_SIDE, "pconv_ws_msssim")
+    _ws_gout("ws_msssim_backward", gout, x)
     if values.device != x.device or values.dtype != torch.float64 or tuple(values.shape) != (n, 7) \
             or not values.is_contiguous():
         raise PconvError("ws_msssim_backward: values must be contiguous float64 (%d, 7) on the inputs' device, got %s %s %s"

@@ -1,24 +1,176 @@
-// WS-PSNR / WS-SSIM of ERP frames (include/pconv_hip.h).  Every row j of an h-row frame is weighted
-// by the area it covers on the sphere, w_j = cos(((j + 0.5)/h - 0.5)·pi) (or 1: "uniform"); the two per-frame sums
-//   Σ_c Σ_j Σ_i w_j·(x - y)²   and   Σ_c Σ_j Σ_i w_j·ssim_map
-// come out of one fused kernel that reads each frame once.  The SSIM map is pytorch_ssim's: 11-tap Gaussian
+// Sphere-weighted quality of ERP frames, forward and backward: WS-PSNR / WS-SSIM and WS-MS-SSIM (DESIGN.md §4b;
+// include/pconv_hip.h states the definitions).  Every row j of an h-row frame is weighted by the area it covers on the
+// sphere, w_j = cos(((j + 0.5)/h - 0.5)·pi) (or 1: "uniform").  The SSIM map is pytorch_ssim's: 11-tap Gaussian
 // (sigma 1.5) as the window g⊗g, zero padding of 5 on all four borders (the seam is not wrapped), C1 = 0.01²,
 // C2 = 0.03², sigma² = blur(x²) - mu².  It is computed in fp32 with a separable filter; every sum is fp64.
+// WS-MS-SSIM: five scales s = 0..4 of h >> s rows and w >> s columns, each the 2x2 mean of the one before; per scale
+// the sphere-weighted mean of the contrast-structure map cs (s < 4) or of the full SSIM map l·cs (s = 4), with the row
+// weights of an (h >> s)-row frame; WS-MS-SSIM = Π_s max(v_s, 0)^β_s.  WS-SSIM is the same chain with one scale, which
+// is both the first (Σ w·(x - y)² is added) and the last (the full map): every kernel below serves both metrics.
 //
-// One workgroup per (tile of 32 rows x 64 columns, frame).  Per channel it stages the 42 x 74 tile with its halo in
-// LDS (zeros outside the frame), runs the horizontal pass into five moment planes (mu_x, mu_y, x², y², xy: 42 x 64
-// each, in LDS), then the vertical pass, 8 rows x 1 column per lane, evaluates the map and adds w_j·map and
-// w_j·(x - y)² into two fp64 registers.  A wave butterfly and a fixed-order sum over the four waves give the tile's
-// partials, stored to partials[frame][tile].  No atomics: a second launch adds each frame's partials in a fixed
-// order, so a frame gives the same bits alone, in any batch and on every run.
-#include "ws_common.h"
+// Forward: one launch of ms_forward_kernel per scale, one workgroup per (tile of 32 rows x 64 columns, frame).  Per
+// channel it stages the 42 x 74 tile with its halo in LDS (zeros outside the frame), runs the horizontal pass into five
+// moment planes (mu_x, mu_y, x², y², xy: 42 x 64 each, in LDS), then the vertical pass, 8 rows x 1 column per lane,
+// evaluates the map and adds w_j·map (at the first scale also w_j·(x - y)²) into fp64 registers.  A wave butterfly and
+// a fixed-order sum over the four waves give the tile's partials, stored to partials[frame][tile].  From the staged
+// tile it also writes the tile's 16 x 32 block of the next scale of x and of y: tile origins are even, so a 2x2 block
+// never straddles tiles, and the pyramid costs no second read of the frame.  No atomics: ms_close_kernel, one workgroup
+// per frame, adds each scale's partials in a fixed order and normalises, so a frame gives the same bits alone, in any
+// batch and on every run.
+//
+// Backward: one launch of ms_backward_kernel per scale, coarse to fine: a gather (halo 10, five passes in LDS, every
+// output stored once) with a compile-time switch between the cs-only and the full coefficients, the fused
+// + 0.25f·g_{s+1}[r >> 1][q >> 1] read and, at scale 0, + km·(y - x).
+#include <math.h>
+
+#include "common.h"
 
 namespace {
 
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr int kTileRows = 32, kTileCols = 64;
+constexpr int kHalo = 5, kTaps = 2 * kHalo + 1;
+constexpr int kInRows = kTileRows + 2 * kHalo;  // 42
+constexpr int kInCols = kTileCols + 2 * kHalo;  // 74
+constexpr int kLd = 76;                         // staged row stride: 16-byte rows, the last float4 read ends at 75
+constexpr int kQuads = kTileCols / 4;           // horizontal pass: 4 adjacent outputs per lane
+constexpr int kRowsPerLane = 8;                 // vertical pass: 8 rows of one column per lane
+constexpr int kStage = (kInRows * kInCols + kBlock - 1) / kBlock;  // staged elements per lane and input
+constexpr int kPlane = kInRows * kTileCols;
+constexpr int kMaxSide = 1 << 20;
+static_assert(kBlock == kTileCols * (kTileRows / kRowsPerLane), "vertical pass: one lane per (column, row group)");
+static_assert(4 * (kQuads - 1) + 16 <= kLd, "horizontal pass: the last float4 read stays inside the staged row");
 
-template <typename T>
-__global__ __launch_bounds__(kBlock, 2) void ws_metrics_kernel(const T *__restrict__ x, const T *__restrict__ y,
-                                                            double *__restrict__ partials, WsGeom G) {
+struct WsGeom {
+  int c, h, w, tiles_x, tiles, uniform;
+  float g[kTaps];  // the normalised 1-D Gaussian in fp32
+};
+
+__host__ __device__ inline double row_weight(int j, int h) {
+  // ((j + 0.5)/h - 0.5)·pi with an exact integer numerator: rows j and h-1-j get the same weight bit for bit
+  return cos((double)(2 * j + 1 - h) / (2.0 * h) * M_PI);
+}
+
+// the frame's plane (f, ch) as a uniform base, a pixel as a 32-bit offset from it (a plane is below 2^31 bytes)
+__device__ __forceinline__ const float *plane_of(const float *__restrict__ p, const WsGeom &G, int f, int ch) {
+  return p + ((long long)f * G.c + ch) * G.h * G.w;
+}
+__device__ __forceinline__ float load_px(const float *__restrict__ plane, const WsGeom &G, int ch, int r, int col) {
+  return plane[(unsigned)(r * G.w + col)];
+}
+
+// uint8 (n, h, w, 3): the frame as the base; float(u8) / 255.f, correctly rounded, as pconv_frames_u8_to_f32
+__device__ __forceinline__ const uint8_t *plane_of(const uint8_t *__restrict__ p, const WsGeom &G, int f, int) {
+  return p + (long long)f * G.h * G.w * 3;
+}
+__device__ __forceinline__ float load_px(const uint8_t *__restrict__ frame, const WsGeom &G, int ch, int r, int col) {
+  return __fdiv_rn((float)frame[(unsigned)((r * G.w + col) * 3 + ch)], 255.f);
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+constexpr int kScales = 5;
+constexpr int kOutCols = kScales + 2;  // v_0..v_4, WS-MSE, WS-MS-SSIM
+__constant__ const double kBetaDev[kScales] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};  // Wang, Simoncelli, Bovik 2003
+
+// the range checks of every entry; a chain of `scales` scales needs 1 << (scales - 1) pixels a side, or its last
+// scale has none
+int ws_sizes(const char *what, int scales, int n, int c, int h, int w) {
+  const int min_side = 1 << (scales - 1);
+  PCONV_REQUIRE(n >= 1 && n <= 65535, "%s: bad frame count %d", what, n);
+  PCONV_REQUIRE(c >= 1 && c <= 4096, "%s: bad channel count %d", what, c);
+  PCONV_REQUIRE(h >= 1 && w >= 1 && h <= kMaxSide && w <= kMaxSide, "%s: bad frame size %dx%d", what, w, h);
+  PCONV_REQUIRE(h >= min_side && w >= min_side, "%s: h and w must be at least %d, got %dx%d", what, min_side, w, h);
+  return PCONV_OK;
+}
+
+// f32_planes: the entry writes float32 planes (a pyramid, a gradient) that are addressed by 32-bit byte offsets
+int ws_geom(const char *what, int scales, int n, int c, int h, int w, int weighting, bool f32_planes, WsGeom *G) {
+  if (ws_sizes(what, scales, n, c, h, w) != PCONV_OK) return PCONV_EINVAL;
+  PCONV_REQUIRE(3LL * h * w < (1LL << 31), "%s: a %dx%d frame exceeds 2^31 bytes per plane", what, w, h);
+  PCONV_REQUIRE(weighting == PCONV_WS_WEIGHT_SPHERE || weighting == PCONV_WS_WEIGHT_UNIFORM,
+                "%s: unknown weighting %d", what, weighting);
+  PCONV_REQUIRE(!f32_planes || 4LL * h * w < (1LL << 31), "%s: a %dx%d plane has 2^31 bytes or more", what, w, h);
+  G->c = c, G->h = h, G->w = w;
+  G->tiles_x = (w + kTileCols - 1) / kTileCols;
+  G->tiles = G->tiles_x * ((h + kTileRows - 1) / kTileRows);
+  G->uniform = weighting == PCONV_WS_WEIGHT_UNIFORM;
+  // pytorch_ssim.gaussian(11, 1.5): exp(-(k - 5)² / (2·1.5²)) in double, normalised; here in fp32
+  double g[kTaps], sum = 0.0;
+  for (int k = 0; k < kTaps; k++) sum += g[k] = exp(-(double)((k - kHalo) * (k - kHalo)) / (2.0 * 1.5 * 1.5));
+  for (int k = 0; k < kTaps; k++) G->g[k] = (float)(g[k] / sum);
+  return PCONV_OK;
+}
+
+// ---- the backward kernel's tile: inputs with a halo of 10, see ms_backward_kernel ----
+constexpr int kBHalo = 2 * kHalo;                 // 10: halo of the staged inputs
+constexpr int kBBlock = 512;                      // two waves per SIMD: the 154 KB of LDS allow one workgroup per CU
+constexpr int kBRows = kTileRows + 2 * kBHalo;    // 52 staged rows (of 84 columns) = rows of the horizontal moments
+constexpr int kBLd = 88;                          // staged row stride: the last float4 read of pass B ends at 87
+constexpr int kMLd = 76;                          // row stride of the 74 moment columns: 19 quads (74, 75 computed, unused)
+constexpr int kMQuads = kMLd / 4;
+constexpr int kPRows = kInRows;                   // 42 rows of ks·a, ks·b, ks·c
+constexpr int kCRowsPerLane = 7;                  // pass C: 7 rows of one column per lane, 42 = 6 x 7
+constexpr int kERowsPerLane = kTileRows * kTileCols / kBBlock;  // pass E: 4 rows of one column per lane
+constexpr int kBStage = (kBRows * kBLd + kBBlock - 1) / kBBlock;
+static_assert(kBBlock >= 64 + kTileRows && kTileRows % kERowsPerLane == 0, "pass E covers the tile in whole groups");
+static_assert(kPRows % kCRowsPerLane == 0, "pass C covers the 42 rows in whole groups");
+static_assert(4 * (kMQuads - 1) + 16 <= kBLd, "pass B: the last float4 read stays inside the staged row");
+static_assert(4 * (kQuads - 1) + 16 <= kMLd, "pass D: the last float4 read stays inside the plane's row");
+static_assert(3 * kPRows * kTileCols <= 5 * kBRows * kMLd, "pass D writes over the moment planes");
+
+inline WsGeom scale_geom(const WsGeom &G0, int s) {
+  WsGeom G = G0;
+  G.h = G0.h >> s, G.w = G0.w >> s;
+  G.tiles_x = (G.w + kTileCols - 1) / kTileCols;
+  G.tiles = G.tiles_x * ((G.h + kTileRows - 1) / kTileRows);
+  return G;
+}
+
+// N = C · w · Σ_j w_j: the sum j-ascending in double on the host, so that every workgroup divides by the same bits
+inline double ws_norm(const WsGeom &G) {
+  double sw = 0.0;
+  for (int j = 0; j < G.h; j++) sw += G.uniform ? 1.0 : row_weight(j, G.h);
+  return (double)G.c * (double)G.w * sw;
+}
+
+// the forward's workspace for a chain of `scales` scales: the pyramid x_1, y_1, ... (none for one scale), then the
+// tiles' partials
+struct MsLayout {
+  long long level[kScales];     // floats from the workspace's start to x_s (s >= 1); y_s follows x_s
+  long long partials[kScales];  // doubles from the partials' start to scale s
+  long long pyramid_floats;     // all of x_1.. and y_1..
+  long long partial_doubles;
+  int tiles[kScales];
+};
+
+inline MsLayout ms_layout(int scales, int n, int c, int h, int w) {
+  MsLayout L = {};
+  long long fl = 0, db = 0;
+  for (int s = 0; s < scales; s++) {
+    const int hs = h >> s, ws = w >> s;
+    L.tiles[s] = ((ws + kTileCols - 1) / kTileCols) * ((hs + kTileRows - 1) / kTileRows);
+    L.level[s] = fl;
+    if (s > 0) fl += 2LL * n * c * hs * ws;
+    L.partials[s] = db;
+    db += 2LL * n * L.tiles[s];
+  }
+  L.pyramid_floats = fl;  // even: the partials behind it stay 8-byte aligned
+  L.partial_doubles = db;
+  return L;
+}
+
+// FIRST: scale 0 (T may be uint8; Σ w·(x - y)² is accumulated).  FINAL: the last scale (the full map, no next scale).
+// WS-SSIM is both at once.
+template <typename T, bool FIRST, bool FINAL>
+__global__ __launch_bounds__(kBlock, 2) void ms_forward_kernel(const T *__restrict__ x, const T *__restrict__ y,
+                                                            float *__restrict__ nx, float *__restrict__ ny,
+                                                            double *__restrict__ partials, WsGeom G, int h2, int w2) {
   __shared__ __attribute__((aligned(16))) float sx[kInRows * kLd];
   __shared__ __attribute__((aligned(16))) float sy[kInRows * kLd];
   __shared__ __attribute__((aligned(16))) float mom[5][kPlane];
@@ -53,6 +205,20 @@ __global__ __launch_bounds__(kBlock, 2) void ws_metrics_kernel(const T *__restri
       }
     }
     __syncthreads();
+    // the next scale: the tile's 16 x 32 block of 2x2 means, ((p00 + p01) + (p10 + p11))·0.25f, from the staged tile.
+    // A block inside the next scale lies inside this frame (2·(h >> 1) <= h) and inside this tile (even origin)
+    if (!FINAL) {
+      float *nxp = nx + ((long long)f * G.c + ch) * h2 * w2, *nyp = ny + ((long long)f * G.c + ch) * h2 * w2;
+      for (int u = tid; u < (kTileRows / 2) * (kTileCols / 2); u += kBlock) {
+        const int pj = u / (kTileCols / 2), pi = u - pj * (kTileCols / 2);
+        const int gj = (r0 >> 1) + pj, gi = (c0 >> 1) + pi;
+        if (gj < h2 && gi < w2) {
+          const int o = (2 * pj + kHalo) * kLd + 2 * pi + kHalo;
+          nxp[(unsigned)(gj * w2 + gi)] = ((sx[o] + sx[o + 1]) + (sx[o + kLd] + sx[o + kLd + 1])) * 0.25f;
+          nyp[(unsigned)(gj * w2 + gi)] = ((sy[o] + sy[o + 1]) + (sy[o + kLd] + sy[o + kLd + 1])) * 0.25f;
+        }
+      }
+    }
     // horizontal pass: 4 adjacent outputs of one staged row per lane, from 14 inputs read as four float4
     for (int u = tid; u < kInRows * kQuads; u += kBlock) {
       const int rr = u / kQuads, q = u - rr * kQuads;
@@ -111,12 +277,18 @@ __global__ __launch_bounds__(kBlock, 2) void ws_metrics_kernel(const T *__restri
         const float mu1 = acc[o][0], mu2 = acc[o][1];
         const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
         const float s1 = acc[o][2] - mu1_sq, s2 = acc[o][3] - mu2_sq, s12 = acc[o][4] - mu1_mu2;
-        const float map = ((2.f * mu1_mu2 + C1) * (2.f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
-        const int centre = (r + kHalo) * kLd + col + kHalo;
-        const float d = sx[centre] - sy[centre];
-        const float e2 = d * d;
-        acc_e += wrow[r] * (double)e2;
+        float map;
+        if (FINAL)
+          map = ((2.f * mu1_mu2 + C1) * (2.f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
+        else
+          map = (2.f * s12 + C2) / (s1 + s2 + C2);
         acc_s += wrow[r] * (double)map;
+        if (FIRST) {
+          const int centre = (r + kHalo) * kLd + col + kHalo;
+          const float d = sx[centre] - sy[centre];
+          const float e2 = d * d;
+          acc_e += wrow[r] * (double)e2;
+        }
       }
     }
   }
@@ -135,66 +307,75 @@ __global__ __launch_bounds__(kBlock, 2) void ws_metrics_kernel(const T *__restri
   }
 }
 
-// one workgroup per frame: its tiles' partials and Σ_j w_j, each in a fixed order, then the normalisation
-__global__ __launch_bounds__(kBlock) void ws_metrics_sum_kernel(const double *__restrict__ partials,
-                                                                double *__restrict__ out, WsGeom G) {
+struct MsClose {
+  long long partials[kScales];  // doubles from the partials' start to scale s
+  int tiles[kScales];
+  int c, h, w, uniform;
+};
+
+// one workgroup per frame: per scale its tiles' partials and Σ_j w_j, each in a fixed order, then the normalisation.
+// SCALES == kScales: out (n, 7) = v_0..v_4, WS-MSE, and the product, formed by thread 0.  SCALES == 1: out (n, 2) =
+// WS-MSE, WS-SSIM, and no product
+template <int SCALES>
+__global__ __launch_bounds__(kBlock) void ms_close_kernel(const double *__restrict__ partials,
+                                                          double *__restrict__ out, MsClose M) {
   __shared__ double red[3][kBlock];
+  __shared__ double v[SCALES];
+  constexpr int cols = SCALES == 1 ? 2 : kOutCols, mse_col = SCALES == 1 ? 0 : SCALES, v_col = SCALES == 1 ? 1 : 0;
   const int f = blockIdx.x, tid = threadIdx.x;
-  const double *p = partials + (long long)f * G.tiles * 2;
-  double se = 0.0, ss = 0.0, sw = 0.0;
-  for (int b = tid; b < G.tiles; b += kBlock) {
-    se += p[2 * b];
-    ss += p[2 * b + 1];
-  }
-  for (int j = tid; j < G.h; j += kBlock) sw += G.uniform ? 1.0 : row_weight(j, G.h);
-  red[0][tid] = se;
-  red[1][tid] = ss;
-  red[2][tid] = sw;
-  __syncthreads();
-  for (int s = kBlock / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-#pragma unroll
-      for (int t = 0; t < 3; t++) red[t][tid] += red[t][tid + s];
+  for (int s = 0; s < SCALES; s++) {
+    const int hs = M.h >> s, ws = M.w >> s, tiles = M.tiles[s];
+    const double *p = partials + M.partials[s] + (long long)f * tiles * 2;
+    double se = 0.0, ss = 0.0, sw = 0.0;
+    for (int b = tid; b < tiles; b += kBlock) {
+      se += p[2 * b];
+      ss += p[2 * b + 1];
     }
+    for (int j = tid; j < hs; j += kBlock) sw += M.uniform ? 1.0 : row_weight(j, hs);
+    red[0][tid] = se;
+    red[1][tid] = ss;
+    red[2][tid] = sw;
     __syncthreads();
+    for (int k = kBlock / 2; k > 0; k >>= 1) {
+      if (tid < k) {
+#pragma unroll
+        for (int t = 0; t < 3; t++) red[t][tid] += red[t][tid + k];
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      const double norm = (double)M.c * (double)ws * red[2][0];
+      v[s] = red[1][0] / norm;
+      out[(long long)cols * f + v_col + s] = v[s];
+      if (s == 0) out[(long long)cols * f + mse_col] = red[0][0] / norm;
+    }
+    __syncthreads();  // red is reused by the next scale
   }
-  if (tid < 2) out[2 * f + tid] = red[tid][0] / ((double)G.c * (double)G.w * red[2][0]);
+  if (SCALES > 1 && tid == 0) {
+    double ms = 1.0;
+    for (int s = 0; s < SCALES; s++) ms *= pow(fmax(v[s], 0.0), kBetaDev[s]);
+    out[(long long)cols * f + SCALES + 1] = ms;
+  }
 }
 
-
-template <typename T>
-int ws_metrics(const char *what, const T *x, const T *y, int n, int c, int h, int w, int weighting, void *workspace,
-               double *out, void *stream) {
-  PCONV_REQUIRE(x && y && workspace && out, "%s: null pointer", what);
-  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
-                "%s: workspace and out must be 8-byte aligned", what);
-  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(x) % sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(y) % sizeof(T)) == 0,
-                "%s: misaligned frames", what);
-  WsGeom G;
-  if (ws_geom(what, n, c, h, w, weighting, &G) != PCONV_OK) return PCONV_EINVAL;
-  double *partials = static_cast<double *>(workspace);
-  hipLaunchKernelGGL(ws_metrics_kernel<T>, dim3(G.tiles, n), dim3(kBlock), 0, as_stream(stream), x, y, partials, G);
-  PCONV_LAUNCH_CHECK(what);
-  hipLaunchKernelGGL(ws_metrics_sum_kernel, dim3(n), dim3(kBlock), 0, as_stream(stream), partials, out, G);
-  PCONV_LAUNCH_CHECK(what);
-  return PCONV_OK;
-}
-
-// ---- backward of WS-MSE + WS-SSIM with respect to y (include/pconv_hip.h states the definition) ----
 // A gather: one workgroup per (32 x 64 output tile, frame, channel), every output element stored exactly once.
 //   A  stage x and y with a halo of 10 (52 x 84, zeros outside the frame)
 //   B  horizontal pass -> the five moment planes on 52 rows x 74 columns
-//   C  vertical pass -> the moments on the tile + a halo of 5 (42 x 74); from them ks·a, ks·b, ks·c, zero outside the
+//   C  vertical pass -> the moments on the tile + a halo of 5 (42 x 74); from them k·a, k·b, k·c, zero outside the
 //      frame, into three planes of their own
 //   D  horizontal pass of these three planes -> 42 rows x 64 columns, over the moment planes (dead after C)
-//   E  vertical pass -> blur(ks·a), blur(ks·b), blur(ks·c) on the tile, the four-term sum, one store per element
-// Every 11-tap sum runs k-ascending as fmaf(g[k], v, acc) from acc = 0, the horizontal pass first.  No atomics, no
-// workspace; the upstream gradients are read from device memory.
-
-__global__ __launch_bounds__(kBBlock) void ws_metrics_backward_kernel(const float *__restrict__ x,
-                                                                    const float *__restrict__ y,
-                                                                    const double *__restrict__ gout,
-                                                                    float *__restrict__ gy, WsGeom G, double norm) {
+//   E  vertical pass -> blur(k·a), blur(k·b), blur(k·c) on the tile, the sum, one store per element
+// Every 11-tap sum runs k-ascending as fmaf(g[k], v, acc) from acc = 0, the horizontal pass first.  No atomics; the
+// upstream gradients are read from device memory.
+// FULL: the last scale, the coefficients of the full map and no coarser gradient.  Otherwise the cs-only coefficients
+// and + 0.25f·coarse[r >> 1][q >> 1].  FIRST: scale 0, + km·(y - x).  MULTI: the per-frame factor is u_s = gs·β_s·MS /
+// v_s, formed in fp64 from the forward's saved values; otherwise (WS-SSIM, one scale) it is gs and `values` is not read.
+template <bool FULL, bool FIRST, bool MULTI>
+__global__ __launch_bounds__(kBBlock) void ms_backward_kernel(const float *__restrict__ x, const float *__restrict__ y,
+                                                            const double *__restrict__ values,
+                                                            const double *__restrict__ gout,
+                                                            const float *__restrict__ coarse, float *__restrict__ gy,
+                                                            WsGeom G, double norm, int scale, int h2, int w2) {
   __shared__ __attribute__((aligned(16))) float sx[kBRows * kBLd];
   __shared__ __attribute__((aligned(16))) float sy[kBRows * kBLd];
   __shared__ __attribute__((aligned(16))) float mom[5 * kBRows * kMLd];
@@ -204,13 +385,22 @@ __global__ __launch_bounds__(kBBlock) void ws_metrics_backward_kernel(const floa
   const int tid = threadIdx.x, tile = blockIdx.x, f = blockIdx.y, ch = blockIdx.z;
   const int ty = tile / G.tiles_x;
   const int r0 = ty * kTileRows, c0 = (tile - ty * G.tiles_x) * kTileCols;
-  // ks_j = gs·w_j / N and km_j = 2·gm·w_j / N in fp64, each rounded once to fp32; ks = 0 on rows outside the frame
+  // k_j = u_s·w_j / N_s with u_s = gs·β_s·MS / v_s (0 when any v_t <= 0; gs alone for one scale), and km_j =
+  // 2·gm·w_j / N_0: fp64, each rounded once to fp32; k = 0 on rows outside the frame
   if (tid < kPRows) {
     const int gr = r0 - kHalo + tid;
     const bool in = gr >= 0 && gr < G.h;
     const double wj = G.uniform ? 1.0 : row_weight(in ? gr : 0, G.h);
-    ks_row[tid] = in ? (float)(gout[2 * f + 1] * wj / norm) : 0.f;
-  } else if (tid >= 64 && tid < 64 + kTileRows) {
+    double u = gout[2 * f + 1];
+    if (MULTI) {
+      const double *v = values + (long long)kOutCols * f;
+      bool positive = true;
+#pragma unroll
+      for (int t = 0; t < kScales; t++) positive = positive && v[t] > 0.0;
+      u = positive ? u * kBetaDev[scale] * v[kScales + 1] / v[scale] : 0.0;
+    }
+    ks_row[tid] = in ? (float)(u * wj / norm) : 0.f;
+  } else if (FIRST && tid >= 64 && tid < 64 + kTileRows) {
     const int gr = min(r0 + tid - 64, G.h - 1);
     const double wj = G.uniform ? 1.0 : row_weight(gr, G.h);
     km_row[tid - 64] = (float)(2.0 * gout[2 * f] * wj / norm);
@@ -229,7 +419,7 @@ __global__ __launch_bounds__(kBBlock) void ws_metrics_backward_kernel(const floa
     }
   }
   __syncthreads();
-  // B: horizontal pass, 4 adjacent outputs of one staged row per lane (as ws_metrics_kernel)
+  // B: horizontal pass, 4 adjacent outputs of one staged row per lane
   for (int u = tid; u < kBRows * kMQuads; u += kBBlock) {
     const int rr = u / kMQuads, qd = u - rr * kMQuads;
     float a[16], b[16];
@@ -290,12 +480,21 @@ __global__ __launch_bounds__(kBBlock) void ws_metrics_backward_kernel(const floa
       const float mux = acc[o][0], muy = acc[o][1];
       const float mux_sq = mux * mux, muy_sq = muy * muy, mux_muy = mux * muy;
       const float s1 = acc[o][2] - mux_sq, s2 = acc[o][3] - muy_sq, s12 = acc[o][4] - mux_muy;
-      const float A1 = 2.f * mux_muy + C1, A2 = 2.f * s12 + C2, B1 = mux_sq + muy_sq + C1, B2 = s1 + s2 + C2;
-      const float D = B1 * B2;
-      const float S = (A1 * A2) / D;
-      const float db = -S / B2;
-      const float dc = (2.f * A1) / D;
-      const float da = (2.f * mux) * A2 / D - (2.f * muy) * S / B1 - mux * dc - (2.f * muy) * db;
+      const float A2 = 2.f * s12 + C2, B2 = s1 + s2 + C2;
+      float da, db, dc;
+      if (FULL) {
+        const float A1 = 2.f * mux_muy + C1, B1 = mux_sq + muy_sq + C1;
+        const float D = B1 * B2;
+        const float S = (A1 * A2) / D;
+        db = -S / B2;
+        dc = (2.f * A1) / D;
+        da = (2.f * mux) * A2 / D - (2.f * muy) * S / B1 - mux * dc - (2.f * muy) * db;
+      } else {
+        const float S = A2 / B2;
+        db = -S / B2;
+        dc = 2.f / B2;
+        da = (-mux * dc) - (2.f * muy) * db;
+      }
       const float ks = ks_row[r];
       abc[0][r * kMLd + col] = in ? ks * da : 0.f;
       abc[1][r * kMLd + col] = in ? ks * db : 0.f;
@@ -326,8 +525,10 @@ __global__ __launch_bounds__(kBBlock) void ws_metrics_backward_kernel(const floa
   }
   __syncthreads();
   // E: vertical pass, rows rg..rg+3 of one column per lane, then
-  //   gy = ((blur(ks·a) + (2·y)·blur(ks·b)) + x·blur(ks·c)) + km·(y - x)
+  //   g = (blur(k·a) + (2·y)·blur(k·b)) + x·blur(k·c), + 0.25f·coarse[r >> 1][q >> 1] inside the coarser scale,
+  //   + km·(y - x) at scale 0
   float *gp = gy + ((long long)f * G.c + ch) * G.h * G.w;
+  const float *cp = FULL ? nullptr : coarse + ((long long)f * G.c + ch) * h2 * w2;
   for (int u = tid; u < (kTileRows / kERowsPerLane) * kTileCols; u += kBBlock) {
     const int col = u & (kTileCols - 1), rg = (u / kTileCols) * kERowsPerLane;
     float acc[kERowsPerLane][3];
@@ -350,18 +551,123 @@ __global__ __launch_bounds__(kBBlock) void ws_metrics_backward_kernel(const floa
     }
 #pragma unroll
     for (int o = 0; o < kERowsPerLane; o++) {
-      const int r = rg + o;
-      if (r0 + r < G.h && c0 + col < G.w) {
+      const int r = rg + o, gr = r0 + r, gc = c0 + col;
+      if (gr < G.h && gc < G.w) {
         const int centre = (r + kBHalo) * kBLd + col + kBHalo;
         const float xv = sx[centre], yv = sy[centre];
-        gp[(unsigned)((r0 + r) * G.w + c0 + col)] =
-            ((acc[o][0] + (2.f * yv) * acc[o][1]) + xv * acc[o][2]) + km_row[r] * (yv - xv);
+        float g = (acc[o][0] + (2.f * yv) * acc[o][1]) + xv * acc[o][2];
+        if (!FULL) {
+          const int cr = gr >> 1, cq = gc >> 1;
+          if (cr < h2 && cq < w2) g = g + 0.25f * cp[(unsigned)(cr * w2 + cq)];
+        }
+        if (FIRST) g = g + km_row[r] * (yv - xv);
+        gp[(unsigned)(gr * G.w + gc)] = g;
       }
     }
   }
 }
 
+// ---- host side: every entry is the chain of `scales` scales, 1 for WS-SSIM and kScales for WS-MS-SSIM ----
+
+template <typename T>
+int ws_forward(const char *what, int scales, const T *x, const T *y, int n, int c, int h, int w, int weighting,
+               void *workspace, double *out, void *stream) {
+  PCONV_REQUIRE(x && y && workspace && out, "%s: null pointer", what);
+  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
+                "%s: workspace and out must be 8-byte aligned", what);
+  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(x) % sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(y) % sizeof(T)) == 0,
+                "%s: misaligned frames", what);
+  WsGeom G0;
+  if (ws_geom(what, scales, n, c, h, w, weighting, scales > 1, &G0) != PCONV_OK) return PCONV_EINVAL;
+  const MsLayout L = ms_layout(scales, n, c, h, w);
+  float *pyr = static_cast<float *>(workspace);
+  double *partials = reinterpret_cast<double *>(pyr + L.pyramid_floats);
+  hipStream_t st = as_stream(stream);
+  for (int s = 0; s < scales; s++) {
+    const WsGeom G = scale_geom(G0, s);
+    const long long plane = (long long)n * c * G.h * G.w;
+    const int h2 = G.h >> 1, w2 = G.w >> 1;
+    const bool last = s + 1 == scales;
+    float *nx = last ? nullptr : pyr + L.level[s + 1];
+    float *ny = last ? nullptr : nx + (long long)n * c * h2 * w2;
+    const float *xs = pyr + L.level[s], *ys = xs + plane;  // read at s > 0
+    double *part = partials + L.partials[s];
+    const dim3 grid(G.tiles, n), block(kBlock);
+    if (s == 0 && last)
+      hipLaunchKernelGGL((ms_forward_kernel<T, true, true>), grid, block, 0, st, x, y, nx, ny, part, G, h2, w2);
+    else if (s == 0)
+      hipLaunchKernelGGL((ms_forward_kernel<T, true, false>), grid, block, 0, st, x, y, nx, ny, part, G, h2, w2);
+    else if (!last)
+      hipLaunchKernelGGL((ms_forward_kernel<float, false, false>), grid, block, 0, st, xs, ys, nx, ny, part, G, h2, w2);
+    else
+      hipLaunchKernelGGL((ms_forward_kernel<float, false, true>), grid, block, 0, st, xs, ys, nx, ny, part, G, h2, w2);
+    PCONV_LAUNCH_CHECK(what);
+  }
+  MsClose M = {};
+  for (int s = 0; s < scales; s++) M.partials[s] = L.partials[s], M.tiles[s] = L.tiles[s];
+  M.c = c, M.h = h, M.w = w, M.uniform = G0.uniform;
+  if (scales == 1)
+    hipLaunchKernelGGL(ms_close_kernel<1>, dim3(n), dim3(kBlock), 0, st, partials, out, M);
+  else
+    hipLaunchKernelGGL(ms_close_kernel<kScales>, dim3(n), dim3(kBlock), 0, st, partials, out, M);
+  PCONV_LAUNCH_CHECK(what);
+  return PCONV_OK;
+}
+
+// pyr, values and grads (the forward's workspace and result, the coarser scales' gradients) are read at scales > 1
+int ws_backward(const char *what, int scales, const float *x, const float *y, const float *pyr, const double *values,
+                const double *gout, int n, int c, int h, int w, int weighting, int swapped, float *grads, float *grad_y,
+                void *stream) {
+  WsGeom G0;
+  if (ws_geom(what, scales, n, c, h, w, weighting, true, &G0) != PCONV_OK) return PCONV_EINVAL;
+  PCONV_REQUIRE(swapped == 0 || swapped == 1, "%s: swapped must be 0 or 1, got %d", what, swapped);
+  const MsLayout L = ms_layout(scales, n, c, h, w);
+  hipStream_t st = as_stream(stream);
+  for (int s = scales - 1; s >= 0; s--) {
+    const WsGeom G = scale_geom(G0, s);
+    const long long plane = (long long)n * c * G.h * G.w;
+    const double norm = ws_norm(G);
+    // the forward's workspace holds (first, second) of the forward call; swapped: y was its first picture
+    const float *first = pyr + L.level[s], *second = first + plane;
+    const float *xs = s == 0 ? x : (swapped ? second : first), *ys = s == 0 ? y : (swapped ? first : second);
+    float *gs = s == 0 ? grad_y : grads + L.level[s] / 2;
+    const float *coarse = s + 1 < scales ? grads + L.level[s + 1] / 2 : nullptr;
+    const int h2 = G.h >> 1, w2 = G.w >> 1;
+    const dim3 grid(G.tiles, n, c), block(kBBlock);
+    if (scales == 1)
+      hipLaunchKernelGGL((ms_backward_kernel<true, true, false>), grid, block, 0, st, xs, ys, values, gout, coarse, gs, G,
+                         norm, s, h2, w2);
+    else if (s == scales - 1)
+      hipLaunchKernelGGL((ms_backward_kernel<true, false, true>), grid, block, 0, st, xs, ys, values, gout, coarse, gs, G,
+                         norm, s, h2, w2);
+    else if (s > 0)
+      hipLaunchKernelGGL((ms_backward_kernel<false, false, true>), grid, block, 0, st, xs, ys, values, gout, coarse, gs, G,
+                         norm, s, h2, w2);
+    else
+      hipLaunchKernelGGL((ms_backward_kernel<false, true, true>), grid, block, 0, st, xs, ys, values, gout, coarse, gs, G,
+                         norm, s, h2, w2);
+    PCONV_LAUNCH_CHECK(what);
+  }
+  return PCONV_OK;
+}
+
 }  // namespace
+
+extern "C" long long pconv_ws_metrics_workspace_bytes(int n, int h, int w) {
+  if (ws_sizes("ws_metrics_workspace_bytes", 1, n, 1, h, w) != PCONV_OK) return PCONV_EINVAL;
+  return ms_layout(1, n, 1, h, w).partial_doubles * (long long)sizeof(double);
+}
+
+extern "C" int pconv_ws_metrics_f32(const float *x, const float *y, int n, int c, int h, int w, int weighting,
+                                    void *workspace, double *out, void *stream) {
+  return ws_forward("ws_metrics_f32", 1, x, y, n, c, h, w, weighting, workspace, out, stream);
+}
+
+extern "C" int pconv_ws_metrics_u8(const uint8_t *x, const uint8_t *y, int n, int c, int h, int w, int weighting,
+                                   void *workspace, double *out, void *stream) {
+  PCONV_REQUIRE(c == 3, "ws_metrics_u8: interleaved (n, h, w, 3) frames have 3 channels, got %d", c);
+  return ws_forward("ws_metrics_u8", 1, x, y, n, c, h, w, weighting, workspace, out, stream);
+}
 
 extern "C" int pconv_ws_metrics_backward_f32(const float *x, const float *y, const double *gout, int n, int c, int h,
                                              int w, int weighting, float *grad_y, void *stream) {
@@ -370,34 +676,41 @@ extern "C" int pconv_ws_metrics_backward_f32(const float *x, const float *y, con
   PCONV_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0 &&
                     (reinterpret_cast<uintptr_t>(grad_y) & 3) == 0 && (reinterpret_cast<uintptr_t>(gout) & 7) == 0,
                 "%s: misaligned tensors", what);
-  WsGeom G;
-  if (ws_geom(what, n, c, h, w, weighting, &G) != PCONV_OK) return PCONV_EINVAL;
-  PCONV_REQUIRE(4LL * h * w < (1LL << 31), "%s: a %dx%d plane has 2^31 bytes or more", what, w, h);
-  // N = C · w · Σ_j w_j: the sum j-ascending in double on the host, so that every workgroup divides by the same bits
-  double sw = 0.0;
-  for (int j = 0; j < h; j++) sw += G.uniform ? 1.0 : row_weight(j, h);
-  const double norm = (double)c * (double)w * sw;
-  hipLaunchKernelGGL(ws_metrics_backward_kernel, dim3(G.tiles, n, c), dim3(kBBlock), 0, as_stream(stream), x, y, gout,
-                     grad_y, G, norm);
-  PCONV_LAUNCH_CHECK(what);
-  return PCONV_OK;
+  return ws_backward(what, 1, x, y, nullptr, nullptr, gout, n, c, h, w, weighting, 0, nullptr, grad_y, stream);
 }
 
-extern "C" long long pconv_ws_metrics_workspace_bytes(int n, int h, int w) {
-  PCONV_REQUIRE(n >= 1 && n <= 65535, "ws_metrics_workspace_bytes: bad frame count %d", n);
-  PCONV_REQUIRE(h >= 1 && w >= 1 && h <= kMaxSide && w <= kMaxSide, "ws_metrics_workspace_bytes: bad frame size %dx%d",
-                w, h);
-  const long long tiles = (long long)((w + kTileCols - 1) / kTileCols) * ((h + kTileRows - 1) / kTileRows);
-  return (long long)n * tiles * 2 * (long long)sizeof(double);
+extern "C" long long pconv_ws_msssim_workspace_bytes(int n, int c, int h, int w) {
+  if (ws_sizes("ws_msssim_workspace_bytes", kScales, n, c, h, w) != PCONV_OK) return PCONV_EINVAL;
+  const MsLayout L = ms_layout(kScales, n, c, h, w);
+  return L.pyramid_floats * (long long)sizeof(float) + L.partial_doubles * (long long)sizeof(double);
 }
 
-extern "C" int pconv_ws_metrics_f32(const float *x, const float *y, int n, int c, int h, int w, int weighting,
-                                    void *workspace, double *out, void *stream) {
-  return ws_metrics("ws_metrics_f32", x, y, n, c, h, w, weighting, workspace, out, stream);
-}
-
-extern "C" int pconv_ws_metrics_u8(const uint8_t *x, const uint8_t *y, int n, int c, int h, int w, int weighting,
+extern "C" int pconv_ws_msssim_f32(const float *x, const float *y, int n, int c, int h, int w, int weighting,
                                    void *workspace, double *out, void *stream) {
-  PCONV_REQUIRE(c == 3, "ws_metrics_u8: interleaved (n, h, w, 3) frames have 3 channels, got %d", c);
-  return ws_metrics("ws_metrics_u8", x, y, n, c, h, w, weighting, workspace, out, stream);
+  return ws_forward("ws_msssim_f32", kScales, x, y, n, c, h, w, weighting, workspace, out, stream);
+}
+
+extern "C" int pconv_ws_msssim_u8(const uint8_t *x, const uint8_t *y, int n, int c, int h, int w, int weighting,
+                                  void *workspace, double *out, void *stream) {
+  PCONV_REQUIRE(c == 3, "ws_msssim_u8: interleaved (n, h, w, 3) frames have 3 channels, got %d", c);
+  return ws_forward("ws_msssim_u8", kScales, x, y, n, c, h, w, weighting, workspace, out, stream);
+}
+
+extern "C" long long pconv_ws_msssim_backward_workspace_bytes(int n, int c, int h, int w) {
+  if (ws_sizes("ws_msssim_backward_workspace_bytes", kScales, n, c, h, w) != PCONV_OK) return PCONV_EINVAL;
+  return ms_layout(kScales, n, c, h, w).pyramid_floats / 2 * (long long)sizeof(float);
+}
+
+extern "C" int pconv_ws_msssim_backward_f32(const float *x, const float *y, const void *workspace, const double *values,
+                                            const double *gout, int n, int c, int h, int w, int weighting, int swapped,
+                                            void *backward_workspace, float *grad_y, void *stream) {
+  const char *what = "ws_msssim_backward_f32";
+  PCONV_REQUIRE(x && y && workspace && values && gout && backward_workspace && grad_y, "%s: null pointer", what);
+  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0 &&
+                    (reinterpret_cast<uintptr_t>(grad_y) & 3) == 0 && (reinterpret_cast<uintptr_t>(gout) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(values) & 7) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(backward_workspace) & 3) == 0,
+                "%s: misaligned tensors", what);
+  return ws_backward(what, kScales, x, y, static_cast<const float *>(workspace), values, gout, n, c, h, w, weighting,
+                     swapped, static_cast<float *>(backward_workspace), grad_y, stream);
 }

@@ -28,8 +28,8 @@ Both metrics are symmetric: the gradient with respect to x is the same with x an
 WS-MS-SSIM (the second half of this module; include/pconv_hip.h states it in full): five scales of 2x2 means (`pool`),
 v_s the weighted mean of cs = A2 / B2 at scales 0-3 and of the full map at scale 4, each with the row weights of a frame
 of that scale's height, and WS-MS-SSIM = Π max(v_s, 0)^β_s (`BETAS`).  ms_metrics / ws_ms_ssim score, ms_loss_terms is
-the autograd entry, ms_scales_torch and ms_backward_torch are the torch statements the kernels of csrc/ws_msssim.hip
-are held to.  Frames of at least 16 x 16.
+the autograd entry, ms_scales_torch and ms_backward_torch are the torch statements the same kernels, launched once per
+scale, are held to.  Frames of at least 16 x 16.
 """
 import math
 
@@ -83,25 +83,54 @@ def _blur(t, g):
     return sum(g[k] * rows[..., k:k + h, :] for k in range(WINDOW))
 
 
+def _check(x, y, weighting, what="sphere metrics", min_side=0):
+    if weighting not in WEIGHTINGS:
+        raise ValueError("weighting must be one of %s, got %r" % (WEIGHTINGS, weighting))
+    if x.dtype != y.dtype or x.shape != y.shape or x.device != y.device:
+        raise PconvError("%s: the two batches differ: %s %s %s vs %s %s %s"
+                         % (what, x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
+    if x.dim() != 4:
+        raise PconvError("%s: 4-D batches expected, got %s" % (what, tuple(x.shape)))
+    h, w = (x.shape[1:3] if x.dtype == torch.uint8 else x.shape[2:])
+    if h < min_side or w < min_side:
+        raise PconvError("%s: h and w must be at least %d, got %dx%d" % (what, min_side, w, h))
+
+
+def _row_weights(t, weighting):
+    """the row weights of t (n, C, h, w) as float64 (1, 1, h, 1) on its device, and N = C·w·Σ_j w_j"""
+    _, c, h, w = t.shape
+    wr = weights(h, weighting).to(t.device)
+    return wr.view(1, 1, h, 1), c * w * float(wr.sum())
+
+
+def _moments(x, y, g):
+    """mux, muy, A2 = 2·sxy + C2, B2 = sx2 + sy2 + C2 and the squares they are made of, in x's dtype"""
+    mux, muy = _blur(x, g), _blur(y, g)
+    mux_sq, muy_sq, mux_muy = mux * mux, muy * muy, mux * muy
+    s1, s2, s12 = _blur(x * x, g) - mux_sq, _blur(y * y, g) - muy_sq, _blur(x * y, g) - mux_muy
+    return mux, muy, mux_sq, muy_sq, mux_muy, 2 * s12 + C2, s1 + s2 + C2
+
+
+def _ssim_map(moments, full):
+    """the full map l·cs, or cs = A2 / B2 alone, from _moments' tuple"""
+    _, _, mux_sq, muy_sq, mux_muy, A2, B2 = moments
+    return ((2 * mux_muy + C1) * A2) / ((mux_sq + muy_sq + C1) * B2) if full else A2 / B2
+
+
+def _terms_torch(a, b, weighting):
+    """float64 (n, 2) [WS-MSE, WS-SSIM] of float32 (n, C, h, w) batches on their device, differentiable: the
+    definitions above in float64 torch"""
+    wr, norm = _row_weights(a, weighting)
+    e2 = ((a - b) * (a - b)).double()
+    ssim_map = _ssim_map(_moments(a.double(), b.double(), gaussian()), True)
+    return torch.stack([(e2 * wr).sum(dim=(1, 2, 3)) / norm, (ssim_map * wr).sum(dim=(1, 2, 3)) / norm], dim=1)
+
+
 def metrics_torch(x, y, weighting="ws"):
     """float64 (n, 2) [WS-MSE, WS-SSIM]: the definitions above in float64 torch, on the batches' device (the CPU
     path of `metrics`, and the reference the GPU tests compare the kernel with)"""
-    if x.dtype != y.dtype or x.shape != y.shape or x.device != y.device:
-        raise PconvError("sphere metrics: the two batches differ: %s %s %s vs %s %s %s"
-                         % (x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
-    a, b = _as_planes(x), _as_planes(y)
-    n, c, h, w = a.shape
-    wr = weights(h, weighting).to(a.device)
-    norm = c * w * float(wr.sum())
-    wr = wr.view(1, 1, h, 1)
-    e2 = ((a - b) * (a - b)).double()
-    a, b = a.double(), b.double()
-    g = gaussian()
-    mu1, mu2 = _blur(a, g), _blur(b, g)
-    mu1_sq, mu2_sq, mu1_mu2 = mu1 * mu1, mu2 * mu2, mu1 * mu2
-    s1, s2, s12 = _blur(a * a, g) - mu1_sq, _blur(b * b, g) - mu2_sq, _blur(a * b, g) - mu1_mu2
-    ssim_map = ((2 * mu1_mu2 + C1) * (2 * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2))
-    return torch.stack([(e2 * wr).sum(dim=(1, 2, 3)) / norm, (ssim_map * wr).sum(dim=(1, 2, 3)) / norm], dim=1).cpu()
+    _check(x, y, weighting)
+    return _terms_torch(_as_planes(x), _as_planes(y), weighting).cpu()
 
 
 def metrics(x, y, weighting="ws"):
@@ -134,23 +163,6 @@ def ws_ssim(x, y, weighting="ws"):
     return metrics(x, y, weighting)[:, 1]
 
 
-def _terms_torch(a, b, weighting):
-    """float64 (n, 2) [WS-MSE, WS-SSIM] of float32 (n, C, h, w) batches on their device: metrics_torch's arithmetic,
-    differentiable"""
-    n, c, h, w = a.shape
-    wr = weights(h, weighting).to(a.device)
-    norm = c * w * float(wr.sum())
-    wr = wr.view(1, 1, h, 1)
-    e2 = ((a - b) * (a - b)).double()
-    a, b = a.double(), b.double()
-    g = gaussian()
-    mu1, mu2 = _blur(a, g), _blur(b, g)
-    mu1_sq, mu2_sq, mu1_mu2 = mu1 * mu1, mu2 * mu2, mu1 * mu2
-    s1, s2, s12 = _blur(a * a, g) - mu1_sq, _blur(b * b, g) - mu2_sq, _blur(a * b, g) - mu1_mu2
-    ssim_map = ((2 * mu1_mu2 + C1) * (2 * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2))
-    return torch.stack([(e2 * wr).sum(dim=(1, 2, 3)) / norm, (ssim_map * wr).sum(dim=(1, 2, 3)) / norm], dim=1)
-
-
 class _WsTerms(torch.autograd.Function):
     """[WS-MSE, WS-SSIM] per frame of GPU tensors: the forward kernel, and its backward kernel once per input that
     needs a gradient"""
@@ -176,12 +188,8 @@ def loss_terms(x, y, weighting="ws"):
     of `metrics`, as a loss.  x, y: float (n, C, h, w) batches of one shape (uint8 carries no gradient and is
     refused).  GPU tensors (float32, contiguous or made so): the HIP kernel forward, the HIP kernel backward.  CPU
     tensors: the float64 torch statement, differentiated by torch"""
-    if weighting not in WEIGHTINGS:
-        raise ValueError("weighting must be one of %s, got %r" % (WEIGHTINGS, weighting))
-    if x.dtype != y.dtype or x.shape != y.shape or x.device != y.device:
-        raise PconvError("sphere loss: the two batches differ: %s %s %s vs %s %s %s"
-                         % (x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
-    if x.dim() != 4 or not x.is_floating_point():
+    _check(x, y, weighting, "sphere loss")
+    if not x.is_floating_point():
         raise PconvError("sphere loss: float (n, C, h, w) batches expected (uint8 frames carry no gradient), got %s %s"
                          % (x.dtype, tuple(x.shape)))
     if x.is_cuda:
@@ -194,6 +202,31 @@ def loss_terms(x, y, weighting="ws"):
     return _terms_torch(x, y, weighting)
 
 
+def _coefficients(moments, full):
+    """(a, b, c) of the module's head from _moments' tuple: the derivatives of the full map with respect to muy,
+    blur(y²) and blur(xy), or (full=False) those of cs = A2 / B2 alone"""
+    mux, muy, mux_sq, muy_sq, mux_muy, A2, B2 = moments
+    if full:
+        A1, B1 = 2 * mux_muy + C1, mux_sq + muy_sq + C1
+        D = B1 * B2
+        S = (A1 * A2) / D
+        b = -S / B2
+        c = (2 * A1) / D
+        a = (2 * mux) * A2 / D - (2 * muy) * S / B1 - mux * c - (2 * muy) * b
+    else:
+        S = A2 / B2
+        b = -S / B2
+        c = 2 / B2
+        a = (-mux * c) - (2 * muy) * b
+    return a, b, c
+
+
+def _own(x, y, k, abc, g):
+    """a scale's own gradient with respect to y: (blur(k·a) + (2y)·blur(k·b)) + x·blur(k·c)"""
+    a, b, c = abc
+    return (_blur(k * a, g) + (2 * y) * _blur(k * b, g)) + x * _blur(k * c, g)
+
+
 def backward_torch(x, y, gout, weighting="ws", dt=torch.float64):
     """the gradient of Σ_f gout[f, 0]·WS-MSE_f + gout[f, 1]·WS-SSIM_f with respect to y, by the explicit formula of
     the module's head, in torch: the statement the HIP kernel is held to.  x, y (n, C, h, w); gout (n, 2).  ks and km
@@ -202,24 +235,14 @@ def backward_torch(x, y, gout, weighting="ws", dt=torch.float64):
     if x.shape != y.shape or x.dim() != 4 or tuple(gout.shape) != (x.shape[0], 2):
         raise PconvError("sphere loss: (n, C, h, w) batches of one shape and gout (n, 2) expected, got %s %s %s"
                          % (tuple(x.shape), tuple(y.shape), tuple(gout.shape)))
-    n, c, h, w = x.shape
-    wr = weights(h, weighting).to(x.device)
-    norm = c * w * float(wr.sum())
+    n = x.shape[0]
+    wr, norm = _row_weights(x, weighting)
     gout = gout.detach().double().to(x.device)
-    ks = (gout[:, 1].view(n, 1, 1, 1) * wr.view(1, 1, h, 1) / norm).to(dt)
-    km = (2.0 * gout[:, 0].view(n, 1, 1, 1) * wr.view(1, 1, h, 1) / norm).to(dt)
+    ks = (gout[:, 1].view(n, 1, 1, 1) * wr / norm).to(dt)
+    km = (2.0 * gout[:, 0].view(n, 1, 1, 1) * wr / norm).to(dt)
     x, y = x.detach().to(dt), y.detach().to(dt)
     g = gaussian()
-    mux, muy = _blur(x, g), _blur(y, g)
-    mux_sq, muy_sq, mux_muy = mux * mux, muy * muy, mux * muy
-    s1, s2, s12 = _blur(x * x, g) - mux_sq, _blur(y * y, g) - muy_sq, _blur(x * y, g) - mux_muy
-    A1, A2, B1, B2 = 2 * mux_muy + C1, 2 * s12 + C2, mux_sq + muy_sq + C1, s1 + s2 + C2
-    D = B1 * B2
-    S = (A1 * A2) / D
-    b = -S / B2
-    c_ = (2 * A1) / D
-    a = (2 * mux) * A2 / D - (2 * muy) * S / B1 - mux * c_ - (2 * muy) * b
-    return ((_blur(ks * a, g) + (2 * y) * _blur(ks * b, g)) + x * _blur(ks * c_, g)) + km * (y - x)
+    return _own(x, y, ks, _coefficients(_moments(x, y, g), True), g) + km * (y - x)
 
 
 # ---- WS-MS-SSIM: five scales of 2x2 means, cs at scales 0-3 and the full map at scale 4 (include/pconv_hip.h) ----
@@ -235,45 +258,18 @@ def pool(t):
     return ((t[..., 0::2, 0::2] + t[..., 0::2, 1::2]) + (t[..., 1::2, 0::2] + t[..., 1::2, 1::2])) * 0.25
 
 
-def _ms_check(x, y, weighting, what="sphere metrics"):
-    if weighting not in WEIGHTINGS:
-        raise ValueError("weighting must be one of %s, got %r" % (WEIGHTINGS, weighting))
-    if x.dtype != y.dtype or x.shape != y.shape or x.device != y.device:
-        raise PconvError("%s: the two batches differ: %s %s %s vs %s %s %s"
-                         % (what, x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
-    if x.dim() != 4:
-        raise PconvError("%s: 4-D batches expected, got %s" % (what, tuple(x.shape)))
-    h, w = (x.shape[1:3] if x.dtype == torch.uint8 else x.shape[2:])
-    if h < MIN_SIDE or w < MIN_SIDE:
-        raise PconvError("%s: h and w must be at least %d, got %dx%d" % (what, MIN_SIDE, w, h))
-
-
-def _moments(x, y, g):
-    """mux, muy, A2 = 2·sxy + C2, B2 = sx2 + sy2 + C2 and the squares they are made of, in x's dtype"""
-    mux, muy = _blur(x, g), _blur(y, g)
-    mux_sq, muy_sq, mux_muy = mux * mux, muy * muy, mux * muy
-    s1, s2, s12 = _blur(x * x, g) - mux_sq, _blur(y * y, g) - muy_sq, _blur(x * y, g) - mux_muy
-    return mux, muy, mux_sq, muy_sq, mux_muy, 2 * s12 + C2, s1 + s2 + C2
-
-
 def ms_scales_torch(x, y, weighting="ws", dt=torch.float64):
     """(n, 5) [v_0..v_4] in dtype dt on the batches' device, differentiable: v_s the weighted mean of cs (s < 4) or
     of the full SSIM map (s = 4) of the s-th scale, with the row weights of an (h >> s)-row frame.  x, y: float
     (n, C, h, w) or uint8 (n, h, w, 3), h, w >= 16"""
-    _ms_check(x, y, weighting)
+    _check(x, y, weighting, min_side=MIN_SIDE)
     a, b = (_as_planes(t) if t.dtype == torch.uint8 else t for t in (x, y))
     a, b = a.to(dt), b.to(dt)
     g, vs = gaussian(), []
     for s in range(SCALES):
-        n, c, h, w = a.shape
-        wr = weights(h, weighting).to(a.device)
-        norm = c * w * float(wr.sum())
-        mux, muy, mux_sq, muy_sq, mux_muy, A2, B2 = _moments(a, b, g)
-        if s == SCALES - 1:
-            m = ((2 * mux_muy + C1) * A2) / ((mux_sq + muy_sq + C1) * B2)
-        else:
-            m = A2 / B2
-        vs.append(((m.double() * wr.view(1, 1, h, 1)).sum(dim=(1, 2, 3)) / norm).to(dt))
+        wr, norm = _row_weights(a, weighting)
+        m = _ssim_map(_moments(a, b, g), s == SCALES - 1)
+        vs.append(((m.double() * wr).sum(dim=(1, 2, 3)) / norm).to(dt))
         if s < SCALES - 1:
             a, b = pool(a), pool(b)
     return torch.stack(vs, dim=1)
@@ -292,18 +288,16 @@ def ms_product(v):
 
 def _ms_terms_torch(a, b, weighting):
     """float64 (n, 2) [WS-MSE, WS-MS-SSIM] of float (n, C, h, w) batches on their device, differentiable"""
-    n, c, h, w = a.shape
-    wr = weights(h, weighting).to(a.device)
-    norm = c * w * float(wr.sum())
+    wr, norm = _row_weights(a, weighting)
     e2 = ((a - b) * (a - b)).double()
-    mse = (e2 * wr.view(1, 1, h, 1)).sum(dim=(1, 2, 3)) / norm
+    mse = (e2 * wr).sum(dim=(1, 2, 3)) / norm
     return torch.stack([mse, ms_product(ms_scales_torch(a, b, weighting, torch.float64))], dim=1)
 
 
 def ms_metrics(x, y, weighting="ws"):
     """float64 CPU tensor (n, 2): [:, 0] WS-MSE, [:, 1] WS-MS-SSIM of each frame; the HIP kernels for GPU tensors,
     the float64 torch path for CPU tensors"""
-    _ms_check(x, y, weighting)
+    _check(x, y, weighting, min_side=MIN_SIDE)
     if x.is_cuda:
         ops = backend.ops()
         if not hasattr(ops, "ws_msssim"):
@@ -344,7 +338,7 @@ def ms_loss_terms(x, y, weighting="ws"):
     """float64 (n, 2) [WS-MSE, WS-MS-SSIM] of each frame, on the inputs' device and attached to autograd: the values
     of `ms_metrics`, as a loss, with the contract of `loss_terms`.  A frame with any v_s <= 0 has WS-MS-SSIM 0 and a
     zero gradient of it"""
-    _ms_check(x, y, weighting, "sphere loss")
+    _check(x, y, weighting, "sphere loss", MIN_SIDE)
     if not x.is_floating_point():
         raise PconvError("sphere loss: float (n, C, h, w) batches expected (uint8 frames carry no gradient), got %s %s"
                          % (x.dtype, tuple(x.shape)))
@@ -363,7 +357,7 @@ def ms_backward_torch(x, y, gout, weighting="ws", dt=torch.float64):
     include/pconv_hip.h, in torch: the statement the HIP kernels are held to.  x, y (n, C, h, w); gout (n, 2).  The
     factors u_s, k and km are formed in float64 and rounded once to dt; everything else runs in dt, operation by
     operation in the kernels' order.  Returns dt (n, C, h, w)"""
-    _ms_check(x, y, weighting, "sphere loss")
+    _check(x, y, weighting, "sphere loss", MIN_SIDE)
     if tuple(gout.shape) != (x.shape[0], 2):
         raise PconvError("sphere loss: gout (n, 2) expected, got %s for %s" % (tuple(gout.shape), tuple(x.shape)))
     n = x.shape[0]
@@ -380,32 +374,16 @@ def ms_backward_torch(x, y, gout, weighting="ws", dt=torch.float64):
         ys.append(pool(ys[-1]))
     for s in range(SCALES):
         a, b = xs[s], ys[s]
-        _, c, h, w = a.shape
-        wr = weights(h, weighting).to(a.device)
-        norm = c * w * float(wr.sum())
+        wr, norm = _row_weights(a, weighting)
         u = torch.where(positive, gs * BETAS[s] * ms / safe[:, s], torch.zeros_like(gs))
-        k = (u.view(n, 1, 1, 1) * wr.view(1, 1, h, 1) / norm).to(dt)
-        mux, muy, mux_sq, muy_sq, mux_muy, A2, B2 = _moments(a, b, g)
-        if s == SCALES - 1:
-            A1, B1 = 2 * mux_muy + C1, mux_sq + muy_sq + C1
-            D = B1 * B2
-            S = (A1 * A2) / D
-            db = -S / B2
-            dc = (2 * A1) / D
-            da = (2 * mux) * A2 / D - (2 * muy) * S / B1 - mux * dc - (2 * muy) * db
-        else:
-            S = A2 / B2
-            db = -S / B2
-            dc = 2 / B2
-            da = (-mux * dc) - (2 * muy) * db
-        own.append((_blur(k * da, g) + (2 * b) * _blur(k * db, g)) + a * _blur(k * dc, g))
+        k = (u.view(n, 1, 1, 1) * wr / norm).to(dt)
+        own.append(_own(a, b, k, _coefficients(_moments(a, b, g), s == SCALES - 1), g))
     grad = own[SCALES - 1]
     for s in range(SCALES - 2, -1, -1):
         up = torch.zeros_like(own[s])
         h2, w2 = grad.shape[-2:]
         up[..., :2 * h2, :2 * w2] = (0.25 * grad).repeat_interleave(2, dim=-2).repeat_interleave(2, dim=-1)
         grad = own[s] + up
-    h = x.shape[2]
-    wr = weights(h, weighting).to(x.device)
-    km = (2.0 * gm.view(n, 1, 1, 1) * wr.view(1, 1, h, 1) / (x.shape[1] * x.shape[3] * float(wr.sum()))).to(dt)
+    wr, norm = _row_weights(x, weighting)
+    km = (2.0 * gm.view(n, 1, 1, 1) * wr / norm).to(dt)
     return grad + km * (y - x)

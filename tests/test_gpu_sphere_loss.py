@@ -1,4 +1,4 @@
-"""GPU: WS-MSE / WS-SSIM as a training loss (csrc/sphere_metrics.hip: ws_metrics_backward_kernel).  The HIP kernel
+"""GPU: WS-MSE / WS-SSIM as a training loss (csrc/sphere_metrics.hip: ms_backward_kernel, one scale).  The HIP kernel
 against the float64 statement of the gradient (sphere_metrics.backward_torch) within a bound taken from the float32
 statement's own error, the pure MSE part bit for bit, batching and repeat determinism, the autograd entry
 (sphere_metrics.loss_terms), refused arguments, and a few training steps on the loss."""

@@ -1,7 +1,7 @@
-"""GPU: WS-PSNR / WS-SSIM (csrc/sphere_metrics.hip).  The HIP kernel against the float64 torch path, the uint8 form
-bit for bit against frames_u8_to_f32 + the float form, batching and repeat determinism, the uniform weighting
-against pytorch_ssim, refused inputs, a codec frame of a non-codable size scored at its own height, and the command
-line's --test --ws against the float64 path on the same PNGs."""
+"""GPU: WS-PSNR / WS-SSIM (csrc/sphere_metrics.hip: ms_forward_kernel<T, 1, 1>, ms_close_kernel<1>).  The HIP kernel
+against the float64 torch path, the uint8 form bit for bit against frames_u8_to_f32 + the float form, batching and
+repeat determinism, the uniform weighting against pytorch_ssim, refused inputs, a codec frame of a non-codable size
+scored at its own height, and the command line's --test --ws against the float64 path on the same PNGs."""
 import numpy as np
 import pytest
 import torch

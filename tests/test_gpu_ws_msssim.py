@@ -1,7 +1,8 @@
-"""GPU: WS-MS-SSIM forward (csrc/ws_msssim.hip: ms_forward_kernel, ms_close_kernel).  The pyramid the kernels write
-bit for bit against `pool` in float32, the WS-MSE column bit for bit against ws_metrics, every scale value and the
-product against the float64 statement within bounds taken from the float32 map, the uint8 form, batching and repeat
-determinism, the clamp, and refused arguments."""
+"""GPU: WS-MS-SSIM forward (csrc/sphere_metrics.hip: ms_forward_kernel once per scale, ms_close_kernel<5>).  The
+pyramid the kernels write bit for bit against `pool` in float32, the WS-MSE column bit for bit against ws_metrics, the
+last scale bit for bit against ws_metrics of the pooled frames, every scale value and the product against the float64
+statement within bounds taken from the float32 map, the uint8 form, batching and repeat determinism, the clamp, and
+refused arguments."""
 import pytest
 import torch
 
@@ -50,6 +51,19 @@ def test_pyramid_is_pool_bit_for_bit(hip_backend, case):
         px, py = S.pool(px), S.pool(py)
         assert lx.shape == ly.shape == (n, c, h >> s, w >> s) and lx.dtype == torch.float32
         assert torch.equal(lx, px) and torch.equal(ly, py), (case, s)
+
+
+# (528, 1040) is 33 x 65 at scale 4: one row and one column past a tile edge, several tiles' partials at the last scale
+@pytest.mark.parametrize("shape", [(1, 1, 16, 16), (2, 3, 17, 19), (1, 1, 130, 258), (1, 1, 528, 1040)], ids=str)
+@pytest.mark.parametrize("weighting", WEIGHTINGS)
+def test_last_scale_is_ws_ssim_of_the_pooled_frames(hip_backend, shape, weighting):
+    """v_4 has the bits of WS-SSIM of (x_4, y_4): the single-scale metric is the chain of one scale, which runs the last
+    scale's map, sums and normalisation"""
+    from pseudocylindrical_convolution_amd import PCONV
+    x, y = (t.to(DEV) for t in inputs(shape))
+    got, workspace = PCONV.ws_msssim(x, y, weighting)
+    x4, y4 = (t.contiguous() for t in PCONV.ws_msssim_levels(workspace, *shape)[-1])
+    assert torch.equal(got[:, 4], PCONV.ws_metrics(x4, y4, weighting)[:, 1]), (shape, weighting)
 
 
 @pytest.mark.parametrize("case", CASES, ids=str)

@@ -1,4 +1,4 @@
-"""GPU: WS-MSE / WS-MS-SSIM as a training loss (csrc/ws_msssim.hip: ms_backward_kernel, one launch per scale).  The
+"""GPU: WS-MSE / WS-MS-SSIM as a training loss (csrc/sphere_metrics.hip: ms_backward_kernel, one launch per scale).  The
 kernels against the float64 statement of the gradient chain (sphere_metrics.ms_backward_torch) within a bound taken
 from the float32 statement's own error, the pure MSE part bit for bit against the single-scale backward, batching
 and repeat determinism, the autograd entry (sphere_metrics.ms_loss_terms), the clamped frame, refused arguments, and

@@ -69,6 +69,18 @@ def numpy_scales(x, y, weighting):
     return out
 
 
+def test_last_scale_is_ws_ssim_of_the_pooled_frames():
+    """v_4 of the float64 statement has the bits of the single-scale statement's WS-SSIM on pool⁴ of the frames"""
+    for shape in [(1, 1, 16, 16), (2, 3, 17, 19), (1, 2, 33, 65), (1, 1, 130, 258), (1, 1, 528, 1040)]:
+        x, y = pair64(shape, sum(shape))
+        a, b = x, y
+        for _ in range(S.SCALES - 1):
+            a, b = S.pool(a), S.pool(b)
+        for weighting in WEIGHTINGS:
+            v4 = S.ms_scales_torch(x, y, weighting, torch.float64)[:, 4]
+            assert torch.equal(v4, S.loss_terms(a, b, weighting)[:, 1]), (shape, weighting)
+
+
 @pytest.mark.parametrize("shape", [(1, 1, 16, 16), (2, 3, 17, 19)])
 @pytest.mark.parametrize("weighting", WEIGHTINGS)
 def test_scales_are_the_numpy_loop(shape, weighting):

@@ -1,4 +1,5 @@
-"""WS-PSNR / WS-SSIM on one GPU: the HIP kernels of csrc/sphere_metrics.hip against the torch composition.
+"""WS-PSNR / WS-SSIM on one GPU: the HIP kernels of csrc/sphere_metrics.hip (ms_forward_kernel<T, 1, 1>,
+ms_close_kernel<1>) against the torch composition.
 
 The torch composition is what a user would write without the kernel: pytorch_ssim's five depthwise 11x11
 convolutions (F.conv2d, MIOpen) for the SSIM map, then the row-weighted means of the map and of (x - y)^2, with

@@ -1,7 +1,7 @@
 """The two training losses on one GPU: forward + backward from the reconstruction to its gradient.
 
   ws        sphere_metrics.loss_terms (the forward kernel of csrc/sphere_metrics.hip), the batch means of WS-MSE and
-            WS-SSIM, .backward() (ws_metrics_backward_kernel: one gather launch, no atomics)
+            WS-SSIM, .backward() (ms_backward_kernel<1, 1, 0>: one gather launch, no atomics)
   viewport  the paper's loss as train.py builds it: two MultiProject(171, 256, 0.5) ops (14 views each), the MSE over
             the views, SSIM(11, 3) (pytorch_ssim: five MIOpen 11 x 11 convolutions a call), .backward() (the
             convolutions' backward and ProjectsOp.backward, a scatter with float atomics)

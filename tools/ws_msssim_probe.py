@@ -1,8 +1,9 @@
-"""WS-MS-SSIM on one GPU: the kernels of csrc/ws_msssim.hip against the single-scale kernels and a torch composition.
+"""WS-MS-SSIM on one GPU: the kernels of csrc/sphere_metrics.hip over five scales against the same kernels over one scale
+and a torch composition.
 
   forward   PCONV.ws_msssim_device (five ms_forward_kernel launches that also write the pyramid, one closing launch)
-            against PCONV.ws_metrics_device (the single-scale kernel of csrc/sphere_metrics.hip) on the same frames,
-            at n = 8 and n = 1 frames of 4096 x 2048 x 3, and against the definition composed from torch on the device
+            against PCONV.ws_metrics_device (ms_forward_kernel<T, 1, 1>, one launch, and its closing launch) on the
+            same frames, at n = 8 and n = 1 frames of 4096 x 2048 x 3, and against the definition composed from torch on the device
             (sphere_metrics.ms_scales_torch in float32: pooling by strided adds, the window as shifted sums)
   backward  PCONV.ws_msssim_backward (five gather launches, coarse to fine) against PCONV.ws_metrics_backward
   loss      sphere_metrics.ms_loss_terms forward + .backward() against sphere_metrics.loss_terms, (2, 3, 512, 1024)
