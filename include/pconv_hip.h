@@ -486,6 +486,87 @@ int pconv_quant_backward(const float *x, const float *val, const float *idx, con
                          float *bins, const int32_t *widths, float top_alpha, int tn, int c, int h,
                          int w, int levels, int npart, void *stream);
 
+/* ---- ordered (atomic-free) forms of the four backward calls above that sum with float atomics ----
+ *
+ * THE ORDER.  For all four: one fp32 accumulator per destination element, starting at +0; every term is one
+ * fp32 product rounded on its own (__fmul_rn), then one fp32 add (__fadd_rn); the terms come in the order given
+ * here, which is the order in which the sequential scatter of oracle/pconv_oracle.c reaches the element.  The
+ * result does not depend on grid size, workgroup size or batch neighbours.
+ *
+ *   slice     destination: ERP pixel (frame, channel, row, column j).  The tile columns tw of that row's tile pt,
+ *             ascending over tw < widths[pt]; within one tw the taps -1, 0, +1, +2 whose column
+ *             (tap_col + tap) mod width is j.  Term: gout[tw] * coef.
+ *   uslice    destination: valid tile column i of (tile, channel, row).  The ERP columns tw of that row,
+ *             ascending; within one tw the taps -1, 0, +1, +2 whose column (tap_col + tap) mod wl is i, wl the
+ *             tile's valid width (wl < 4: one tw meets a column twice, both terms are added, in tap order).
+ *             Term: gout[tw] * coef.  The kernel writes every element outside the valid interior as zero.
+ *   projects  destination: ERP pixel of a plane.  Viewport pixel ps ascending, then view tb ascending; within a
+ *             sample the corners (th,tw), (th,pw), (ph,tw), (ph,pw) (the pole clamp makes ph == th on the last
+ *             row: both terms are added).  With tx = fx - tw, ntx = 1. - tx (a double subtraction rounded to
+ *             float) and ty, nty alike, the corner weights are the float products ntx*nty, tx*nty, ntx*ty, tx*ty
+ *             and the term is weight * g.  nearest: one term 1 * g per sample.  `count` is the same ordered sum
+ *             of the weights.  A pixel no sample reaches gets 0 and count 0.
+ *   quant     g_in is elementwise (as pconv_quant_backward).  bins[c][q] = sum of val - x (each difference one
+ *             fp32 rounding, then widened to fp64) over the live elements of channel c at level q, in a fixed
+ *             shape:  (1) per (tile-image t, channel c) plane of h*w elements, lane l = e mod 256 of 256 adds
+ *             the plane's live elements e = l, l + 256, ... (e = row*w + column, ascending) to one fp64
+ *             accumulator a[q][l], from +0;  (2) per level the tree  for s = 128, 64, ..., 1:
+ *             a[q][l] = a[q][l] + a[q][l + s] for l < s  leaves the plane's partial in a[q][0];  (3) bins[c][q]
+ *             = the partials of planes t = 0 .. tn-1 of channel c, ascending, added in fp64 from +0, rounded
+ *             once to fp32.  g_weight is the suffix sum over q of pconv_quant_backward, unchanged.
+ */
+
+/* Entries pconv_host_tap_reverse writes: 4 per forward output of a row (slice: the tiles' valid columns;
+ * uslice: npart * width). */
+long long pconv_host_tap_reverse_size(const int32_t *widths, int npart, int width, int uslice);
+
+/* Transpose of the tap table of pconv_host_slice_taps (uslice = 0) / pconv_host_uslice_taps (uslice = 1) as a
+ * CSR list per (tile, destination column), entries (source column, coefficient) in THE ORDER: rev_start
+ * npart*width + 1 ints, rev_src / rev_coef pconv_host_tap_reverse_size entries.  The lists do not depend on
+ * the row.  Refuses -- before it writes anything -- null pointers, widths outside 1..width, entry counts beyond
+ * int32 and tap columns outside their period (width, or the tile's width for uslice).  Returns the number of
+ * entries. */
+int pconv_host_tap_reverse(const int32_t *widths, int npart, int width, const int32_t *tap_col,
+                           const float *tap_coef, int uslice, int32_t *rev_start, int32_t *rev_src,
+                           float *rev_coef);
+
+/* Entries pconv_host_project_reverse writes: nview * inner samples, 4 corners each (1 when nearest). */
+long long pconv_host_project_reverse_size(int nview, int inner, int nearest);
+
+/* Transpose of the viewport sampling of pconv_host_project_table's table tf (nview, inner = h_out*w_out, 2)
+ * as a CSR list per ERP pixel, entries (sample index tb*inner + ps, weight) in THE ORDER, built by a stable
+ * counting sort of the forward walk: rev_start height*width + 1 ints, rev_sample / rev_wgt
+ * pconv_host_project_reverse_size entries.  Refuses -- before it writes anything -- null pointers, sizes whose
+ * entry count or pixel count does not fit int32 and samples outside the frame.  Returns the number of entries. */
+int pconv_host_project_reverse(const float *tf, int nview, int inner, int height, int width, int nearest,
+                               int32_t *rev_start, int32_t *rev_sample, float *rev_wgt);
+
+/* pconv_sphere_slice_backward / pconv_sphere_uslice_backward in THE ORDER, through the lists of
+ * pconv_host_tap_reverse; shapes and the 64 KB row limit as there.  The uslice form writes all of gin. */
+int pconv_sphere_slice_backward_ordered(const float *gout, float *gin, const int32_t *widths,
+                                        const int32_t *rev_start, const int32_t *rev_src,
+                                        const float *rev_coef, int n, int c, int height, int width,
+                                        int npart, int pad, void *stream);
+int pconv_sphere_uslice_backward_ordered(const float *gout, float *gin, const int32_t *widths,
+                                         const int32_t *rev_start, const int32_t *rev_src,
+                                         const float *rev_coef, int n, int c, int h, int width,
+                                         int npart, int pad, void *stream);
+
+/* pconv_project_backward in THE ORDER, through the lists of pconv_host_project_reverse (which hold the
+ * nearest / bilinear choice); writes all of gin and count. */
+int pconv_project_backward_ordered(const float *gout, const int32_t *rev_start, const int32_t *rev_sample,
+                                   const float *rev_wgt, float *gin, float *count, int n, int c,
+                                   int height, int width, int nview, int h_out, int w_out, void *stream);
+
+/* pconv_quant_backward with the level sums in THE ORDER; workspace: device memory of
+ * pconv_quant_backward_ordered_workspace_bytes(tn, c, levels) bytes (one fp64 per plane and level).
+ * levels <= 32. */
+long long pconv_quant_backward_ordered_workspace_bytes(int tn, int c, int levels);
+int pconv_quant_backward_ordered(const float *x, const float *val, const float *idx, const float *g_val,
+                                 const float *g_idx, const float *level_tab, float *g_in, float *g_weight,
+                                 float *bins, void *workspace, const int32_t *widths, float top_alpha,
+                                 int tn, int c, int h, int w, int levels, int npart, void *stream);
+
 /* MaskConstrainOp.forward, in place on a conv weight (nout, cin, k, k)
  * (mask_constrain_cuda.cu:19-88); constrain in {1,2,5,6} */
 int pconv_mask_constrain(float *weight, int nout, int cin, int k, int ngroup, int constrain,

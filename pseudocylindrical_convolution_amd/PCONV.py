@@ -122,6 +122,45 @@ class _HbmTimed(object):
         return False
 
 
+# The backward calls of SphereSliceOp, SphereUsliceOp, ProjectsOp and PseudoQuantOp sum with float atomics by
+# default; with this switch on they take the ordered (atomic-free) kernels of csrc/backward_ordered.hip, whose
+# sums run in the order include/pconv_hip.h defines.  Read at every backward call.
+_ordered_backward = False
+backward_launches = collections.Counter()   # entry point -> backward calls of those four ops that launched it
+
+
+class _PreviousSwitch(int):
+    """what ordered_backward() returns: the switch's previous value (an int that compares like the bool), and a
+    context manager that puts that value back on leaving the block"""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _ordered_backward
+        _ordered_backward = bool(self)
+        return False
+
+
+def ordered_backward(on=None):
+    """Set the switch (None leaves it) and return its previous value.  `with PCONV.ordered_backward(True): ...`
+    restores the previous value at the end of the block, also after an exception."""
+    global _ordered_backward
+    previous = _PreviousSwitch(_ordered_backward)
+    if on is not None:
+        _ordered_backward = bool(on)
+    return previous
+
+
+def backward_is_ordered():
+    return _ordered_backward
+
+
+def _backward_call(fn, *args):
+    backward_launches[fn] += 1
+    call(fn, *args)
+
+
 class _Op(object):
     """State shared by all ops: target device and re-used output buffers
     (base_opt.hpp:12-72)."""
@@ -455,14 +494,31 @@ class _SphereResample(_Op):
     def _widths(self, height, width):
         return tile_widths(self.weight_, self.npart_, height, width)
 
+    def _host_taps(self, builder, height, width):
+        wh = self._widths(height, width)
+        col = np.zeros(self.npart_ * width, np.int32)
+        coef = np.zeros(self.npart_ * width * 4, np.float32)
+        call(builder, _np_ptr(wh), self.npart_, width, _np_ptr(col), _np_ptr(coef))
+        return wh, col, coef
+
     def _tables(self, builder, height, width, like):
         key = (int(height), int(width), like.device)
         if key not in self._tabs:
-            wh = self._widths(height, width)
-            col = np.zeros(self.npart_ * width, np.int32)
-            coef = np.zeros(self.npart_ * width * 4, np.float32)
-            call(builder, _np_ptr(wh), self.npart_, width, _np_ptr(col), _np_ptr(coef))
-            self._tabs[key] = tuple(self._upload(a, like) for a in (wh, col, coef))
+            self._tabs[key] = tuple(self._upload(a, like) for a in self._host_taps(builder, height, width))
+        return self._tabs[key]
+
+    def _reverse_tables(self, builder, uslice, height, width, like):
+        """widths and the reverse CSR of _tables (pconv_host_tap_reverse) for the ordered backward, cached beside
+        the forward tables"""
+        key = ("reverse", int(height), int(width), like.device)
+        if key not in self._tabs:
+            wh, col, coef = self._host_taps(builder, height, width)
+            count = call("pconv_host_tap_reverse_size", _np_ptr(wh), self.npart_, width, uslice)
+            start = np.zeros(self.npart_ * width + 1, np.int32)
+            src, rcoef = np.zeros(count, np.int32), np.zeros(count, np.float32)
+            call("pconv_host_tap_reverse", _np_ptr(wh), self.npart_, width, _np_ptr(col), _np_ptr(coef), uslice,
+                 _np_ptr(start), _np_ptr(src), _np_ptr(rcoef))
+            self._tabs[key] = tuple(self._upload(a, like) for a in (wh, start, src, rcoef))
         return self._tabs[key]
 
 
@@ -495,10 +551,15 @@ class SphereSliceOp(_SphereResample):
         tn, c, hp, wp = grad.shape
         p = self.pad_
         n, h, w = tn // self.npart_, (hp - 2 * p) * self.npart_, wp - 2 * p
-        wd, col, coef = self._tables("pconv_host_slice_taps", h, w, grad)
         out = self._out(1, (n, c, h, w), grad)
-        call("pconv_sphere_slice_backward", _ptr(grad), _ptr(out), _ptr(wd), _ptr(col), _ptr(coef), n, c, h, w,
-             self.npart_, p, _stream(grad.device))
+        if _ordered_backward:
+            wd, rs, rc, rw = self._reverse_tables("pconv_host_slice_taps", 0, h, w, grad)
+            _backward_call("pconv_sphere_slice_backward_ordered", _ptr(grad), _ptr(out), _ptr(wd), _ptr(rs), _ptr(rc),
+                           _ptr(rw), n, c, h, w, self.npart_, p, _stream(grad.device))
+            return [out]
+        wd, col, coef = self._tables("pconv_host_slice_taps", h, w, grad)
+        _backward_call("pconv_sphere_slice_backward", _ptr(grad), _ptr(out), _ptr(wd), _ptr(col), _ptr(coef), n, c, h, w,
+                       self.npart_, p, _stream(grad.device))
         return [out]
 
 
@@ -544,10 +605,15 @@ class SphereUsliceOp(_SphereResample):
         n, c, hh, w = grad.shape
         p = self.pad_
         h = hh // self.npart_
-        wd, col, coef = self._tables("pconv_host_uslice_taps", hh, w, grad)
         out = self._out(1, (n * self.npart_, c, h + 2 * p, w + 2 * p), grad)
-        call("pconv_sphere_uslice_backward", _ptr(grad), _ptr(out), _ptr(wd), _ptr(col), _ptr(coef), n, c, h, w,
-             self.npart_, p, _stream(grad.device))
+        if _ordered_backward:
+            wd, rs, rc, rw = self._reverse_tables("pconv_host_uslice_taps", 1, hh, w, grad)
+            _backward_call("pconv_sphere_uslice_backward_ordered", _ptr(grad), _ptr(out), _ptr(wd), _ptr(rs), _ptr(rc),
+                           _ptr(rw), n, c, h, w, self.npart_, p, _stream(grad.device))
+            return [out]
+        wd, col, coef = self._tables("pconv_host_uslice_taps", hh, w, grad)
+        _backward_call("pconv_sphere_uslice_backward", _ptr(grad), _ptr(out), _ptr(wd), _ptr(col), _ptr(coef), n, c, h, w,
+                       self.npart_, p, _stream(grad.device))
         return [out]
 
 
@@ -746,7 +812,16 @@ class PseudoQuantOp(_Op):
         g_in = self._out("g_in", x.shape, x)
         g_w = self._out("g_w", (c, self.bin_num_), x)
         bins = self._out("bins", (c, self.bin_num_), x)
-        call("pconv_quant_backward", _ptr(x), _ptr(out), _ptr(self._top[1]), _ptr(g_val), _ptr(g_idx),
+        if _ordered_backward:
+            nbytes = call("pconv_quant_backward_ordered_workspace_bytes", tn, c, self.bin_num_)
+            ws = self._top.get("partials")
+            if ws is None or ws.numel() != nbytes or ws.device != x.device:
+                ws = self._top["partials"] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            _backward_call("pconv_quant_backward_ordered", _ptr(x), _ptr(out), _ptr(self._top[1]), _ptr(g_val), _ptr(g_idx),
+                           _ptr(self._top["tab"]), _ptr(g_in), _ptr(g_w), _ptr(bins), _ptr(ws), _ptr(wd), self.top_alpha_,
+                           tn, c, h, w, self.bin_num_, self.npart_, _stream(x.device))
+            return [g_in, g_w, self.count_data_]
+        _backward_call("pconv_quant_backward", _ptr(x), _ptr(out), _ptr(self._top[1]), _ptr(g_val), _ptr(g_idx),
              _ptr(self._top["tab"]), _ptr(g_in), _ptr(g_w), _ptr(bins), _ptr(wd), self.top_alpha_, tn, c, h, w,
              self.bin_num_, self.npart_, _stream(x.device))
         return [g_in, g_w, self.count_data_]
@@ -790,22 +865,42 @@ class ProjectsOp(_Op):
         self.nview_ = int(self.theta_.shape[0])
         self.fov_, self.near_ = float(fov), bool(near)
         self._tf = {}
+        self._rev = {}
 
     def _moved(self):
         self._tf = {}
+        self._rev = {}
 
-    def forward(self, x):
-        _require_gpu(x, "ProjectsOp")
-        n, c, h, w = x.shape
-        key = (h, w, x.device)
+    def _table(self, h, w, like):
+        key = (h, w, like.device)
         if key not in self._tf:
             tf = np.zeros(self.nview_ * self.h_out_ * self.w_out_ * 2, np.float32)
             call("pconv_host_project_table", _np_ptr(self.theta_), _np_ptr(self.phi_), self.nview_, self.fov_,
                  self.h_out_, self.w_out_, h, w, _np_ptr(tf))
-            self._tf[key] = self._upload(tf, x)
+            self._tf[key] = self._upload(tf, like)
+        return self._tf[key]
+
+    def _reverse_tables(self, h, w, like):
+        """reverse CSR of the sampling table (pconv_host_project_reverse) for the ordered backward, cached beside it"""
+        key = (h, w, like.device)
+        if key not in self._rev:
+            tf = self._table(h, w, like).cpu().numpy()
+            inner = self.h_out_ * self.w_out_
+            count = call("pconv_host_project_reverse_size", self.nview_, inner, int(self.near_))
+            start = np.zeros(h * w + 1, np.int32)
+            sample, wgt = np.zeros(count, np.int32), np.zeros(count, np.float32)
+            call("pconv_host_project_reverse", _np_ptr(tf), self.nview_, inner, h, w, int(self.near_), _np_ptr(start),
+                 _np_ptr(sample), _np_ptr(wgt))
+            self._rev[key] = tuple(self._upload(a, like) for a in (start, sample, wgt))
+        return self._rev[key]
+
+    def forward(self, x):
+        _require_gpu(x, "ProjectsOp")
+        n, c, h, w = x.shape
+        tf = self._table(h, w, x)
         out = self._out(0, (n * self.nview_, c, self.h_out_, self.w_out_), x)
         self._fwd_shape = (n, c, h, w)
-        call("pconv_project", _ptr(x), _ptr(self._tf[key]), _ptr(out), n, c, h, w, self.nview_, self.h_out_,
+        call("pconv_project", _ptr(x), _ptr(tf), _ptr(out), n, c, h, w, self.nview_, self.h_out_,
              self.w_out_, int(self.near_), _stream(x.device))
         return [out]
 
@@ -814,11 +909,15 @@ class ProjectsOp(_Op):
         (projects_cuda.cu:257-329)"""
         _require_gpu(grad, "ProjectsOp.backward")
         n, c, h, w = self._fwd_shape
-        key = (h, w, grad.device)
         gin = self._out(1, (n, c, h, w), grad)
         cnt = self._out(2, (n, c, h, w), grad)
-        call("pconv_project_backward", _ptr(grad), _ptr(self._tf[key]), _ptr(gin), _ptr(cnt), n, c, h, w, self.nview_,
-             self.h_out_, self.w_out_, int(self.near_), _stream(grad.device))
+        if _ordered_backward:
+            rs, rc, rw = self._reverse_tables(h, w, grad)
+            _backward_call("pconv_project_backward_ordered", _ptr(grad), _ptr(rs), _ptr(rc), _ptr(rw), _ptr(gin), _ptr(cnt),
+                           n, c, h, w, self.nview_, self.h_out_, self.w_out_, _stream(grad.device))
+            return [gin, cnt]
+        _backward_call("pconv_project_backward", _ptr(grad), _ptr(self._table(h, w, grad)), _ptr(gin), _ptr(cnt), n, c, h, w,
+                       self.nview_, self.h_out_, self.w_out_, int(self.near_), _stream(grad.device))
         return [gin, cnt]
 
 

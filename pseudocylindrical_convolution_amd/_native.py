@@ -74,6 +74,16 @@ _HIP_SIGNATURES = {
     "pconv_pseudo_pad_backward": [P, P, P, P, P, P, I, I, I, I, I, I, P],
     "pconv_quant_backward": [P, P, P, P, P, P, P, P, P, P, F, I, I, I, I, I, I, P],
     "pconv_project_backward": [P, P, P, P, I, I, I, I, I, I, I, I, P],
+    # ... and their ordered (atomic-free) forms with the reverse lists they walk
+    "pconv_host_tap_reverse_size": [P, I, I, I],
+    "pconv_host_tap_reverse": [P, I, I, P, P, I, P, P, P],
+    "pconv_host_project_reverse_size": [I, I, I],
+    "pconv_host_project_reverse": [P, I, I, I, I, I, P, P, P],
+    "pconv_sphere_slice_backward_ordered": [P, P, P, P, P, P, I, I, I, I, I, I, P],
+    "pconv_sphere_uslice_backward_ordered": [P, P, P, P, P, P, I, I, I, I, I, I, P],
+    "pconv_project_backward_ordered": [P, P, P, P, P, P, I, I, I, I, I, I, I, P],
+    "pconv_quant_backward_ordered_workspace_bytes": [I, I, I],
+    "pconv_quant_backward_ordered": [P, P, P, P, P, P, P, P, P, P, P, F, I, I, I, I, I, I, P],
     "pconv_entropy_pad": [P, P, P, P, P, I, I, I, I, I, I, P],
     "pconv_host_entropy_pad_table": [P, I, I, I, I, I, P, P],
     "pconv_host_causal_reverse": [P, I, I, I, I, I, P, P, P],
@@ -184,6 +194,9 @@ def hip_lib():
         lib.pconv_ws_msssim_workspace_bytes.restype = c_longlong
         lib.pconv_ws_msssim_backward_workspace_bytes.restype = c_longlong
         lib.pconv_erp_resample_workspace_bytes.restype = c_longlong
+        lib.pconv_host_tap_reverse_size.restype = c_longlong
+        lib.pconv_host_project_reverse_size.restype = c_longlong
+        lib.pconv_quant_backward_ordered_workspace_bytes.restype = c_longlong
         _hip = lib
     return _hip
 

@@ -37,6 +37,7 @@ HIP_SOURCES = [
     "wino_flat.hip",   # wino.hip again with a 2-row x 128-column workgroup tile (the row split's remainders)
     "wino42.hip",
     "backward.hip",
+    "backward_ordered.hip",  # the atomic-free forms of the four backward kernels that sum with float atomics
     "options.cpp",  # the one reader of the library's PCONV_ variables, and pconv_option
     "engine.cpp",
     "coder.cpp",  # the engine drives the arithmetic coder natively

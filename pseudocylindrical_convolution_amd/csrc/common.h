@@ -37,6 +37,9 @@ static inline unsigned pconv_grid(long long work_items, int block = 256) {
 
 static inline hipStream_t as_stream(void *s) { return (hipStream_t)s; }
 
+// pointwise.hip: the suffix sum over the quantiser's level bins, shared by both forms of its backward
+int pconv_launch_quant_weight_grad(const float *bins, const float *tab, float *g_w, int c, int levels, hipStream_t stream);
+
 // The dynamic-LDS limit is a per-device attribute of the function: raise it once on every device
 // this process launches `kernel` on (one process may drive several GPUs: nn.DataParallel replicas
 // of BaseOpModule).  `raised` is the caller's static mask of that kernel instantiation, one bit

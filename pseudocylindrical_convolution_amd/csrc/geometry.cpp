@@ -530,3 +530,154 @@ extern "C" int pconv_host_project_table(const float *theta, const float *phi, in
   }
   return PCONV_OK;
 }
+
+// ---- reverse lists of the ordered (atomic-free) backward kernels: include/pconv_hip.h, "the order" ----
+
+static inline int wrap_col(int col, int period) {
+  col %= period;
+  return col < 0 ? col + period : col;
+}
+
+// forward outputs per row of tile t: the tile's valid columns (slice) or every ERP column (uslice)
+static inline int tap_sources(const int32_t *widths, int t, int width, int uslice) {
+  return uslice ? width : (widths[t] < width ? widths[t] : width);
+}
+
+extern "C" long long pconv_host_tap_reverse_size(const int32_t *widths, int npart, int width, int uslice) {
+  PCONV_REQUIRE(widths && npart > 0 && width > 0, "tap_reverse_size: bad argument");
+  long long total = 0;
+  for (int t = 0; t < npart; t++) {
+    PCONV_REQUIRE(widths[t] > 0 && widths[t] <= width, "tap_reverse_size: tile %d has width %d of %d", t, widths[t], width);
+    total += 4LL * tap_sources(widths, t, width, uslice);
+  }
+  return total;
+}
+
+// Transpose of a forward tap table as a CSR list per (tile, destination column): the forward walk -- source
+// column tw ascending, taps -1, 0, +1, +2 -- sorted by destination with a stable counting sort, so every list
+// keeps the walk's order.  Slice (uslice == 0): sources are the tile's valid columns, destinations the ERP
+// columns, period = width.  Uslice: sources are the ERP columns, destinations the tile's valid columns, period
+// = the tile's width (a tile narrower than 4 columns meets a column twice within one tw: both entries stay).
+// rev_start: npart*width + 1 ints; rev_src / rev_coef: pconv_host_tap_reverse_size entries.  Returns the
+// number of entries.  Nothing is written unless every argument passes.
+extern "C" int pconv_host_tap_reverse(const int32_t *widths, int npart, int width, const int32_t *tap_col,
+                                      const float *tap_coef, int uslice, int32_t *rev_start, int32_t *rev_src,
+                                      float *rev_coef) {
+  PCONV_REQUIRE(widths && tap_col && tap_coef && rev_start && rev_src && rev_coef, "tap_reverse: null pointer");
+  PCONV_REQUIRE(npart > 0 && width > 0, "tap_reverse: bad shape");
+  const long long total = pconv_host_tap_reverse_size(widths, npart, width, uslice);
+  if (total < 0) return (int)total;
+  PCONV_REQUIRE(total <= INT32_MAX && (long long)npart * width < INT32_MAX,
+                "tap_reverse: %lld entries do not fit int32", total);
+  for (int t = 0; t < npart; t++) {
+    const int period = uslice ? widths[t] : width, nsrc = tap_sources(widths, t, width, uslice);
+    for (int tw = 0; tw < nsrc; tw++) {
+      const int col = tap_col[(size_t)t * width + tw];
+      PCONV_REQUIRE(col >= 0 && col < period, "tap_reverse: tap column %d of tile %d, source %d is outside its period %d",
+                    col, t, tw, period);
+    }
+  }
+  const size_t keys = (size_t)npart * width;
+  std::vector<int32_t> fill(keys + 1, 0);
+  for (int pass = 0; pass < 2; pass++) {
+    for (int t = 0; t < npart; t++) {
+      const int period = uslice ? widths[t] : width, nsrc = tap_sources(widths, t, width, uslice);
+      for (int tw = 0; tw < nsrc; tw++) {
+        const size_t e = (size_t)t * width + tw;
+        for (int j = -1; j < 3; j++) {
+          const size_t key = (size_t)t * width + wrap_col(tap_col[e] + j, period);
+          if (pass == 0) {
+            fill[key + 1]++;
+          } else {
+            const int32_t k = fill[key]++;
+            rev_src[k] = tw;
+            rev_coef[k] = tap_coef[e * 4 + j + 1];
+          }
+        }
+      }
+    }
+    if (pass == 0) {
+      for (size_t k = 0; k < keys; k++) fill[k + 1] += fill[k];
+      for (size_t k = 0; k <= keys; k++) rev_start[k] = fill[k];
+    }
+  }
+  return (int)total;
+}
+
+extern "C" long long pconv_host_project_reverse_size(int nview, int inner, int nearest) {
+  PCONV_REQUIRE(nview > 0 && inner > 0, "project_reverse_size: bad argument");
+  return (long long)nview * inner * (nearest ? 1 : 4);
+}
+
+// the ERP pixels and weights one viewport sample touches, in ProjectsOp.backward's order and arithmetic
+// (projects_cuda.cu:257-329); returns false when a pixel lies outside the frame
+static inline bool project_corners(float fx, float fy, int hs, int ws, int nearest, int32_t *pix, float *wgt) {
+  if (nearest) {
+    const int tw = static_cast<int>(floor(fx + 0.5)) % ws;
+    int th = static_cast<int>(floor(fy + 0.5));
+    th = th >= hs ? hs - 1 : th;
+    if (tw < 0 || th < 0) return false;
+    pix[0] = th * ws + tw;
+    wgt[0] = 1.f;
+    return true;
+  }
+  const int tw = static_cast<int>(floorf(fx));
+  const int th = static_cast<int>(floorf(fy));
+  if (tw < 0 || tw >= ws || th < 0 || th >= hs) return false;
+  const int pw = (tw + 1) % ws;
+  const int ph = th + 1 >= hs ? hs - 1 : th + 1;
+  const float tx = fx - tw;
+  const float ty = fy - th;
+  const float ntx = 1. - tx;
+  const float nty = 1. - ty;
+  pix[0] = th * ws + tw, wgt[0] = ntx * nty;
+  pix[1] = th * ws + pw, wgt[1] = tx * nty;
+  pix[2] = ph * ws + tw, wgt[2] = ntx * ty;
+  pix[3] = ph * ws + pw, wgt[3] = tx * ty;
+  return true;
+}
+
+// Transpose of the viewport sampling as a CSR list per ERP pixel: the forward walk -- viewport pixel ps
+// ascending, then view tb ascending, then the corners (th,tw), (th,pw), (ph,tw), (ph,pw) (one corner of weight
+// 1 when nearest) -- sorted by pixel with a stable counting sort.  tf: pconv_host_project_table's table;
+// inner = h_out*w_out.  rev_start: height*width + 1 ints; rev_sample (tb*inner + ps) / rev_wgt:
+// pconv_host_project_reverse_size entries.  Returns the number of entries; nothing is written unless every
+// argument passes.
+extern "C" int pconv_host_project_reverse(const float *tf, int nview, int inner, int height, int width, int nearest,
+                                          int32_t *rev_start, int32_t *rev_sample, float *rev_wgt) {
+  PCONV_REQUIRE(tf && rev_start && rev_sample && rev_wgt, "project_reverse: null pointer");
+  PCONV_REQUIRE(nview > 0 && inner > 0 && height > 0 && width > 0, "project_reverse: bad shape");
+  const long long total = pconv_host_project_reverse_size(nview, inner, nearest);
+  PCONV_REQUIRE(total <= INT32_MAX && (long long)height * width < INT32_MAX,
+                "project_reverse: %lld entries / %lld pixels do not fit int32", total, (long long)height * width);
+  const int ncorner = nearest ? 1 : 4;
+  int32_t pix[4];
+  float wgt[4];
+  for (long long s = 0; s < (long long)nview * inner; s++)
+    PCONV_REQUIRE(project_corners(tf[s * 2], tf[s * 2 + 1], height, width, nearest, pix, wgt),
+                  "project_reverse: sample %lld (%g, %g) lies outside the %d x %d frame", s, tf[s * 2], tf[s * 2 + 1],
+                  height, width);
+  const size_t keys = (size_t)height * width;
+  std::vector<int32_t> fill(keys + 1, 0);
+  for (int pass = 0; pass < 2; pass++) {
+    for (int ps = 0; ps < inner; ps++)
+      for (int tb = 0; tb < nview; tb++) {
+        const int32_t s = tb * inner + ps;
+        project_corners(tf[(size_t)s * 2], tf[(size_t)s * 2 + 1], height, width, nearest, pix, wgt);
+        for (int k = 0; k < ncorner; k++) {
+          if (pass == 0) {
+            fill[(size_t)pix[k] + 1]++;
+          } else {
+            const int32_t at = fill[pix[k]]++;
+            rev_sample[at] = s;
+            rev_wgt[at] = wgt[k];
+          }
+        }
+      }
+    if (pass == 0) {
+      for (size_t k = 0; k < keys; k++) fill[k + 1] += fill[k];
+      for (size_t k = 0; k <= keys; k++) rev_start[k] = fill[k];
+    }
+  }
+  return (int)total;
+}

@@ -430,6 +430,12 @@ __global__ void quant_weight_grad_kernel(const float *__restrict__ bins, const f
 
 }  // namespace
 
+int pconv_launch_quant_weight_grad(const float *bins, const float *tab, float *g_w, int c, int levels, hipStream_t stream) {
+  hipLaunchKernelGGL(quant_weight_grad_kernel, dim3((c + 255) / 256), dim3(256), 0, stream, bins, tab, g_w, c, levels);
+  PCONV_LAUNCH_CHECK("quant_weight_grad");
+  return PCONV_OK;
+}
+
 extern "C" int pconv_quant(const float *x, const float *weight, float *level_tab, float *out_val,
                            float *out_idx, float *count, const int32_t *widths, int tn, int c,
                            int h, int w, int levels, int npart, void *stream) {

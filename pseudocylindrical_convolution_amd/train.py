@@ -13,10 +13,13 @@ checkpoint naming follow the reference.  What differs: ranks come from the launc
 (RANK / LOCAL_RANK / WORLD_SIZE) instead of mp.spawn, every path is an argument, and
 `--synthetic N` / `--procedural N` train on generated images where no dataset exists, and
 `--time-budget S` ends the run after S seconds of wall time (the epoch in flight stops at its next
-step, is tested and saved as usual)."""
+step, is tested and saved as usual), and `--deterministic` trains on the ordered (atomic-free) backward kernels
+(PCONV.ordered_backward) under torch's deterministic settings and logs the parameter checksum two runs from one
+seed are compared on."""
 from __future__ import print_function
 
 import argparse
+import contextlib
 import os
 import sys
 import time
@@ -26,7 +29,7 @@ import torch
 import torch.distributed as dist
 from torch.nn.parallel import DistributedDataParallel as DDP
 
-from . import model_zoo_v2, sphere_metrics
+from . import PCONV, model_zoo_v2, sphere_metrics
 from .PCONV_operator import Logger, ModuleSaver, MultiProject, SSIM
 from .RDMetric import mse_tb
 from .SphereDataset import (ProceduralSphereDataSet, SphereDataSet, SyntheticSphereDataSet,
@@ -163,8 +166,33 @@ def make_datasets(args):
     return train_data, test_data, args.values
 
 
+@contextlib.contextmanager
+def deterministic_mode():
+    """what --deterministic sets, put back afterwards: this project's four float-atomic backward kernels give way to
+    their ordered forms, and torch is asked for deterministic algorithms of its own (warn_only: an op of torch's
+    that has none warns and runs)"""
+    before = (torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark,
+              torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled())
+    with PCONV.ordered_backward(True):
+        torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = True, False
+        torch.use_deterministic_algorithms(True, warn_only=True)
+        try:
+            yield
+        finally:
+            torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = before[:2]
+            torch.use_deterministic_algorithms(before[2], warn_only=before[3])
+
+
 def Job(rank, world_size, args):
     """what one rank does (reference: trainDDP_Full.py:102-163)"""
+    if getattr(args, 'deterministic', False):
+        with deterministic_mode():
+            return _job(rank, world_size, args)
+    return _job(rank, world_size, args)
+
+
+def _job(rank, world_size, args):
+    deterministic = getattr(args, 'deterministic', False)
     on_gpu = args.device == 'cuda'
     cid = int(os.environ.get('LOCAL_RANK', rank)) if (on_gpu and not args.share_gpu) else 0
     args.gpu_id = cid
@@ -238,6 +266,11 @@ def Job(rank, world_size, args):
                                         {'params': [model.module.quant.weight]}], lr=args.lr)
     optimizer_ent = None if args.base else torch.optim.Adam(model.module.ent.parameters(), lr=args.lr * 10)
     log.log('lr:{}'.format(args.lr))
+    if deterministic:
+        log.log('deterministic: ordered backward kernels {}, cudnn.deterministic {}, cudnn.benchmark {}, '
+                'torch deterministic algorithms {} (warn only)'.format(
+                    'on' if PCONV.backward_is_ordered() else 'off', torch.backends.cudnn.deterministic,
+                    torch.backends.cudnn.benchmark, torch.are_deterministic_algorithms_enabled()))
     if args.loss in SPHERE_LOSSES:
         log.log('loss: WS-MSE / {} over the ERP frames (--viewport_size is ignored)'.format(
             'WS-SSIM' if args.loss == 'ws' else 'WS-MS-SSIM'))
@@ -256,8 +289,9 @@ def Job(rank, world_size, args):
         history.append((last, ls))
         if rank == 0:
             log.log(saver.save(model, ls))
-    if world_size > 1:
+    if world_size > 1 or deterministic:
         # the ranks end with the same parameters (DDP averaged every gradient): spread of a checksum over the ranks
+        # (--deterministic: the figure two runs from one seed are compared on, one rank included)
         chk = torch.zeros(1, dtype=torch.float64, device=device)
         for p in model.module.parameters():
             chk += p.detach().double().abs().sum()
@@ -332,6 +366,12 @@ def build_parser():
     parser.add_argument('--share-gpu', action='store_true', default=False,
                         help='every rank on cuda:0 (with --dist-backend gloo): rehearsal on a one-GPU box')
     parser.add_argument('--seed', type=int, default=0)
+    parser.add_argument('--deterministic', action='store_true', default=False,
+                        help='reproducible training: the ordered (atomic-free) forms of the slice, uslice, viewport and '
+                             'quantiser backward kernels (PCONV.ordered_backward), cudnn.deterministic, no cudnn benchmark, '
+                             'torch.use_deterministic_algorithms(True, warn_only=True); logs the parameter checksum to '
+                             'compare two runs on.  Guaranteed for this project\'s own kernels; the vendor library\'s '
+                             'convolution backward is outside it')
     parser.add_argument('--verbose', action='store_true', default=False)
     return parser
 
