@@ -597,7 +597,20 @@ int pconv_gmm_loss(const float *weight, const float *delta, const float *mean,
  * views (may be NULL = all dense NCHW): 12 element strides, (tile, channel, row)
  * for in, out, residual, gate in this order; columns are always contiguous.
  * Lets a convolution write the interior of a padded buffer (whose ring
- * pconv_pseudo_pad_ring then fills) and read such interiors. */
+ * pconv_pseudo_pad_ring then fills) and read such interiors.
+ * Number range: the chain is IEEE over all of fp32 -- subnormal inputs, weights,
+ * products, partial sums and results are kept, never flushed (the matrix
+ * instructions run under the kernel's default denormal mode); the chain starts
+ * at +0, so an all-zero sum is +0 whatever the signs of its terms, and -0
+ * appears only where IEEE gives it (a later product, bias, PReLU or residual);
+ * overflow goes to +-Inf and Inf - Inf to NaN in chain order.  The same holds
+ * for pconv_gdn (x*x may underflow or overflow on its own), for the entropy
+ * model's kernels in all three forms, for pconv_expf (its results below 2^-126
+ * are correctly scaled subnormals) and for the quantiser.  Measured on the
+ * MI355X against the CPU restatement, bit for bit incl. the sign of zero
+ * (tests/test_gpu_fp32_edges.py).  The Winograd kernels promise exact
+ * power-of-two scaling in the normal range, no bit equality below it.  NaN
+ * INPUTS stay unspecified beyond what single entries state. */
 int pconv_conv_packed_size(int cout, int cin, int k, int *cout_pad, int *red_pad);
 int pconv_conv_pack_weight(const float *w, float *packed, int cout, int cin, int k,
                            void *stream);

@@ -492,6 +492,11 @@ class PseudoQuantOp(_Base):
         self.tab_, self.quant_, self.top_alpha_used_ = tab, quant, None
         return [val, idx] if idx is not None else [val]
 
+    def level_table(self):
+        """(channel, levels) copy of the level table of the last forward: column 0 the first level, the others
+        exp of the weight (read-only: tests compare the device's table with it)"""
+        return torch.from_numpy(self.tab_.reshape(self.channel_, self.bin_num_).copy())
+
     def backward(self, grads, x, out):
         # pseudo_quant_cuda.cu:197-311
         num, c, h, w = x.shape
@@ -520,7 +525,12 @@ class PseudoDQuantOp(_Base):
         out = self._top(0, x.shape)
         lib().orc_dquant_forward(_p(x), _p(weight.detach().contiguous()), _p(tab), _p(out), _p(hidx), I(num), I(c),
                                  I(h), I(w), I(self.nchannel_), I(self.bin_num_), I(self.npart_))
+        self.tab_ = tab
         return [out]
+
+    def level_table(self):
+        """(channel, levels) copy of the cumulative level table of the last forward"""
+        return torch.from_numpy(self.tab_.reshape(self.nchannel_, self.bin_num_).copy())
 
 
 class ProjectsOp(_Base):

@@ -197,3 +197,38 @@ def test_row_split_equals_the_direct_kernel(cfg, hip_backend, monkeypatch):
         if ring:
             buf, r = yw._pconv_ring
             assert buf.shape[2] == ho + 2 * r and torch.equal(buf[:, :, r:-r, r:-r], yw)
+
+
+@pytest.mark.parametrize("cfg", [(2, 192, 12, 70, 768), (16, 96, 20, 134, 64)])
+def test_row_split_with_the_depth_to_width_store(cfg, hip_backend, monkeypatch):
+    """default dispatch of a Dtow layer whose output rows leave a remainder (10 = 8 + 2, 18 = 16 + 2): F(4x2) stores rows
+    [0, 2 * blocks) of the shuffled output, the remainder's launch the rows behind them (test_conv_plan.py::
+    test_depth_to_width_layers is the dispatch; this is the arithmetic).  The fused store equals DtowOp(2) of the
+    un-fused split result bit for bit, dense and into a ring buffer; the un-fused result is within the kernels' bounds
+    of the direct kernel and of float64."""
+    tn, cin, h, w, cout = cfg
+    x, wt, b, sl = data(*cfg, seed=14)
+    rec = type("Probe", (), {"records": []})()
+    monkeypatch.setattr(P(), "conv_probe", rec)
+    split = ["wino42_conv3x3_kernel", "wino_conv3x3_kernel"]
+    ref64 = torch.nn.functional.conv2d(x.double(), wt.double(), b.double())
+    for slope in (None, sl):
+        want = ref64 if slope is None else torch.where(ref64 < 0, ref64 * slope.double().view(1, -1, 1, 1), ref64)
+        gs = slope.to(DEV) if slope is not None else None
+        rec.records.clear()
+        plain = conv(monkeypatch, "wino42", x.to(DEV), wt.to(DEV), b.to(DEV), 1, gs)
+        assert [r[0] for r in rec.records] == split
+        assert (plain.cpu().double() - want).abs().max().item() < 3e-5
+        shuffled = P().DtowOp(2, True, 0, False).forward(plain)[0].clone()
+        direct = conv(monkeypatch, "direct", x.to(DEV), wt.to(DEV), b.to(DEV), 1, gs, d2w=True)
+        assert (direct - shuffled).abs().max().item() < 3e-5
+        for ring in (0, 2):
+            rec.records.clear()
+            fused = conv(monkeypatch, "wino42", x.to(DEV), wt.to(DEV), b.to(DEV), 1, gs, d2w=True, ring=ring)
+            assert [r[0] for r in rec.records] == split
+            assert "rows %d of %d" % ((h - 2) // 8 * 8, h - 2) in rec.records[0][1]
+            assert tuple(fused.shape) == tuple(shuffled.shape) == (tn, cout // 4, 2 * (h - 2), 2 * (w - 2))
+            assert torch.equal(fused, shuffled)                     # same arithmetic, another store
+            if ring:
+                buf, r = fused._pconv_ring
+                assert r == ring and buf.shape[2] == 2 * (h - 2) + 2 * r and torch.equal(buf[:, :, r:-r, r:-r], fused)
