@@ -620,6 +620,53 @@ int pconv_conv2d(const float *in, const float *packed_w, const float *bias, floa
                  const float *residual, const float *gate, int trim, int d2w,
                  const long long *views, void *stream);
 
+/* Backward of pconv_conv2d's layers in a defined order (csrc/conv_backward.hip): k in {1,3}, stride in {1,2},
+ * no padding, dense NCHW fp32: in (tn, cin, h, w), w (cout, cin, k, k), gout (tn, cout, ho, wo).  Stream-ordered;
+ * no atomics, no allocation and no memset inside a call: the caller brings the workspaces.  Null pointers,
+ * unsupported k / stride and shapes beyond int32 are refused before any launch.  Results do not depend on the
+ * grid, the device's CU count, an option or the workspace's size.
+ *
+ * Data gradient: gin (tn, cin, h, w) = pconv_conv2d, stride 1, no bias, no activation, of the PREPARED gradient
+ * with the flipped, transposed weights wT[ci][co][kh'][kw'] = w[co][ci][k-1-kh'][k-1-kw']
+ * (pconv_conv_pack_weight_transposed writes them in pconv_conv_pack_weight's layout:
+ * pconv_conv_packed_size(cin, cout, k) floats).  The prepared gradient (tn, cout, h + k - 1, w + k - 1) holds
+ * element (y, x) of a gout plane at (k-1 + stride*y, k-1 + stride*x) and +0 everywhere else: zero-stuffed to the
+ * stride, padded by k - 1 on every side, with (h-k) % stride / (w-k) % stride further zero rows / columns at the
+ * bottom / right.  pconv_conv_grad_prepare writes all of it in one pass (16-byte aligned buffer).  Every gin
+ * element is therefore ONE fp32 fmaf chain from +0 over (co, kh', kw') ascending, in which stuffed and padded
+ * positions enter as products with +0.  pconv_conv2d_dgrad chains prepare and pconv_conv2d; workspace: device
+ * memory of pconv_conv2d_dgrad_workspace_bytes(...) bytes (0 for k = 1, stride 1, where the prepared gradient
+ * is gout itself and workspace may be NULL).
+ *
+ * Weight gradient: for every tile t a partial P_t[co][ci][kh][kw] = ONE fp32 fmaf chain from +0 over the tile's
+ * output pixels, y ascending then x ascending: acc = fmaf(gout[t,co,y,x], in[t,ci,stride*y+kh,stride*x+kw], acc)
+ * (v_mfma_f32_32x32x2_f32: M = couts, N = (ci, kh, kw), K = pixels).  The pixels are taken in runs of up to 64
+ * of one output row, [64 j, 64 j + 64) for j = 0 .. (wo-1)/64; a run of odd length -- a function of wo alone --
+ * is followed by one step fmaf(-0, +0, acc), which returns acc for every acc (-0, Inf and NaN included), so the
+ * chain has no zero-product step that could turn a -0 into +0.  Then gw = (((P_0 + P_1) + P_2) + ...), fp32
+ * round-to-nearest adds, t ascending.
+ * Bias gradient: gb[co] = the two-stage reduction of pconv_quant_backward_ordered: per plane (t, co), lane l of
+ * 256 adds elements l, l + 256, ... ascending in fp64 from +0; the tree a[l] += a[l + s], s = 128 .. 1; then the
+ * planes t ascending in fp64 from +0; one rounding to fp32.
+ * pconv_conv2d_wgrad writes gw and gb (either may be NULL: not computed; in may be NULL without gw);
+ * workspace: 16-byte aligned device memory of pconv_conv2d_wgrad_workspace_bytes(tn, cin, cout, k) bytes (the
+ * partials, then one fp64 per plane; without gw the planes alone: tn * cout * 8 bytes suffice).
+ *
+ * Number range: as for pconv_conv2d -- subnormal operands, products and sums are kept, never flushed, and every
+ * chain starts at +0 -- with one exception: Inf / NaN in gout are UNSPECIFIED for the data gradient, whose
+ * stuffed and padded zeros multiply them (0 * Inf = NaN reaches gin elements the value has no part in).  The
+ * weight and bias gradients carry Inf / NaN in chain order. */
+int pconv_conv_pack_weight_transposed(const float *w, float *packed, int cout, int cin, int k,
+                                      void *stream);
+long long pconv_conv2d_dgrad_workspace_bytes(int tn, int cout, int h, int w, int k, int stride);
+int pconv_conv_grad_prepare(const float *gout, float *prepared, int tn, int cout, int h, int w,
+                            int k, int stride, void *stream);
+int pconv_conv2d_dgrad(const float *gout, const float *packed_wt, float *gin, void *workspace,
+                       int tn, int cin, int h, int w, int cout, int k, int stride, void *stream);
+long long pconv_conv2d_wgrad_workspace_bytes(int tn, int cin, int cout, int k);
+int pconv_conv2d_wgrad(const float *in, const float *gout, float *gw, float *gb, void *workspace,
+                       int tn, int cin, int h, int w, int cout, int k, int stride, void *stream);
+
 /* The same convolution for k = 3, stride 1 by Winograd F(2x2, 3x3) on the fp32 matrix cores
  * (csrc/wino.hip): 4 instead of 9 multiply-adds per input channel, output channel and pixel -- the
  * algorithm cuDNN runs the reference's fp32 3x3 nn.Conv2d layers with (model_zoo_v2.py:41-45,83-86,

@@ -161,6 +161,38 @@ def _backward_call(fn, *args):
     call(fn, *args)
 
 
+# The convolutions of a training step go to the vendor library's forward and backward by default (TileConv2d under
+# autograd); with this switch on they stay on this project's kernels: tile_conv2d forward, tile_conv2d_backward
+# (csrc/conv_backward.hip) for the three gradients.  Read at every TileConv2d call under autograd.
+_native_conv_grad = False
+
+
+class _PreviousConvSwitch(int):
+    """what native_conv_grad() returns: as _PreviousSwitch, for the convolution switch"""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _native_conv_grad
+        _native_conv_grad = bool(self)
+        return False
+
+
+def native_conv_grad(on=None):
+    """Set the switch (None leaves it) and return its previous value.  `with PCONV.native_conv_grad(True): ...`
+    restores the previous value at the end of the block, also after an exception."""
+    global _native_conv_grad
+    previous = _PreviousConvSwitch(_native_conv_grad)
+    if on is not None:
+        _native_conv_grad = bool(on)
+    return previous
+
+
+def conv_grad_is_native():
+    return _native_conv_grad
+
+
 class _Op(object):
     """State shared by all ops: target device and re-used output buffers
     (base_opt.hpp:12-72)."""
@@ -1889,3 +1921,66 @@ def tile_conv2d(owner, x, weight, bias, stride, slope=None, col_limit=None, npar
         else:
             winograd(kind, r0, rows)
     return out
+
+
+def _packed_weight_transposed(owner, weight, stream):
+    """the flipped, transposed weights of the data gradient in pconv_conv2d's slab layout, cached on `owner` under
+    _packed_weight's key: an in-place optimiser step (weight._version) makes it stale"""
+    from .PCONV_operator import backend
+    key = (weight.data_ptr(), weight._version, weight.device, backend.param_epoch())
+    cached = getattr(owner, "_pconv_packed_t", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    cout, cin, k = weight.shape[:3]
+    size = _native.hip_lib().pconv_conv_packed_size(cin, cout, k, None, None)
+    packed = torch.empty(int(size), dtype=torch.float32, device=weight.device)
+    call("pconv_conv_pack_weight_transposed", _ptr(weight.detach().contiguous()), _ptr(packed), cout, cin, k, stream)
+    setattr(owner, "_pconv_packed_t", (key, packed))
+    return packed
+
+
+def tile_conv2d_backward(x, weight, gout, stride, need=(True, True, True), owner=None):
+    """(gin, gw, gb) of y = conv2d(x, weight, bias, stride), no padding, from gout = dL/dy, in the orders
+    include/pconv_hip.h defines; a gradient `need` does not ask for is neither computed nor returned (None).
+    x (tn, cin, h, w), weight (cout, cin, k, k), gout (tn, cout, ho, wo): dense fp32 on the GPU.  owner: the object
+    that caches the transposed pack (default: the weight tensor itself)."""
+    need_x, need_w, need_b = (bool(n) for n in need)
+    # the entry points take raw addresses: every tensor is checked here, whether this call reads it or not
+    for name, t in (("x", x), ("weight", weight), ("gout", gout)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise PconvError("tile_conv2d_backward: %s must be a 4-D tensor" % name)
+        _require_gpu(t.detach(), "tile_conv2d_backward: %s" % name)
+        if t.device != gout.device:
+            raise PconvError("tile_conv2d_backward: %s is on %s, gout on %s" % (name, t.device, gout.device))
+    tn, cout, ho, wo = gout.shape
+    cout_w, cin, k, k2 = weight.shape
+    stride = int(stride)
+    tn_x, cin_x, h, w = x.shape
+    if (tn_x, cin_x, cout_w, k2) != (tn, cin, cout, k) or k not in (1, 3) or stride not in (1, 2) or \
+            ((h - k) // stride + 1, (w - k) // stride + 1) != (ho, wo):
+        raise PconvError("tile_conv2d_backward: x %s, weight %s, gout %s, stride %d do not fit"
+                         % (tuple(x.shape), tuple(weight.shape), tuple(gout.shape), stride))
+    stream = _stream(gout.device)
+    lib = _native.hip_lib()
+
+    def workspace(nbytes):
+        if nbytes < 0:
+            raise PconvError("tile_conv2d_backward: workspace query failed: %s" % (lib.pconv_last_error() or b"").decode())
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=gout.device) if nbytes else None
+
+    gin = gw = gb = None
+    if need_x:
+        packed = _packed_weight_transposed(weight if owner is None else owner, weight, stream)
+        gin = torch.empty((tn, cin, h, w), dtype=torch.float32, device=gout.device)
+        ws = workspace(lib.pconv_conv2d_dgrad_workspace_bytes(tn, cout, h, w, k, stride))
+        call("pconv_conv2d_dgrad", _ptr(gout), _ptr(packed), _ptr(gin), _ptr(ws), tn, cin, h, w, cout, k, stride, stream)
+    if need_w or need_b:
+        if need_w:
+            gw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=gout.device)
+        if need_b:
+            gb = torch.empty((cout,), dtype=torch.float32, device=gout.device)
+        # (a bias-only call needs the fp64 planes alone, not the partials in front of them)
+        ws = workspace(lib.pconv_conv2d_wgrad_workspace_bytes(tn, cin, cout, k) if need_w else tn * cout * 8)
+        call("pconv_conv2d_wgrad", _ptr(x) if need_w else None, _ptr(gout), _ptr(gw), _ptr(gb), _ptr(ws), tn, cin, h, w,
+             cout, k, stride, stream)
+    return gin, gw, gb

@@ -231,7 +231,16 @@ class PseudoGDNV2(nn.Module):
         inputs = inputs * self.mask
         beta = LowerBound.apply(self.beta, self.beta_bound) ** 2 - self.pedestal
         gamma = LowerBound.apply(self.gamma, self.gamma_bound) ** 2 - self.pedestal
-        norm_ = nn.functional.conv2d(inputs ** 2, gamma.view(ch, ch, 1, 1), beta)
+        ops = backend.ops()
+        trains = torch.is_grad_enabled() and (inputs.requires_grad or gamma.requires_grad or beta.requires_grad)
+        if trains and inputs.is_cuda and hasattr(ops, "tile_conv2d_backward") and ops.conv_grad_is_native():
+            # PCONV.native_conv_grad, and something asks for a gradient (TileConv2d's own condition): the 1x1
+            # contraction stays on this project's kernels, forward and backward.  gamma and beta are results of the
+            # graph that change with every optimiser step: their two packs (forward, transposed) live for this call
+            norm_ = TileConvCall.apply(None, (inputs ** 2).contiguous(), gamma.view(ch, ch, 1, 1).contiguous(),
+                                       beta.contiguous(), 1)
+        else:
+            norm_ = nn.functional.conv2d(inputs ** 2, gamma.view(ch, ch, 1, 1), beta)
         norm_ = torch.sqrt(norm_)
         norm_ = norm_ * self.mask + 1 - self.mask
         return inputs * norm_ if self.inverse else inputs / norm_
@@ -255,6 +264,35 @@ class _QuantCall(torch.autograd.Function):
         g = [t.contiguous() if t is not None else torch.zeros_like(x) for t in grads]
         gx, gw, gc = ctx.op.backward(g, x, out)
         return None, gx, gw, gc.clone().detach(), None
+
+
+class _Uncached(object):
+    """owner of the packed weights of one TileConvCall whose weight is not a parameter"""
+
+
+class TileConvCall(torch.autograd.Function):
+    """autograd bridge of the tile convolution under PCONV.native_conv_grad: forward is the backend's tile_conv2d
+    (the plan inference takes, no fused epilogue), backward its tile_conv2d_backward -- the data, weight and bias
+    gradients in the orders include/pconv_hip.h defines.  No double backward.  owner: the module the packed
+    weights are cached on; None for a weight that is a result of the graph (nothing outlives the call: a cache key of
+    (address, version) would meet the next result at the same address)."""
+
+    @staticmethod
+    def forward(ctx, owner, x, weight, bias, stride):
+        ops = backend.ops()
+        owner = owner if owner is not None else _Uncached()
+        ctx.owner, ctx.stride, ctx.has_bias = owner, int(stride), bias is not None
+        ctx.save_for_backward(x, weight)
+        return ops.tile_conv2d(owner, x, weight, bias, int(stride))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        x, weight = ctx.saved_tensors
+        need = (ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3])
+        gin, gw, gb = backend.ops().tile_conv2d_backward(x.contiguous(), weight, gout.contiguous(), ctx.stride, need,
+                                                         owner=ctx.owner)
+        return None, gin, gw, gb, None
 
 
 class PseudoQUANTV2(BaseOpModule):

@@ -92,6 +92,12 @@ _HIP_SIGNATURES = {
     "pconv_conv_packed_size": [I, I, I, P, P],
     "pconv_conv_pack_weight": [P, P, I, I, I, P],
     "pconv_conv2d": [P, P, P, P, I, I, I, I, I, I, I, I, P, P, I, P, P, I, I, P, P],
+    "pconv_conv_pack_weight_transposed": [P, P, I, I, I, P],
+    "pconv_conv2d_dgrad_workspace_bytes": [I, I, I, I, I, I],
+    "pconv_conv_grad_prepare": [P, P, I, I, I, I, I, I, P],
+    "pconv_conv2d_dgrad": [P, P, P, P, I, I, I, I, I, I, I, P],
+    "pconv_conv2d_wgrad_workspace_bytes": [I, I, I, I],
+    "pconv_conv2d_wgrad": [P, P, P, P, P, I, I, I, I, I, I, I, P],
     "pconv_gdn": [P, P, P, P, I, I, I, I, I, P, I, P, P, P],
     "pconv_wino_packed_size": [I, I],
     "pconv_wino_pack_weight": [P, P, I, I, P],
@@ -197,6 +203,8 @@ def hip_lib():
         lib.pconv_host_tap_reverse_size.restype = c_longlong
         lib.pconv_host_project_reverse_size.restype = c_longlong
         lib.pconv_quant_backward_ordered_workspace_bytes.restype = c_longlong
+        lib.pconv_conv2d_dgrad_workspace_bytes.restype = c_longlong
+        lib.pconv_conv2d_wgrad_workspace_bytes.restype = c_longlong
         _hip = lib
     return _hip
 

@@ -33,6 +33,7 @@ HIP_SOURCES = [
     "entropy_engine.hip",
     "entropy_mfma.hip",
     "conv.hip",
+    "conv_backward.hip",  # data / weight / bias gradient of the tile convolutions in a defined order (--conv native)
     "wino.hip",
     "wino_flat.hip",   # wino.hip again with a 2-row x 128-column workgroup tile (the row split's remainders)
     "wino42.hip",

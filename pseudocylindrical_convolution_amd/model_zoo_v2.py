@@ -13,7 +13,7 @@ from torch import nn
 
 from .PCONV_operator import (ContextReshape, DropGrad, Dtow, EntropyGmm, Extract, MaskConv2, PseudoContextV2,
                              PseudoEntropyContext, PseudoEntropyPad, PseudoFillV2, PseudoGDNV2, PseudoPadV2,
-                             PseudoQUANTV2, SphereSlice, SphereUslice, StubMask, backend)
+                             PseudoQUANTV2, SphereSlice, SphereUslice, StubMask, TileConvCall, backend)
 
 __all__ = ["ClipData", "TileConv2d", "ResidualBlock", "AttentionBlock", "ResidualBlockV2", "ResidualBlockDown",
            "SphereConv2", "EncoderV2", "ResidualBlockUp", "SphereConvOld", "DecoderV2", "EntropyConv",
@@ -70,7 +70,8 @@ class TileConv2d(nn.Conv2d):
     without being computed (they are dead: every consumer either trims them or
     never reads them).  Without fusion support (the CPU oracle backend of the tests) and
     under autograd (training: the library convolution with its own backward, as the
-    reference's nn.Conv2d) the same operations run one by one, in the same order.  On the
+    reference's nn.Conv2d; with PCONV.native_conv_grad on: this project's tile convolution and its
+    own backward, csrc/conv_backward.hip) the same operations run one by one, in the same order.  On the
     HIP backend inference never leaves the hand-written kernels: there is no knob that
     routes it to the vendor library."""
 
@@ -79,10 +80,14 @@ class TileConv2d(nn.Conv2d):
         ops = backend.ops()
         slope = prelu.weight if prelu is not None else None
         vendor = not hasattr(ops, "tile_conv2d")
+        native_grad = False
         if torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad):
             # training: the convolution and its activation go through autograd's library
             # kernels, as the reference's nn.Conv2d does; the tile ops around them use their own backward
             vendor, live = True, None
+            # ... unless PCONV.native_conv_grad is on: then the convolution alone is this project's, forward
+            # (tile_conv2d, no fused epilogue) and backward (tile_conv2d_backward), and what follows it stays torch's
+            native_grad = hasattr(ops, "tile_conv2d_backward") and ops.conv_grad_is_native()
         fused = (not vendor) and getattr(ops, "FUSED_EPILOGUE", False)
         limit, npart = None, 0
         if live is not None and hasattr(ops, "conv_col_limit") and os.environ.get("PCONV_SKIP_DEAD", "1") == "1":
@@ -97,7 +102,10 @@ class TileConv2d(nn.Conv2d):
                                    sigmoid=sigmoid, gate=gate, residual=residual, trim=trim is not None,
                                    ring=ring, d2w=d2w is not None)
         if vendor:
-            y = nn.functional.conv2d(x, self.weight, self.bias, self.stride)
+            if native_grad:
+                y = TileConvCall.apply(self, x, self.weight, self.bias, self.stride[0])
+            else:
+                y = nn.functional.conv2d(x, self.weight, self.bias, self.stride)
             y = nn.functional.prelu(y, slope) if slope is not None else y
         else:
             y = ops.tile_conv2d(self, x, self.weight, self.bias, self.stride[0], slope, limit, npart)

@@ -15,7 +15,8 @@ checkpoint naming follow the reference.  What differs: ranks come from the launc
 `--time-budget S` ends the run after S seconds of wall time (the epoch in flight stops at its next
 step, is tested and saved as usual), and `--deterministic` trains on the ordered (atomic-free) backward kernels
 (PCONV.ordered_backward) under torch's deterministic settings and logs the parameter checksum two runs from one
-seed are compared on."""
+seed are compared on, and `--conv native` keeps the 1x1 / 3x3 convolutions on this project's kernels, forward and
+backward (PCONV.native_conv_grad)."""
 from __future__ import print_function
 
 import argparse
@@ -30,7 +31,7 @@ import torch.distributed as dist
 from torch.nn.parallel import DistributedDataParallel as DDP
 
 from . import PCONV, model_zoo_v2, sphere_metrics
-from .PCONV_operator import Logger, ModuleSaver, MultiProject, SSIM
+from .PCONV_operator import Logger, ModuleSaver, MultiProject, SSIM, backend
 from .RDMetric import mse_tb
 from .SphereDataset import (ProceduralSphereDataSet, SphereDataSet, SyntheticSphereDataSet,
                             load_train_test_distribute)
@@ -183,12 +184,28 @@ def deterministic_mode():
             torch.use_deterministic_algorithms(before[2], warn_only=before[3])
 
 
+def native_conv_mode():
+    """what --conv native sets, put back afterwards: the convolutions of a training step (TileConv2d and the GDN's
+    1x1 contraction) stay on this project's kernels, forward and backward (PCONV.native_conv_grad).  Refused on a
+    backend that has no such kernels."""
+    ops = backend.ops()
+    if not hasattr(ops, 'tile_conv2d_backward'):
+        raise RuntimeError('--conv native needs the HIP backend: {} has no convolution backward kernels '
+                           '(tile_conv2d_backward); use --conv vendor'.format(getattr(ops, '__name__', ops)))
+    return ops.native_conv_grad(True)
+
+
 def Job(rank, world_size, args):
     """what one rank does (reference: trainDDP_Full.py:102-163)"""
-    if getattr(args, 'deterministic', False):
-        with deterministic_mode():
-            return _job(rank, world_size, args)
-    return _job(rank, world_size, args)
+    native = getattr(args, 'conv', 'vendor') == 'native'
+    if native and args.device != 'cuda':
+        raise RuntimeError('--conv native needs --device cuda: the convolution backward kernels are HIP kernels; '
+                           'use --conv vendor')
+    with native_conv_mode() if native else contextlib.nullcontext():
+        if getattr(args, 'deterministic', False):
+            with deterministic_mode():
+                return _job(rank, world_size, args)
+        return _job(rank, world_size, args)
 
 
 def _job(rank, world_size, args):
@@ -268,9 +285,12 @@ def _job(rank, world_size, args):
     log.log('lr:{}'.format(args.lr))
     if deterministic:
         log.log('deterministic: ordered backward kernels {}, cudnn.deterministic {}, cudnn.benchmark {}, '
-                'torch deterministic algorithms {} (warn only)'.format(
+                'torch deterministic algorithms {} (warn only){}'.format(
                     'on' if PCONV.backward_is_ordered() else 'off', torch.backends.cudnn.deterministic,
-                    torch.backends.cudnn.benchmark, torch.are_deterministic_algorithms_enabled()))
+                    torch.backends.cudnn.benchmark, torch.are_deterministic_algorithms_enabled(),
+                    '' if not PCONV.conv_grad_is_native() else ', convolutions native' + (
+                        '' if args.loss in SPHERE_LOSSES else
+                        ' (not the 11x11 blur of the viewport loss\'s SSIM, which stays the library\'s: --loss ws / ws-ms have none)')))
     if args.loss in SPHERE_LOSSES:
         log.log('loss: WS-MSE / {} over the ERP frames (--viewport_size is ignored)'.format(
             'WS-SSIM' if args.loss == 'ws' else 'WS-MS-SSIM'))
@@ -371,7 +391,15 @@ def build_parser():
                              'quantiser backward kernels (PCONV.ordered_backward), cudnn.deterministic, no cudnn benchmark, '
                              'torch.use_deterministic_algorithms(True, warn_only=True); logs the parameter checksum to '
                              'compare two runs on.  Guaranteed for this project\'s own kernels; the vendor library\'s '
-                             'convolution backward is outside it')
+                             'convolution backward is outside it (--conv native replaces it)')
+    parser.add_argument('--conv', default='vendor', choices=['vendor', 'native'],
+                        help='whose kernels the convolutions of a training step run on.  vendor: the library behind '
+                             'torch (forward and backward).  native: this project\'s fp32-MFMA kernels, the backward in '
+                             'the defined order of include/pconv_hip.h (PCONV.native_conv_grad) -- every 1x1 / 3x3 '
+                             'convolution of the transforms and the GDN.  Two convolutions stay with the library: the '
+                             'entropy model\'s masked 5x5 ones, and the 11x11 blur of the SSIM term of --loss viewport '
+                             '(--loss ws / ws-ms have none: with them the --base stage reaches no library convolution).  '
+                             'HIP backend only')
     parser.add_argument('--verbose', action='store_true', default=False)
     return parser
 
