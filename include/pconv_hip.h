@@ -667,6 +667,45 @@ long long pconv_conv2d_wgrad_workspace_bytes(int tn, int cin, int cout, int k);
 int pconv_conv2d_wgrad(const float *in, const float *gout, float *gw, float *gb, void *workspace,
                        int tn, int cin, int h, int w, int cout, int k, int stride, void *stream);
 
+/* The 5x5 convolution of the entropy model's masked layers under training (MaskConstrain.py:24-38: MaskConv2 /
+ * MaskConv3 call nn.functional.conv2d on the masked weight), forward and backward: stride 1, no padding, dense NCHW
+ * fp32: in (tn, cin, h, w), w (cout, cin, 5, 5), out / gout (tn, cout, h - 4, w - 4).  Entry points of their own:
+ * pconv_conv2d, pconv_conv_pack_weight[_transposed], pconv_conv2d_dgrad and pconv_conv2d_wgrad keep refusing k = 5.
+ * THE ORDERS ARE THE SAME as those defined above for pconv_conv2d and its backward, taken at k = 5, stride 1:
+ *   forward: every output is one fp32 fmaf chain from +0 over (ci, kh, kw) ascending, then + bias (may be NULL).
+ *     EVERY tap is a step of the chain, also a tap whose weight is zero: the kernels do not know the causal mask
+ *     (fmaf(x, +0, acc) differs from acc for acc = -0 and for x not finite), the definition is the dense chain on
+ *     the masked weight;
+ *   data gradient: pconv_conv5 of the prepared gradient -- gout padded by 4 with +0 on every side, (tn, cout,
+ *     h + 4, w + 4); there is no stuffing at stride 1 -- with the flipped, transposed weights
+ *     wT[ci][co][kh'][kw'] = w[co][ci][4-kh'][4-kw'] (pconv_conv5_pack_weight_transposed, pconv_conv5_packed_size(cin,
+ *     cout) floats): one fmaf chain from +0 over (co, kh', kw') ascending per gin element;
+ *   weight gradient: per tile t the partial P_t[co][ci][kh][kw] = one fmaf chain from +0 over the tile's output
+ *     pixels, y then x ascending, on v_mfma_f32_32x32x2_f32, in runs of up to 64 pixels of one output row, a run of
+ *     odd length followed by the step fmaf(-0, +0, acc); then gw = (((P_0 + P_1) + P_2) + ...) in fp32, t ascending;
+ *   bias gradient: the fixed-shape two-stage fp64 reduction of pconv_conv2d_wgrad.
+ * No atomics, no allocation and no memset inside a call; 64-bit flat indices; subnormals are kept; results do not
+ * depend on the grid, the CU count, an option or the workspace's size; null pointers, h or w below 5, shapes beyond
+ * int32 and a missing or misaligned workspace are refused before any launch.  Inf / NaN in gout are unspecified
+ * for the data gradient only (its padded zeros multiply them).
+ * Packed weights: pconv_conv5_packed_size(cout, cin) floats, 16-byte aligned ([red_pad][cout_pad], cin padded to
+ * 2, cout to 32 / 96 / 192; negative when the weight exceeds int32).  Workspaces, 16-byte aligned device memory:
+ *   pconv_conv5_dgrad_workspace_bytes(tn, cout, h, w) = tn * cout * (h + 4) * (w + 4) * 4 (h, w: the INPUT's);
+ *   pconv_conv5_wgrad_workspace_bytes(tn, cin, cout) = tn * cout * cin * 25 * 4 rounded up to 16, + tn * cout * 8
+ *   (the partials, then one fp64 per plane; without gw the planes alone: tn * cout * 8 bytes suffice).
+ * pconv_conv5_wgrad writes gw and gb (either may be NULL: not computed; in may be NULL without gw). */
+int pconv_conv5_packed_size(int cout, int cin, int *cout_pad, int *red_pad);
+int pconv_conv5_pack_weight(const float *w, float *packed, int cout, int cin, void *stream);
+int pconv_conv5_pack_weight_transposed(const float *w, float *packed, int cout, int cin, void *stream);
+int pconv_conv5(const float *in, const float *packed_w, const float *bias, float *out, int tn, int cin,
+                int h, int w, int cout, void *stream);
+long long pconv_conv5_dgrad_workspace_bytes(int tn, int cout, int h, int w);
+int pconv_conv5_dgrad(const float *gout, const float *packed_wt, float *gin, void *workspace, int tn,
+                      int cin, int h, int w, int cout, void *stream);
+long long pconv_conv5_wgrad_workspace_bytes(int tn, int cin, int cout);
+int pconv_conv5_wgrad(const float *in, const float *gout, float *gw, float *gb, void *workspace, int tn,
+                      int cin, int h, int w, int cout, void *stream);
+
 /* The same convolution for k = 3, stride 1 by Winograd F(2x2, 3x3) on the fp32 matrix cores
  * (csrc/wino.hip): 4 instead of 9 multiply-adds per input channel, output channel and pixel -- the
  * algorithm cuDNN runs the reference's fp32 3x3 nn.Conv2d layers with (model_zoo_v2.py:41-45,83-86,

@@ -193,6 +193,39 @@ def conv_grad_is_native():
     return _native_conv_grad
 
 
+# The masked 5x5 convolutions of the entropy model (MaskConv2 / MaskConv3 with kernel size 5) call the vendor
+# library's conv2d by default, also under native_conv_grad; with this switch on they go to conv5x5 /
+# conv5x5_backward (csrc/conv.hip, csrc/conv_backward.hip).  A switch of its own: neither native_conv_grad nor
+# ordered_backward changes it or is changed by it.  Read at every _MaskConv.forward.
+_native_masked_conv = False
+
+
+class _PreviousMaskedSwitch(int):
+    """what native_masked_conv() returns: as _PreviousSwitch, for the masked-convolution switch"""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _native_masked_conv
+        _native_masked_conv = bool(self)
+        return False
+
+
+def native_masked_conv(on=None):
+    """Set the switch (None leaves it) and return its previous value.  `with PCONV.native_masked_conv(True): ...`
+    restores the previous value at the end of the block, also after an exception."""
+    global _native_masked_conv
+    previous = _PreviousMaskedSwitch(_native_masked_conv)
+    if on is not None:
+        _native_masked_conv = bool(on)
+    return previous
+
+
+def masked_conv_is_native():
+    return _native_masked_conv
+
+
 class _Op(object):
     """State shared by all ops: target device and re-used output buffers
     (base_opt.hpp:12-72)."""
@@ -1983,4 +2016,96 @@ def tile_conv2d_backward(x, weight, gout, stride, need=(True, True, True), owner
         ws = workspace(lib.pconv_conv2d_wgrad_workspace_bytes(tn, cin, cout, k) if need_w else tn * cout * 8)
         call("pconv_conv2d_wgrad", _ptr(x) if need_w else None, _ptr(gout), _ptr(gw), _ptr(gb), _ptr(ws), tn, cin, h, w,
              cout, k, stride, stream)
+    return gin, gw, gb
+
+
+# ---- the masked 5x5 convolutions of the entropy model under training (native_masked_conv) ------------------------
+
+def _packed_weight5(owner, weight, stream, transposed):
+    """a (cout, cin, 5, 5) weight in pconv_conv5's slab layout, or flipped and transposed for its data gradient:
+    cached on `owner` in slots of their own under _packed_weight's key.  The causal mask is written through
+    weight.data (no version bump) -- but always to the same values at the same places, and _MaskConv.forward writes
+    it before it comes here, so a pack made under a key is the pack of the masked weight under that key."""
+    from .PCONV_operator import backend
+    slot = "_pconv_packed5_t" if transposed else "_pconv_packed5"
+    key = (weight.data_ptr(), weight._version, weight.device, backend.param_epoch())
+    cached = getattr(owner, slot, None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    cout, cin = weight.shape[:2]
+    size = _native.hip_lib().pconv_conv5_packed_size(*((cin, cout) if transposed else (cout, cin)) + (None, None))
+    if size < 0:
+        raise PconvError("conv5x5: weight %s is too large to pack" % (tuple(weight.shape),))
+    packed = torch.empty(int(size), dtype=torch.float32, device=weight.device)
+    call("pconv_conv5_pack_weight_transposed" if transposed else "pconv_conv5_pack_weight",
+         _ptr(weight.detach().contiguous()), _ptr(packed), cout, cin, stream)
+    setattr(owner, slot, (key, packed))
+    return packed
+
+
+def _conv5_tensors(where, tensors):
+    """every tensor of a conv5x5 call is checked, whether the call reads it or not: the entry points take raw
+    addresses"""
+    first = tensors[0][1]
+    for name, t, dims in tensors:
+        if not isinstance(t, torch.Tensor) or t.dim() != dims:
+            raise PconvError("%s: %s must be a %d-D tensor" % (where, name, dims))
+        _require_gpu(t.detach(), "%s: %s" % (where, name))
+        if t.device != first.device:
+            raise PconvError("%s: %s is on %s, %s on %s" % (where, name, t.device, tensors[0][0], first.device))
+
+
+def conv5x5(owner, x, weight, bias):
+    """y = conv2d(x, weight, bias) for a 5x5 weight, stride 1, no padding, on the fp32 matrix cores: x (tn, cin, h, w)
+    -> (tn, cout, h - 4, w - 4), every output one fmaf chain over (ci, kh, kw) ascending, then + bias
+    (include/pconv_hip.h).  The weight is taken as it is -- the caller has masked it.  owner: the object the pack is
+    cached on."""
+    _conv5_tensors("conv5x5", [("x", x, 4), ("weight", weight, 4)] + ([("bias", bias, 1)] if bias is not None else []))
+    tn, cin, h, w = x.shape
+    cout, cin_w, k, k2 = weight.shape
+    if cin != cin_w or (k, k2) != (5, 5) or h < 5 or w < 5 or (bias is not None and bias.shape[0] != cout):
+        raise PconvError("conv5x5: weight %s does not fit input %s" % (tuple(weight.shape), tuple(x.shape)))
+    stream = _stream(x.device)
+    out = torch.empty((tn, cout, h - 4, w - 4), dtype=torch.float32, device=x.device)
+    call("pconv_conv5", _ptr(x), _ptr(_packed_weight5(owner, weight, stream, False)),
+         _ptr(bias.detach()) if bias is not None else None, _ptr(out), tn, cin, h, w, cout, stream)
+    return out
+
+
+def conv5x5_backward(x, weight, gout, need=(True, True, True), owner=None):
+    """(gin, gw, gb) of y = conv5x5(x, weight, bias) from gout = dL/dy, in the orders include/pconv_hip.h defines; a
+    gradient `need` does not ask for is neither computed nor returned (None).  gw is the dense gradient, masked taps
+    included (what the vendor path returns too: the weights are masked again at every forward).  owner: the object
+    that caches the transposed pack (default: the weight tensor itself)."""
+    need_x, need_w, need_b = (bool(n) for n in need)
+    _conv5_tensors("conv5x5_backward", [("gout", gout, 4), ("x", x, 4), ("weight", weight, 4)])
+    tn, cout, ho, wo = gout.shape
+    cout_w, cin, k, k2 = weight.shape
+    tn_x, cin_x, h, w = x.shape
+    if (tn_x, cin_x, cout_w, k, k2) != (tn, cin, cout, 5, 5) or (h - 4, w - 4) != (ho, wo) or ho < 1 or wo < 1:
+        raise PconvError("conv5x5_backward: x %s, weight %s, gout %s do not fit"
+                         % (tuple(x.shape), tuple(weight.shape), tuple(gout.shape)))
+    stream = _stream(gout.device)
+    lib = _native.hip_lib()
+
+    def workspace(nbytes):
+        if nbytes < 0:
+            raise PconvError("conv5x5_backward: workspace query failed: %s" % (lib.pconv_last_error() or b"").decode())
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=gout.device)
+
+    gin = gw = gb = None
+    if need_x:
+        packed = _packed_weight5(weight if owner is None else owner, weight, stream, True)
+        gin = torch.empty((tn, cin, h, w), dtype=torch.float32, device=gout.device)
+        ws = workspace(lib.pconv_conv5_dgrad_workspace_bytes(tn, cout, h, w))
+        call("pconv_conv5_dgrad", _ptr(gout), _ptr(packed), _ptr(gin), _ptr(ws), tn, cin, h, w, cout, stream)
+    if need_w or need_b:
+        if need_w:
+            gw = torch.empty((cout, cin, 5, 5), dtype=torch.float32, device=gout.device)
+        if need_b:
+            gb = torch.empty((cout,), dtype=torch.float32, device=gout.device)
+        # (a bias-only call needs the fp64 planes alone, not the partials in front of them)
+        ws = workspace(lib.pconv_conv5_wgrad_workspace_bytes(tn, cin, cout) if need_w else tn * cout * 8)
+        call("pconv_conv5_wgrad", _ptr(x) if need_w else None, _ptr(gout), _ptr(gw), _ptr(gb), _ptr(ws), tn, cin, h, w,
+             cout, stream)
     return gin, gw, gb

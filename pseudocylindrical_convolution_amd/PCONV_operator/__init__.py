@@ -12,4 +12,4 @@ from .ops import (MultiProject, MultiProjectM, Dtow, EntropyGmm, ContextReshape,
                   EntropyContextNew, EntropyConv2, EntropyConv2Batch, EntropyCtxPadRun2, DExtract2, DInput2,
                   DExtract2Batch, EntropyAdd, EntropyConvD, EntropyResidualBlockD, PseudoFillV2,
                   PseudoContextV2, PseudoGDNV2, PseudoPadV2, PseudoEntropyContext, PseudoEntropyPad,
-                  PseudoQUANTV2, PseudoDQUANT, TileConvCall)
+                  PseudoQUANTV2, PseudoDQUANT, TileConvCall, MaskConvCall)

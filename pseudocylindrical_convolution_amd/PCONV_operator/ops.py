@@ -295,6 +295,28 @@ class TileConvCall(torch.autograd.Function):
         return None, gin, gw, gb, None
 
 
+class MaskConvCall(torch.autograd.Function):
+    """autograd bridge of the masked 5x5 convolutions under PCONV.native_masked_conv: forward is the backend's
+    conv5x5 on the weight as it stands (the caller has zeroed the non-causal taps), backward its conv5x5_backward --
+    the data, weight and bias gradients in the orders include/pconv_hip.h defines; the weight gradient is the dense
+    one, masked taps included, as the library's is.  No double backward.  owner: the module the two packs are cached
+    on; they are made here, i.e. after the mask was written in the same forward."""
+
+    @staticmethod
+    def forward(ctx, owner, x, weight, bias):
+        ctx.owner, ctx.has_bias = owner, bias is not None
+        ctx.save_for_backward(x, weight)
+        return backend.ops().conv5x5(owner, x, weight, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        x, weight = ctx.saved_tensors
+        need = (ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3])
+        gin, gw, gb = backend.ops().conv5x5_backward(x, weight, gout.contiguous(), need, owner=ctx.owner)
+        return None, gin, gw, gb
+
+
 class PseudoQUANTV2(BaseOpModule):
     """learned 8-level per-channel quantiser (reference: PseudoContextV2.py:241-255)."""
 
@@ -538,6 +560,12 @@ class _MaskConv(BaseOpModule):
 
     def forward(self, x):
         self.native(self.weight.data).forward(self.weight.data)  # zero the non-causal taps in place
+        ops = backend.ops()
+        if x.is_cuda and self.weight.shape[2] == 5 and hasattr(ops, "conv5x5_backward") and ops.masked_conv_is_native():
+            # PCONV.native_masked_conv: the convolution is this project's, forward and backward, on the weight as
+            # masked just above (the packs are made after the zeroing: the mask goes through .data and leaves
+            # weight._version as it is).  Other kernel sizes and a backend without the kernels stay on the library.
+            return MaskConvCall.apply(self, x.contiguous(), self.weight, self.bias)
         return nn.functional.conv2d(x, self.weight, self.bias)
 
 

@@ -98,6 +98,15 @@ _HIP_SIGNATURES = {
     "pconv_conv2d_dgrad": [P, P, P, P, I, I, I, I, I, I, I, P],
     "pconv_conv2d_wgrad_workspace_bytes": [I, I, I, I],
     "pconv_conv2d_wgrad": [P, P, P, P, P, I, I, I, I, I, I, I, P],
+    # the masked 5x5 convolutions under training (PCONV.native_masked_conv)
+    "pconv_conv5_packed_size": [I, I, P, P],
+    "pconv_conv5_pack_weight": [P, P, I, I, P],
+    "pconv_conv5_pack_weight_transposed": [P, P, I, I, P],
+    "pconv_conv5": [P, P, P, P, I, I, I, I, I, P],
+    "pconv_conv5_dgrad_workspace_bytes": [I, I, I, I],
+    "pconv_conv5_dgrad": [P, P, P, P, I, I, I, I, I, P],
+    "pconv_conv5_wgrad_workspace_bytes": [I, I, I],
+    "pconv_conv5_wgrad": [P, P, P, P, P, I, I, I, I, I, P],
     "pconv_gdn": [P, P, P, P, I, I, I, I, I, P, I, P, P, P],
     "pconv_wino_packed_size": [I, I],
     "pconv_wino_pack_weight": [P, P, I, I, P],
@@ -205,6 +214,8 @@ def hip_lib():
         lib.pconv_quant_backward_ordered_workspace_bytes.restype = c_longlong
         lib.pconv_conv2d_dgrad_workspace_bytes.restype = c_longlong
         lib.pconv_conv2d_wgrad_workspace_bytes.restype = c_longlong
+        lib.pconv_conv5_dgrad_workspace_bytes.restype = c_longlong
+        lib.pconv_conv5_wgrad_workspace_bytes.restype = c_longlong
         _hip = lib
     return _hip
 

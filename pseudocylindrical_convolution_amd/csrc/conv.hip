@@ -1530,6 +1530,68 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
   return PCONV_OK;
 }
 
+// ---- 5x5, stride 1: the masked convolutions of the entropy model under training (MaskConstrain.py:24-38) ----------
+// conv_mfma_kernel at KS = 5 with two input channels per LDS stage: 50 reduction entries = 25 k-pairs per chunk, a
+// patch of (ROWS + 4) x 68 per channel and a 50 x BM weight slab -- 9 KB (32 couts) / 23 KB (96 couts) / 41 KB
+// (192 couts) per stage; two stages of the 192-cout tile are 81 KB, one workgroup per CU (the entropy model's widest
+// layers, 144 couts; not tuned).  The pair (2 kp, 2 kp + 1) of the odd 25-tap window steps to the next column,
+// the next row or the next channel: the three deltas ConvCfg already keeps one LDS base register for.  The weight is
+// taken as it is: a tap the causal mask zeroed is a step fmaf(x, +0, acc) of the chain like any other.
+constexpr int kKC5 = 2;
+
+extern "C" int pconv_conv5_packed_size(int cout, int cin, int *cout_pad, int *red_pad) {
+  // cout padded to the widest workgroup tile, reduction to whole chunks, as pconv_conv_packed_size
+  const int tile = cout > 96 ? 192 : (cout > 32 ? 96 : 32);
+  const long long cp = ((long long)cout + tile - 1) / tile * tile;
+  const long long rp = ((long long)cin + kKC5 - 1) / kKC5 * kKC5 * 25;
+  PCONV_REQUIRE(cout > 0 && cin > 0 && cp * rp <= 0x7fffffffLL, "conv5_packed_size: bad shape or weight exceeds int32");
+  if (cout_pad) *cout_pad = (int)cp;
+  if (red_pad) *red_pad = (int)rp;
+  return (int)(cp * rp);
+}
+
+extern "C" int pconv_conv5_pack_weight(const float *w, float *packed, int cout, int cin, void *stream) {
+  PCONV_REQUIRE(w && packed, "conv5_pack_weight: null pointer");
+  int cp, rp;
+  const int total = pconv_conv5_packed_size(cout, cin, &cp, &rp);
+  if (total < 0) return total;
+  hipLaunchKernelGGL(pack_weight_kernel, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream), w, packed, cout,
+                     cin * 25, cp, rp);
+  PCONV_LAUNCH_CHECK("conv5_pack_weight");
+  return PCONV_OK;
+}
+
+extern "C" int pconv_conv5(const float *in, const float *packed_w, const float *bias, float *out, int tn, int cin, int h,
+                           int w, int cout, void *stream) {
+  PCONV_REQUIRE(in && packed_w && out, "conv5: null pointer");
+  PCONV_REQUIRE(tn > 0 && cin > 0 && cout > 0 && h >= 5 && w >= 5, "conv5: bad shape (%d, %d, %d, %d) -> %d: h and w >= 5", tn,
+                cin, h, w, cout);
+  int cp, rp;
+  PCONV_REQUIRE(pconv_conv5_packed_size(cout, cin, &cp, &rp) > 0 && (long long)h * w <= 0x7fffffffLL &&
+                    (long long)tn * cin <= 0x7fffffffLL && (long long)tn * cout <= 0x7fffffffLL,
+                "conv5: shape exceeds int32");
+  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(packed_w) & 15) == 0, "conv5: the packed weight must be 16-byte aligned");
+  const int ho = h - 4, wo = w - 4;
+  const ConvView vin = dense_view(cin, h, w), vout = dense_view(cout, ho, wo);
+  // a stage addresses its kKC5 channels as a 64-bit uniform base + a 32-bit byte offset per lane
+  PCONV_REQUIRE(((long long)(kKC5 - 1) * vin.cs + (long long)(h - 1) * vin.rs + w) * 4 < (1LL << 32),
+                "conv5: plane too large for 32-bit byte offsets inside a chunk");
+  const ConvEpilogue ep = {bias, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, vout, vout, 0};
+  const ConvOptions opt = ConvOptions::from_env();  // (PCONV_CONV_XCD is a 3x3 option: nothing here depends on it)
+  hipStream_t s = as_stream(stream);
+  int rc;
+  // the workgroup tiles of pconv_conv2d: 192 couts x 2 rows, 96 couts x 4 rows, 32 couts x 2 rows of 64 columns
+  if (cout > 96)
+    rc = launch_conv<3, 1, 2, 4, 5, 1, kKC5>(in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, opt, s);
+  else if (cout > 32)
+    rc = launch_conv<3, 1, 1, 8, 5, 1, kKC5>(in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, opt, s);
+  else
+    rc = launch_conv<1, 1, 1, 4, 5, 1, kKC5>(in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, opt, s);
+  if (rc != PCONV_OK) return rc;
+  PCONV_LAUNCH_CHECK("conv5");
+  return PCONV_OK;
+}
+
 // GDN / inverse GDN of PseudoGDNV2.forward (PseudoContextV2.py:133-216) as ONE launch:
 // norm = conv1x1(x^2, gamma) + beta on the matrix cores, then x / sqrt(norm) (or
 // x * sqrt(norm)) in the epilogue, (+ residual,) zeros past each tile's valid width.

@@ -1,7 +1,9 @@
 // Backward of the dense per-tile convolution (conv.hip) in a defined order: the data gradient, the weight
 // gradient and the bias gradient of pconv_conv2d's layers (k in {1, 3}, stride in {1, 2}, no padding, dense
 // NCHW fp32).  No atomics, no allocation and no memset: what a call needs comes from the caller as a workspace.
-// The orders are part of the contract (include/pconv_hip.h) and the CPU twin of the tests restates them.
+// The orders are part of the contract (include/pconv_hip.h) and the CPU twin of the tests restates them.  The masked
+// 5x5 stride-1 convolutions of the entropy model take the same orders at k = 5 through entry points of their own
+// (pconv_conv5_*, at the end of the file).
 //
 //   data gradient    = pconv_conv2d, stride 1, of the PREPARED output gradient (zero-stuffed to the stride, padded
 //                      by k - 1) with the flipped, transposed weights.  New here: the transposed pack and the
@@ -91,8 +93,8 @@ struct WgradCfg {
   static constexpr int PS = (KS == 1) ? S : 1;
   static constexpr int Q = S / PS;  // LDS step between neighbouring output pixels
   static constexpr int PC = (kSeg - 1) * Q + KS;
-  // patch row in LDS: the next length that is 1 (1x1) / 3 (3x3) modulo 64, so that the 32 columns a half wave reads
-  // -- consecutive n = (ci*KS + kh)*KS + kw -- fall into 32 different banks
+  // patch row in LDS: the next length that is KS modulo 64 (1 for 1x1, 3 for 3x3, 5 for 5x5), so that the 32 columns
+  // a half wave reads -- consecutive n = (ci*KS + kh)*KS + kw, at (ci*KS + kh) * PCS + kw -- fall into 32 different banks
   static constexpr int PCS = (KS == 1) ? PC + 1 : PC + (S == 1 ? 1 : 2);
   static constexpr int NCI = (KS == 1) ? kBN : (kBN - 1) / KK + 2;  // input channels 128 consecutive columns can touch
   static constexpr int ASZ = kBM * kAStride;
@@ -101,9 +103,9 @@ struct WgradCfg {
   static constexpr int STAGE = BOFF + (BSZ + 63) / 64 * 64;
   static constexpr int ALD = (ASZ + kBlock - 1) / kBlock;  // LDS-DMA dwords per thread
   static constexpr int BLD = (BSZ + kBlock - 1) / kBlock;
-  static_assert(PCS >= PC && PCS % 64 == (KS == 1 ? 1 : 3), "patch rows spread the columns over the banks");
+  static_assert(PCS >= PC && PCS % 64 == KS, "patch rows spread the columns over the banks");
   static_assert(2 * STAGE * 4 <= 160 * 1024, "two stages fit the CU's LDS");
-  // workgroups per CU the kernel is compiled for: two where two stage pairs fit the LDS (the 3x3 stride-1 layers)
+  // workgroups per CU the kernel is compiled for: two where two stage pairs fit the LDS (the 3x3 and 5x5 stride-1 layers)
   static constexpr int WGS = (2 * 2 * STAGE * 4 <= 160 * 1024) ? 2 : 1;
 };
 
@@ -378,27 +380,30 @@ extern "C" long long pconv_conv2d_wgrad_workspace_bytes(int tn, int cin, int cou
   return align_up((long long)tn * cout * cin * k * k * (long long)sizeof(float), 16) + (long long)tn * cout * (long long)sizeof(double);
 }
 
-extern "C" int pconv_conv2d_wgrad(const float *in, const float *gout, float *gw, float *gb, void *workspace, int tn,
-                                  int cin, int h, int w, int cout, int k, int stride, void *stream) {
-  PCONV_REQUIRE(gout && workspace && (gw || gb) && (in || !gw), "conv2d_wgrad: null pointer");
-  PCONV_REQUIRE(conv_shape_ok(tn, cin, h, w, cout, k, stride), "conv2d_wgrad: unsupported k=%d stride=%d or bad shape", k,
-                stride);
-  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "conv2d_wgrad: the workspace must be 16-byte aligned");
+namespace {
+
+// the weight and bias gradient of a (k, stride) the entry point `what` has accepted: checks that depend on the
+// sizes alone, then the launches
+int run_wgrad(const char *what, const float *in, const float *gout, float *gw, float *gb, void *workspace, int tn, int cin,
+              int h, int w, int cout, int k, int stride, void *stream) {
+  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", what);
   const int ho = (h - k) / stride + 1, wo = (w - k) / stride + 1;
   const long long ncol = (long long)cin * k * k, nw = (long long)cout * ncol;
-  PCONV_REQUIRE(fits_int32(nw) && fits_int32((long long)h * w) && fits_int32((long long)tn * cout),
-                "conv2d_wgrad: shape exceeds int32");
+  PCONV_REQUIRE(fits_int32(nw) && fits_int32((long long)h * w) && fits_int32((long long)tn * cout), "%s: shape exceeds int32",
+                what);
   // a workgroup addresses its 96 couts of gout / its <= 128 channels of the input as a 64-bit uniform base + a
   // 32-bit byte offset per lane
   PCONV_REQUIRE((long long)kBM * ho * wo * 4 < (1LL << 32) && (long long)kBN * h * w * 4 < (1LL << 32),
-                "conv2d_wgrad: plane too large for 32-bit byte offsets inside a block");
+                "%s: plane too large for 32-bit byte offsets inside a block", what);
   hipStream_t s = as_stream(stream);
   float *partial = static_cast<float *>(workspace);
   // (without gw there are no partials: the planes start the workspace)
   double *planes = reinterpret_cast<double *>(static_cast<char *>(workspace) + (gw ? align_up(tn * nw * (long long)sizeof(float), 16) : 0));
   if (gw) {
     int rc;
-    if (k == 3 && stride == 1)
+    if (k == 5)
+      rc = launch_wgrad<5, 1>(in, gout, partial, tn, cin, h, w, cout, ho, wo, s);
+    else if (k == 3 && stride == 1)
       rc = launch_wgrad<3, 1>(in, gout, partial, tn, cin, h, w, cout, ho, wo, s);
     else if (k == 3)
       rc = launch_wgrad<3, 2>(in, gout, partial, tn, cin, h, w, cout, ho, wo, s);
@@ -415,6 +420,73 @@ extern "C" int pconv_conv2d_wgrad(const float *in, const float *gout, float *gw,
     hipLaunchKernelGGL(conv_bgrad_plane_kernel, dim3(grid), dim3(kBlock), 0, s, gout, planes, (long long)ho * wo, nplanes);
     hipLaunchKernelGGL(conv_bgrad_sum_kernel, dim3((cout + kBlock - 1) / kBlock), dim3(kBlock), 0, s, planes, gb, tn, cout);
   }
-  PCONV_LAUNCH_CHECK("conv2d_wgrad");
+  PCONV_LAUNCH_CHECK(what);
   return PCONV_OK;
+}
+
+}  // namespace
+
+extern "C" int pconv_conv2d_wgrad(const float *in, const float *gout, float *gw, float *gb, void *workspace, int tn,
+                                  int cin, int h, int w, int cout, int k, int stride, void *stream) {
+  PCONV_REQUIRE(gout && workspace && (gw || gb) && (in || !gw), "conv2d_wgrad: null pointer");
+  PCONV_REQUIRE(conv_shape_ok(tn, cin, h, w, cout, k, stride), "conv2d_wgrad: unsupported k=%d stride=%d or bad shape", k,
+                stride);
+  return run_wgrad("conv2d_wgrad", in, gout, gw, gb, workspace, tn, cin, h, w, cout, k, stride, stream);
+}
+
+// ---- 5x5, stride 1 (the masked convolutions of the entropy model): the same orders at k = 5 -----------------------
+// data gradient: the prepared gradient is gout padded by 4 (no stuffing at stride 1), the convolution pconv_conv5 on
+// the transposed pack; weight gradient: conv_wgrad_kernel<5, 1> -- a patch of 5 input rows of 68 (+ 1: bank spread)
+// columns for each of the <= 7 channels that 128 consecutive (ci, kh, kw) columns of 25 taps touch, 35 KB per stage;
+// bias gradient: the kernels above.
+
+extern "C" int pconv_conv5_pack_weight_transposed(const float *w, float *packed, int cout, int cin, void *stream) {
+  PCONV_REQUIRE(w && packed, "conv5_pack_weight_transposed: null pointer");
+  int rowp, redp;  // the transposed layer has cin output and cout input channels
+  const int total = pconv_conv5_packed_size(cin, cout, &rowp, &redp);
+  if (total < 0) return total;
+  hipLaunchKernelGGL(pack_weight_transposed_kernel, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, as_stream(stream),
+                     w, packed, cout, cin, 5, rowp, redp);
+  PCONV_LAUNCH_CHECK("conv5_pack_weight_transposed");
+  return PCONV_OK;
+}
+
+extern "C" long long pconv_conv5_dgrad_workspace_bytes(int tn, int cout, int h, int w) {
+  PCONV_REQUIRE(tn > 0 && cout > 0 && h >= 5 && w >= 5, "conv5_dgrad_workspace_bytes: bad shape");
+  return (long long)tn * cout * (h + 4) * (w + 4) * (long long)sizeof(float);
+}
+
+extern "C" int pconv_conv5_dgrad(const float *gout, const float *packed_wt, float *gin, void *workspace, int tn, int cin,
+                                 int h, int w, int cout, void *stream) {
+  PCONV_REQUIRE(gout && packed_wt && gin, "conv5_dgrad: null pointer");
+  PCONV_REQUIRE(tn > 0 && cin > 0 && cout > 0 && h >= 5 && w >= 5, "conv5_dgrad: bad shape (%d, %d, %d, %d) -> %d: h and w >= 5",
+                tn, cin, h, w, cout);
+  PCONV_REQUIRE(workspace, "conv5_dgrad: null workspace");
+  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "conv5_dgrad: the workspace must be 16-byte aligned");
+  const int ho = h - 4, wo = w - 4, hp = h + 4, wp = w + 4;
+  PCONV_REQUIRE(fits_int32((long long)hp * wp) && fits_int32((long long)tn * cout) && fits_int32((long long)tn * cin) &&
+                    fits_int32((long long)cout * cin * 25),
+                "conv5_dgrad: shape exceeds int32");
+  float *prepared = static_cast<float *>(workspace);
+  const long long total = (long long)tn * cout * hp * wp;
+  hipLaunchKernelGGL(conv_grad_prepare_kernel, dim3(pconv_grid((total + 3) / 4, kBlock)), dim3(kBlock), 0, as_stream(stream),
+                     gout, prepared, total, hp, wp, ho, wo, 5, 1);
+  PCONV_LAUNCH_CHECK("conv5_dgrad");
+  // (tn, cout, h + 4, w + 4) * wT (cin, cout, 5, 5) -> (tn, cin, h, w)
+  return pconv_conv5(prepared, packed_wt, nullptr, gin, tn, cout, hp, wp, cin, stream);
+}
+
+extern "C" long long pconv_conv5_wgrad_workspace_bytes(int tn, int cin, int cout) {
+  PCONV_REQUIRE(tn > 0 && cin > 0 && cout > 0, "conv5_wgrad_workspace_bytes: bad shape");
+  // the partials P_t (tn, cout, cin, 5, 5) fp32, then the bias planes (tn, cout) fp64
+  return align_up((long long)tn * cout * cin * 25 * (long long)sizeof(float), 16) + (long long)tn * cout * (long long)sizeof(double);
+}
+
+extern "C" int pconv_conv5_wgrad(const float *in, const float *gout, float *gw, float *gb, void *workspace, int tn, int cin,
+                                 int h, int w, int cout, void *stream) {
+  PCONV_REQUIRE(gout && (gw || gb) && (in || !gw), "conv5_wgrad: null pointer");
+  PCONV_REQUIRE(workspace, "conv5_wgrad: null workspace");
+  PCONV_REQUIRE(tn > 0 && cin > 0 && cout > 0 && h >= 5 && w >= 5, "conv5_wgrad: bad shape (%d, %d, %d, %d) -> %d: h and w >= 5",
+                tn, cin, h, w, cout);
+  return run_wgrad("conv5_wgrad", in, gout, gw, gb, workspace, tn, cin, h, w, cout, 5, 1, stream);
 }

@@ -16,7 +16,9 @@ checkpoint naming follow the reference.  What differs: ranks come from the launc
 step, is tested and saved as usual), and `--deterministic` trains on the ordered (atomic-free) backward kernels
 (PCONV.ordered_backward) under torch's deterministic settings and logs the parameter checksum two runs from one
 seed are compared on, and `--conv native` keeps the 1x1 / 3x3 convolutions on this project's kernels, forward and
-backward (PCONV.native_conv_grad)."""
+backward (PCONV.native_conv_grad), and `--conv native-all` the entropy model's masked 5x5 convolutions too
+(PCONV.native_masked_conv), with the SSIM term of --loss viewport computed by sphere_metrics.loss_terms(uniform): no
+convolution of a training step is the vendor library's then."""
 from __future__ import print_function
 
 import argparse
@@ -49,7 +51,10 @@ def get_params(model, ent):
 def forward_losses(args, model, data, pr1, pr2, sim_func):
     """(mse, ssim, rate) of one batch; rate is None for the base model.  --loss viewport: MSE and SSIM over the 14
     projected views; --loss ws: the batch means of WS-MSE and WS-SSIM over the ERP frames themselves (pr1, pr2 and
-    sim_func are None); --loss ws-ms: the same with WS-MS-SSIM in the place of WS-SSIM"""
+    sim_func are None); --loss ws-ms: the same with WS-MS-SSIM in the place of WS-SSIM.  --loss viewport without a
+    sim_func (--conv native-all): the SSIM term is sphere_metrics.loss_terms(uniform) over the views -- pytorch_ssim's
+    map (the 11-tap sigma 1.5 window, zero padding of 5, its C1 and C2) on this project's kernels; all views have one
+    size, so the mean of the frame means is the mean of the map"""
     out = model(data)
     y, ent_vec, mask = out if isinstance(out, tuple) else (out, None, None)
     if args.loss in SPHERE_LOSSES:
@@ -58,9 +63,20 @@ def forward_losses(args, model, data, pr1, pr2, sim_func):
     else:
         py, px = pr1(y), pr2(data)
         mse = torch.mean((px - py) * (px - py))
-        ssim = sim_func(px, py)
+        if sim_func is None:
+            ssim = sphere_metrics.loss_terms(px, py, weighting="uniform")[:, 1].mean()
+        else:
+            ssim = sim_func(px, py)
     rate = None if ent_vec is None else torch.sum(ent_vec) / torch.sum(mask).item()
     return mse, ssim, rate
+
+
+def make_sim_func(args, device):
+    """the SSIM module of the viewport loss; None where forward_losses needs none: the sphere-weighted losses, and
+    --conv native-all (SSIM(11, 3) blurs with the library's convolution and is not constructed there)"""
+    if args.loss in SPHERE_LOSSES or getattr(args, 'conv', 'vendor') == 'native-all':
+        return None
+    return SSIM(11, 3).to(device)
 
 
 def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, log, pr1, pr2, ent=True):
@@ -68,7 +84,7 @@ def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, 
     model.train()
     train_loader.sampler.set_epoch(epoch)
     acc_grad = AccGrad(get_params(model, ent))
-    sim_func = None if args.loss in SPHERE_LOSSES else SSIM(11, 3).to(device)
+    sim_func = make_sim_func(args, device)
     gamma, beta, alpha, clip = args.gamma, args.beta, args.alpha, args.clip
     log.log('clip:{}'.format(clip))
     acc_batch = args.acc_batch
@@ -109,7 +125,7 @@ def test(args, model, device, test_loader, log, pr1, pr2):
     (reference: trainDDP_Full.py:58-86).  --loss ws / ws-ms: WS-MSE / WS-SSIM / rate, scored by the training loss itself
     (the anchor curve is one of viewport MSE)"""
     model.eval()
-    sim_func = None if args.loss in SPHERE_LOSSES else SSIM(11, 3).to(device)
+    sim_func = make_sim_func(args, device)
     test_mse, test_ssim, test_ent, n = 0., 0., 0., 0
     vd = args.valid_dim / 256. * .815
     for data in test_loader:
@@ -195,13 +211,28 @@ def native_conv_mode():
     return ops.native_conv_grad(True)
 
 
+@contextlib.contextmanager
+def native_all_conv_mode():
+    """what --conv native-all sets, put back afterwards: native_conv_mode, and the entropy model's masked 5x5
+    convolutions on this project's kernels as well (PCONV.native_masked_conv).  Refused on a backend that has no such
+    kernels, before either switch is touched."""
+    ops = backend.ops()
+    if not hasattr(ops, 'tile_conv2d_backward') or not hasattr(ops, 'conv5x5_backward'):
+        raise RuntimeError('--conv native-all needs the HIP backend: {} has no convolution backward kernels '
+                           '(tile_conv2d_backward, conv5x5_backward); use --conv vendor'.format(getattr(ops, '__name__', ops)))
+    with ops.native_conv_grad(True), ops.native_masked_conv(True):
+        yield
+
+
 def Job(rank, world_size, args):
     """what one rank does (reference: trainDDP_Full.py:102-163)"""
-    native = getattr(args, 'conv', 'vendor') == 'native'
+    conv = getattr(args, 'conv', 'vendor')
+    native = conv in ('native', 'native-all')
     if native and args.device != 'cuda':
-        raise RuntimeError('--conv native needs --device cuda: the convolution backward kernels are HIP kernels; '
-                           'use --conv vendor')
-    with native_conv_mode() if native else contextlib.nullcontext():
+        raise RuntimeError('--conv {} needs --device cuda: the convolution backward kernels are HIP kernels; '
+                           'use --conv vendor'.format(conv))
+    mode = native_all_conv_mode if conv == 'native-all' else native_conv_mode
+    with mode() if native else contextlib.nullcontext():
         if getattr(args, 'deterministic', False):
             with deterministic_mode():
                 return _job(rank, world_size, args)
@@ -288,7 +319,9 @@ def _job(rank, world_size, args):
                 'torch deterministic algorithms {} (warn only){}'.format(
                     'on' if PCONV.backward_is_ordered() else 'off', torch.backends.cudnn.deterministic,
                     torch.backends.cudnn.benchmark, torch.are_deterministic_algorithms_enabled(),
-                    '' if not PCONV.conv_grad_is_native() else ', convolutions native' + (
+                    '' if not PCONV.conv_grad_is_native() else
+                    ', convolutions native, incl. the masked 5x5 and the viewport SSIM' if PCONV.masked_conv_is_native() else
+                    ', convolutions native' + (
                         '' if args.loss in SPHERE_LOSSES else
                         ' (not the 11x11 blur of the viewport loss\'s SSIM, which stays the library\'s: --loss ws / ws-ms have none)')))
     if args.loss in SPHERE_LOSSES:
@@ -391,15 +424,20 @@ def build_parser():
                              'quantiser backward kernels (PCONV.ordered_backward), cudnn.deterministic, no cudnn benchmark, '
                              'torch.use_deterministic_algorithms(True, warn_only=True); logs the parameter checksum to '
                              'compare two runs on.  Guaranteed for this project\'s own kernels; the vendor library\'s '
-                             'convolution backward is outside it (--conv native replaces it)')
-    parser.add_argument('--conv', default='vendor', choices=['vendor', 'native'],
+                             'convolution backward is outside it (--conv native replaces it for the 1x1 / 3x3 layers, '
+                             '--conv native-all for every convolution of a training step)')
+    parser.add_argument('--conv', default='vendor', choices=['vendor', 'native', 'native-all'],
                         help='whose kernels the convolutions of a training step run on.  vendor: the library behind '
                              'torch (forward and backward).  native: this project\'s fp32-MFMA kernels, the backward in '
                              'the defined order of include/pconv_hip.h (PCONV.native_conv_grad) -- every 1x1 / 3x3 '
                              'convolution of the transforms and the GDN.  Two convolutions stay with the library: the '
                              'entropy model\'s masked 5x5 ones, and the 11x11 blur of the SSIM term of --loss viewport '
                              '(--loss ws / ws-ms have none: with them the --base stage reaches no library convolution).  '
-                             'HIP backend only')
+                             'native-all: as native, and the masked 5x5 convolutions on this project\'s kernels too '
+                             '(PCONV.native_masked_conv: the dense fmaf chain on the masked weight), and the SSIM term '
+                             'of --loss viewport by sphere_metrics.loss_terms(uniform) -- the same 11-tap window on this '
+                             'project\'s kernels -- in the place of pytorch_ssim\'s SSIM(11, 3): no configuration reaches '
+                             'a library convolution.  native and native-all: HIP backend only')
     parser.add_argument('--verbose', action='store_true', default=False)
     return parser
 
