@@ -122,38 +122,47 @@ class _HbmTimed(object):
         return False
 
 
-# The backward calls of SphereSliceOp, SphereUsliceOp, ProjectsOp and PseudoQuantOp sum with float atomics by
-# default; with this switch on they take the ordered (atomic-free) kernels of csrc/backward_ordered.hip, whose
-# sums run in the order include/pconv_hip.h defines.  Read at every backward call.
-_ordered_backward = False
-backward_launches = collections.Counter()   # entry point -> backward calls of those four ops that launched it
-
-
 class _PreviousSwitch(int):
-    """what ordered_backward() returns: the switch's previous value (an int that compares like the bool), and a
+    """what a call of a _Switch returns: the switch's previous value (an int that compares like the bool), and a
     context manager that puts that value back on leaving the block"""
+
+    def __new__(cls, switch):
+        self = int.__new__(cls, switch.on)
+        self.switch = switch
+        return self
 
     def __enter__(self):
         return self
 
     def __exit__(self, *exc):
-        global _ordered_backward
-        _ordered_backward = bool(self)
+        self.switch.on = bool(self)
         return False
 
 
-def ordered_backward(on=None):
-    """Set the switch (None leaves it) and return its previous value.  `with PCONV.ordered_backward(True): ...`
-    restores the previous value at the end of the block, also after an exception."""
-    global _ordered_backward
-    previous = _PreviousSwitch(_ordered_backward)
-    if on is not None:
-        _ordered_backward = bool(on)
-    return previous
+class _Switch(object):
+    """A process-wide boolean, off by default, read where it matters at every call.  switch(on) sets it (None leaves
+    it) and returns its previous value; `with switch(True): ...` restores the previous value at the end of the block,
+    also after an exception.  switch.is_on() reads it."""
+
+    def __init__(self):
+        self.on = False
+
+    def __call__(self, on=None):
+        previous = _PreviousSwitch(self)
+        if on is not None:
+            self.on = bool(on)
+        return previous
+
+    def is_on(self):
+        return self.on
 
 
-def backward_is_ordered():
-    return _ordered_backward
+# The backward calls of SphereSliceOp, SphereUsliceOp, ProjectsOp and PseudoQuantOp sum with float atomics by
+# default; with this switch on they take the ordered (atomic-free) kernels of csrc/backward_ordered.hip, whose
+# sums run in the order include/pconv_hip.h defines.  Read at every backward call.
+ordered_backward = _Switch()
+backward_is_ordered = ordered_backward.is_on
+backward_launches = collections.Counter()   # entry point -> backward calls of those four ops that launched it
 
 
 def _backward_call(fn, *args):
@@ -164,66 +173,15 @@ def _backward_call(fn, *args):
 # The convolutions of a training step go to the vendor library's forward and backward by default (TileConv2d under
 # autograd); with this switch on they stay on this project's kernels: tile_conv2d forward, tile_conv2d_backward
 # (csrc/conv_backward.hip) for the three gradients.  Read at every TileConv2d call under autograd.
-_native_conv_grad = False
-
-
-class _PreviousConvSwitch(int):
-    """what native_conv_grad() returns: as _PreviousSwitch, for the convolution switch"""
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        global _native_conv_grad
-        _native_conv_grad = bool(self)
-        return False
-
-
-def native_conv_grad(on=None):
-    """Set the switch (None leaves it) and return its previous value.  `with PCONV.native_conv_grad(True): ...`
-    restores the previous value at the end of the block, also after an exception."""
-    global _native_conv_grad
-    previous = _PreviousConvSwitch(_native_conv_grad)
-    if on is not None:
-        _native_conv_grad = bool(on)
-    return previous
-
-
-def conv_grad_is_native():
-    return _native_conv_grad
-
+native_conv_grad = _Switch()
+conv_grad_is_native = native_conv_grad.is_on
 
 # The masked 5x5 convolutions of the entropy model (MaskConv2 / MaskConv3 with kernel size 5) call the vendor
 # library's conv2d by default, also under native_conv_grad; with this switch on they go to conv5x5 /
 # conv5x5_backward (csrc/conv.hip, csrc/conv_backward.hip).  A switch of its own: neither native_conv_grad nor
 # ordered_backward changes it or is changed by it.  Read at every _MaskConv.forward.
-_native_masked_conv = False
-
-
-class _PreviousMaskedSwitch(int):
-    """what native_masked_conv() returns: as _PreviousSwitch, for the masked-convolution switch"""
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        global _native_masked_conv
-        _native_masked_conv = bool(self)
-        return False
-
-
-def native_masked_conv(on=None):
-    """Set the switch (None leaves it) and return its previous value.  `with PCONV.native_masked_conv(True): ...`
-    restores the previous value at the end of the block, also after an exception."""
-    global _native_masked_conv
-    previous = _PreviousMaskedSwitch(_native_masked_conv)
-    if on is not None:
-        _native_masked_conv = bool(on)
-    return previous
-
-
-def masked_conv_is_native():
-    return _native_masked_conv
+native_masked_conv = _Switch()
+masked_conv_is_native = native_masked_conv.is_on
 
 
 class _Op(object):
@@ -617,7 +575,7 @@ class SphereSliceOp(_SphereResample):
         p = self.pad_
         n, h, w = tn // self.npart_, (hp - 2 * p) * self.npart_, wp - 2 * p
         out = self._out(1, (n, c, h, w), grad)
-        if _ordered_backward:
+        if ordered_backward.on:
             wd, rs, rc, rw = self._reverse_tables("pconv_host_slice_taps", 0, h, w, grad)
             _backward_call("pconv_sphere_slice_backward_ordered", _ptr(grad), _ptr(out), _ptr(wd), _ptr(rs), _ptr(rc),
                            _ptr(rw), n, c, h, w, self.npart_, p, _stream(grad.device))
@@ -671,7 +629,7 @@ class SphereUsliceOp(_SphereResample):
         p = self.pad_
         h = hh // self.npart_
         out = self._out(1, (n * self.npart_, c, h + 2 * p, w + 2 * p), grad)
-        if _ordered_backward:
+        if ordered_backward.on:
             wd, rs, rc, rw = self._reverse_tables("pconv_host_uslice_taps", 1, hh, w, grad)
             _backward_call("pconv_sphere_uslice_backward_ordered", _ptr(grad), _ptr(out), _ptr(wd), _ptr(rs), _ptr(rc),
                            _ptr(rw), n, c, h, w, self.npart_, p, _stream(grad.device))
@@ -877,7 +835,7 @@ class PseudoQuantOp(_Op):
         g_in = self._out("g_in", x.shape, x)
         g_w = self._out("g_w", (c, self.bin_num_), x)
         bins = self._out("bins", (c, self.bin_num_), x)
-        if _ordered_backward:
+        if ordered_backward.on:
             nbytes = call("pconv_quant_backward_ordered_workspace_bytes", tn, c, self.bin_num_)
             ws = self._top.get("partials")
             if ws is None or ws.numel() != nbytes or ws.device != x.device:
@@ -976,7 +934,7 @@ class ProjectsOp(_Op):
         n, c, h, w = self._fwd_shape
         gin = self._out(1, (n, c, h, w), grad)
         cnt = self._out(2, (n, c, h, w), grad)
-        if _ordered_backward:
+        if ordered_backward.on:
             rs, rc, rw = self._reverse_tables(h, w, grad)
             _backward_call("pconv_project_backward_ordered", _ptr(grad), _ptr(rs), _ptr(rc), _ptr(rw), _ptr(gin), _ptr(cnt),
                            n, c, h, w, self.nview_, self.h_out_, self.w_out_, _stream(grad.device))
@@ -1292,26 +1250,41 @@ CONV_KERNELS = {
 }
 
 
-def _packed_weight(owner, weight, kind, stream):
-    """a conv weight in the layout of CONV_KERNELS[kind] (direct: the [k][cout] fp32 slab), cached on `owner`
-    until the parameter is modified (in place, by load_state_dict, or -- for writes
-    through `.data` -- after backend.invalidate_derived())."""
+def _cached_pack(owner, slot, weight, make, *args):
+    """make(weight, *args): a pack of `weight`, kept in attribute `slot` of `owner` until the parameter is modified
+    (in place -- an optimiser step bumps weight._version --, by load_state_dict, or -- for writes through `.data` --
+    after backend.invalidate_derived()).  Every packed weight of the module goes through here."""
     from .PCONV_operator import backend
-    kernel = CONV_KERNELS[kind]
     key = (weight.data_ptr(), weight._version, weight.device, backend.param_epoch())
-    cached = getattr(owner, kernel.slot, None)
+    cached = getattr(owner, slot, None)
     if cached is not None and cached[0] == key:
         return cached[1]
-    cout, cin, k = weight.shape[:3]
-    size_fn = getattr(_native.hip_lib(), kernel.packed_size)
-    if kind == "direct":   # 1x1 or 3x3; the size call could also report the padded extents
-        dims, size = (cout, cin, k), size_fn(cout, cin, k, None, None)
-    else:                  # the Winograd packers are 3x3 by construction
-        dims, size = (cout, cin), size_fn(cout, cin)
-    packed = torch.empty(int(size), dtype=torch.float32, device=weight.device)
-    call(kernel.pack_weight, _ptr(weight.detach().contiguous()), _ptr(packed), *dims + (stream,))
-    setattr(owner, kernel.slot, (key, packed))
+    packed = make(weight, *args)
+    setattr(owner, slot, (key, packed))
     return packed
+
+
+def _pack(weight, packed_size, size_dims, pack_weight, dims, stream):
+    """a new buffer of packed_size(*size_dims) floats, filled by pack_weight(weight, buffer, *dims, stream)"""
+    size = getattr(_native.hip_lib(), packed_size)(*size_dims)
+    if size < 0:
+        raise PconvError("%s: weight %s is too large to pack" % (pack_weight, tuple(weight.shape)))
+    packed = torch.empty(int(size), dtype=torch.float32, device=weight.device)
+    call(pack_weight, _ptr(weight.detach().contiguous()), _ptr(packed), *dims + (stream,))
+    return packed
+
+
+def _pack_forward(weight, kind, stream):
+    kernel = CONV_KERNELS[kind]
+    cout, cin, k = weight.shape[:3]
+    if kind == "direct":   # 1x1 or 3x3; the size call could also report the padded extents
+        return _pack(weight, kernel.packed_size, (cout, cin, k, None, None), kernel.pack_weight, (cout, cin, k), stream)
+    return _pack(weight, kernel.packed_size, (cout, cin), kernel.pack_weight, (cout, cin), stream)   # Winograd: 3x3 by construction
+
+
+def _packed_weight(owner, weight, kind, stream):
+    """a conv weight in the layout of CONV_KERNELS[kind] (direct: the [k][cout] fp32 slab), cached on `owner`"""
+    return _cached_pack(owner, CONV_KERNELS[kind].slot, weight, _pack_forward, kind, stream)
 
 
 def packed_conv_weight(owner, weight, stream):
@@ -1956,96 +1929,8 @@ def tile_conv2d(owner, x, weight, bias, stride, slope=None, col_limit=None, npar
     return out
 
 
-def _packed_weight_transposed(owner, weight, stream):
-    """the flipped, transposed weights of the data gradient in pconv_conv2d's slab layout, cached on `owner` under
-    _packed_weight's key: an in-place optimiser step (weight._version) makes it stale"""
-    from .PCONV_operator import backend
-    key = (weight.data_ptr(), weight._version, weight.device, backend.param_epoch())
-    cached = getattr(owner, "_pconv_packed_t", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    cout, cin, k = weight.shape[:3]
-    size = _native.hip_lib().pconv_conv_packed_size(cin, cout, k, None, None)
-    packed = torch.empty(int(size), dtype=torch.float32, device=weight.device)
-    call("pconv_conv_pack_weight_transposed", _ptr(weight.detach().contiguous()), _ptr(packed), cout, cin, k, stream)
-    setattr(owner, "_pconv_packed_t", (key, packed))
-    return packed
-
-
-def tile_conv2d_backward(x, weight, gout, stride, need=(True, True, True), owner=None):
-    """(gin, gw, gb) of y = conv2d(x, weight, bias, stride), no padding, from gout = dL/dy, in the orders
-    include/pconv_hip.h defines; a gradient `need` does not ask for is neither computed nor returned (None).
-    x (tn, cin, h, w), weight (cout, cin, k, k), gout (tn, cout, ho, wo): dense fp32 on the GPU.  owner: the object
-    that caches the transposed pack (default: the weight tensor itself)."""
-    need_x, need_w, need_b = (bool(n) for n in need)
-    # the entry points take raw addresses: every tensor is checked here, whether this call reads it or not
-    for name, t in (("x", x), ("weight", weight), ("gout", gout)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 4:
-            raise PconvError("tile_conv2d_backward: %s must be a 4-D tensor" % name)
-        _require_gpu(t.detach(), "tile_conv2d_backward: %s" % name)
-        if t.device != gout.device:
-            raise PconvError("tile_conv2d_backward: %s is on %s, gout on %s" % (name, t.device, gout.device))
-    tn, cout, ho, wo = gout.shape
-    cout_w, cin, k, k2 = weight.shape
-    stride = int(stride)
-    tn_x, cin_x, h, w = x.shape
-    if (tn_x, cin_x, cout_w, k2) != (tn, cin, cout, k) or k not in (1, 3) or stride not in (1, 2) or \
-            ((h - k) // stride + 1, (w - k) // stride + 1) != (ho, wo):
-        raise PconvError("tile_conv2d_backward: x %s, weight %s, gout %s, stride %d do not fit"
-                         % (tuple(x.shape), tuple(weight.shape), tuple(gout.shape), stride))
-    stream = _stream(gout.device)
-    lib = _native.hip_lib()
-
-    def workspace(nbytes):
-        if nbytes < 0:
-            raise PconvError("tile_conv2d_backward: workspace query failed: %s" % (lib.pconv_last_error() or b"").decode())
-        return torch.empty(int(nbytes), dtype=torch.uint8, device=gout.device) if nbytes else None
-
-    gin = gw = gb = None
-    if need_x:
-        packed = _packed_weight_transposed(weight if owner is None else owner, weight, stream)
-        gin = torch.empty((tn, cin, h, w), dtype=torch.float32, device=gout.device)
-        ws = workspace(lib.pconv_conv2d_dgrad_workspace_bytes(tn, cout, h, w, k, stride))
-        call("pconv_conv2d_dgrad", _ptr(gout), _ptr(packed), _ptr(gin), _ptr(ws), tn, cin, h, w, cout, k, stride, stream)
-    if need_w or need_b:
-        if need_w:
-            gw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=gout.device)
-        if need_b:
-            gb = torch.empty((cout,), dtype=torch.float32, device=gout.device)
-        # (a bias-only call needs the fp64 planes alone, not the partials in front of them)
-        ws = workspace(lib.pconv_conv2d_wgrad_workspace_bytes(tn, cin, cout, k) if need_w else tn * cout * 8)
-        call("pconv_conv2d_wgrad", _ptr(x) if need_w else None, _ptr(gout), _ptr(gw), _ptr(gb), _ptr(ws), tn, cin, h, w,
-             cout, k, stride, stream)
-    return gin, gw, gb
-
-
-# ---- the masked 5x5 convolutions of the entropy model under training (native_masked_conv) ------------------------
-
-def _packed_weight5(owner, weight, stream, transposed):
-    """a (cout, cin, 5, 5) weight in pconv_conv5's slab layout, or flipped and transposed for its data gradient:
-    cached on `owner` in slots of their own under _packed_weight's key.  The causal mask is written through
-    weight.data (no version bump) -- but always to the same values at the same places, and _MaskConv.forward writes
-    it before it comes here, so a pack made under a key is the pack of the masked weight under that key."""
-    from .PCONV_operator import backend
-    slot = "_pconv_packed5_t" if transposed else "_pconv_packed5"
-    key = (weight.data_ptr(), weight._version, weight.device, backend.param_epoch())
-    cached = getattr(owner, slot, None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    cout, cin = weight.shape[:2]
-    size = _native.hip_lib().pconv_conv5_packed_size(*((cin, cout) if transposed else (cout, cin)) + (None, None))
-    if size < 0:
-        raise PconvError("conv5x5: weight %s is too large to pack" % (tuple(weight.shape),))
-    packed = torch.empty(int(size), dtype=torch.float32, device=weight.device)
-    call("pconv_conv5_pack_weight_transposed" if transposed else "pconv_conv5_pack_weight",
-         _ptr(weight.detach().contiguous()), _ptr(packed), cout, cin, stream)
-    setattr(owner, slot, (key, packed))
-    return packed
-
-
-def _conv5_tensors(where, tensors):
-    """every tensor of a conv5x5 call is checked, whether the call reads it or not: the entry points take raw
-    addresses"""
+def _conv_tensors(where, tensors):
+    """every tensor of a call is checked, whether the call reads it or not: the entry points take raw addresses"""
     first = tensors[0][1]
     for name, t, dims in tensors:
         if not isinstance(t, torch.Tensor) or t.dim() != dims:
@@ -2055,19 +1940,100 @@ def _conv5_tensors(where, tensors):
             raise PconvError("%s: %s is on %s, %s on %s" % (where, name, t.device, tensors[0][0], first.device))
 
 
+# The two families of convolutions with a native backward: the kernel sizes and strides their entry points accept,
+# whether those entry points take (k, stride) as arguments (those of one size and one stride do not), the slot of the
+# transposed pack on its owner, and the entry points.
+ConvFamily = collections.namedtuple(
+    "ConvFamily", "ksizes strides sized slot_t packed_size pack_weight_transposed dgrad_workspace dgrad wgrad_workspace wgrad")
+_TILE_CONV = ConvFamily((1, 3), (1, 2), True, "_pconv_packed_t", "pconv_conv_packed_size", "pconv_conv_pack_weight_transposed",
+                        "pconv_conv2d_dgrad_workspace_bytes", "pconv_conv2d_dgrad", "pconv_conv2d_wgrad_workspace_bytes",
+                        "pconv_conv2d_wgrad")
+_CONV5 = ConvFamily((5,), (1,), False, "_pconv_packed5_t", "pconv_conv5_packed_size", "pconv_conv5_pack_weight_transposed",
+                    "pconv_conv5_dgrad_workspace_bytes", "pconv_conv5_dgrad", "pconv_conv5_wgrad_workspace_bytes",
+                    "pconv_conv5_wgrad")
+
+
+def _pack_transposed(weight, family, stream):
+    """the flipped, transposed weights of the data gradient in the slab layout of the family's forward (the
+    transposed layer has cin output and cout input channels)"""
+    cout, cin, k = weight.shape[:3]
+    ks = (k,) if family.sized else ()
+    return _pack(weight, family.packed_size, (cin, cout) + ks + (None, None), family.pack_weight_transposed, (cout, cin) + ks,
+                 stream)
+
+
+def _conv_backward(where, family, x, weight, gout, stride, need, owner):
+    """(gin, gw, gb) of y = conv2d(x, weight, bias, stride), no padding, for a convolution of `family`, from
+    gout = dL/dy; a gradient `need` does not ask for is neither computed nor returned (None)"""
+    need_x, need_w, need_b = (bool(n) for n in need)
+    _conv_tensors(where, [("gout", gout, 4), ("x", x, 4), ("weight", weight, 4)])
+    tn, cout, ho, wo = gout.shape
+    cout_w, cin, k, k2 = weight.shape
+    stride = int(stride)
+    tn_x, cin_x, h, w = x.shape
+    if (tn_x, cin_x, cout_w, k2) != (tn, cin, cout, k) or k not in family.ksizes or stride not in family.strides or \
+            ((h - k) // stride + 1, (w - k) // stride + 1) != (ho, wo) or ho < 1 or wo < 1:
+        raise PconvError("%s: x %s, weight %s, gout %s, stride %d do not fit"
+                         % (where, tuple(x.shape), tuple(weight.shape), tuple(gout.shape), stride))
+    stream = _stream(gout.device)
+    lib = _native.hip_lib()
+    ks, kst = ((k,), (k, stride)) if family.sized else ((), ())
+
+    def workspace(nbytes):
+        if nbytes < 0:
+            raise PconvError("%s: workspace query failed: %s" % (where, (lib.pconv_last_error() or b"").decode()))
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=gout.device) if nbytes else None
+
+    gin = gw = gb = None
+    if need_x:
+        packed = _cached_pack(weight if owner is None else owner, family.slot_t, weight, _pack_transposed, family, stream)
+        gin = torch.empty((tn, cin, h, w), dtype=torch.float32, device=gout.device)
+        ws = workspace(getattr(lib, family.dgrad_workspace)(tn, cout, h, w, *kst))
+        call(family.dgrad, _ptr(gout), _ptr(packed), _ptr(gin), _ptr(ws), tn, cin, h, w, cout, *kst + (stream,))
+    if need_w or need_b:
+        if need_w:
+            gw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=gout.device)
+        if need_b:
+            gb = torch.empty((cout,), dtype=torch.float32, device=gout.device)
+        # (a bias-only call needs the fp64 planes alone, not the partials in front of them)
+        ws = workspace(getattr(lib, family.wgrad_workspace)(tn, cin, cout, *ks) if need_w else tn * cout * 8)
+        call(family.wgrad, _ptr(x) if need_w else None, _ptr(gout), _ptr(gw), _ptr(gb), _ptr(ws), tn, cin, h, w, cout,
+             *kst + (stream,))
+    return gin, gw, gb
+
+
+def tile_conv2d_backward(x, weight, gout, stride, need=(True, True, True), owner=None):
+    """(gin, gw, gb) of y = conv2d(x, weight, bias, stride), no padding, from gout = dL/dy, in the orders
+    include/pconv_hip.h defines; a gradient `need` does not ask for is neither computed nor returned (None).
+    x (tn, cin, h, w), weight (cout, cin, k, k), gout (tn, cout, ho, wo): dense fp32 on the GPU.  owner: the object
+    that caches the transposed pack (default: the weight tensor itself)."""
+    return _conv_backward("tile_conv2d_backward", _TILE_CONV, x, weight, gout, stride, need, owner)
+
+
+# ---- the masked 5x5 convolutions of the entropy model under training (native_masked_conv) ------------------------
+
+def _pack5(weight, stream):
+    """a (cout, cin, 5, 5) weight in pconv_conv5's slab layout.  The causal mask is written through weight.data (no
+    version bump) -- but always to the same values at the same places, and _MaskConv.forward writes it before it
+    comes here, so a pack made under a key of _cached_pack is the pack of the masked weight under that key (its
+    transposed pack likewise)."""
+    cout, cin = weight.shape[:2]
+    return _pack(weight, "pconv_conv5_packed_size", (cout, cin, None, None), "pconv_conv5_pack_weight", (cout, cin), stream)
+
+
 def conv5x5(owner, x, weight, bias):
     """y = conv2d(x, weight, bias) for a 5x5 weight, stride 1, no padding, on the fp32 matrix cores: x (tn, cin, h, w)
     -> (tn, cout, h - 4, w - 4), every output one fmaf chain over (ci, kh, kw) ascending, then + bias
     (include/pconv_hip.h).  The weight is taken as it is -- the caller has masked it.  owner: the object the pack is
     cached on."""
-    _conv5_tensors("conv5x5", [("x", x, 4), ("weight", weight, 4)] + ([("bias", bias, 1)] if bias is not None else []))
+    _conv_tensors("conv5x5", [("x", x, 4), ("weight", weight, 4)] + ([("bias", bias, 1)] if bias is not None else []))
     tn, cin, h, w = x.shape
     cout, cin_w, k, k2 = weight.shape
     if cin != cin_w or (k, k2) != (5, 5) or h < 5 or w < 5 or (bias is not None and bias.shape[0] != cout):
         raise PconvError("conv5x5: weight %s does not fit input %s" % (tuple(weight.shape), tuple(x.shape)))
     stream = _stream(x.device)
     out = torch.empty((tn, cout, h - 4, w - 4), dtype=torch.float32, device=x.device)
-    call("pconv_conv5", _ptr(x), _ptr(_packed_weight5(owner, weight, stream, False)),
+    call("pconv_conv5", _ptr(x), _ptr(_cached_pack(owner, "_pconv_packed5", weight, _pack5, stream)),
          _ptr(bias.detach()) if bias is not None else None, _ptr(out), tn, cin, h, w, cout, stream)
     return out
 
@@ -2077,35 +2043,4 @@ def conv5x5_backward(x, weight, gout, need=(True, True, True), owner=None):
     gradient `need` does not ask for is neither computed nor returned (None).  gw is the dense gradient, masked taps
     included (what the vendor path returns too: the weights are masked again at every forward).  owner: the object
     that caches the transposed pack (default: the weight tensor itself)."""
-    need_x, need_w, need_b = (bool(n) for n in need)
-    _conv5_tensors("conv5x5_backward", [("gout", gout, 4), ("x", x, 4), ("weight", weight, 4)])
-    tn, cout, ho, wo = gout.shape
-    cout_w, cin, k, k2 = weight.shape
-    tn_x, cin_x, h, w = x.shape
-    if (tn_x, cin_x, cout_w, k, k2) != (tn, cin, cout, 5, 5) or (h - 4, w - 4) != (ho, wo) or ho < 1 or wo < 1:
-        raise PconvError("conv5x5_backward: x %s, weight %s, gout %s do not fit"
-                         % (tuple(x.shape), tuple(weight.shape), tuple(gout.shape)))
-    stream = _stream(gout.device)
-    lib = _native.hip_lib()
-
-    def workspace(nbytes):
-        if nbytes < 0:
-            raise PconvError("conv5x5_backward: workspace query failed: %s" % (lib.pconv_last_error() or b"").decode())
-        return torch.empty(int(nbytes), dtype=torch.uint8, device=gout.device)
-
-    gin = gw = gb = None
-    if need_x:
-        packed = _packed_weight5(weight if owner is None else owner, weight, stream, True)
-        gin = torch.empty((tn, cin, h, w), dtype=torch.float32, device=gout.device)
-        ws = workspace(lib.pconv_conv5_dgrad_workspace_bytes(tn, cout, h, w))
-        call("pconv_conv5_dgrad", _ptr(gout), _ptr(packed), _ptr(gin), _ptr(ws), tn, cin, h, w, cout, stream)
-    if need_w or need_b:
-        if need_w:
-            gw = torch.empty((cout, cin, 5, 5), dtype=torch.float32, device=gout.device)
-        if need_b:
-            gb = torch.empty((cout,), dtype=torch.float32, device=gout.device)
-        # (a bias-only call needs the fp64 planes alone, not the partials in front of them)
-        ws = workspace(lib.pconv_conv5_wgrad_workspace_bytes(tn, cin, cout) if need_w else tn * cout * 8)
-        call("pconv_conv5_wgrad", _ptr(x) if need_w else None, _ptr(gout), _ptr(gw), _ptr(gb), _ptr(ws), tn, cin, h, w,
-             cout, stream)
-    return gin, gw, gb
+    return _conv_backward("conv5x5_backward", _CONV5, x, weight, gout, 1, need, owner)

@@ -41,6 +41,7 @@ constexpr int kTileCols = 64;
 #ifndef PCONV_KC1
 #define PCONV_KC1 16  // input channels per LDS stage of the 1x1 layers
 #endif
+constexpr int kKC5 = 2;  // ... of the 5x5 layers (see pconv_conv5); the 3x3 layers stage 4
 // quads requested ahead of their turn in conv_epilogue_quads (4 registers each; 8 for the GDN with a residual).
 // Measured 2 / 4 / 6 / 8 ahead (profiles/round4_quad_ahead.txt): level within 2 %, two is never behind.
 #ifndef PCONV_QUAD_AHEAD
@@ -1398,29 +1399,51 @@ int launch_conv(const float *in, const float *wp, float *out, int tn, int cin, i
   return PCONV_OK;
 }
 
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+// the workgroup tiles of a (KS, S) without a kernel of its own (measured on MI355X, 192->192 3x3 at 16 x 64 x 2048:
+// 127 TFLOP/s):
+//   cout > 96 : 192 couts x (2 rows x 64 px), 8 waves of 96 x 32: 135.8 TFLOP/s (4 waves of 96 x 64 px
+//               = 3 x 2 accumulator tiles each: 128.3; 6 such waves on 3 rows x 64 px: 97)
+//   cout > 32 :  96 couts x (4 rows x 64 px), 8 waves of 96 x 32
+//   else      :  32 couts x (2 rows x 64 px), 4 waves of 32 x 32
+// args: launch_conv's, from `in` on
+template <int KS, int S, int KC, class... Args>
+int launch_by_tile(int cout, const Args &...args) {
+  if (cout > 96) return launch_conv<3, 1, 2, 4, KS, S, KC>(args...);
+  if (cout > 32) return launch_conv<3, 1, 1, 8, KS, S, KC>(args...);
+  return launch_conv<1, 1, 1, 4, KS, S, KC>(args...);
+}
+
+// the packer of both families, for a (k, shape) the entry point `what` has accepted
+int run_pack(const char *what, const float *w, float *packed, int cout, int cin, int k, void *stream) {
+  PCONV_REQUIRE(w && packed, "%s: null pointer", what);
+  int cp, rp;
+  const long long total = pconv_conv_packed_floats(cout, cin, k, &cp, &rp);
+  PCONV_REQUIRE(total <= 0x7fffffffLL, "%s: weight exceeds int32", what);
+  hipLaunchKernelGGL(pack_weight_kernel, dim3(((int)total + 255) / 256), dim3(256), 0, as_stream(stream), w, packed, cout,
+                     cin * k * k, cp, rp);
+  PCONV_LAUNCH_CHECK(what);
+  return PCONV_OK;
+}
 
 }  // namespace
 
-extern "C" int pconv_conv_packed_size(int cout, int cin, int k, int *cout_pad, int *red_pad) {
-  // cout padded to the widest workgroup tile, reduction to whole chunks
-  const int cp = round_up(cout, cout > 96 ? 192 : (cout > 32 ? 96 : 32));
-  const int kc = (k == 1) ? PCONV_KC1 : 4;
-  const int rp = round_up(cin, kc) * k * k;
-  if (cout_pad) *cout_pad = cp;
-  if (red_pad) *red_pad = rp;
+long long pconv_conv_packed_floats(int cout, int cin, int k, int *cout_pad, int *red_pad) {
+  const int tile = cout > 96 ? 192 : (cout > 32 ? 96 : 32);   // the widest workgroup tile the layer is given
+  const int kc = k == 1 ? PCONV_KC1 : (k == 5 ? kKC5 : 4);    // input channels per LDS stage
+  const long long cp = ((long long)cout + tile - 1) / tile * tile, rp = ((long long)cin + kc - 1) / kc * kc * k * k;
+  if (cout_pad) *cout_pad = (int)cp;
+  if (red_pad) *red_pad = (int)rp;
   return cp * rp;
+}
+
+extern "C" int pconv_conv_packed_size(int cout, int cin, int k, int *cout_pad, int *red_pad) {
+  return (int)pconv_conv_packed_floats(cout, cin, k, cout_pad, red_pad);
 }
 
 extern "C" int pconv_conv_pack_weight(const float *w, float *packed, int cout, int cin, int k,
                                       void *stream) {
-  PCONV_REQUIRE(w && packed && cout > 0 && cin > 0 && (k == 1 || k == 3), "conv_pack: bad argument");
-  int cp, rp;
-  const int total = pconv_conv_packed_size(cout, cin, k, &cp, &rp);
-  hipLaunchKernelGGL(pack_weight_kernel, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream),
-                     w, packed, cout, cin * k * k, cp, rp);
-  PCONV_LAUNCH_CHECK("conv_pack_weight");
-  return PCONV_OK;
+  PCONV_REQUIRE(cout > 0 && cin > 0 && (k == 1 || k == 3), "conv_pack_weight: bad argument");
+  return run_pack("conv_pack_weight", w, packed, cout, cin, k, stream);
 }
 
 extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float *bias, float *out,
@@ -1460,22 +1483,11 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
                 "conv2d: output / residual channel stride too large for 32-bit byte offsets inside a round");
   int rc;
 #define ARGS in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, opt, s
-  // workgroup tiles (measured on MI355X, 192->192 3x3 at 16 x 64 x 2048: 127 TFLOP/s):
-  //   cout > 96 : 192 couts x (2 rows x 64 px), 8 waves of 96 x 32: 135.8 TFLOP/s (4 waves of 96 x 64 px
-  //               = 3 x 2 accumulator tiles each: 128.3; 6 such waves on 3 rows x 64 px: 97)
-  //   cout > 32 :  96 couts x (4 rows x 64 px), 8 waves of 96 x 32
-  //   else      :  32 couts x (2 rows x 64 px), 4 waves of 32 x 32
-#define BY_TILE(KS, S, KC)                                         \
-  if (cout > 96)                                                   \
-    rc = launch_conv<3, 1, 2, 4, KS, S, KC>(ARGS);                 \
-  else if (cout > 32)                                              \
-    rc = launch_conv<3, 1, 1, 8, KS, S, KC>(ARGS);                 \
-  else                                                             \
-    rc = launch_conv<1, 1, 1, 4, KS, S, KC>(ARGS);
+  // (launch_by_tile: the workgroup tile by cout alone)
   if (k == 3 && stride == 1 && cout <= 16 && !residual && !gate && act != 4 && (!d2w || cout % 4 == 0) && use_small_cout(opt)) {
     rc = launch_conv_small(in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, s);
   } else if (k == 3 && stride == 1) {
-    BY_TILE(3, 1, 4)
+    rc = launch_by_tile<3, 1, 4>(cout, ARGS);
   } else if (k == 3 && stride == 2 && cout > 32 && !gate && !d2w && act != 4 && quad_way_out(opt)) {
     // (the stride-2 3x3 layers of the Down blocks: the same workgroup tiles, the same quad way out)
     if (cout > 96)
@@ -1483,7 +1495,7 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
     else
       rc = residual ? launch_conv<3, 1, 1, 8, 3, 2, 4, false, 4>(ARGS) : launch_conv<3, 1, 1, 8, 3, 2, 4, false, 3>(ARGS);
   } else if (k == 3 && stride == 2) {
-    BY_TILE(3, 2, 4)
+    rc = launch_by_tile<3, 2, 4>(cout, ARGS);
   } else if (k == 1 && stride == 1 && !gate && !d2w && act != 4 && use_resident_1x1(opt, cin, cout, tn, h, w)) {
     if (cout > 96 && residual)
       rc = launch_conv1x1<2, false, true>(in, packed_w, out, tn, cin, h, w, cout, cp, vin, vout, ep, opt, s);
@@ -1513,7 +1525,7 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
     else
       rc = launch_conv<1, 1, 1, 4, 1, 1, PCONV_KC1, false, 2>(ARGS);
   } else if (k == 1 && stride == 1) {
-    BY_TILE(1, 1, PCONV_KC1)
+    rc = launch_by_tile<1, 1, PCONV_KC1>(cout, ARGS);
   } else if (cout > 32 && !gate && !d2w && act != 4 && quad_way_out(opt)) {
     // (1x1 stride 2, the shortcuts of the Down blocks: same tiles, same quad way out)
     if (cout > 96)
@@ -1521,9 +1533,8 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
     else
       rc = residual ? launch_conv<3, 1, 1, 8, 1, 2, PCONV_KC1, false, 4>(ARGS) : launch_conv<3, 1, 1, 8, 1, 2, PCONV_KC1, false, 3>(ARGS);
   } else {
-    BY_TILE(1, 2, PCONV_KC1)
+    rc = launch_by_tile<1, 2, PCONV_KC1>(cout, ARGS);
   }
-#undef BY_TILE
 #undef ARGS
   if (rc != PCONV_OK) return rc;
   PCONV_LAUNCH_CHECK("conv2d");
@@ -1537,28 +1548,18 @@ extern "C" int pconv_conv2d(const float *in, const float *packed_w, const float 
 // layers, 144 couts; not tuned).  The pair (2 kp, 2 kp + 1) of the odd 25-tap window steps to the next column,
 // the next row or the next channel: the three deltas ConvCfg already keeps one LDS base register for.  The weight is
 // taken as it is: a tap the causal mask zeroed is a step fmaf(x, +0, acc) of the chain like any other.
-constexpr int kKC5 = 2;
+constexpr int kK5 = 5;
 
 extern "C" int pconv_conv5_packed_size(int cout, int cin, int *cout_pad, int *red_pad) {
-  // cout padded to the widest workgroup tile, reduction to whole chunks, as pconv_conv_packed_size
-  const int tile = cout > 96 ? 192 : (cout > 32 ? 96 : 32);
-  const long long cp = ((long long)cout + tile - 1) / tile * tile;
-  const long long rp = ((long long)cin + kKC5 - 1) / kKC5 * kKC5 * 25;
-  PCONV_REQUIRE(cout > 0 && cin > 0 && cp * rp <= 0x7fffffffLL, "conv5_packed_size: bad shape or weight exceeds int32");
-  if (cout_pad) *cout_pad = (int)cp;
-  if (red_pad) *red_pad = (int)rp;
-  return (int)(cp * rp);
+  PCONV_REQUIRE(cout > 0 && cin > 0, "conv5_packed_size: bad shape");
+  const long long total = pconv_conv_packed_floats(cout, cin, kK5, cout_pad, red_pad);
+  PCONV_REQUIRE(total <= 0x7fffffffLL, "conv5_packed_size: weight exceeds int32");
+  return (int)total;
 }
 
 extern "C" int pconv_conv5_pack_weight(const float *w, float *packed, int cout, int cin, void *stream) {
-  PCONV_REQUIRE(w && packed, "conv5_pack_weight: null pointer");
-  int cp, rp;
-  const int total = pconv_conv5_packed_size(cout, cin, &cp, &rp);
-  if (total < 0) return total;
-  hipLaunchKernelGGL(pack_weight_kernel, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream), w, packed, cout,
-                     cin * 25, cp, rp);
-  PCONV_LAUNCH_CHECK("conv5_pack_weight");
-  return PCONV_OK;
+  PCONV_REQUIRE(cout > 0 && cin > 0, "conv5_pack_weight: bad shape");
+  return run_pack("conv5_pack_weight", w, packed, cout, cin, kK5, stream);
 }
 
 extern "C" int pconv_conv5(const float *in, const float *packed_w, const float *bias, float *out, int tn, int cin, int h,
@@ -1579,15 +1580,9 @@ extern "C" int pconv_conv5(const float *in, const float *packed_w, const float *
   const ConvEpilogue ep = {bias, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, vout, vout, 0};
   const ConvOptions opt = ConvOptions::from_env();  // (PCONV_CONV_XCD is a 3x3 option: nothing here depends on it)
   hipStream_t s = as_stream(stream);
-  int rc;
-  // the workgroup tiles of pconv_conv2d: 192 couts x 2 rows, 96 couts x 4 rows, 32 couts x 2 rows of 64 columns
-  if (cout > 96)
-    rc = launch_conv<3, 1, 2, 4, 5, 1, kKC5>(in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, opt, s);
-  else if (cout > 32)
-    rc = launch_conv<3, 1, 1, 8, 5, 1, kKC5>(in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, opt, s);
-  else
-    rc = launch_conv<1, 1, 1, 4, 5, 1, kKC5>(in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, opt, s);
-  if (rc != PCONV_OK) return rc;
+  // (the workgroup tiles of pconv_conv2d)
+  if (int rc = launch_by_tile<kK5, 1, kKC5>(cout, in, packed_w, out, tn, cin, h, w, cout, cp, ho, wo, vin, vout, ep, opt, s))
+    return rc;
   PCONV_LAUNCH_CHECK("conv5");
   return PCONV_OK;
 }

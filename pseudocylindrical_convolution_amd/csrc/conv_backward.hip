@@ -1,14 +1,15 @@
 // Backward of the dense per-tile convolution (conv.hip) in a defined order: the data gradient, the weight
-// gradient and the bias gradient of pconv_conv2d's layers (k in {1, 3}, stride in {1, 2}, no padding, dense
-// NCHW fp32).  No atomics, no allocation and no memset: what a call needs comes from the caller as a workspace.
-// The orders are part of the contract (include/pconv_hip.h) and the CPU twin of the tests restates them.  The masked
-// 5x5 stride-1 convolutions of the entropy model take the same orders at k = 5 through entry points of their own
-// (pconv_conv5_*, at the end of the file).
+// gradient and the bias gradient of pconv_conv2d's layers (k in {1, 3}, stride in {1, 2}) and of pconv_conv5's (the
+// masked 5x5 stride-1 convolutions of the entropy model); no padding, dense NCHW fp32.  No atomics, no allocation and
+// no memset: what a call needs comes from the caller as a workspace.  The orders are part of the contract
+// (include/pconv_hip.h) and the CPU twin of the tests restates them.  The two families have entry points of their own
+// (pconv_conv2d_* / pconv_conv_*, pconv_conv5_*): each checks the (k, stride) it accepts and calls the one host
+// routine of its step (run_*), which takes k and stride as arguments.
 //
-//   data gradient    = pconv_conv2d, stride 1, of the PREPARED output gradient (zero-stuffed to the stride, padded
-//                      by k - 1) with the flipped, transposed weights.  New here: the transposed pack and the
-//                      prepare kernel; the convolution itself is conv.hip's, so every gin element is one fmaf chain
-//                      from +0 over (co, kh', kw') ascending.
+//   data gradient    = the forward convolution, stride 1, of the PREPARED output gradient (zero-stuffed to the
+//                      stride, padded by k - 1) with the flipped, transposed weights.  New here: the transposed pack
+//                      and the prepare kernel; the convolution itself is conv.hip's (pconv_conv2d, at k = 5
+//                      pconv_conv5), so every gin element is one fmaf chain from +0 over (co, kh', kw') ascending.
 //   weight gradient  = per tile t a GEMM over the tile's pixels on v_mfma_f32_32x32x2_f32:
 //                        P_t[co][n] = sum_p gout[t][co][p] * in[t][ci][s y + kh][s x + kw],  n = (ci*k + kh)*k + kw
 //                      M = couts (A operand), N = the (ci, kh, kw) columns (B operand, gathered from an LDS patch of
@@ -21,7 +22,9 @@
 //                      of the chunk's matrix loop), and the chunks continue the chain in the same accumulators.  A
 //                      chunk of odd length ends with one step whose product is -0 (A = -0, B = +0):
 //                      fmaf(-0, +0, acc) = acc for EVERY acc, -0 and NaN included, so the pad is not part of the
-//                      arithmetic.  Then a second kernel adds the partials, t ascending.
+//                      arithmetic.  Then a second kernel adds the partials, t ascending.  At k = 5 the patch is 5 input
+//                      rows of 68 (+ 1: bank spread) columns for each of the <= 7 channels that 128 consecutive
+//                      (ci, kh, kw) columns of 25 taps touch, 35 KB per stage.
 //   bias gradient    = the fixed-shape two-stage fp64 reduction of quant_backward_ordered_kernel.
 #include "conv_host.h"
 
@@ -315,77 +318,79 @@ int launch_wgrad(const float *in, const float *gout, float *partial, int tn, int
   return PCONV_OK;
 }
 
-inline bool conv_shape_ok(int tn, int cin, int h, int w, int cout, int k, int stride) {
-  return tn > 0 && cin > 0 && cout > 0 && h >= k && w >= k && (k == 1 || k == 3) && (stride == 1 || stride == 2);
+// ---- host: one routine per step, for every (k, stride) -------------------------------------------------------------
+// An entry point (at the end of the file) checks the shape against the kernel sizes and strides IT accepts, then calls
+// the routine of its step with its own name `what` for the messages.  The routines make every other check -- pointers,
+// alignment, the int32 ranges -- so that a check exists once, for both families.
+
+constexpr int kK5 = 5;  // the kernel size of the pconv_conv5_* entries (their stride is 1)
+constexpr unsigned kSizes13 = (1u << 1) | (1u << 3), kSize5 = 1u << kK5;  // sets of kernel sizes: bit k
+
+// ksizes: the kernel sizes the caller accepts; stride in {1, 2} (the 5x5 entries pass their 1)
+inline bool conv_shape_ok(unsigned ksizes, int tn, int cin, int h, int w, int cout, int k, int stride) {
+  return tn > 0 && cin > 0 && cout > 0 && k > 0 && k < 32 && ((ksizes >> k) & 1) && h >= k && w >= k &&
+         (stride == 1 || stride == 2);
 }
 
 inline bool fits_int32(long long v) { return v >= 0 && v <= 0x7fffffffLL; }
 
 inline long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
 
-}  // namespace
-
-extern "C" int pconv_conv_pack_weight_transposed(const float *w, float *packed, int cout, int cin, int k, void *stream) {
-  PCONV_REQUIRE(w && packed, "conv_pack_weight_transposed: null pointer");
-  PCONV_REQUIRE(cout > 0 && cin > 0 && (k == 1 || k == 3), "conv_pack_weight_transposed: bad argument");
-  PCONV_REQUIRE(fits_int32((long long)cout * cin * k * k), "conv_pack_weight_transposed: weight too large");
+int run_pack_transposed(const char *what, const float *w, float *packed, int cout, int cin, int k, void *stream) {
+  PCONV_REQUIRE(w && packed, "%s: null pointer", what);
   int rowp, redp;  // the transposed layer has cin output and cout input channels
-  const int total = pconv_conv_packed_size(cin, cout, k, &rowp, &redp);
-  hipLaunchKernelGGL(pack_weight_transposed_kernel, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, as_stream(stream),
-                     w, packed, cout, cin, k, rowp, redp);
-  PCONV_LAUNCH_CHECK("conv_pack_weight_transposed");
+  const long long total = pconv_conv_packed_floats(cin, cout, k, &rowp, &redp);
+  PCONV_REQUIRE(fits_int32(total), "%s: weight exceeds int32", what);
+  hipLaunchKernelGGL(pack_weight_transposed_kernel, dim3(((int)total + kBlock - 1) / kBlock), dim3(kBlock), 0,
+                     as_stream(stream), w, packed, cout, cin, k, rowp, redp);
+  PCONV_LAUNCH_CHECK(what);
   return PCONV_OK;
 }
 
-extern "C" long long pconv_conv2d_dgrad_workspace_bytes(int tn, int cout, int h, int w, int k, int stride) {
-  PCONV_REQUIRE(conv_shape_ok(tn, 1, h, w, cout, k, stride), "conv2d_dgrad_workspace_bytes: bad shape");
+long long dgrad_workspace_bytes(int tn, int cout, int h, int w, int k, int stride) {
   if (k == 1 && stride == 1) return 0;  // the prepared gradient is gout itself
   return (long long)tn * cout * (h + k - 1) * (w + k - 1) * (long long)sizeof(float);
 }
 
-extern "C" int pconv_conv_grad_prepare(const float *gout, float *prepared, int tn, int cout, int h, int w, int k,
-                                       int stride, void *stream) {
-  PCONV_REQUIRE(gout && prepared, "conv_grad_prepare: null pointer");
-  PCONV_REQUIRE(conv_shape_ok(tn, 1, h, w, cout, k, stride), "conv_grad_prepare: unsupported k=%d stride=%d or bad shape", k,
-                stride);
-  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(prepared) & 15) == 0, "conv_grad_prepare: the buffer must be 16-byte aligned");
+int run_prepare(const char *what, const float *gout, float *prepared, int tn, int cout, int h, int w, int k, int stride,
+                void *stream) {
+  PCONV_REQUIRE(gout && prepared, "%s: null pointer", what);
+  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(prepared) & 15) == 0, "%s: the prepared gradient must be 16-byte aligned", what);
   const int ho = (h - k) / stride + 1, wo = (w - k) / stride + 1, hp = h + k - 1, wp = w + k - 1;
-  PCONV_REQUIRE(fits_int32((long long)hp * wp) && fits_int32((long long)tn * cout), "conv_grad_prepare: plane too large");
+  PCONV_REQUIRE(fits_int32((long long)hp * wp) && fits_int32((long long)tn * cout), "%s: plane exceeds int32", what);
   const long long total = (long long)tn * cout * hp * wp;
   hipLaunchKernelGGL(conv_grad_prepare_kernel, dim3(pconv_grid((total + 3) / 4, kBlock)), dim3(kBlock), 0, as_stream(stream),
                      gout, prepared, total, hp, wp, ho, wo, k, stride);
-  PCONV_LAUNCH_CHECK("conv_grad_prepare");
+  PCONV_LAUNCH_CHECK(what);
   return PCONV_OK;
 }
 
-extern "C" int pconv_conv2d_dgrad(const float *gout, const float *packed_wt, float *gin, void *workspace, int tn, int cin,
-                                  int h, int w, int cout, int k, int stride, void *stream) {
-  PCONV_REQUIRE(gout && packed_wt && gin, "conv2d_dgrad: null pointer");
-  PCONV_REQUIRE(conv_shape_ok(tn, cin, h, w, cout, k, stride), "conv2d_dgrad: unsupported k=%d stride=%d or bad shape", k,
-                stride);
+int run_dgrad(const char *what, const float *gout, const float *packed_wt, float *gin, void *workspace, int tn, int cin, int h,
+              int w, int cout, int k, int stride, void *stream) {
+  PCONV_REQUIRE(gout && packed_wt && gin, "%s: null pointer", what);
+  PCONV_REQUIRE(fits_int32((long long)tn * cin) && fits_int32((long long)cout * cin * k * k), "%s: shape exceeds int32", what);
   const float *prepared = gout;
   if (k != 1 || stride != 1) {
-    PCONV_REQUIRE(workspace, "conv2d_dgrad: null workspace");
-    if (int rc = pconv_conv_grad_prepare(gout, static_cast<float *>(workspace), tn, cout, h, w, k, stride, stream)) return rc;
+    PCONV_REQUIRE(workspace, "%s: null workspace", what);
+    if (int rc = run_prepare(what, gout, static_cast<float *>(workspace), tn, cout, h, w, k, stride, stream)) return rc;
     prepared = static_cast<const float *>(workspace);
   }
   // (tn, cout, h + k - 1, w + k - 1) * wT (cin, cout, k, k), stride 1 -> (tn, cin, h, w)
+  if (k == 5) return pconv_conv5(prepared, packed_wt, nullptr, gin, tn, cout, h + k - 1, w + k - 1, cin, stream);
   return pconv_conv2d(prepared, packed_wt, nullptr, gin, tn, cout, h + k - 1, w + k - 1, cin, k, 1, 0, nullptr, nullptr, 0,
                       nullptr, nullptr, 0, 0, nullptr, stream);
 }
 
-extern "C" long long pconv_conv2d_wgrad_workspace_bytes(int tn, int cin, int cout, int k) {
-  PCONV_REQUIRE(tn > 0 && cin > 0 && cout > 0 && (k == 1 || k == 3), "conv2d_wgrad_workspace_bytes: bad shape");
+long long wgrad_workspace_bytes(int tn, int cin, int cout, int k) {
   // the partials P_t (tn, cout, cin, k, k) fp32, then the bias planes (tn, cout) fp64
   return align_up((long long)tn * cout * cin * k * k * (long long)sizeof(float), 16) + (long long)tn * cout * (long long)sizeof(double);
 }
 
-namespace {
-
-// the weight and bias gradient of a (k, stride) the entry point `what` has accepted: checks that depend on the
-// sizes alone, then the launches
+// the weight and bias gradient: checks that depend on the sizes alone, then the launches
 int run_wgrad(const char *what, const float *in, const float *gout, float *gw, float *gb, void *workspace, int tn, int cin,
               int h, int w, int cout, int k, int stride, void *stream) {
+  PCONV_REQUIRE(gout && (gw || gb) && (in || !gw), "%s: null pointer", what);
+  PCONV_REQUIRE(workspace, "%s: null workspace", what);
   PCONV_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", what);
   const int ho = (h - k) / stride + 1, wo = (w - k) / stride + 1;
   const long long ncol = (long long)cin * k * k, nw = (long long)cout * ncol;
@@ -426,67 +431,71 @@ int run_wgrad(const char *what, const float *in, const float *gout, float *gw, f
 
 }  // namespace
 
+// ---- entry points: k in {1, 3}, stride in {1, 2} -------------------------------------------------------------------
+
+extern "C" int pconv_conv_pack_weight_transposed(const float *w, float *packed, int cout, int cin, int k, void *stream) {
+  PCONV_REQUIRE(cout > 0 && cin > 0 && (k == 1 || k == 3), "conv_pack_weight_transposed: bad argument");
+  return run_pack_transposed("conv_pack_weight_transposed", w, packed, cout, cin, k, stream);
+}
+
+extern "C" long long pconv_conv2d_dgrad_workspace_bytes(int tn, int cout, int h, int w, int k, int stride) {
+  PCONV_REQUIRE(conv_shape_ok(kSizes13, tn, 1, h, w, cout, k, stride), "conv2d_dgrad_workspace_bytes: bad shape");
+  return dgrad_workspace_bytes(tn, cout, h, w, k, stride);
+}
+
+extern "C" int pconv_conv_grad_prepare(const float *gout, float *prepared, int tn, int cout, int h, int w, int k,
+                                       int stride, void *stream) {
+  PCONV_REQUIRE(conv_shape_ok(kSizes13, tn, 1, h, w, cout, k, stride), "conv_grad_prepare: unsupported k=%d stride=%d or bad shape",
+                k, stride);
+  return run_prepare("conv_grad_prepare", gout, prepared, tn, cout, h, w, k, stride, stream);
+}
+
+extern "C" int pconv_conv2d_dgrad(const float *gout, const float *packed_wt, float *gin, void *workspace, int tn, int cin,
+                                  int h, int w, int cout, int k, int stride, void *stream) {
+  PCONV_REQUIRE(conv_shape_ok(kSizes13, tn, cin, h, w, cout, k, stride), "conv2d_dgrad: unsupported k=%d stride=%d or bad shape",
+                k, stride);
+  return run_dgrad("conv2d_dgrad", gout, packed_wt, gin, workspace, tn, cin, h, w, cout, k, stride, stream);
+}
+
+extern "C" long long pconv_conv2d_wgrad_workspace_bytes(int tn, int cin, int cout, int k) {
+  PCONV_REQUIRE(conv_shape_ok(kSizes13, tn, cin, k, k, cout, k, 1), "conv2d_wgrad_workspace_bytes: bad shape");
+  return wgrad_workspace_bytes(tn, cin, cout, k);
+}
+
 extern "C" int pconv_conv2d_wgrad(const float *in, const float *gout, float *gw, float *gb, void *workspace, int tn,
                                   int cin, int h, int w, int cout, int k, int stride, void *stream) {
-  PCONV_REQUIRE(gout && workspace && (gw || gb) && (in || !gw), "conv2d_wgrad: null pointer");
-  PCONV_REQUIRE(conv_shape_ok(tn, cin, h, w, cout, k, stride), "conv2d_wgrad: unsupported k=%d stride=%d or bad shape", k,
-                stride);
+  PCONV_REQUIRE(conv_shape_ok(kSizes13, tn, cin, h, w, cout, k, stride), "conv2d_wgrad: unsupported k=%d stride=%d or bad shape",
+                k, stride);
   return run_wgrad("conv2d_wgrad", in, gout, gw, gb, workspace, tn, cin, h, w, cout, k, stride, stream);
 }
 
-// ---- 5x5, stride 1 (the masked convolutions of the entropy model): the same orders at k = 5 -----------------------
-// data gradient: the prepared gradient is gout padded by 4 (no stuffing at stride 1), the convolution pconv_conv5 on
-// the transposed pack; weight gradient: conv_wgrad_kernel<5, 1> -- a patch of 5 input rows of 68 (+ 1: bank spread)
-// columns for each of the <= 7 channels that 128 consecutive (ci, kh, kw) columns of 25 taps touch, 35 KB per stage;
-// bias gradient: the kernels above.
+// ---- entry points: 5x5, stride 1 (the masked convolutions of the entropy model) ------------------------------------
 
 extern "C" int pconv_conv5_pack_weight_transposed(const float *w, float *packed, int cout, int cin, void *stream) {
-  PCONV_REQUIRE(w && packed, "conv5_pack_weight_transposed: null pointer");
-  int rowp, redp;  // the transposed layer has cin output and cout input channels
-  const int total = pconv_conv5_packed_size(cin, cout, &rowp, &redp);
-  if (total < 0) return total;
-  hipLaunchKernelGGL(pack_weight_transposed_kernel, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, as_stream(stream),
-                     w, packed, cout, cin, 5, rowp, redp);
-  PCONV_LAUNCH_CHECK("conv5_pack_weight_transposed");
-  return PCONV_OK;
+  PCONV_REQUIRE(cout > 0 && cin > 0, "conv5_pack_weight_transposed: bad shape");
+  return run_pack_transposed("conv5_pack_weight_transposed", w, packed, cout, cin, kK5, stream);
 }
 
 extern "C" long long pconv_conv5_dgrad_workspace_bytes(int tn, int cout, int h, int w) {
-  PCONV_REQUIRE(tn > 0 && cout > 0 && h >= 5 && w >= 5, "conv5_dgrad_workspace_bytes: bad shape");
-  return (long long)tn * cout * (h + 4) * (w + 4) * (long long)sizeof(float);
+  PCONV_REQUIRE(conv_shape_ok(kSize5, tn, 1, h, w, cout, kK5, 1), "conv5_dgrad_workspace_bytes: bad shape");
+  return dgrad_workspace_bytes(tn, cout, h, w, kK5, 1);
 }
 
 extern "C" int pconv_conv5_dgrad(const float *gout, const float *packed_wt, float *gin, void *workspace, int tn, int cin,
                                  int h, int w, int cout, void *stream) {
-  PCONV_REQUIRE(gout && packed_wt && gin, "conv5_dgrad: null pointer");
-  PCONV_REQUIRE(tn > 0 && cin > 0 && cout > 0 && h >= 5 && w >= 5, "conv5_dgrad: bad shape (%d, %d, %d, %d) -> %d: h and w >= 5",
+  PCONV_REQUIRE(conv_shape_ok(kSize5, tn, cin, h, w, cout, kK5, 1), "conv5_dgrad: bad shape (%d, %d, %d, %d) -> %d: h and w >= 5",
                 tn, cin, h, w, cout);
-  PCONV_REQUIRE(workspace, "conv5_dgrad: null workspace");
-  PCONV_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "conv5_dgrad: the workspace must be 16-byte aligned");
-  const int ho = h - 4, wo = w - 4, hp = h + 4, wp = w + 4;
-  PCONV_REQUIRE(fits_int32((long long)hp * wp) && fits_int32((long long)tn * cout) && fits_int32((long long)tn * cin) &&
-                    fits_int32((long long)cout * cin * 25),
-                "conv5_dgrad: shape exceeds int32");
-  float *prepared = static_cast<float *>(workspace);
-  const long long total = (long long)tn * cout * hp * wp;
-  hipLaunchKernelGGL(conv_grad_prepare_kernel, dim3(pconv_grid((total + 3) / 4, kBlock)), dim3(kBlock), 0, as_stream(stream),
-                     gout, prepared, total, hp, wp, ho, wo, 5, 1);
-  PCONV_LAUNCH_CHECK("conv5_dgrad");
-  // (tn, cout, h + 4, w + 4) * wT (cin, cout, 5, 5) -> (tn, cin, h, w)
-  return pconv_conv5(prepared, packed_wt, nullptr, gin, tn, cout, hp, wp, cin, stream);
+  return run_dgrad("conv5_dgrad", gout, packed_wt, gin, workspace, tn, cin, h, w, cout, kK5, 1, stream);
 }
 
 extern "C" long long pconv_conv5_wgrad_workspace_bytes(int tn, int cin, int cout) {
-  PCONV_REQUIRE(tn > 0 && cin > 0 && cout > 0, "conv5_wgrad_workspace_bytes: bad shape");
-  // the partials P_t (tn, cout, cin, 5, 5) fp32, then the bias planes (tn, cout) fp64
-  return align_up((long long)tn * cout * cin * 25 * (long long)sizeof(float), 16) + (long long)tn * cout * (long long)sizeof(double);
+  PCONV_REQUIRE(conv_shape_ok(kSize5, tn, cin, kK5, kK5, cout, kK5, 1), "conv5_wgrad_workspace_bytes: bad shape");
+  return wgrad_workspace_bytes(tn, cin, cout, kK5);
 }
 
 extern "C" int pconv_conv5_wgrad(const float *in, const float *gout, float *gw, float *gb, void *workspace, int tn, int cin,
                                  int h, int w, int cout, void *stream) {
-  PCONV_REQUIRE(gout && (gw || gb) && (in || !gw), "conv5_wgrad: null pointer");
-  PCONV_REQUIRE(workspace, "conv5_wgrad: null workspace");
-  PCONV_REQUIRE(tn > 0 && cin > 0 && cout > 0 && h >= 5 && w >= 5, "conv5_wgrad: bad shape (%d, %d, %d, %d) -> %d: h and w >= 5",
+  PCONV_REQUIRE(conv_shape_ok(kSize5, tn, cin, h, w, cout, kK5, 1), "conv5_wgrad: bad shape (%d, %d, %d, %d) -> %d: h and w >= 5",
                 tn, cin, h, w, cout);
-  return run_wgrad("conv5_wgrad", in, gout, gw, gb, workspace, tn, cin, h, w, cout, 5, 1, stream);
+  return run_wgrad("conv5_wgrad", in, gout, gw, gb, workspace, tn, cin, h, w, cout, kK5, 1, stream);
 }

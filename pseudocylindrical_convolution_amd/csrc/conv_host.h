@@ -4,6 +4,10 @@
 #pragma once
 #include "common.h"
 
+// conv.hip: floats of the [red_pad][cout_pad] slab a (cout, cin, k, k) weight packs to, k in {1, 3, 5}: cout padded to
+// the widest workgroup tile, cin to whole LDS stages.  64-bit: the caller checks the range.
+long long pconv_conv_packed_floats(int cout, int cin, int k, int *cout_pad, int *red_pad);
+
 // (anonymous like the kernels that take these structs by value: every translation unit has its own)
 namespace {
 

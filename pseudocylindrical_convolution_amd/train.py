@@ -200,28 +200,25 @@ def deterministic_mode():
             torch.use_deterministic_algorithms(before[2], warn_only=before[3])
 
 
-def native_conv_mode():
-    """what --conv native sets, put back afterwards: the convolutions of a training step (TileConv2d and the GDN's
-    1x1 contraction) stay on this project's kernels, forward and backward (PCONV.native_conv_grad).  Refused on a
-    backend that has no such kernels."""
+def native_conv_mode(conv='native'):
+    """what --conv native / native-all sets, put back when the returned context ends: the convolutions of a training
+    step (TileConv2d and the GDN's 1x1 contraction) stay on this project's kernels, forward and backward
+    (PCONV.native_conv_grad); under native-all the entropy model's masked 5x5 convolutions as well
+    (PCONV.native_masked_conv).  Refused on a backend that has no such kernels, before a switch is touched."""
     ops = backend.ops()
-    if not hasattr(ops, 'tile_conv2d_backward'):
-        raise RuntimeError('--conv native needs the HIP backend: {} has no convolution backward kernels '
-                           '(tile_conv2d_backward); use --conv vendor'.format(getattr(ops, '__name__', ops)))
-    return ops.native_conv_grad(True)
+    kernels = ('tile_conv2d_backward', 'conv5x5_backward') if conv == 'native-all' else ('tile_conv2d_backward',)
+    if not all(hasattr(ops, name) for name in kernels):
+        raise RuntimeError('--conv {} needs the HIP backend: {} has no convolution backward kernels '
+                           '({}); use --conv vendor'.format(conv, getattr(ops, '__name__', ops), ', '.join(kernels)))
+    switches = contextlib.ExitStack()
+    switches.enter_context(ops.native_conv_grad(True))
+    if conv == 'native-all':
+        switches.enter_context(ops.native_masked_conv(True))
+    return switches
 
 
-@contextlib.contextmanager
 def native_all_conv_mode():
-    """what --conv native-all sets, put back afterwards: native_conv_mode, and the entropy model's masked 5x5
-    convolutions on this project's kernels as well (PCONV.native_masked_conv).  Refused on a backend that has no such
-    kernels, before either switch is touched."""
-    ops = backend.ops()
-    if not hasattr(ops, 'tile_conv2d_backward') or not hasattr(ops, 'conv5x5_backward'):
-        raise RuntimeError('--conv native-all needs the HIP backend: {} has no convolution backward kernels '
-                           '(tile_conv2d_backward, conv5x5_backward); use --conv vendor'.format(getattr(ops, '__name__', ops)))
-    with ops.native_conv_grad(True), ops.native_masked_conv(True):
-        yield
+    return native_conv_mode('native-all')
 
 
 def Job(rank, world_size, args):
@@ -231,8 +228,7 @@ def Job(rank, world_size, args):
     if native and args.device != 'cuda':
         raise RuntimeError('--conv {} needs --device cuda: the convolution backward kernels are HIP kernels; '
                            'use --conv vendor'.format(conv))
-    mode = native_all_conv_mode if conv == 'native-all' else native_conv_mode
-    with mode() if native else contextlib.nullcontext():
+    with native_conv_mode(conv) if native else contextlib.nullcontext():
         if getattr(args, 'deterministic', False):
             with deterministic_mode():
                 return _job(rank, world_size, args)

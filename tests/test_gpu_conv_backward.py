@@ -93,7 +93,9 @@ def test_tensors_that_are_not_dense_float32_on_the_gpu_are_refused(hip_backend):
     case = C.BY_NAME["c"]
     x, weight, gout = (t.to(DEV) for t in C.inputs(case))
     bad = [(x.cpu(), weight, gout), (x, weight.cpu(), gout), (x, weight.double(), gout), (x.double(), weight, gout),
-           (x, weight, gout.transpose(2, 3).contiguous().transpose(2, 3)), (x, weight[:, :, 0, 0], gout)]
+           (x, weight, gout.transpose(2, 3).contiguous().transpose(2, 3)), (x, weight[:, :, 0, 0], gout),
+           # a 5x5 layer whose shapes fit: conv5x5_backward's, not this entry's
+           (x.new_zeros(2, 5, 8, 12), x.new_zeros(3, 5, 5, 5), x.new_zeros(2, 3, 4, 8))]
     for need in ((True, False, False), (False, True, True)):
         for xs, ws, gs in bad:
             with pytest.raises(PconvError):
