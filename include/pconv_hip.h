@@ -953,6 +953,71 @@ int pconv_ee_decode(pconv_entropy_engine *e, const uint8_t *const *streams, cons
  * Refused while an encode_begin is pending and for engines whose rows are not 8 symbols of total 65536. */
 int pconv_ee_rate(pconv_entropy_engine *e, const float *symbols, double *bits_dev, float *map_dev_or_null, void *stream);
 
+/* ------------------------------------------------------------------------
+ * The optimiser step of training (optim.Adam, train.py --optim native): global gradient norm, clip
+ * coefficient and Adam update of a list of T dense fp32 tensors in three launches.  No reference
+ * counterpart: the reference calls clip_grad_norm_ and torch.optim.Adam (trainDDP_Full.py:43-47).
+ * ---------------------------------------------------------------------- */
+
+/* One record per tensor, in device memory: nine 8-byte words (the Python side builds the table as int64).  acc may be
+ * NULL (no accumulator).  step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t), both computed by the
+ * caller in fp64 and rounded once to fp32, t the tensor's own step count after the increment: tensors of one list
+ * may differ in lr and in t. */
+typedef struct pconv_optim_tensor {
+  float *p;
+  const float *grad;
+  float *acc;
+  float *m;
+  float *v;
+  long long n;
+  float step_size, bc2_sqrt, eps, one_minus_beta1, beta2, one_minus_beta2;
+} pconv_optim_tensor;
+
+/* THE ORDER of the optimiser step.
+ *
+ *   segments  Tensor t is cut into segments of 4096 elements, the last may be shorter; segments are numbered
+ *             tensor-ascending, then offset-ascending.  A quad is four consecutive elements of a segment, the last
+ *             may be short.  The segment table holds two int32 per segment: (tensor, segment within the tensor).
+ *   gradient  g = grad where the tensor has no accumulator, else g = acc + grad, one fp32 rounding (__fadd_rn):
+ *             what AccGrad.copy_back leaves in grad.
+ *   sqnorm    (1) per segment, lane l of 256 adds (double)g * (double)g to one fp64 accumulator, from +0: quads
+ *             q = l, l + 256, ... ascending, the elements of a quad ascending;  (2) the tree  for s = 128, 64, ..., 1:
+ *             a[l] = a[l] + a[l + s] for l < s  leaves the segment's partial in a[0];  (3) one closing workgroup adds
+ *             the partials in the same shape: lane l takes partials l, l + 256, ... ascending from +0, then the tree:
+ *             `total`;  (4) norm = sqrt(total) in fp64;  (5) coef = 1 when clip <= 0, else
+ *             min(1, clip / (norm + 1e-6)) in fp64 (clip_grad_norm_'s formula), rounded once to fp32.  A NaN norm gives
+ *             a NaN coef (the minimum does not drop it), an infinite norm coef 0.
+ *   adam      element-wise, fp32, every operation rounded on its own (nothing contracted), / and sqrt correctly
+ *             rounded:
+ *               g   = g * coef
+ *               m'  = m + one_minus_beta1 * (g - m)
+ *               v'  = (beta2 * v) + one_minus_beta2 * (g * g)
+ *               den = sqrtf(v') / bc2_sqrt + eps
+ *               p'  = p - step_size * (m' / den)
+ *               acc = +0                                   (where the tensor has an accumulator)
+ *             grad is not written.
+ * The result of a tensor does not depend on the grid or, with clip <= 0, on the other tensors of the list.  The quad
+ * mapping lets a tensor whose pointers are all 16-byte aligned move as 16-byte accesses; any other takes 4-byte
+ * accesses in the same order.
+ *
+ * Workspace (device memory of pconv_optim_workspace_bytes bytes): double total at byte 0, double norm at byte 8,
+ * float coef at byte 16, the segment partials (double) from byte 32.  They stay on the device; nothing is copied to
+ * the host and no call synchronises.  The entry points allocate nothing and are stream-ordered. */
+
+/* The segment table of tensors of counts[t] elements (host): returns the number of segments and, where `segments` is
+ * not NULL, writes 2 int32 per segment.  Refuses -- before it writes -- a NULL counts, ntensor < 1, a negative count
+ * and more than 2^31 - 1 segments. */
+long long pconv_host_optim_segments(const long long *counts, int ntensor, int32_t *segments);
+long long pconv_optim_workspace_bytes(int ntensor, int nsegment);
+/* records (ntensor) and segments (2 * nsegment int32) are device tables, counts (ntensor) the host array the segment
+ * table was built from.  pconv_optim_sqnorm: steps (1) - (5) into the workspace.  pconv_optim_adam: the update, with
+ * the coef the workspace holds.  Both return PCONV_EINVAL before anything is written or launched for a NULL pointer,
+ * ntensor or nsegment < 1, a negative count, or counts that do not give nsegment segments. */
+int pconv_optim_sqnorm(const pconv_optim_tensor *records, const int32_t *segments, const long long *counts,
+                       int ntensor, int nsegment, float clip, void *workspace, void *stream);
+int pconv_optim_adam(const pconv_optim_tensor *records, const int32_t *segments, const long long *counts,
+                     int ntensor, int nsegment, const void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

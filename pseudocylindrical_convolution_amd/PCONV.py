@@ -2010,6 +2010,39 @@ def tile_conv2d_backward(x, weight, gout, stride, need=(True, True, True), owner
     return _conv_backward("tile_conv2d_backward", _TILE_CONV, x, weight, gout, stride, need, owner)
 
 
+# ---- the optimiser step (optim.Adam on GPU tensors) ----------------------------------------------------------------
+
+OptimSegments = collections.namedtuple("OptimSegments", "table counts ntensor nsegment")
+
+
+def optim_segments(counts, device):
+    """the segment table (pconv_host_optim_segments) of tensors of `counts` elements, on `device`; depends on the
+    sizes alone"""
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    if counts.ndim != 1 or counts.size < 1:
+        raise PconvError("optim_segments: a non-empty list of element counts expected")
+    nsegment = call("pconv_host_optim_segments", _np_ptr(counts), counts.size, None)
+    table = np.empty((nsegment, 2), dtype=np.int32)
+    call("pconv_host_optim_segments", _np_ptr(counts), counts.size, _np_ptr(table))
+    return OptimSegments(torch.from_numpy(table).to(device), counts, int(counts.size), int(nsegment))
+
+
+def optim_step(records, segments, clip, device):
+    """pconv_optim_sqnorm + pconv_optim_adam over the device table `records` ((ntensor, 9) int64: pconv_optim_tensor)
+    in THE ORDER of include/pconv_hip.h: two launches and the closing launch of the norm.  Returns the workspace as
+    float64: [0] total, [1] norm, the low half of [2] the fp32 clip coefficient, then the segment partials."""
+    if records.dtype != torch.int64 or tuple(records.shape) != (segments.ntensor, 9) or not records.is_cuda or \
+            not records.is_contiguous() or records.device != segments.table.device or records.device != torch.device(device):
+        raise PconvError("optim_step: records must be a contiguous (%d, 9) int64 tensor on %s" % (segments.ntensor, device))
+    stream = _stream(records.device)
+    nbytes = call("pconv_optim_workspace_bytes", segments.ntensor, segments.nsegment)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=records.device)
+    args = (_ptr(records), _ptr(segments.table), _np_ptr(segments.counts), segments.ntensor, segments.nsegment)
+    call("pconv_optim_sqnorm", *args + (float(clip), _ptr(ws), stream))
+    call("pconv_optim_adam", *args + (_ptr(ws), stream))
+    return ws
+
+
 # ---- the masked 5x5 convolutions of the entropy model under training (native_masked_conv) ------------------------
 
 def _pack5(weight, stream):

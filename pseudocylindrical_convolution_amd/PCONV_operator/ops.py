@@ -342,6 +342,16 @@ class PseudoQUANTV2(BaseOpModule):
         outs = self.native(x).forward(x, self.weight, self.count, self.training)
         return outs[0] if len(outs) == 1 else (outs[0], outs[1])
 
+    def call_counters(self):
+        """{gpu id: training-mode calls of that device's op so far}: the op's hidden state -- it decides on which call
+        the levels are merged (update_weight, every check_iters calls) and is in no state_dict.  What
+        optim.TrainState saves of a quantiser beside its parameters."""
+        return {int(g): int(op.iter_) for g, op in self.op.items()}
+
+    def set_call_counters(self, counters):
+        for g, n in counters.items():
+            self.op[int(g)].iter_ = int(n)
+
 
 class PseudoDQUANT(BaseOpModule):
     """index -> level value (reference: PseudoContextV2.py:271-280)."""

@@ -7,9 +7,9 @@ import torch
 
 class Logger(object):
 
-    def __init__(self, fname, screen=True, file=True):
+    def __init__(self, fname, screen=True, file=True, append=False):
         self.file = file
-        self.fout = open(fname, 'w') if file else None
+        self.fout = open(fname, 'a' if append else 'w') if file else None
         self.screen_out = screen
 
     def log(self, *args):

@@ -220,6 +220,7 @@ class MyDistributeSampler(torch.utils.data.distributed.DistributedSampler):
         self.ws = batch_size * num_replicas * acc_batch
         self.thr = mean * self.ws
         self.seed_ext = 0
+        self.skip = 0   # samples of this rank the next iteration leaves out at its start (a resumed epoch); one-shot
 
     def global_order(self):
         """the balanced order over all ranks for the current epoch"""
@@ -243,7 +244,8 @@ class MyDistributeSampler(torch.utils.data.distributed.DistributedSampler):
     def __iter__(self):
         indices = self.global_order()[self.rank:self.total_size:self.num_replicas]
         assert len(indices) == self.num_samples
-        return iter(indices)
+        skip, self.skip = self.skip, 0   # (the length stays the epoch's: nothing is loaded to be thrown away)
+        return iter(indices[skip:])
 
 
 def load_train_test_distribute(world_size, rank, batch_size, test_batch_size, shuffle=True, seed=0, mean=1.4,

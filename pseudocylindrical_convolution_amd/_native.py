@@ -147,6 +147,11 @@ _HIP_SIGNATURES = {
     "pconv_ee_encode_end": [P, P],
     "pconv_ee_decode": [P, P, P, P, P],
     "pconv_ee_rate": [P, P, P, P, P],
+    # the optimiser step (optim.Adam)
+    "pconv_host_optim_segments": [P, I, P],
+    "pconv_optim_workspace_bytes": [I, I],
+    "pconv_optim_sqnorm": [P, P, P, I, I, F, P, P],
+    "pconv_optim_adam": [P, P, P, I, I, P, P],
 }
 
 _CODER_SIGNATURES = {
@@ -216,6 +221,8 @@ def hip_lib():
         lib.pconv_conv2d_wgrad_workspace_bytes.restype = c_longlong
         lib.pconv_conv5_dgrad_workspace_bytes.restype = c_longlong
         lib.pconv_conv5_wgrad_workspace_bytes.restype = c_longlong
+        lib.pconv_host_optim_segments.restype = c_longlong
+        lib.pconv_optim_workspace_bytes.restype = c_longlong
         _hip = lib
     return _hip
 

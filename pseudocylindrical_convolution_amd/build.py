@@ -39,6 +39,7 @@ HIP_SOURCES = [
     "wino42.hip",
     "backward.hip",
     "backward_ordered.hip",  # the atomic-free forms of the four backward kernels that sum with float atomics
+    "optim.hip",  # the optimiser step: global gradient norm, clip and Adam over a tensor list (--optim native)
     "options.cpp",  # the one reader of the library's PCONV_ variables, and pconv_option
     "engine.cpp",
     "coder.cpp",  # the engine drives the arithmetic coder natively

@@ -18,7 +18,11 @@ step, is tested and saved as usual), and `--deterministic` trains on the ordered
 seed are compared on, and `--conv native` keeps the 1x1 / 3x3 convolutions on this project's kernels, forward and
 backward (PCONV.native_conv_grad), and `--conv native-all` the entropy model's masked 5x5 convolutions too
 (PCONV.native_masked_conv), with the SSIM term of --loss viewport computed by sphere_metrics.loss_terms(uniform): no
-convolution of a training step is the vendor library's then."""
+convolution of a training step is the vendor library's then, and `--optim native` takes the step of the two Adam
+optimisers (accumulated gradient, global norm, clip, update) to optim.Adam, whose every operation include/pconv_hip.h
+defines.  The whole state of a run is written to `<prefix>_state.pt` at the end of every epoch and at an early stop
+(`--time-budget`, `--stop-after N` batches); `--resume` continues from it at the recorded epoch and batch and ends
+with the bits of the run that was never interrupted (optim.TrainState)."""
 from __future__ import print_function
 
 import argparse
@@ -32,7 +36,7 @@ import torch
 import torch.distributed as dist
 from torch.nn.parallel import DistributedDataParallel as DDP
 
-from . import PCONV, model_zoo_v2, sphere_metrics
+from . import PCONV, model_zoo_v2, optim, sphere_metrics
 from .PCONV_operator import Logger, ModuleSaver, MultiProject, SSIM, backend
 from .RDMetric import mse_tb
 from .SphereDataset import (ProceduralSphereDataSet, SphereDataSet, SyntheticSphereDataSet,
@@ -79,22 +83,57 @@ def make_sim_func(args, device):
     return SSIM(11, 3).to(device)
 
 
-def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, log, pr1, pr2, ent=True):
-    """one epoch (reference: trainDDP_Full.py:21-56)"""
+def should_stop(args, run, device):
+    """whether the run ends here: the time budget is used up, or --stop-after batches are trained.  With more than
+    one rank it is rank 0's answer, broadcast, that every rank acts on -- a deadline read per rank would let one rank
+    leave the loop for the checksum all-reduce while another enters the next batch's gradient all-reduce.  Every rank
+    asks at the same places: before each batch and before each epoch."""
+    deadline, after = getattr(args, 'deadline', None), getattr(args, 'stop_after', 0)
+    if not deadline and not after:
+        return False
+    stop = bool(deadline and time.monotonic() >= deadline) or bool(after and run.global_batch >= after)
+    if run.world_size > 1:
+        flag = torch.tensor([int(stop)], dtype=torch.int32, device=device)
+        dist.broadcast(flag, 0)
+        stop = bool(flag.item())
+    return stop
+
+
+def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, log, pr1, pr2, ent=True, run=None):
+    """one epoch (reference: trainDDP_Full.py:21-56), or what is left of it: with run.next_batch > 0 (a resumed run,
+    optim.TrainState) the sampler yields the epoch's order from that batch on, the accumulators start from the saved
+    ones, and the loader's iterator is made from the random state the epoch began with.  Sets run.stopped where
+    should_stop ended the epoch early; run.next_batch is then the batch a resumed run starts at."""
+    run = run if run is not None else optim.TrainState()
     model.train()
     train_loader.sampler.set_epoch(epoch)
     acc_grad = AccGrad(get_params(model, ent))
+    start = run.next_batch if run.epoch == epoch else 0
+    if start:
+        train_loader.sampler.skip = start * args.batch_size
+        for a, saved in zip(acc_grad.acc_grad, run.acc):
+            a.copy_(saved)
+        optim.rng_set(run.rng_epoch, device)
+    else:
+        run.rng_epoch = optim.rng_get(device)
+    run.epoch, run.next_batch, run.acc = epoch, start, None
+    batches = enumerate(train_loader, start)   # the loader draws its seeds here
+    if start:
+        optim.rng_set(run.rng, device)
+    native_step = isinstance(optimizer, optim.Adam)
     sim_func = make_sim_func(args, device)
     gamma, beta, alpha, clip = args.gamma, args.beta, args.alpha, args.clip
     log.log('clip:{}'.format(clip))
     acc_batch = args.acc_batch
-    last = None
-    for batch_idx, data in enumerate(train_loader):
+    last = run.last if start else None
+    for batch_idx, data in batches:
         if not data.shape[0] == args.batch_size:
+            run.next_batch = batch_idx + 1
             continue
         if args.max_steps and batch_idx >= args.max_steps:
             break
-        if getattr(args, 'deadline', None) and time.monotonic() >= args.deadline:
+        if should_stop(args, run, device):
+            run.stopped = True
             break
         data = data.to(device)
         optimizer.zero_grad()
@@ -107,7 +146,10 @@ def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, 
         loss.backward()
         optimizer_quant.step()
         param = list(get_params(model, ent))
-        if batch_idx % acc_batch == acc_batch - 1:
+        if batch_idx % acc_batch == acc_batch - 1 and native_step:
+            # copy_back, clip_grad_norm_ and Adam.step in the three launches of csrc/optim.hip (include/pconv_hip.h)
+            optimizer.step(acc=acc_grad.acc_grad, clip=clip)
+        elif batch_idx % acc_batch == acc_batch - 1:
             acc_grad.copy_back(param)
             if clip > 0:
                 torch.nn.utils.clip_grad_norm_(param, clip)
@@ -117,6 +159,8 @@ def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, 
         last = (loss.item(), mse_loss.item(), 1 - ssim_loss.item(), float('nan') if ent_loss is None else ent_loss.item())
         log.log('Train Epoch: {} [{}/{} ({:.0f}%)]\tLoss: {:.6f} mse:{:.6f} ssim:{:.3} rate:{:.3}'.format(
             epoch, batch_idx * len(data), len(train_loader.dataset), 100. * batch_idx / len(train_loader), *last))
+        run.global_batch, run.next_batch = run.global_batch + 1, batch_idx + 1
+    run.acc, run.last = acc_grad.acc_grad, last
     return last
 
 
@@ -256,7 +300,10 @@ def _job(rank, world_size, args):
     prex = '{}_{}_{}_{}_{}'.format('base' if args.base else 'ent', 'opt' if args.opt else 'normal', args.channels,
                                    args.valid_dim, args.npart)
     prex = '{}_init'.format(prex) if args.init else prex
-    log = Logger('{}/{:s}_logs_{}.txt'.format(save_dir, prex, cid), screen=args.verbose and rank == 0, file=(rank == 0))
+    resume = getattr(args, 'resume', None)
+    state_path = '{}/{}_state.pt'.format(save_dir, prex)
+    log = Logger('{}/{:s}_logs_{}.txt'.format(save_dir, prex, cid), screen=args.verbose and rank == 0, file=(rank == 0),
+                 append=resume is not None)
     if args.loss in SPHERE_LOSSES:
         pr1 = pr2 = None  # the sphere-weighted loss reads the ERP frames themselves
     else:
@@ -269,7 +316,9 @@ def _job(rank, world_size, args):
     saver = ModuleSaver(save_dir + '/', prex) if rank == 0 else None
     wrap = lambda m: DDP(m.to(device), [cid] if on_gpu else None)
     best, latest = '{}/{}_best_0.pt'.format(save_dir, prex), '{}/{}_latest.pt'.format(save_dir, prex)
-    if args.init:
+    if resume is not None:
+        model = wrap(model)   # weights, best losses and everything else come from the state file, below
+    elif args.init:
         # stage 2 trains the entropy model on top of the stage-1 transforms: an own checkpoint of this
         # stage, else --init-from, else what `--base` wrote (trainDDP_Full.py:118-122 loads
         # save_models/base_opt_192_{valid_dim}_16_best_0.pt).  Never from random transforms.
@@ -305,16 +354,32 @@ def _job(rank, world_size, args):
             log.log('no checkpoint at {}: training from random weights'.format(of))
         model = wrap(model)
     optimizer_quant = torch.optim.SGD([model.module.quant.count], lr=0.001)
-    optimizer_other = torch.optim.Adam([{'params': model.module.encoder.parameters()},
-                                        {'params': model.module.decoder.parameters()},
-                                        {'params': [model.module.quant.weight]}], lr=args.lr)
-    optimizer_ent = None if args.base else torch.optim.Adam(model.module.ent.parameters(), lr=args.lr * 10)
+    native_optim = getattr(args, 'optim', 'torch') == 'native'
+    Adam = optim.Adam if native_optim else torch.optim.Adam
+    optimizer_other = Adam([{'params': model.module.encoder.parameters()},
+                            {'params': model.module.decoder.parameters()},
+                            {'params': [model.module.quant.weight]}], lr=args.lr)
+    optimizer_ent = None if args.base else Adam(model.module.ent.parameters(), lr=args.lr * 10)
+    optimizers = {'other': optimizer_other, 'ent': optimizer_ent, 'quant': optimizer_quant}
+    run = optim.TrainState()
+    if resume is not None:
+        run = optim.TrainState.load(resume or state_path, args, world_size, model.module, optimizers, saver,
+                                    train_loader.sampler, device)
+        log.log('resumed from {}: epoch {}, batch {}, {} batches trained so far'.format(
+            resume or state_path, run.epoch, run.next_batch, run.global_batch))
+    run.world_size = world_size
+
+    def save_state():
+        if rank == 0:
+            run.save(state_path, args, world_size, model.module, optimizers, saver, train_loader.sampler, device)
+
     log.log('lr:{}'.format(args.lr))
     if deterministic:
         log.log('deterministic: ordered backward kernels {}, cudnn.deterministic {}, cudnn.benchmark {}, '
-                'torch deterministic algorithms {} (warn only){}'.format(
+                'torch deterministic algorithms {} (warn only), optimiser step {}{}'.format(
                     'on' if PCONV.backward_is_ordered() else 'off', torch.backends.cudnn.deterministic,
                     torch.backends.cudnn.benchmark, torch.are_deterministic_algorithms_enabled(),
+                    'native (optim.Adam, in the order of include/pconv_hip.h)' if native_optim else "torch's",
                     '' if not PCONV.conv_grad_is_native() else
                     ', convolutions native, incl. the masked 5x5 and the viewport SSIM' if PCONV.masked_conv_is_native() else
                     ', convolutions native' + (
@@ -324,20 +389,28 @@ def _job(rank, world_size, args):
         log.log('loss: WS-MSE / {} over the ERP frames (--viewport_size is ignored)'.format(
             'WS-SSIM' if args.loss == 'ws' else 'WS-MS-SSIM'))
     log.log('valid dims:{} \t alpha:{}'.format(args.valid_dim, args.alpha))
-    history = []
+    history = run.history   # of a resumed run: the epochs finished before it
     args.deadline = time.monotonic() + args.time_budget if args.time_budget > 0 else None
-    for epoch in range(1, args.epochs + 1):
-        if args.deadline and time.monotonic() >= args.deadline:
-            log.log('time budget of {} s used up after {} epoch(s)'.format(args.time_budget, epoch - 1))
+    for epoch in range(run.epoch, args.epochs + 1):
+        if should_stop(args, run, device):
+            log.log('time budget of {} s used up or --stop-after {} reached: {} batches trained, {} epoch(s) begun'.format(
+                args.time_budget, getattr(args, 'stop_after', 0), run.global_batch, epoch - 1))
             break
         if args.base or (not args.init and epoch % 4 == 1):
-            last = train(args, model, device, train_loader, optimizer_other, optimizer_quant, epoch, log, pr1, pr2, False)
+            last = train(args, model, device, train_loader, optimizer_other, optimizer_quant, epoch, log, pr1, pr2, False, run)
         else:
-            last = train(args, model, device, train_loader, optimizer_ent, optimizer_quant, epoch, log, pr1, pr2, True)
+            last = train(args, model, device, train_loader, optimizer_ent, optimizer_quant, epoch, log, pr1, pr2, True, run)
+        if run.stopped:
+            # the state of the stop itself, before the evaluation below that the uninterrupted run never makes: the
+            # resumed run finds the best losses, the random generators and the history of the finished epochs
+            save_state()
         ls = test(args, model, device, test_loader, log, pr1, pr2)
         history.append((last, ls))
         if rank == 0:
             log.log(saver.save(model, ls))
+        if not run.stopped:
+            run.epoch, run.next_batch, run.acc, run.last = epoch + 1, 0, None, None
+            save_state()
     if world_size > 1 or deterministic:
         # the ranks end with the same parameters (DDP averaged every gradient): spread of a checksum over the ranks
         # (--deterministic: the figure two runs from one seed are compared on, one rank included)
@@ -434,6 +507,25 @@ def build_parser():
                              'of --loss viewport by sphere_metrics.loss_terms(uniform) -- the same 11-tap window on this '
                              'project\'s kernels -- in the place of pytorch_ssim\'s SSIM(11, 3): no configuration reaches '
                              'a library convolution.  native and native-all: HIP backend only')
+    parser.add_argument('--optim', default='torch', choices=['torch', 'native'],
+                        help='whose arithmetic the two Adam optimisers\' step is.  torch: AccGrad.copy_back, clip_grad_norm_ '
+                             'and torch.optim.Adam.step.  native: optim.Adam -- the accumulated gradient, its global norm '
+                             '(a two-stage fp64 sum of fixed shape), the clip and the update in three launches of '
+                             'csrc/optim.hip, every operation defined in include/pconv_hip.h; on --device cpu its twin in '
+                             'numpy, bit for bit the same.  The state layout is torch\'s: a state file of one loads into the '
+                             'other (not under --resume, which refuses a changed --optim like any other changed argument)')
+    parser.add_argument('--resume', nargs='?', const='', default=None, metavar='PATH',
+                        help='continue the run whose state PATH holds (default: <base-dir>/save_models/<prefix>_state.pt, '
+                             'written at the end of every epoch and when --time-budget or --stop-after stops a run): model, '
+                             'optimisers, epoch and batch, gradient accumulators, the quantiser\'s call counters, best losses, '
+                             'sampler and random generators.  The resumed run ends with the bits of the uninterrupted one.  '
+                             'Refused, naming the argument, when an argument that shapes the trajectory differs (all but '
+                             '--epochs, --time-budget, --stop-after, --resume, --verbose, --workers, --base-dir) or the world '
+                             'size does; a missing file is an error.  Not held equal: the evaluation at an early stop may '
+                             'write a _best_ checkpoint of a moment the uninterrupted run never evaluates')
+    parser.add_argument('--stop-after', type=int, default=0, metavar='N',
+                        help='stop when N batches are trained over the whole run, resumed parts included, exactly as a '
+                             'time budget that ran out there (0: no such stop)')
     parser.add_argument('--verbose', action='store_true', default=False)
     return parser
 
