@@ -90,6 +90,43 @@ def test_only_the_options_unit_reads_the_environment():
             assert name == "LOCAL_WORLD_SIZE", "%s: getenv(%s)" % (f, name)
 
 
+def xmacro_names():
+    """the variable of every X(...) row of options.h, in the file's order"""
+    return re.findall(r'\bX\("(PCONV_[A-Z0-9_]+)",', open(os.path.join(CSRC, "options.h")).read())
+
+
+def test_every_option_has_a_gpu_test():
+    """tests/option_cases.py names, for every option row of options.h, a GPU test that launches the code the option
+    selects: the test exists in the file named (read with ast: nothing of it is imported), its source names the option,
+    and the values that once had no launch at all stay listed"""
+    import ast
+    import option_cases
+    names = xmacro_names()
+    assert len(names) == len(set(names)) >= 31
+    assert set(option_cases.OPTIONS) == set(names), "tests/option_cases.py and options.h list different options: %s" % sorted(
+        set(option_cases.OPTIONS) ^ set(names))
+    assert set(names) == set(DEFAULTS) - {"PCONV_ENGINE_CU_MASK_FIRST", "PCONV_ENGINE_CU_MASK_COUNT"}   # every row was found
+    sources = {}
+    for name in names:
+        row = option_cases.OPTIONS[name]
+        assert row.values and all(isinstance(v, str) and v for v in row.values), name
+        assert row.file.startswith("test_gpu_"), (name, row.file)
+        if row.file not in sources:
+            text = open(os.path.join(ROOT, "tests", row.file)).read()
+            tree = ast.parse(text)
+            marked = any(isinstance(n, ast.Assign) and any(getattr(t, "id", None) == "pytestmark" for t in n.targets) and
+                         "pytest.mark.gpu" in ast.get_source_segment(text, n) for n in tree.body)
+            sources[row.file] = ({n.name: ast.get_source_segment(text, n) for n in tree.body if isinstance(n, ast.FunctionDef)},
+                                 marked)
+        tests, marked = sources[row.file]
+        assert marked, "%s is not a GPU test file" % row.file
+        assert row.test in tests, "%s: no test %s in tests/%s" % (name, row.test, row.file)
+        assert re.search(r"\b%s\b" % name, tests[row.test]), "%s::%s does not name %s" % (row.file, row.test, name)
+    for name, values in option_cases.MUST_RUN.items():
+        assert set(values) <= set(option_cases.OPTIONS[name].values), (name, values, option_cases.OPTIONS[name].values)
+    assert len(option_cases.MUST_RUN) == 10
+
+
 def test_every_option_has_a_row_in_the_default_table():
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     section = design.split("## What runs by default", 1)[1].split("\n## ", 1)[0]
