@@ -410,6 +410,42 @@ int pconv_erp_rotation_map(int32_t *map, int h, int w, int yaw, int pitch, int r
 int pconv_erp_remap_f32(const float *in, float *out, const int32_t *map, const float *phases, int n, int c, int h, int w,
                         int clamp, void *stream);
 
+/* Rectilinear viewports of ERP frames (csrc/viewport.hip; pseudocylindrical_convolution_amd/viewport.py states the same
+ * definition in torch and numpy): float32 (n, C, h, w) -> n frames of (C, vh, vw), what a pinhole camera at the centre
+ * of the sphere sees.  A map says where on the source each sample of the view lies; a renderer reads the source there
+ * and averages ss x ss samples per pixel.
+ * View: five int32 in units of 2^-16 degree.  yaw, pitch, roll: the meaning and ranges of the sphere rotation above;
+ *   hfov, vfov (the full horizontal and vertical field of view) in [1*2^16, 170*2^16].
+ *   M = pconv_host_erp_rotation_matrix(yaw, pitch, roll, 0).  pconv_host_viewport_basis (host, in double) returns
+ *   out[0..8] = M row-major, out[9] = tan(hfov/2), out[10] = tan(vfov/2), the angles as k * (pi / 180 / 65536) / 2.
+ * Grid: a view of vh x vw pixels with supersampling ss in {1, 2, 3, 4} has gh = vh*ss rows and gw = vw*ss columns of
+ *   samples.  Sample (row r, column q) looks along d = (1, a, b), all in fp64:
+ *   a = (2*(q + 1/2)/gw - 1) * tan(hfov/2),  b = (1 - 2*(r + 1/2)/gh) * tan(vfov/2):  right is +y and up is +z, the
+ *   picture centre is direction (1, 0, 0), as in the ERP convention above.  It reads the source at s = M * d (not
+ *   normalised: u and v below depend on the direction alone).
+ * Map record (pconv_viewport_map: (gh, gw, 2) int32 on the device): u, v and (qu, qv) are those of pconv_erp_rotation_map
+ *   for the source size h x w: u = (atan2(s_y, s_x)/(2*pi) + 1/2)*w - 1/2, v = (1/2 - atan2(s_z, hypot(s_x, s_y))/pi)*h
+ *   - 1/2, qu = rint(u*P) reduced modulo w*P, qv = rint(v*P), P = 256, rint rounds halves to even.
+ * Sample: the sampler of pconv_erp_remap_f32, word for word: 6 x 6 Lanczos-3 from the phase table of
+ *   pconv_host_lanczos_phases, columns wrapped, rows by the pole rule with the half turn, both sums ascending, one fp32
+ *   rounding per product and per addition, never contracted.
+ * Pixel (j, i): the sum of its ss*ss samples (j*ss + p, i*ss + t) in the order p outer, t inner, in fp32 additions, the
+ *   first sample starting the chain; then one fp32 multiplication by (float)(1.0 / (ss*ss)), skipped for ss = 1; then,
+ *   with clamp != 0, min(max(v, 0), 1).  A box average over the pixel: no wider reconstruction filter.
+ * pconv_viewport_render_f32: in (n, C, h, w); out holds n frames of (C, vh, vw), out_frame_stride floats apart (at least
+ *   C*vh*vw: one view can be written into slot k of an (n, V, C, vh, vw) tensor); map (vh*ss, vw*ss, 2) int32 and phases
+ *   (P x 6 float32) on the device.  Every record is reduced to a position inside the frame, so no map content makes the
+ *   renderer read outside `in`; each lane stores only its own pixel.  Tensors 4-byte aligned, the map 8-byte aligned; no
+ *   allocation, no atomics, no workspace.  Refused on the host, before any launch, with PCONV_EINVAL: null pointers or
+ *   misalignment, a source or view side outside 2 .. 2^20, a source plane, a map or an output frame of 2^31 bytes or
+ *   more, ss outside 1 .. 4, n * C outside 1 .. 65535, a stride below C*vh*vw, in == out, angles out of range. */
+#define PCONV_VIEWPORT_MAX_SS 4
+int pconv_host_viewport_basis(int yaw, int pitch, int roll, int hfov, int vfov, double *out);
+int pconv_viewport_map(int32_t *map, int h, int w, int gh, int gw, int yaw, int pitch, int roll, int hfov, int vfov,
+                       void *stream);
+int pconv_viewport_render_f32(const float *in, float *out, const int32_t *map, const float *phases, int n, int c, int h,
+                              int w, int vh, int vw, int ss, long long out_frame_stride, int clamp, void *stream);
+
 /* PseudoDQuantOp.forward  (pseudo_dquant_cuda.cu:24-70)
  * weight (wc, levels) raw parameter, level_tab (wc, levels) scratch */
 int pconv_dquant(const float *x, const float *weight, float *level_tab, float *out,

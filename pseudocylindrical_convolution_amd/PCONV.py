@@ -1693,6 +1693,75 @@ def erp_remap_f32(x, map, clamp=False, out=None):
     return out
 
 
+def _viewport_phases(device):
+    if device not in _rotate_phases:
+        from .erp_rotate import phases
+        _rotate_phases[device] = phases().to(device)
+    return _rotate_phases[device]
+
+
+def viewport_map(h, w, gh, gw, view, device=None, out=None):
+    """int32 (gh, gw, 2) GPU tensor: where on the h x w source each sample of the gh x gw grid of a rectilinear view
+    lies, in 1/256 pixel (viewport.py, pconv_viewport_map).  view: (yaw, pitch, roll, hfov, vfov) in units of 2^-16
+    degree.  One launch; the trigonometry runs in fp64 on the device"""
+    h, w, gh, gw = int(h), int(w), int(gh), int(gw)
+    try:
+        yaw, pitch, roll, hfov, vfov = (int(v) for v in view)
+    except (TypeError, ValueError):
+        raise PconvError("viewport_map: a view is five integers in units of 2^-16 degree, got %r" % (view,))
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise PconvError("viewport_map: expected a GPU device (this build has no CPU path), got %s" % device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if not (2 <= gh <= 1 << 22 and 2 <= gw <= 1 << 22) or 8 * gh * gw >= 1 << 31:
+        raise PconvError("viewport_map: a grid of %dx%d: sides of 2 .. 2^22 and a map below 2^31 bytes expected" % (gw, gh))
+    if out is None:
+        out = torch.empty((gh, gw, 2), dtype=torch.int32, device=device)
+    elif tuple(out.shape) != (gh, gw, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != device:
+        raise PconvError("viewport_map: out must be contiguous int32 (%d, %d, 2) on %s" % (gh, gw, device))
+    with torch.cuda.device(device), _HbmTimed("viewport_map_kernel", "ViewportMap %dx%d" % (gw, gh), 8.0 * gh * gw, device):
+        call("pconv_viewport_map", _ptr(out), h, w, gh, gw, yaw, pitch, roll, hfov, vfov, _stream(device))
+    return out
+
+
+def viewport_render_f32(x, map, vh, vw, ss, clamp=False, out=None, slot=0):
+    """float32 (n, C, h, w) GPU tensor -> one rectilinear view of vh x vw pixels, read through `map` (int32 (vh * ss,
+    vw * ss, 2) on the same device, from viewport_map) and averaged over ss x ss samples per pixel (viewport.py,
+    pconv_viewport_render_f32).  out: a contiguous float32 (n, V, C, vh, vw) tensor whose view `slot` is written, the
+    others left alone; None: a new (n, 1, C, vh, vw)"""
+    _require_gpu(x, "viewport_render_f32")
+    if x.dim() != 4:
+        raise PconvError("viewport_render_f32: float32 (n, C, h, w) expected")
+    n, c, h, w = x.shape
+    vh, vw, ss, slot = int(vh), int(vw), int(ss), int(slot)
+    if not (2 <= vh <= 1 << 20 and 2 <= vw <= 1 << 20 and 1 <= ss <= 4):
+        raise PconvError("viewport_render_f32: a view of %dx%d with ss = %d: sides of 2 .. 2^20 and ss of 1 .. 4 expected"
+                         % (vw, vh, ss))
+    if map.dtype != torch.int32 or tuple(map.shape) != (vh * ss, vw * ss, 2) or not map.is_contiguous() or map.device != x.device:
+        raise PconvError("viewport_render_f32: the map must be contiguous int32 (%d, %d, 2) on the input's device"
+                         % (vh * ss, vw * ss))
+    table = _viewport_phases(x.device)
+    if out is None:
+        out = torch.empty((n, 1, c, vh, vw), dtype=torch.float32, device=x.device)
+    elif out.dim() != 5 or out.shape[0] != n or tuple(out.shape[2:]) != (c, vh, vw) or out.dtype != torch.float32 \
+            or not out.is_contiguous() or out.device != x.device:
+        raise PconvError("viewport_render_f32: out must be contiguous float32 (%d, V, %d, %d, %d) on the input's device"
+                         % (n, c, vh, vw))
+    views = out.shape[1]
+    if not 0 <= slot < views:
+        raise PconvError("viewport_render_f32: slot %d of %d views" % (slot, views))
+    frame = c * vh * vw
+    # every sample's 36 source values (what the caches make of their overlap is not counted away) + its record per
+    # plane + the output written
+    counted = 4.0 * 36 * n * c * vh * vw * ss * ss + 8.0 * n * c * vh * vw * ss * ss + 4.0 * n * frame
+    with _HbmTimed("viewport_render_f32_kernel", "ViewportRender %dx%d->%dx%d ss%d n%d" % (w, h, vw, vh, ss, n), counted,
+                   x.device):
+        call("pconv_viewport_render_f32", _ptr(x), out.data_ptr() + 4 * slot * frame, _ptr(map), _ptr(table), n, c, h, w,
+             vh, vw, ss, views * frame, 1 if clamp else 0, _stream(x.device))
+    return out
+
+
 WS_WEIGHTINGS = {"ws": 0, "uniform": 1}   # PCONV_WS_WEIGHT_SPHERE, PCONV_WS_WEIGHT_UNIFORM
 
 

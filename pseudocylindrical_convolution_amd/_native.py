@@ -63,6 +63,9 @@ _HIP_SIGNATURES = {
     "pconv_host_lanczos_phases": [P],
     "pconv_erp_rotation_map": [P, I, I, I, I, I, I, P],
     "pconv_erp_remap_f32": [P, P, P, P, I, I, I, I, I, P],
+    "pconv_host_viewport_basis": [I, I, I, I, I, P],
+    "pconv_viewport_map": [P, I, I, I, I, I, I, I, I, I, P],
+    "pconv_viewport_render_f32": [P, P, P, P, I, I, I, I, I, I, I, LL, I, P],
     "pconv_project": [P, P, P, I, I, I, I, I, I, I, I, P],
     "pconv_context_reshape": [P, P, I, I, I, I, I, P],
     "pconv_mask_constrain": [P, I, I, I, I, I, P],

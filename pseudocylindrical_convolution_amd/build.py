@@ -28,6 +28,7 @@ HIP_SOURCES = [
     "yuv.hip",         # YUV 4:2:0 frames: colour conversion fused with the pad / the crop
     "erp_resample.hip",  # sphere-aware Lanczos-3 resize of ERP frames (seam wrapped, poles continued)
     "erp_rotate.hip",  # sphere rotation of ERP frames: the source map and the 6 x 6 Lanczos-3 sampler
+    "viewport.hip",    # rectilinear viewports of ERP frames: the gnomonic source map and the supersampled renderer
     "sphere_metrics.hip",  # WS-PSNR / WS-SSIM / WS-MS-SSIM of ERP frames, forward and backward
     "entropy.hip",
     "entropy_engine.hip",

@@ -451,6 +451,14 @@ class CodecEngine(object):
                 worker.join()
         return geometry.from_coded(torch.cat(out, 0))
 
+    @torch.no_grad()
+    def decode_views(self, streams, height, width, renderer, out_size=None, rotation=None):
+        """n byte strings -> (frames, views): frames (n, 3, H, W) is decode() with the same arguments, views
+        (n, V, 3, vh, vw) = renderer.render(frames, clamp=True), the viewports of a viewport.Renderer built for the
+        frames' size on this device.  Nothing leaves the device between the two."""
+        frames = self.decode(streams, height, width, out_size, rotation)
+        return frames, renderer.render(frames, clamp=True)
+
 
 class FramePipe(object):
     """Frames between pinned host memory and HBM beside the codec's compute (the two ends of the reference's

@@ -152,9 +152,11 @@ def _check(x, map=None):
     return h, w
 
 
-def rotate_torch(x, map, clamp=False):
-    """the sampler in torch, float32 operation by operation, on any device (the CPU path and the kernel's twin)"""
-    h, w = _check(x, map)
+def sample_torch(x, map):
+    """the 6 x 6 footprint of every record of `map` (int32 (.., .., 2): any grid, not only the frames' own) on float32
+    (n, C, h, w) frames, float32 operation by operation: (n, C) + map.shape[:2].  What rotate_torch and
+    viewport.render_torch sample with"""
+    h, w = x.shape[2:]
     table = phases().to(x.device)
     q = map.long()
     col0, row0 = torch.div(q[..., 0], PHASES, rounding_mode="floor") - 2, torch.div(q[..., 1], PHASES, rounding_mode="floor") - 2
@@ -172,6 +174,13 @@ def rotate_torch(x, map, clamp=False):
             line = term if line is None else line + term
         term = line * wy[..., a]
         out = term if out is None else out + term
+    return out
+
+
+def rotate_torch(x, map, clamp=False):
+    """the sampler in torch, float32 operation by operation, on any device (the CPU path and the kernel's twin)"""
+    _check(x, map)
+    out = sample_torch(x, map)
     return out.clamp(0.0, 1.0) if clamp else out
 
 

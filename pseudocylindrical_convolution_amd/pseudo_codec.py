@@ -475,13 +475,23 @@ def _decode_file(t1, fc, model_idx, mse, height, width, raw, to_source=True):
     return t1.decode_coded(fc, height, width, raw=head is None)
 
 
-def decoding(code_list, decoded_img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False):
-    """reference: pseudo_codec.py:249-260"""
+def decoding(code_list, decoded_img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False,
+             view=None, view_size=None, view_list=None):
+    """reference: pseudo_codec.py:249-260.  view (--view: yaw, pitch, roll, hfov in degrees) with view_size = (vh, vw)
+    and view_list (--view-out, one name per code file): the rectilinear view of every decoded picture (viewport.py:
+    square pixels, the supersampling of viewport.plan, clamped to [0, 1]) is written beside the panorama.  A picture
+    coded with --rotate / --code-size is viewed in the source's orientation and at the source's size"""
     t1, _, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
-    for fc, fo in zip(code_list, decoded_img_list):
+    for k, (fc, fo) in enumerate(zip(code_list, decoded_img_list)):
         rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw)
-        write_image(fo, tensor2img(geometry.from_coded(rec)))
+        picture = geometry.from_coded(rec)
+        write_image(fo, tensor2img(picture))
         print('Decoding {}, output to {}'.format(fc, fo))
+        if view is not None:
+            from . import viewport
+            seen = viewport.render(picture, viewport.view(*view, size=view_size), view_size, clamp=True)
+            write_image(view_list[k], tensor2img(seen))
+            print('Viewport {}x{} of {}, output to {}'.format(view_size[1], view_size[0], fc, view_list[k]))
 
 
 class ViewportMetrics(object):
@@ -524,10 +534,46 @@ class SphericalMetrics(object):
         return sphere_metrics.ws_ms_ssim(self._frames(original), self._frames(decoded), self.weighting)[0].item()
 
 
+class ViewportScore(object):
+    """--vp: PSNR / SSIM of the 14 paper directions rendered by viewport.py at a size that follows the picture (default
+    vw = w // 4, vh = (2 vw + 1) // 3: 256x171 at 1024 columns, 1024x683 at 4096) or at size = (vh, vw), anti-aliased by
+    the rule of viewport.plan.  Called on (original, decoded), float32 (1, 3, h, w) on the device, it returns (PSNR in dB
+    of the views' mean MSE, the views' mean SSIM, the text that names the views).  One renderer per picture size"""
+
+    def __init__(self, device_id=0, size=None):
+        self.dev = torch.device(backend.device_of(device_id))
+        self.size = size
+        self.renderers = {}
+
+    def __call__(self, original, decoded):
+        from . import viewport
+        h, w = original.shape[2:]
+        if (h, w) not in self.renderers:
+            size = self.size if self.size is not None else ((2 * (w // 4) + 1) // 3, w // 4)
+            self.renderers[(h, w)] = viewport.Renderer(h, w, viewport.paper_views(size), size, device=self.dev)
+        r = self.renderers[(h, w)]
+        mse_loss, ssim = viewport.metrics(r, original.to(self.dev).contiguous(), decoded.to(self.dev).contiguous())[0].tolist()
+        return sphere_metrics.psnr(mse_loss), ssim, '({} views {}x{}, ss={})'.format(len(r.views), r.vw, r.vh, r.ss)
+
+
 _VIEWPORT = 'Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'
 _WS = 'WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'
 _WS_YUV = 'WS-PSNR-Y:{:.2f}dB, WS-PSNR-U:{:.2f}dB, WS-PSNR-V:{:.2f}dB'
 _WS_MS = 'WS-MS-SSIM:{:.4f}'
+_VP = 'VP-PSNR:{:.2f}dB, VP-SSIM:{:.4f} '
+
+
+def _vp_row(scorer, rows, texts, original, decoded):
+    """--vp: the two figures join the image's row, its line is printed and its text kept for the average's line"""
+    pr, ssim, text = scorer(original, decoded)
+    rows[-1] += (pr, ssim)
+    texts.append(text)
+    print(' ' + _VP.format(pr, ssim) + text)
+
+
+def _vp_line(texts):
+    """the format of the average's --vp line: the images' text when they agree, else the bare figures"""
+    return _VP + (texts[0] if len(set(texts)) == 1 else '(sizes differ)')
 
 
 def _report(rows, lines):
@@ -543,8 +589,9 @@ def _report(rows, lines):
 
 
 def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False,
-                      ws=False, rotation=None, ms_ssim=False):
-    """reference: pseudo_codec.py:263-290.  ws=True (--ws): each row also carries the WS-PSNR and WS-SSIM of the
+                      ws=False, rotation=None, ms_ssim=False, vp=None):
+    """reference: pseudo_codec.py:263-290.  vp (--vp: True, or a size (vh, vw)): two more columns and one more line, the
+    PSNR / SSIM of ViewportScore, after whatever ws adds.  ws=True (--ws): each row also carries the WS-PSNR and WS-SSIM of the
     decoded image as written (tensor2img) against the source at the image's own size: (bpp, vpsnr, vssim, ws_psnr,
     ws_ssim), with a WS line per image and for the average.  A file coded at a reduced size (--code-size, container
     version 3) is scored end to end: the picture resized back to the source size against the source, bpp over the
@@ -554,6 +601,7 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
     t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
+    scorer, texts = (ViewportScore(device_id, None if vp is True else vp), []) if vp else (None, [])
     rows = []
     for fc, fn in zip(code_list, img_list):
         rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw)
@@ -571,11 +619,13 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
             if ms_ssim:
                 rows[-1] += (spherical.ms_ssim(img, tensor2img(rdata)),)
                 print(' ' + _WS_MS.format(rows[-1][-1]))
-    return _report(rows, ([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT])
+        if vp:
+            _vp_row(scorer, rows, texts, img2tensor(img, dev), rdata)
+    return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp))
 
 
 def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False,
-                    code_size=None, rotation=None, ms_ssim=False):
+                    code_size=None, rotation=None, ms_ssim=False, vp=None):
     """--rd: what encoding() + decoding_and_test() report for the images, without a file in between.  The rate is
     the code length of the CDF rows the coder would get (rate.py: within a few bits of the stream), the
     reconstruction is the synthesis of the encoder's own symbols -- what the entropy decoder would hand back.
@@ -584,13 +634,15 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     coded at H2 x W2 under the rule of erp_resample.py and scored end to end at its own size, bpp over its own pixels.
     rotation (--rotate): every image is coded in that orientation (erp_rotate.py) and scored, turned back, against the
     unrotated source.
-    Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim[, ws_ms_ssim]]): the last with ms_ssim=True (--ms-ssim)."""
+    Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim[, ws_ms_ssim]]): the last with ms_ssim=True (--ms-ssim); vp (--vp) adds
+    ViewportScore's two columns at the end, as in decoding_and_test."""
     from .engine import CodecEngine
     from . import rate
     (enc, dev), (dec, _) = _load("encoder", model_idx, mse, device_id), _load("decoder", model_idx, mse, device_id)
     codec = CodecEngine(enc.valid_dim, device_id, enc, dec)
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
+    scorer, texts = (ViewportScore(device_id, None if vp is True else vp), []) if vp else (None, [])
     rows = []
     for fn in img_list:
         img = read_image(fn)
@@ -609,7 +661,9 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
             if ms_ssim:
                 rows[-1] += (spherical.ms_ssim(img, tensor2img(rdata)),)
                 print(' ' + _WS_MS.format(rows[-1][-1]))
-    return _report(rows, ([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT])
+        if vp:
+            _vp_row(scorer, rows, texts, data, rdata)
+    return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp))
 
 
 def _yuv_rgb(frames, h, w, yuv_opts, dev):
@@ -771,6 +825,51 @@ def _rotate_flag(parser, args):
     return rotation
 
 
+def _view_flags(parser, args):
+    """the checks of --view / --view-size / --view-out[-file] and --vp; returns (view, view size, vp): view the four
+    angles in degrees or None, view size (vh, vw) or None, vp None, True (the default size) or (vh, vw).  Contradictions
+    end the run with a message (parser.error)"""
+    from . import viewport
+    view = size = vp = None
+    named = args.view_out is not None or args.view_out_file is not None
+    if args.view is None:
+        for flag, given in (("--view-size", args.view_size is not None), ("--view-out", named)):
+            if given:
+                parser.error("%s needs --view YAW,PITCH,ROLL,HFOV" % flag)
+    else:
+        try:
+            view = tuple(float(v) for v in args.view.split(","))
+            if len(view) != 4:
+                raise ValueError
+        except ValueError:
+            parser.error("--view takes YAW,PITCH,ROLL,HFOV in degrees, for example 30,-45,0,90; got %r" % args.view)
+        if not args.dec:
+            parser.error("--view goes with --dec: it writes a view of every decoded picture (--test / --rd: --vp)")
+        if args.yuv is not None or args.yuv_out is not None:
+            parser.error("--view is for images: the YUV path stops at the coded frame")
+        if args.view_size is None or not named:
+            parser.error("--view needs --view-size WxH and --view-out (or --view-out-file)")
+        if args.view_out is not None and args.view_out_file is not None:
+            parser.error("--view-out and --view-out-file are two lists of the same names: give one")
+        size = _parse_wxh(parser, "--view-size", args.view_size)
+        try:
+            viewport.view(*view, size=size)
+        except viewport.PconvError as exc:
+            parser.error("--view %s --view-size %s: %s (yaw and roll in [-180, 180), pitch in [-90, 90], hfov and the "
+                         "vfov of square pixels in [1, 170], sides of 2 .. 2^20)" % (args.view, args.view_size, exc))
+    if args.vp is not None:
+        if not (args.test or args.rd) or args.enc or args.dec:
+            parser.error("--vp goes with --test or --rd")
+        if args.yuv is not None or args.yuv_out is not None:
+            parser.error("--vp is for images: with --yuv the viewport figures stay those of the first line")
+        vp = True
+        if args.vp != "":
+            vp = _parse_wxh(parser, "--vp", args.vp)
+            if not all(2 <= v <= 1 << 20 for v in vp):
+                parser.error("--vp %s: each side must be in 2 .. 2^20" % args.vp)
+    return view, size, vp
+
+
 def read_list(fname):
     with open(fname) as f:
         return [line.rstrip('\n') for line in f.readlines()]
@@ -831,6 +930,17 @@ def main(argv=None):
     parser.add_argument('--ms-ssim', action='store_true', default=False,
                         help='Testing: with --ws, also report WS-MS-SSIM (five scales of 2x2 means, sphere-weighted '
                              'per scale) of each decoded image; images of at least 16 x 16')
+    parser.add_argument('--view', help='Decoding: YAW,PITCH,ROLL,HFOV in degrees: also write the rectilinear view of every '
+                                       'decoded picture that looks at longitude YAW, latitude PITCH with a horizontal '
+                                       'field of view HFOV (1 .. 170) and square pixels, anti-aliased (viewport.py).  '
+                                       'Needs --view-size and --view-out')
+    parser.add_argument('--view-size', help='WIDTHxHEIGHT of the views of --view')
+    parser.add_argument('--view-out', nargs='*', help='The names of the views of --view, one per code file')
+    parser.add_argument('--view-out-file', help='The file contains the names of the views of --view')
+    parser.add_argument('--vp', nargs='?', const='', help='Testing (--test / --rd): also report VP-PSNR / VP-SSIM, the plain '
+                                                          'PSNR / SSIM of 14 anti-aliased rectilinear views of '
+                                                          'WIDTHxHEIGHT (default: a quarter of the picture\'s width, 3:2) '
+                                                          'rendered from each picture at its own size')
     parser.add_argument('--yuv', help='Encoding / testing: a raw YUV 4:2:0 file as the source instead of images, one '
                                       'code file per frame (needs --size and --pix-fmt)')
     parser.add_argument('--yuv-out', help='Decoding: write the decoded frames to this raw YUV 4:2:0 file, in the order '
@@ -844,6 +954,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     code_size = _code_size_flag(parser, args)
     rotation = _rotate_flag(parser, args)
+    view, view_size, vp = _view_flags(parser, args)
     yuv_call = _yuv_flags(parser, args)   # contradictory YUV flags end the run here, before anything is loaded
     assert not args.ws or ((args.test or args.rd) and not args.enc and not args.dec), '--ws needs --test or --rd'
     assert not args.ms_ssim or args.ws, '--ms-ssim needs --ws'
@@ -876,7 +987,7 @@ def main(argv=None):
     elif args.rd:
         assert img_list is not None, 'No input images for scoring'
         rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws,
-                        code_size=code_size, rotation=rotation, ms_ssim=args.ms_ssim, **size)
+                        code_size=code_size, rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, **size)
     elif args.enc:
         assert img_list is not None, 'No input images for encoding'
         assert code_list is not None, 'No code files for saving the codes'
@@ -889,12 +1000,15 @@ def main(argv=None):
         if args.dec:
             assert out_list is not None, 'No out files for saving the decoded images'
             assert len(code_list) == len(out_list), 'The number of codes and reconstructed images should be the same'
-            decoding(code_list, out_list, midx, not args.ssim, args.gpu_id, raw=args.raw, **size)
+            view_list = pick(args.view_out, args.view_out_file)
+            assert view is None or len(view_list) == len(code_list), 'The number of codes and views should be the same'
+            decoding(code_list, out_list, midx, not args.ssim, args.gpu_id, raw=args.raw, view=view, view_size=view_size,
+                     view_list=view_list, **size)
         else:
             assert img_list is not None, 'No source images for evaluation.'
             assert len(code_list) == len(img_list), 'The number of codes and corresponding source images should be the same'
             decoding_and_test(code_list, img_list, midx, not args.ssim, args.gpu_id, raw=args.raw, ws=args.ws,
-                              rotation=rotation, ms_ssim=args.ms_ssim, **size)
+                              rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, **size)
 
 
 if __name__ == '__main__':
