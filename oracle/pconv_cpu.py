@@ -8,8 +8,10 @@ bench.py's cpu_baseline leg may import it; they plug it under the operator layer
 with `PCONV_operator.backend.use(oracle.pconv_cpu, oracle.coder_cpu)`.
 
 Parity status: pinned to the reference's own kernels compiled for the CPU (oracle/ref_ops.py,
-tests/test_reference_ops_cpu.py, bit for bit with libm on both sides) -- every op but EntropyConv2Op, which
-stays on the invariants of tests/test_oracle_properties.py.
+tests/test_reference_ops_cpu.py, bit for bit with libm on both sides) -- every op.  EntropyConv2Op is held to the
+reference's 128-thread kernels (run as cooperating fibers) bit for bit in the reference's summation order,
+CONV_ORDER = 0, and in the default order 1, the product's, under the bound derived in
+tests/ref_ops_cases.py:econv_bound (divergence 2).
 """
 import ctypes
 import os

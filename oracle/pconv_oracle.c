@@ -10,11 +10,12 @@
  * are kept as 64-bit integers (hard part 3).
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load
- * this library.  Parity status: the reference publishes no vectors for these
- * kernels and its CUDA build cannot run here, so this restatement is pinned by
- * the invariants in tests/test_oracle_properties.py only ("parity unpinned" by
- * reference data).  The arithmetic coder IS pinned against the
- * compiled reference (oracle/_ref).
+ * this library.  Parity status: pinned to the reference's own kernels compiled
+ * for the CPU (oracle/ref_ops.py, tests/test_reference_ops_cpu.py; DESIGN.md
+ * section 2), bit for bit -- the masked convolution (orc_entropy_conv) in the
+ * reference's summation order, order = 0, against its 128-thread blocks run as
+ * cooperating fibers; its default order 1 under a derived bound.  The
+ * arithmetic coder is pinned against the compiled reference (oracle/_ref).
  *
  * Compile: gcc -O2 -std=c99 -ffp-contract=off (no fused multiply-add unless
  * written as fmaf).
@@ -903,7 +904,8 @@ void orc_ctx_pad_run2(float *data, const i64 *dstoff, const i64 *srcoff, const i
 /* ---- entropy_conv_cuda_v2.cu:326-380 ----------------------------------------------------------------- */
 /* order = 0: the reference's own summation order (128 threads striding over
  *            25*group_in, each looping over the allowed groups; shared-memory
- *            halving 128->64->32, then shuffle-down 16..1);
+ *            halving 128->64->32, then shuffle-down 16..1): the bits of the
+ *            reference's four kernels (tests/test_reference_ops_cpu.py, econv);
  * order = 1: the product's published order (64 lanes striding over the flattened
  *            tap-major index kk = (kh*5+kw)*cin + ci with fmaf, xor-butterfly 32..1). */
 static float reduce_ref128(float *s) {

@@ -20,6 +20,11 @@
 
 namespace py = pybind11;
 
+// oracle/ref_shim/coop_selfcheck.cu
+std::vector<float> coop_neighbour(int n, int blocks, int launches);
+std::vector<float> coop_tree(std::vector<float> in);
+std::vector<float> coop_shuffle(std::vector<float> in, int n);
+
 namespace {
 
 template <class T> struct ZeroedDelete {
@@ -79,7 +84,7 @@ typedef std::vector<float> floats;
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.doc() = "the reference's extension ops, one CPU thread per kernel grid";
+  m.doc() = "the reference's extension ops, one CPU thread per kernel grid (the masked convolution: cooperating fibers)";
 
   context<pseudo_context_opt>(m, "PseudoContextOp")
       .def(py::init([](int npart, int rt, floats weight, int device, bool timeit) {
@@ -134,6 +139,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   op<entropy_add_opt, int, int, int, int, std::string, int, bool>(m, "EntropyAddOp")
       .def("restart", &entropy_add_opt::restart)
       .def("forward", &entropy_add_opt::forward_cuda);
+  // the masked convolution: blocks of 128 cooperating threads, run by oracle/ref_shim/coop_launch.cpp
+  op<entropy_conv_opt2, int, int, int, int, int, int, int, int, std::string, int, bool>(m, "EntropyConv2Op")
+      .def("restart", &entropy_conv_opt2::restart)
+      .def("forward", &entropy_conv_opt2::forward_cuda)
+      .def("forward_act", &entropy_conv_opt2::forward_act_cuda)
+      .def("forward_batch", &entropy_conv_opt2::forward_cuda_batch)
+      .def("forward_act_batch", &entropy_conv_opt2::forward_act_cuda_batch);
+  // the launcher's self-check (oracle/ref_shim/coop_selfcheck.cu)
+  m.def("coop_neighbour", &coop_neighbour);
+  m.def("coop_tree", &coop_tree);
+  m.def("coop_shuffle", &coop_shuffle);
   op<pseudo_pad_opt, int, int, std::string, int, bool>(m, "PseudoPadOp")
       .def("forward", &pseudo_pad_opt::forward_cuda)
       .def("backward", &pseudo_pad_opt::backward_cuda);

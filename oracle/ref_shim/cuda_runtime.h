@@ -1,8 +1,9 @@
 // TEST INFRASTRUCTURE -- stand-in for the CUDA runtime header, so that the reference's extension/*.cu compile as
 // ordinary C++ for the CPU (oracle/ref_ops.py).  A kernel is a plain function that runs as the only thread of the
 // only block: every kernel but the masked convolution is a grid-stride loop, which one thread walks in index order.
-// Atomics are serial; the few cuBLAS calls are plain loops.  The masked convolution's file only has to compile:
-// its kernels need 128 cooperating threads and are never called through this build.
+// Atomics are serial; the few cuBLAS calls are plain loops.  The masked convolution's kernels need 128 cooperating
+// threads (shared memory, __syncthreads, warp shuffles): its file alone is compiled with -DSHIM_COOPERATIVE and
+// gets per-thread indices, a warp of 32, a real barrier and a real shuffle from coop_launch.h instead.
 #pragma once
 #include <algorithm>
 #include <cassert>
@@ -17,10 +18,15 @@
 #define __host__
 #define __forceinline__ inline
 #define __inline__ inline
-// Dynamic shared memory, "extern __shared__ int __smem[]" inside a function of the masked convolution's file: here an
-// extern array that nobody defines and nobody reads.  Declared weak at namespace scope first (a block-scope
-// declaration cannot carry the attribute), so that the module still loads.
 #define __shared__
+#ifdef SHIM_COOPERATIVE
+// blocks of cooperating threads; the dynamic shared array "extern __shared__ int __smem[]" is the launcher's
+#include "coop_launch.h"
+extern int __smem[];
+#else
+// Dynamic shared memory, "extern __shared__ int __smem[]" inside a function of the masked convolution's file: in a
+// one-thread file an extern array that nobody reads.  Declared weak at namespace scope first (a block-scope
+// declaration cannot carry the attribute).
 extern int __smem[] __attribute__((weak));
 
 struct shim_dim3 { unsigned x, y, z; };
@@ -28,6 +34,7 @@ static const shim_dim3 threadIdx{0, 0, 0}, blockIdx{0, 0, 0}, blockDim{1, 1, 1},
 static const int warpSize = 1;
 inline void __syncthreads() {}
 template <class T> inline T __shfl_down_sync(unsigned, T v, int) { return v; }
+#endif
 
 typedef void *cudaStream_t;
 typedef void *cudaEvent_t;

@@ -21,6 +21,8 @@ authoring container:
                   of tests/ref_ops_cases.py: arguments, inputs, results and the masks of the
                   elements the reference never writes (found by running twice in fresh
                   processes with different allocator fills)
+  ref_ops_econv.npz  the same for the masked 5x5 wavefront convolution, whose 128-thread blocks run as
+                  cooperating fibers (oracle/ref_shim/coop_launch.cpp): four cases, in a file of their own
 
 The fixtures are data (inputs + expected outputs); no reference source is copied.
 Run from the repo root:  python tests/golden/gen_golden.py
@@ -225,10 +227,28 @@ def ref_ops_fixtures():
         print("wrote %s (%d bytes)" % (name, size))
         assert size <= largest, name
     assert sum(sizes.values()) <= 1100000
+    econv_fixture()
+
+
+def econv_fixture():
+    """ref_ops_econv.npz: the reference's masked convolution, its 128-thread blocks run by the cooperative launcher
+    of oracle/ref_shim/, on ECONV_FIXTURE_CASES of tests/ref_ops_cases.py"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_ops_cases as cases
+    from oracle.ref_ops import ref_ops
+    assert ref_ops() is not None, "the reference tree is needed: python oracle/ref_ops.py"
+    results, masks = cases.reference_results(tempfile.mkdtemp(), cases.ECONV_FIXTURE_CASES)
+    assert not any(masks[name] for name in cases.ECONV_FIXTURE_CASES)      # step 0 zeroes the whole result
+    for name, size in cases.write_econv_fixtures(OUT, results, masks).items():
+        print("wrote %s (%d bytes)" % (name, size))
+        assert size <= os.path.getsize(os.path.join(OUT, "reference_graph.npz")), name
 
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
+    if "--econv-only" in sys.argv:
+        econv_fixture()
+        sys.exit(0)
     if "--ref-ops-only" in sys.argv:
         ref_ops_fixtures()
         sys.exit(0)

@@ -13,6 +13,10 @@ tiles are a few columns wide (W16 at 40, 72 and 128 columns gives 9, 17 and 30; 
 3 and 4, narrower than twice the pad), an all-full-width set in
 which every tile wraps, the cosine rule, and the one weight total (3 * npart) at which the reference's two
 width functions take different branches.
+
+The masked 5x5 wavefront convolution is a family of its own (ECONV_CASES, `econv`): its reference kernels are
+blocks of 128 cooperating threads, run by the cooperative launcher of oracle/ref_shim/.  Only the oracle's
+summation order 0 has the reference's bits; the default order 1 and the HIP op are held under econv_bound.
 """
 import collections
 
@@ -106,7 +110,32 @@ def _cases():
     return collections.OrderedDict((x["name"], x) for x in c)
 
 
+def _econv_cases():
+    c = []
+    # -- the masked 5x5 wavefront convolution: entry point, constrain, pad_out, groups, input channels per group, rows
+    #    per tile, width, weights, images, weight sets (group_out is 3 throughout).  The first four are stored.
+    for name, entry, k, po, ng, gin, h, w, wt, n, nset in [
+            ("plain_c5_p2_g4_i1_h1_w24_nopt", "forward", 5, 2, 4, 1, 1, 24, "WNOPT", 1, 1),
+            ("act_c6_p0_g2_i3_h2_w40", "forward_act", 6, 0, 2, 3, 2, 40, "W16", 1, 1),
+            ("batch_c6_p2_g2_i2_h1_w24_nopt_n2_s1", "forward_batch", 6, 2, 2, 2, 1, 24, "WNOPT", 2, 1),
+            ("actbatch_c5_p0_g2_i1_h1_w40_n2_s2", "forward_act_batch", 5, 0, 2, 1, 1, 40, "W16", 2, 2),
+            ("act_c6_p2_g4_i3_h4_w40", "forward_act", 6, 2, 4, 3, 4, 40, "W16", 1, 1),
+            ("batch_c5_p0_g3_i2_h1_w72_n2_s2", "forward_batch", 5, 0, 3, 2, 1, 72, "W16", 2, 2),
+            ("plain_c6_p2_g2_i3_h1_w40_full", "forward", 6, 2, 2, 3, 1, 40, "WFULL", 1, 1),
+            ("actbatch_c6_p2_g3_i3_h2_w40_n2_s2", "forward_act_batch", 6, 2, 3, 3, 2, 40, "W16", 2, 2),
+            ("plain_c5_p0_g4_i2_h2_w72", "forward", 5, 0, 4, 2, 2, 72, "W16", 1, 1),
+            # the production shape: 14 groups, 42 -> 42 channels, one row per tile
+            ("actbatch_c6_p2_g14_i3_h1_w24_nopt", "forward_act_batch", 6, 2, 14, 3, 1, 24, "WNOPT", 1, 1)]:
+        c.append(_case("econv_" + name, "econv", entry=entry, constrain=k, pad_out=po, ngroup=ng, group_in=gin, h=h, w=w,
+                       weight=wt, n=n, nset=nset))
+    return collections.OrderedDict((x["name"], x) for x in c)
+
+
 CASES = _cases()
+# the masked convolution is a family of its own: held bit for bit only with the oracle's summation order 0, and
+# stored in a fixture file of its own (ECONV_FIXTURE_FILE below)
+ECONV_CASES = _econv_cases()
+ALL_CASES = collections.OrderedDict(list(CASES.items()) + list(ECONV_CASES.items()))
 TRANSCENDENTAL = ("gmm", "gmm_table", "gmm_table_batch", "quant", "projects")
 
 
@@ -160,6 +189,17 @@ def inputs(case):
         d["feat"] = rnd(n * NPART, ng * case["cpg"], h + 4, w + 4)
         d["feat2"] = rnd(n * NPART, ng * case["cpg"], h + 4, w + 4)
         d["dense"] = rnd(3 * n * NPART, ng * case["cpg"], h, w)
+    elif op == "econv":
+        # random everywhere -- the pad_in ring and the positions that are not yet causal too: the mask, not zeros in
+        # the data, has to keep them out.  Bias and slopes are non-zero, the slopes inside (0, 1).
+        cin, cout, nset = case["ngroup"] * case["group_in"], case["ngroup"] * 3, case["nset"]
+        sets = (nset,) if "batch" in case["entry"] else ()
+        d["x"] = rnd(case["n"] * NPART, cin, case["h"] + 4, case["w"] + 4)
+        d["weight"] = rnd(*sets, cout, cin, 5, 5) * 0.1
+        b = rnd(*sets, cout) * 0.1
+        d["bias"] = torch.where(b.abs() < 1e-3, torch.full_like(b, 0.05), b)
+        if "act" in case["entry"]:
+            d["act"] = torch.rand(*sets, cout, generator=g) * 0.9 + 0.05
     elif op == "gmm":
         m, ng = case["m"], case["ng"]
         d["weight"] = torch.softmax(rnd(m, ng), 1).contiguous()
@@ -213,7 +253,7 @@ def interior(case, name, shape):
     pad = TILE_STACKS.get(case["op"], {}).get(name)
     if pad is None:
         return keep
-    p = case["pad"] if pad == "pad" else pad
+    p = case[pad] if isinstance(pad, str) else pad
     wd = widths(case)
     keep[:] = False
     for t in range(shape[0]):
@@ -228,6 +268,7 @@ TILE_STACKS = {
     "fill": {"y": 0, "gy": 0},
     "quant": {"val": 0, "idx": 0, "g_in": 0, "dq": 0},
     "wave": {"ctx": 2, "padded": 2, "padded_in": 2, "added": 2, "restart_ctx": 2},
+    "econv": {"step0": "pad_out", "third": "pad_out", "last": "pad_out"},
 }
 
 
@@ -362,6 +403,8 @@ def run(M, case, ins, dev="cpu", tables=True):
         out["w"], out["grad"] = _cpu(x["w"]), _cpu(x["grad"])
     elif op == "wave":
         _run_wave(M, case, x, out, dev, tables)
+    elif op == "econv":
+        _run_econv(M, case, x, out)
     elif op == "gmm":
         o = M.EntropyGmmOp(case["ng"], 0, 0, False)
         out["loss"] = _cpu(o.forward(x["weight"], x["delta"], x["mean"], x["label"])[0])
@@ -451,6 +494,116 @@ def _run_wave(M, case, x, out, dev, tables):
     out["restart_added_window"] = _cpu(added)[:, :, 2:-2, 2:6]      # the first diagonals lie in the first columns
 
 
+def econv_steps(case):
+    """wavefront steps of the case's frame, and the step after which `third` is taken"""
+    nsteps = case["h"] * NPART + case["w"] + case["ngroup"] - 2
+    return nsteps, nsteps // 3
+
+
+def _run_econv(M, case, x, out):
+    """one masked layer (EntropyConv2Op, the case's entry point) stepped over every diagonal of the frame and two
+    steps past the end, then restarted.  The op reuses one result tensor: each step adds its diagonals to it."""
+    ng, po = case["ngroup"], case["pad_out"]
+    ctx = M.EntropyContextOp(NPART, 18, WEIGHTS[case["weight"]], 0, False)
+    ctx.start_context(case["w"])
+    conv = M.EntropyConv2Op(NPART, ng * case["group_in"], ng, ng * 3, 5, case["constrain"], 2, po, ctx.addr(), 0, False)
+    args = [x["x"], x["weight"], x["bias"]] + ([x["act"]] if "act" in x else [])
+    step = getattr(conv, case["entry"])
+    nsteps, third = econv_steps(case)
+    for s in range(nsteps):
+        y = step(*args)[0]
+        if s == 0:
+            out["step0"] = _cpu(y)
+        if s == third:
+            out["third"] = _cpu(y)
+    out["last"] = _cpu(y)
+    for _ in range(2):                     # past the end the op must leave its result alone
+        y = step(*args)[0]
+    out["past_the_end_unchanged"] = torch.tensor([int(torch.equal(_cpu(y), out["last"]))])
+    conv.restart()                         # begins again at the first diagonal: step 0 zeroes the result
+    for _ in range(3):
+        y = step(*args)[0]
+    out["restart_columns"] = _cpu(y)[:, :, :, :po + 4]      # the first diagonals lie in the first columns
+
+
+def econv_diagonal(case, shape):
+    """int array of a result's shape: the step that writes each element -- column + frame row + output group, the
+    frame row being tile * rows per tile + row (entropy_conv_cuda_v2.cu: psum = tw + hp + tc); -1 on the pad_out ring"""
+    h, w, po = case["h"], case["w"], case["pad_out"]
+    d = np.full(shape, -1, np.int64)
+    tile = (np.arange(shape[0]) % NPART)[:, None, None, None]
+    group = (np.arange(shape[1]) // 3)[None, :, None, None]
+    row, col = np.arange(h)[None, None, :, None], np.arange(w)[None, None, None, :]
+    d[:, :, po:po + h, po:po + w] = col + tile * h + row + group
+    return d
+
+
+def econv_mask(case):
+    """bool (cout, cin, 5, 5): the terms the causal channel limit lets through.  Output group tc at position
+    (row, col) runs at step psum = col + row + tc; tap (kh, kw) reads position (row - 2 + kh, col - 2 + kw) and
+    takes input channels below (psum - (row - 2 + kh) - (col - 2 + kw) [+ 1 for constrain 6]) * group_in =
+    (tc + 4 - kh - kw [+ 1]) * group_in: the same for every position, so the layer is a dense masked convolution"""
+    ng, gin = case["ngroup"], case["group_in"]
+    tc = (np.arange(ng * 3) // 3)[:, None, None, None]
+    ci = np.arange(ng * gin)[None, :, None, None]
+    kh, kw = np.arange(5)[None, None, :, None], np.arange(5)[None, None, None, :]
+    return ci < (tc + 4 - kh - kw + (1 if case["constrain"] == 6 else 0)) * gin
+
+
+def econv_bound(case, ins):
+    """per element of the padded result (float64 tensor): how far the masked convolution summed in the product's
+    order (64 lanes over the tap-major index with fmaf, xor butterfly, bias) may lie from the reference's (products,
+    128 threads each chaining its terms, seven tree levels, bias).  Either side is a sum of the same exact terms in
+    which a term passes through at most d roundings, so it lies within gamma(d) * S of the exact value, with
+    gamma(d) = d u / (1 - d u), u = 2^-24 and S = |bias| + sum |x| |w| over the unmasked terms:
+        |y1 - y_ref| <= (gamma(d0) + gamma(d1)) * S
+        d0 = 1 + ceil(25 group_in / 128) * ngroup + 7 + 1      product, per-thread chain, tree, bias
+        d1 = ceil(25 channel / 64) + 6 + 1                      fmaf chain, butterfly, bias
+    The _act entries multiply a negative sum by a slope in (0, 1): one more rounding on either side (d + 1), and
+    nothing else -- where both sums are negative the slope shrinks their distance; where their signs differ, the
+    positive one and slope * the negative one are no further apart than the two sums themselves.
+    S is evaluated in float64 (a dense convolution of |x| with the masked |w|), with a relative margin of 1e-3 for
+    that evaluation.  Zero on the pad_out ring."""
+    ng, gin, po, h, w = case["ngroup"], case["group_in"], case["pad_out"], case["h"], case["w"]
+    cin = ng * gin
+    act = 1 if "act" in case["entry"] else 0
+    d0 = 1 + -(-25 * gin // 128) * ng + 7 + 1 + act
+    d1 = -(-25 * cin // 64) + 6 + 1 + act
+    u = 2.0 ** -24
+    gamma = lambda d: d * u / (1 - d * u)
+    x = ins["x"].double().abs()
+    wt, bias = ins["weight"].double().abs(), ins["bias"].double().abs()
+    if wt.dim() == 4:
+        wt, bias = wt[None], bias[None]
+    wt = wt * torch.from_numpy(econv_mask(case))[None]
+    n, nset = case["n"], wt.shape[0]
+    per_set = max(n // nset, 1)
+    S = torch.zeros(n * NPART, ng * 3, h + 2 * po, w + 2 * po, dtype=torch.float64)
+    for img in range(n):
+        k = img // per_set
+        tiles = slice(img * NPART, (img + 1) * NPART)
+        S[tiles, :, po:po + h, po:po + w] = torch.nn.functional.conv2d(x[tiles], wt[k]) + bias[k][None, :, None, None]
+    return (gamma(d0) + gamma(d1)) * S * (1 + 1e-3)
+
+
+def econv_within_bound(case, ins, got, ref):
+    """asserts: results `got`, summed in the product's order, lie within econv_bound of the reference's `ref`, are
+    exactly zero wherever the reference wrote nothing (not yet reached, outside the tile, the pad_out ring), and the
+    flag agrees; returns the worst difference / bound"""
+    bound = econv_bound(case, ins)
+    po, worst = case["pad_out"], 0.0
+    for key in ("step0", "third", "last", "restart_columns"):
+        a, b = got[key].double(), ref[key].double()
+        lim = bound if key != "restart_columns" else bound[:, :, :, :po + 4]
+        assert tuple(a.shape) == tuple(b.shape) == tuple(lim.shape), key
+        assert (a[b == 0] == 0).all(), "%s/%s: written where the reference wrote nothing" % (case["name"], key)
+        diff = (a - b).abs()
+        assert (diff <= lim).all(), "%s/%s: %g times the bound" % (case["name"], key, (diff / lim)[lim > 0].max().item())
+        worst = max(worst, (diff / lim)[lim > 0].max().item())
+    assert torch.equal(got["past_the_end_unchanged"], ref["past_the_end_unchanged"])
+    return worst
+
+
 def compare(case, got, ref, masks, exact=True, tol=None):
     """`got` against the reference's `ref` under the unwritten-element masks; returns a list of
     (name, worst absolute difference, scale, elements that differ) for the results that are not bit-equal"""
@@ -508,7 +661,7 @@ def dump_reference(path, names=None):
     from oracle.ref_ops import ref_ops
     R = ref_ops()
     arrays = {}
-    for name, case in CASES.items():
+    for name, case in ALL_CASES.items():
         if names and name not in names:
             continue
         for k, v in run(R, case, inputs(case)).items():
@@ -544,11 +697,11 @@ def reference_results(tmpdir, names=None):
             if va.size else np.zeros(va.shape, bool)
         results.setdefault(name, collections.OrderedDict())[k] = torch.from_numpy(np.where(differ, 0, va).astype(va.dtype))
         if differ.any():
-            inside = differ & interior(CASES[name], k, va.shape)
+            inside = differ & interior(ALL_CASES[name], k, va.shape)
             assert not inside.any(), "%s/%s: %d unwritten elements inside the valid interior" % (name, k, int(inside.sum()))
             masks.setdefault(name, collections.OrderedDict())[k] = differ
         masks.setdefault(name, collections.OrderedDict())
-    ordered = collections.OrderedDict((n, results[n]) for n in CASES if n in results)
+    ordered = collections.OrderedDict((n, results[n]) for n in ALL_CASES if n in results)
     return ordered, masks
 
 
@@ -573,16 +726,26 @@ FIXTURE_CASES = (
 )
 
 
-def write_fixtures(out_dir, results, masks):
+# the masked convolution's file, outside FIXTURE_FILES (whose total size is capped as it stands): between them the
+# stored cases hold all four entry points, both constraints, both pad_out values, the narrow WNOPT tiles, 1 and 2
+# rows per tile, and batch entries with two weight sets and with one set for two images
+ECONV_FIXTURE_FILE = "ref_ops_econv.npz"
+ECONV_FIXTURE_CASES = (
+    "econv_plain_c5_p2_g4_i1_h1_w24_nopt", "econv_act_c6_p0_g2_i3_h2_w40", "econv_batch_c6_p2_g2_i2_h1_w24_nopt_n2_s1",
+    "econv_actbatch_c5_p0_g2_i1_h1_w40_n2_s2",
+)
+
+
+def write_fixtures(out_dir, results, masks, files=None, names=None):
     """one .npz per family: per case its arguments (JSON), inputs, the reference's results and the
     unwritten-element masks (bit-packed)"""
     import json
     import os
     sizes = {}
-    for fname, ops in FIXTURE_FILES.items():
+    for fname, ops in (files or FIXTURE_FILES).items():
         arrays = {}
-        for name in FIXTURE_CASES:
-            case = CASES[name]
+        for name in (names or FIXTURE_CASES):
+            case = ALL_CASES[name]
             if case["op"] not in ops:
                 continue
             arrays[name + "/spec"] = np.array(json.dumps(case, sort_keys=True))
@@ -599,12 +762,21 @@ def write_fixtures(out_dir, results, masks):
     return sizes
 
 
-def load_fixtures(golden_dir):
+def write_econv_fixtures(out_dir, results, masks):
+    return write_fixtures(out_dir, results, masks, {ECONV_FIXTURE_FILE: ("econv",)}, ECONV_FIXTURE_CASES)
+
+
+def load_econv_fixtures(golden_dir):
+    """{case name: (case, inputs, results, masks)} from tests/golden/ref_ops_econv.npz"""
+    return load_fixtures(golden_dir, (ECONV_FIXTURE_FILE,))
+
+
+def load_fixtures(golden_dir, files=None):
     """{case name: (case, inputs, results, masks)} from tests/golden/ref_ops_*.npz"""
     import json
     import os
     out = collections.OrderedDict()
-    for fname in FIXTURE_FILES:
+    for fname in (files or FIXTURE_FILES):
         z = np.load(os.path.join(golden_dir, fname))
         names = [k[:-5] for k in z.files if k.endswith("/spec")]
         for name in names:

@@ -14,6 +14,11 @@ after a training-mode merge within 1e-6.  One departure from the bounds those fi
 between two sides that run the same erf, is held here to the per-row bound that follows from the polynomial's
 published accuracy (ref_ops_cases.gmm_loss_bound) -- against libm's erf 1e-5 cannot hold on
 rows whose probability is near 1e-7, for the oracle as for the kernel.
+
+The masked 5x5 wavefront convolution (tests/golden/ref_ops_econv.npz: the reference's 128-thread blocks run on the
+cooperative launcher of oracle/ref_shim/) sums in another order than the reference (divergence 2): the HIP op is
+held to the reference's stored results under the bound derived in ref_ops_cases.econv_bound, to exact zeros wherever
+the reference wrote nothing, and to the bits of the oracle's order 1 on the stored inputs.
 """
 import os
 
@@ -27,6 +32,7 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DEV = "cuda:0"
 _stored = {}
+_stored_econv = {}
 
 
 def stored(name):
@@ -102,6 +108,26 @@ def test_index_work_is_bit_exact(hip_backend, name):
     case, got, ref, masks = run_product(hip_backend, name)
     for key in got:
         same(got, ref, masks, key)
+
+
+@pytest.mark.parametrize("name", C.ECONV_FIXTURE_CASES)
+def test_masked_convolution(hip_backend, name):
+    """EntropyConv2Op, every entry point, stepped over the whole wavefront, past its end and restarted"""
+    from oracle import pconv_cpu as O
+    if not _stored_econv:
+        _stored_econv.update(C.load_econv_fixtures(GOLDEN))
+    case, ins, ref, masks = _stored_econv[name]
+    assert not masks                       # the reference leaves nothing unwritten: zero reads "not written"
+    got = C.run(hip_backend, case, ins, DEV, tables=False)
+    assert list(got) == list(ref)
+    # within the derived bound of the reference; exactly 0 wherever the reference's result is 0 (nothing written
+    # early or outside the wavefront, the pad_out ring left alone); the flag and the restart result agree
+    print(name, "worst difference / bound: %.3f" % C.econv_within_bound(case, ins, got, ref))
+    # and the product's own order, bit for bit
+    assert O.CONV_ORDER == 1
+    want = C.run(O, case, ins)
+    for key in ref:
+        assert torch.equal(got[key], want[key]), "%s: max abs diff %g" % (key, (got[key] - want[key]).abs().max().item())
 
 
 @pytest.mark.parametrize("name", names("quant"))

@@ -11,8 +11,13 @@ sides are serial fp32 with contraction off), and -- with libm on both sides, set
 ops too.  With the product's published polynomials, set_detmath(True) (divergence 1), the
 CDF tables stay within one count and the float results within bounds derived from the polynomials' published
 accuracy (include/pconv_detmath.h: |erff - erf| < 1.2e-7 absolute, expf within 2 ulp); the derivations are at
-the checks.  EntropyConv2Op needs 128 cooperating threads and stays on the dense masked-convolution invariant
-of tests/test_oracle_properties.py.
+the checks.
+
+EntropyConv2Op, the masked 5x5 wavefront convolution, is blocks of 128 cooperating threads: its file alone runs on
+the cooperative launcher of oracle/ref_shim/ (fibers, a real barrier, a real 32-lane shuffle), which is checked on
+kernels of our own first.  The oracle in the reference's summation order (CONV_ORDER = 0) is held to it bit for
+bit, every result of every econv case; the default order 1 (the product's, DESIGN.md section 2, divergence 2) under
+the bound derived in ref_ops_cases.econv_bound.  Its four stored cases live in tests/golden/ref_ops_econv.npz.
 """
 import os
 
@@ -82,7 +87,7 @@ def test_only_the_ring_of_a_padded_slice_is_unwritten(live):
     unwritten, whole, and writes every other element of every result (dead columns included: zeros)"""
     results, masks = live
     for name, m in masks.items():
-        case = C.CASES[name]
+        case = C.ALL_CASES[name]
         if case["op"] == "slice" and case["pad"] > 0:
             assert list(m) == ["y"]
             ring = np.ones(m["y"].shape, bool)
@@ -184,7 +189,147 @@ def test_detmath_oracle_close_to_reference(live, name):
     print(name, check_detmath(case, got, results[name]))
 
 
+# -- the masked convolution: the reference's 128-thread blocks on the cooperative launcher ------------------------
+def test_cooperative_launcher_on_kernels_of_our_own():
+    """oracle/ref_shim/coop_launch.cpp, before the reference's kernels are trusted to it (coop_selfcheck.cu)"""
+    R = ref_build.ref_ops()
+    if R is None:
+        pytest.skip("neither the reference tree nor a built oracle/_ref module is here")
+    # a neighbour exchange through shared memory: wrong wherever a reader runs before its writer (a barrier that
+    # does nothing under serial execution); two blocks, three launches in a row, then a smaller and a larger block
+    for n, blocks, launches in ((128, 2, 3), (64, 3, 1), (256, 1, 2)):
+        got = np.array(R.coop_neighbour(n, blocks, launches), np.float32).reshape(launches, blocks, n)
+        t = (np.arange(n) + 1) % n
+        for l in range(launches):
+            for b in range(blocks):
+                assert np.array_equal(got[l, b], (100000 * l + 1000 * b + 3 * t + 1).astype(np.float32)), (n, l, b)
+    # the 128 -> 1 tree of the reference's shape against the same order in plain loops, bit for bit; values of mixed
+    # magnitude, so that another order of the additions gives other bits; four blocks, launched twice
+    rng = np.random.default_rng(3)
+    data = (rng.standard_normal(4 * 128) * 10.0 ** rng.integers(-3, 4, 4 * 128)).astype(np.float32)
+    want, serial = [], []
+    for blk in data.reshape(4, 128):
+        s = blk.copy()
+        for half in (64, 32, 16, 8, 4, 2, 1):
+            s[:half] = s[:half] + s[half:2 * half]
+        want.append(s[0])
+        serial.append(np.add.accumulate(blk, dtype=np.float32)[-1])
+    assert want != serial                                      # (the order does matter for these values)
+    for _ in range(2):
+        got = np.array(R.coop_tree(data.tolist()), np.float32)
+        assert got.tobytes() == np.array(want, np.float32).tobytes()
+    # shuffle-down at 16 .. 1 by the first warp alone, the other threads of the block gone: a lane whose source
+    # lies in the warp takes the source's value of the stage before, every other lane keeps its own
+    for n in (128, 32, 48):
+        vals = rng.standard_normal(2 * n).astype(np.float32)
+        got = np.array(R.coop_shuffle(vals.tolist(), n), np.float32).reshape(2, 5, n)
+        for b in range(2):
+            v = vals[b * n:(b + 1) * n].copy()
+            for stage, off in enumerate((16, 8, 4, 2, 1)):
+                nxt = v.copy()
+                nxt[:32 - off] = v[off:32]
+                v = nxt
+                assert np.array_equal(got[b, stage], v), (n, b, off)
+
+
+ECONV_RESULTS = ("step0", "third", "last", "past_the_end_unchanged", "restart_columns")
+
+
+def with_conv_order(order, case, ins):
+    assert O.CONV_ORDER == 1
+    O.CONV_ORDER = order
+    try:
+        return C.run(O, case, ins)
+    finally:
+        O.CONV_ORDER = 1
+
+
+def check_econv_reference(case, ref, masks):
+    """what the reference's own results must look like for the other checks to mean something: nothing unwritten
+    (step 0 zeroes the whole result), every written element non-zero -- so that "exactly zero" reads "not written"
+    -- and after step 0, after a third of the steps and at the end exactly the valid positions whose diagonal has
+    been reached written"""
+    assert not masks, list(masks)
+    assert list(ref) == list(ECONV_RESULTS)
+    nsteps, third = C.econv_steps(case)
+    shape = tuple(ref["last"].shape)
+    valid, diagonal = C.interior(case, "last", shape), C.econv_diagonal(case, shape)
+    assert 2 < third < diagonal[valid].max() < nsteps
+    for key, reached in (("step0", 0), ("third", third), ("last", nsteps)):
+        assert np.array_equal(ref[key].numpy() != 0, valid & (diagonal <= reached)), key
+    assert int(ref["past_the_end_unchanged"]) == 1
+    po = case["pad_out"]
+    assert np.array_equal(ref["restart_columns"].numpy() != 0, (valid & (diagonal <= 2))[:, :, :, :po + 4])
+    assert torch.equal(ref["restart_columns"], torch.where(torch.from_numpy(diagonal <= 2), ref["last"],
+                                                           torch.zeros(()))[:, :, :, :po + 4])
+    if "act" in case["entry"]:             # both branches of the activation
+        assert (ref["last"] < 0).any() and (ref["last"] > 0).any()
+
+
+@pytest.mark.parametrize("name", list(C.ECONV_CASES))
+def test_econv_reference_writes_the_reached_diagonals(live, name):
+    results, masks = live
+    check_econv_reference(C.ECONV_CASES[name], results[name], masks[name])
+
+
+@pytest.mark.parametrize("name", list(C.ECONV_CASES))
+def test_econv_oracle_order0_equals_reference(live, name):
+    """the oracle in the reference's summation order against the reference's kernels: every result, bit for bit"""
+    results, masks = live
+    case = C.ECONV_CASES[name]
+    assert_bit_equal(case, with_conv_order(0, case, C.inputs(case)), results[name], masks[name])
+
+
+@pytest.mark.parametrize("name", list(C.ECONV_CASES))
+def test_econv_oracle_order1_within_bound(live, name):
+    """the oracle's default order, the product's, against the reference (divergence 2)"""
+    results, _ = live
+    case = C.ECONV_CASES[name]
+    ins = C.inputs(case)
+    print(name, "worst difference / bound: %.3f" % C.econv_within_bound(case, ins, C.run(O, case, ins), results[name]))
+
+
 # -- fixtures: the same pin where the reference is absent ---------------------------------------------------------
+@pytest.fixture(scope="module")
+def stored_econv():
+    return C.load_econv_fixtures(GOLDEN)
+
+
+def test_econv_fixture_file_is_small_and_whole(stored_econv):
+    assert C.ECONV_FIXTURE_FILE not in C.FIXTURE_FILES
+    size = os.path.getsize(os.path.join(GOLDEN, C.ECONV_FIXTURE_FILE))
+    assert size <= os.path.getsize(os.path.join(GOLDEN, "reference_graph.npz"))
+    assert list(stored_econv) == list(C.ECONV_FIXTURE_CASES)
+    cases = [C.ECONV_CASES[n] for n in C.ECONV_FIXTURE_CASES]
+    for name, case in zip(C.ECONV_FIXTURE_CASES, cases):
+        assert stored_econv[name][0] == case                   # the stored arguments are the case's
+        for k, v in C.inputs(case).items():
+            assert torch.equal(stored_econv[name][1][k], v), (name, k)
+    assert {c["entry"] for c in cases} == {"forward", "forward_act", "forward_batch", "forward_act_batch"}
+    assert {c["constrain"] for c in cases} == {5, 6} and {c["pad_out"] for c in cases} == {0, 2}
+    assert any(c["weight"] == "WNOPT" for c in cases)
+    assert {(c["n"], c["nset"]) for c in cases if "batch" in c["entry"]} == {(2, 2), (2, 1)}
+    assert any(c["entry"] == "forward_act_batch" and c["nset"] == 2 for c in cases)      # slopes per weight set
+
+
+@pytest.mark.parametrize("name", C.ECONV_FIXTURE_CASES)
+def test_econv_fixture_reference_writes_the_reached_diagonals(stored_econv, name):
+    case, ins, res, masks = stored_econv[name]
+    check_econv_reference(case, res, masks)
+
+
+@pytest.mark.parametrize("name", C.ECONV_FIXTURE_CASES)
+def test_econv_fixture_oracle_order0_equals_reference(stored_econv, name):
+    case, ins, res, masks = stored_econv[name]
+    assert_bit_equal(case, with_conv_order(0, case, ins), res, masks)
+
+
+@pytest.mark.parametrize("name", C.ECONV_FIXTURE_CASES)
+def test_econv_fixture_oracle_order1_within_bound(stored_econv, name):
+    case, ins, res, _ = stored_econv[name]
+    print(name, "worst difference / bound: %.3f" % C.econv_within_bound(case, ins, C.run(O, case, ins), res))
+
+
 def test_fixture_files_are_small_and_whole(stored):
     largest = os.path.getsize(os.path.join(GOLDEN, "reference_graph.npz"))
     total = 0
