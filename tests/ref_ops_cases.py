@@ -17,6 +17,10 @@ width functions take different branches.
 The masked 5x5 wavefront convolution is a family of its own (ECONV_CASES, `econv`): its reference kernels are
 blocks of 128 cooperating threads, run by the cooperative launcher of oracle/ref_shim/.  Only the oracle's
 summation order 0 has the reference's bits; the default order 1 and the HIP op are held under econv_bound.
+
+MID_CASES are the same families on the weight sets other than W16 at 264, 520 and 131 columns: live only, kept
+outside CASES / ALL_CASES / FIXTURE_CASES.  `check_against_oracle(case, got, want)` is the one rule that holds the
+HIP ops' results to the oracle's on every case, small and mid (tests/test_gpu_ref_cases_vs_oracle.py).
 """
 import collections
 
@@ -137,6 +141,37 @@ CASES = _cases()
 ECONV_CASES = _econv_cases()
 ALL_CASES = collections.OrderedDict(list(CASES.items()) + list(ECONV_CASES.items()))
 TRANSCENDENTAL = ("gmm", "gmm_table", "gmm_table_batch", "quant", "projects")
+
+
+def _mid_cases():
+    """mid-size cases: the weight sets other than W16 at widths at which a kernel's loop over a row takes a second and
+    a third trip with a ragged tail (264, 520: past 256 threads once and twice) and at an odd width (131: no tile row
+    is 16-byte aligned, every 4-column form has to fall back or handle its tail).  They run live only -- against the
+    reference on the CPU, against the oracle on the GPU -- and are stored nowhere."""
+    c = []
+    for wt in ("WNOPT", "WFULL", "WCOS", "WCOSB"):
+        for w in (264, 520, 131):
+            tag = "w%d_%s" % (w, wt[1:].lower())
+            c.append(_case("mid_slice_" + tag, "slice", n=1, c=2, h=4, w=w, pad=1, weight=wt))
+            c.append(_case("mid_uslice_" + tag, "uslice", n=1, c=2, h=4, w=w, pad=2, weight=wt))
+            c.append(_case("mid_pad_" + tag, "pad", n=1, c=2, h=4, w=w, pad=2, weight=wt, fill=True))
+            c.append(_case("mid_epad_" + tag, "epad", n=1, c=2, h=4, w=w, pad=2, weight=wt, version=1))
+            c.append(_case("mid_fill_" + tag, "fill", n=1, c=2, h=4, w=w, pad=2, trim=1, fvalue=3, version=0, weight=wt))
+            c.append(_case("mid_quant_" + tag, "quant", n=1, c=6, h=2, w=w, bins=8, ntop=2, train=False, weight=wt))
+        tag = "w264_%s" % wt[1:].lower()
+        c.append(_case("mid_wave_" + tag, "wave", n=1, h=2, w=264, ngroup=14, cpg=3, weight=wt))
+        c.append(_case("mid_econv_" + tag, "econv", entry="forward_act_batch", constrain=6, pad_out=2, ngroup=14, group_in=3,
+                       h=2, w=264, weight=wt, n=1, nset=1))
+    return collections.OrderedDict((x["name"], x) for x in c)
+
+
+# outside CASES / ALL_CASES / FIXTURE_CASES: the fixture files and the existing cases' name-derived seeds stay as they are
+MID_CASES = _mid_cases()
+
+
+def case_of(name):
+    """the case of that name, small or mid"""
+    return ALL_CASES[name] if name in ALL_CASES else MID_CASES[name]
 
 
 def _gen(case):
@@ -625,6 +660,152 @@ def compare(case, got, ref, masks, exact=True, tol=None):
     return report
 
 
+# -- the HIP ops against the oracle: one rule per result of each family -------------------------------------------
+# ("equal",) bit for bit; ("scale", tol) |got - want| <= tol * max(1, |want|.max()); ("abs", tol) |got - want| <= tol.
+# Each is the tightest bound the op already holds against the oracle in tests/test_gpu_ops.py (bit for bit: index
+# work, gathers and lerps, the quantiser's forward, the masked convolution in the oracle's order 1, the CDF tables),
+# tests/test_gpu_backward.py (1e-5 of scale for the backward sums of slice / uslice / pad / entropy pad, whose order
+# differs; 1e-6 for the entropy pad's forward and the quantiser's input gradient; 1e-4 for the float-atomic sums;
+# 1e-5 absolute for the GMM loss, 1e-4 of scale for its gradients) and, under ordered=True,
+# tests/test_gpu_backward_ordered.py (slice, uslice and the viewport sampling walk the oracle's own order).
+EQUAL = ("equal",)
+_ORACLE_RULES = {
+    "slice": {"y": EQUAL, "gx": ("scale", 1e-5)},
+    "uslice": {"y": EQUAL, "gx": ("scale", 1e-5)},
+    "pad": {"fill_param": EQUAL, "filled": EQUAL, "y": EQUAL, "gx": ("scale", 1e-5)},
+    "epad": {"y": ("scale", 1e-6), "gx": ("scale", 1e-5)},
+    "fill": {"y": EQUAL, "gy": EQUAL},
+    "quant": {"val": EQUAL, "idx": EQUAL, "dq": EQUAL, "histogram": EQUAL, "weight_after": EQUAL, "count_after": EQUAL,
+              "g_in": ("scale", 1e-6), "g_weight": ("scale", 1e-4)},
+    "projects": {"y": EQUAL, "gx": ("scale", 1e-4), "count": ("scale", 1e-4)},
+    "gmm": {"loss": ("abs", 1e-5), "g_weight": ("scale", 1e-4), "g_delta": ("scale", 1e-4), "g_mean": ("scale", 1e-4),
+            "g_label": ("scale", 1e-4)},
+}
+_ORDERED_EQUAL = {"slice": ("gx",), "uslice": ("gx",), "projects": ("gx", "count")}
+# every result of these is bit for bit (dtow, context_reshape and mask are permutations and masks; the wave ops index
+# work; econv the oracle's CONV_ORDER 1; the CDF tables and the softmax written in place run the same polynomials)
+_ALL_EQUAL = ("dtow", "context_reshape", "mask", "wave", "econv", "gmm_table", "gmm_table_batch")
+BACKWARD_FAMILIES = ("slice", "uslice", "projects", "quant")      # what PCONV.ordered_backward(True) changes
+
+
+def oracle_rule(case, name, ordered=False):
+    """how result `name` of the case is held to the oracle's: ("equal",), ("scale", tol) or ("abs", tol)"""
+    op = case["op"]
+    if op in _ALL_EQUAL or (ordered and name in _ORDERED_EQUAL.get(op, ())):
+        return EQUAL
+    return _ORACLE_RULES[op][name]
+
+
+def dead_columns(case, name, t):
+    """bool mask of result `name`'s shape (a torch tensor `t` of that shape): the columns at or beyond each tile's valid
+    width inside the rows and columns the op owns -- where slice `y` and the quantiser's `g_in` are exactly zero"""
+    p = case["pad"] if case["op"] == "slice" else 0
+    dead = torch.zeros(t.shape, dtype=torch.bool)
+    for tile, v in enumerate(widths(case)):
+        dead[tile::NPART, :, p:t.shape[2] - p, p + v:t.shape[3] - p] = True
+    return dead
+
+
+LIBM_ULPS = 1.0     # expf / logf of the C library and of the device library: each documented within 1 ulp
+
+
+def quant_merge_bound(case, ins):
+    """(channel, levels) float64: how far the level weights may lie from the oracle's after the training-mode merge
+    of unused levels (pseudo_quant_cuda.cu:97-143).  That step is three libm calls per channel -- the oracle's are
+    the C library's logf / expf, the product's the device library's through torch.log / torch.exp -- and there is no
+    published polynomial for it: the reason is arithmetic, and the bound follows the step's own operations.  With
+    sp(v) the float32 spacing at v, and either library within LIBM_ULPS of the exact function, so that two results
+    of one call lie within 2 LIBM_ULPS sp(.) of each other:
+        t = w[top] - log(k), k = levels - top > 1:   d_t = 2 L sp(log k) + sp(t)      (the subtraction rounds on either
+                                                     side by half a spacing; k = 1: log 1 = 0 exactly, nothing moves)
+        e_i = exp(w_i), i = 1, 2:                    d_i = e_i (exp(d_w_i) - 1) + 2 L sp(e_i)
+        w0' = w0 + e_1:                              d_0 = d_1 + sp(w0')
+        s = (e_1 + e_2) / 2:                         d_s = (d_1 + d_2) / 2 + sp(s)    (the halving is exact)
+        m = log(s):                                  d_m = -log(1 - d_s / s) + 2 L sp(m)
+    evaluated in float64 at the exact values, spacings taken a part in 1e5 above them and the whole with a relative
+    margin of 1e-6 for that evaluation.  Zero for every weight the step leaves alone."""
+    levels = case["bins"]
+    w, cnt = ins["weight"].double().numpy().copy(), ins["count"].numpy()
+    err = np.zeros_like(w)
+    sp = lambda v: float(np.spacing(np.float32(abs(v) * (1 + 1e-5))))
+    for i in range(case["c"]):
+        j = levels - 1
+        while j > 1 and not cnt[i, j] >= np.float32(1e-3):
+            j -= 1
+        k = levels - j
+        if k > 1:
+            t = w[i, j] - np.log(k)
+            w[i, j:], err[i, j:] = t, 2 * LIBM_ULPS * sp(np.log(k)) + sp(t)
+        if cnt[i, 0] < np.float32(1e-3):
+            e = [np.exp(w[i, q]) for q in (1, 2)]
+            d = [e[q] * np.expm1(err[i, q + 1]) + 2 * LIBM_ULPS * sp(e[q]) for q in (0, 1)]
+            w0 = w[i, 0] + e[0]
+            s, ds = (e[0] + e[1]) / 2, (d[0] + d[1]) / 2 + sp((e[0] + e[1]) / 2)
+            m = np.log(s)
+            w[i, 0], err[i, 0] = w0, d[0] + sp(w0)
+            w[i, 1:3], err[i, 1:3] = m, -np.log1p(-ds / s) + 2 * LIBM_ULPS * sp(m)
+    return torch.from_numpy(err) * (1 + 1e-6)
+
+
+def check_against_oracle(case, got, want, ordered=False):
+    """the one place that says how each result of each family is held to the oracle: `got` (the HIP ops', run with
+    tables=False) against `want` (the oracle's, set_detmath(True), CONV_ORDER 1).  Returns the list of violations, one
+    line each; empty when the case holds.  `ordered`: the results were computed under PCONV.ordered_backward(True).
+
+    One departure from bit-equality, derived here: a training-mode quantiser case merges unused levels with libm
+    calls (quant_merge_bound).  Its `weight_after` is held to that bound, `count_after` bit for bit, and every other
+    result -- all of them computed from the merged weights -- to its usual rule against the oracle started from the
+    weights `got` holds: the libm step is isolated, and nothing after it is any looser for it."""
+    bad = []
+    name = case["name"]
+    expect = [k for k in want if not k.startswith("table_")]
+    if [k for k in got if not k.startswith("table_")] != expect:
+        return ["%s: results %s, the oracle's %s" % (name, list(got), expect)]
+    merged = None
+    if case["op"] == "quant" and case["train"]:
+        ins = inputs(case)
+        merged = quant_merge_bound(case, ins)
+        if tuple(got["weight_after"].shape) == tuple(merged.shape) and bool(torch.isfinite(got["weight_after"]).all()):
+            from oracle import pconv_cpu as O
+            ins["weight"], ins["count"] = got["weight_after"].clone(), got["count_after"].clone()
+            again = run(O, dict(case, train=False), ins)
+            want = type(want)((k, v if k in ("weight_after", "count_after") else again[k]) for k, v in want.items())
+    for key in expect:
+        a, b = got[key], want[key]
+        if tuple(a.shape) != tuple(b.shape):
+            bad.append("%s/%s: shape %s, the oracle's %s" % (name, key, tuple(a.shape), tuple(b.shape)))
+            continue
+        if merged is not None and key == "weight_after":
+            diff = (a.double() - b.double()).abs()
+            if not bool((diff <= merged).all()):      # (NaN fails)
+                bad.append("%s/%s: %g times the merge bound (worst |diff| %g)"
+                           % (name, key, (diff / merged.clamp_min(1e-300)).max().item(), diff.max().item()))
+            continue
+        rule = oracle_rule(case, key, ordered)
+        if case["op"] == "slice" and key == "y" and case["pad"] > 0:
+            # the reference leaves the ring of a padded slice undefined: the interior, dead columns included
+            p = case["pad"]
+            a, b = a[:, :, p:-p, p:-p], b[:, :, p:-p, p:-p]
+        if rule == EQUAL:
+            if not torch.equal(a, b):
+                ne = (a != b) if a.dtype == b.dtype else torch.ones(a.shape, dtype=torch.bool)
+                worst = (a.double() - b.double()).abs()
+                worst = worst[~torch.isnan(worst)].max().item() if bool((~torch.isnan(worst)).any()) else float("nan")
+                bad.append("%s/%s: not bit-equal, %d elements differ, first at %s, max abs diff %g"
+                           % (name, key, int(ne.sum()), tuple(ne.nonzero()[0].tolist()) if bool(ne.any()) else (), worst))
+        else:
+            tol = rule[1] * (max(1.0, b.abs().max().item()) if rule[0] == "scale" else 1.0)
+            diff = (a.double() - b.double()).abs()
+            worst = diff.max().item() if diff.numel() else 0.0
+            if not worst <= tol:      # (NaN fails)
+                bad.append("%s/%s: %g > %g (%s %g)" % (name, key, worst, tol, rule[0], rule[1]))
+        if (case["op"], key) in (("slice", "y"), ("quant", "g_in")):
+            dead = dead_columns(case, key, got[key])
+            if bool((got[key][dead] != 0).any()):
+                bad.append("%s/%s: %d non-zero elements in dead columns" % (name, key, int((got[key][dead] != 0).sum())))
+    return bad
+
+
 def gmm_loss_bound(ref_loss, erf_abs=1.2e-7):
     """per element: how far the GMM loss may move when erf is the product's published polynomial (|erff - erf| <
     erf_abs absolute, include/pconv_detmath.h) and not libm's.  loss = -log(p + 1e-7), p = sum_i w_i (fb_i - fa_i),
@@ -661,8 +842,9 @@ def dump_reference(path, names=None):
     from oracle.ref_ops import ref_ops
     R = ref_ops()
     arrays = {}
-    for name, case in ALL_CASES.items():
-        if names and name not in names:
+    # every small case, or the named ones (the mid cases run only when named)
+    for name, case in (list(ALL_CASES.items()) + list(MID_CASES.items())):
+        if (names and name not in names) or (not names and name in MID_CASES):
             continue
         for k, v in run(R, case, inputs(case)).items():
             arrays[name + "/" + k] = v.numpy()
@@ -697,11 +879,11 @@ def reference_results(tmpdir, names=None):
             if va.size else np.zeros(va.shape, bool)
         results.setdefault(name, collections.OrderedDict())[k] = torch.from_numpy(np.where(differ, 0, va).astype(va.dtype))
         if differ.any():
-            inside = differ & interior(ALL_CASES[name], k, va.shape)
+            inside = differ & interior(case_of(name), k, va.shape)
             assert not inside.any(), "%s/%s: %d unwritten elements inside the valid interior" % (name, k, int(inside.sum()))
             masks.setdefault(name, collections.OrderedDict())[k] = differ
         masks.setdefault(name, collections.OrderedDict())
-    ordered = collections.OrderedDict((n, results[n]) for n in ALL_CASES if n in results)
+    ordered = collections.OrderedDict((n, results[n]) for n in list(ALL_CASES) + list(MID_CASES) if n in results)
     return ordered, masks
 
 
