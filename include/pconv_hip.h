@@ -446,6 +446,45 @@ int pconv_viewport_map(int32_t *map, int h, int w, int gh, int gw, int yaw, int 
 int pconv_viewport_render_f32(const float *in, float *out, const int32_t *map, const float *phases, int n, int c, int h,
                               int w, int vh, int vw, int ss, long long out_frame_stride, int clamp, void *stream);
 
+/* Ordered backward of the renderer and of the sphere rotation (csrc/remap_backward.hip, csrc/geometry.cpp; viewport.py
+ * states the same definition in torch: render_backward_torch).  The forward of view pixel (j, i) of plane (n, c) is the
+ * one above without the clamp: S = sum_a wy[a] * (sum_b wx[b] * x[r_a][c_b]) at each of the ss*ss records (j*ss + p,
+ * i*ss + t), the ss*ss results summed and multiplied by inv = (float)(1.0 / (ss*ss)) (no factor for ss = 1).  The sphere
+ * rotation is the case ss = 1 with the frame as the grid (gh = vh = h, gw = vw = w).  The backward is the adjoint of
+ * that linear map, gin = A^T gout, in THIS ORDER:
+ * Destination: source pixel (row, column) of plane (n, c): one fp32 accumulator, starting at +0, or, with accumulate
+ *   != 0, at the value gin already holds.
+ * Term: ((g' * wy[a]) * wx[b]), g' = gout[j][i] for ss = 1, else gout[j][i] * inv, (j, i) = (floor(r / ss), floor(q /
+ *   ss)) of grid sample (r, q); every product one fp32 rounding (__fmul_rn), then one __fadd_rn into the accumulator;
+ *   never contracted.
+ * Order of the terms of a destination: the order in which a sequential walk of the forward reaches it: grid sample
+ *   s = r*gw + q ascending, then tap row a = 0 .. 5, then tap column b = 0 .. 5.
+ * Which destination a tap (s, a, b) has: the sampler's rule, word for word: column = floor(qu / P), row = floor(qv / P)
+ *   of the record map[s]; tap row row - 2 + a through the pole rule (r < 0 -> -1 - r; r >= h -> 2*h - 1 - r), then
+ *   clamped to [0, h - 1]; tap column (column - 2 + b) mod w, and in a tap row that crossed a pole (before the clamp)
+ *   (c_b + floor(w / 2)) mod w; the mathematical modulo and floor for whatever the map holds.  wy = row (qv mod P) and
+ *   wx = row (qu mod P) of the phase table.
+ * Taps that coincide (w < 6; an h small enough that the pole rule or the clamp sends two tap rows to one) are terms of
+ *   their own, all added, in order.  A destination no term reaches gets +0, or with accumulate != 0 is left untouched.
+ *   Nothing depends on the launch grid, the workgroup or the neighbours in the batch: one form, no float atomics.
+ * pconv_host_remap_reverse_size(gh, gw): 36*gh*gw, the number of list entries; negative where that exceeds int32.
+ * pconv_host_remap_reverse (host): the lists as CSR per source pixel from the map the forward read (a host copy of it):
+ *   rev_start h*w + 1 int32, rev_entry 36*gh*gw int32 (144 bytes per grid sample), entry e = s*36 + a*6 + b, ascending
+ *   within each list: a stable counting sort of the forward walk by destination.  Returns the entry count.  Refused,
+ *   before anything is written: null pointers, a source side outside 2 .. 2^20 or a plane of 2^31 bytes or more, a grid
+ *   side outside 2 .. 4*2^20 or a map of 2^31 bytes or more, more entries than int32 holds.
+ * pconv_remap_backward_f32: gout holds n frames of (C, vh, vw), gout_frame_stride floats apart (at least C*vh*vw: slot k
+ *   of an (n, V, C, vh, vw) gradient is read in place); gin (n, C, h, w); map, phases and the two lists on the device.  A
+ *   gather: a lane owns one destination and walks its list; a list is never split.  No atomics, no allocation, no
+ *   memset, 64-bit flat indices.  An entry outside 0 .. 36*gh*gw - 1 is skipped and a start outside it clamped, so no
+ *   list content makes the kernel read outside `map` or `gout`.  Refused on the host, before any launch, with
+ *   PCONV_EINVAL: what pconv_viewport_render_f32 refuses, and gin == gout, null list pointers, lists beyond int32. */
+long long pconv_host_remap_reverse_size(int gh, int gw);
+int pconv_host_remap_reverse(const int32_t *map, int gh, int gw, int h, int w, int32_t *rev_start, int32_t *rev_entry);
+int pconv_remap_backward_f32(const float *gout, float *gin, const int32_t *map, const float *phases, const int32_t *rev_start,
+                             const int32_t *rev_entry, int n, int c, int h, int w, int vh, int vw, int ss,
+                             long long gout_frame_stride, int accumulate, void *stream);
+
 /* PseudoDQuantOp.forward  (pseudo_dquant_cuda.cu:24-70)
  * weight (wc, levels) raw parameter, level_tab (wc, levels) scratch */
 int pconv_dquant(const float *x, const float *weight, float *level_tab, float *out,

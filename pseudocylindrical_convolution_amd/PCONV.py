@@ -1762,7 +1762,59 @@ def viewport_render_f32(x, map, vh, vw, ss, clamp=False, out=None, slot=0):
     return out
 
 
-WS_WEIGHTINGS = {"ws": 0, "uniform": 1}   # PCONV_WS_WEIGHT_SPHERE, PCONV_WS_WEIGHT_UNIFORM
+def remap_backward_f32(gout, map, lists, h, w, vh, vw, ss, gin=None, slot=0, accumulate=False):
+    """the gradient of viewport_render_f32 (and, with ss = 1 and vh x vw = h x w, of erp_remap_f32) with respect to its
+    input, in the order of include/pconv_hip.h (pconv_remap_backward_f32): float32 (n, C, h, w).  gout: the contiguous
+    float32 gradient of the views, (n, V, C, vh, vw), of which view `slot` is read in place, or (n, C, vh, vw); map: the
+    int32 (vh * ss, vw * ss, 2) map the forward read; lists: (start, entry) of viewport.reverse_lists on the same
+    device.  gin: the contiguous tensor to write (None: a new one); accumulate=True adds to what gin holds, leaving
+    the pixels no sample reads untouched"""
+    _require_gpu(gout, "remap_backward_f32")
+    h, w, vh, vw, ss, slot = int(h), int(w), int(vh), int(vw), int(ss), int(slot)
+    if gout.dim() == 4:
+        gout = gout.unsqueeze(1)
+    if gout.dim() != 5 or tuple(gout.shape[3:]) != (vh, vw) or not gout.is_contiguous():
+        raise PconvError("remap_backward_f32: a contiguous float32 (n, V, C, %d, %d) or (n, C, %d, %d) gradient expected, got %s"
+                         % (vh, vw, vh, vw, tuple(gout.shape)))
+    n, views, c = gout.shape[:3]
+    if not 0 <= slot < views:
+        raise PconvError("remap_backward_f32: slot %d of %d views" % (slot, views))
+    if not (2 <= vh <= 1 << 20 and 2 <= vw <= 1 << 20 and 1 <= ss <= 4):
+        raise PconvError("remap_backward_f32: a view of %dx%d with ss = %d: sides of 2 .. 2^20 and ss of 1 .. 4 expected"
+                         % (vw, vh, ss))
+    if map.dtype != torch.int32 or tuple(map.shape) != (vh * ss, vw * ss, 2) or not map.is_contiguous() or map.device != gout.device:
+        raise PconvError("remap_backward_f32: the map must be contiguous int32 (%d, %d, 2) on the gradient's device"
+                         % (vh * ss, vw * ss))
+    entries = 36 * vh * ss * vw * ss
+    try:
+        start, entry = lists
+        good = all(t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.device == gout.device
+                   for t in (start, entry)) and start.numel() == h * w + 1 and entry.numel() == entries
+    except (TypeError, ValueError, AttributeError):
+        good = False
+    if not good:
+        raise PconvError("remap_backward_f32: lists must be (start, entry) of viewport.reverse_lists for this map and a %dx%d "
+                         "source: contiguous int32 of %d and %d elements on the gradient's device" % (w, h, h * w + 1, entries))
+    if gin is None:
+        if accumulate:
+            raise PconvError("remap_backward_f32: accumulate needs the gin to add to")
+        gin = torch.empty((n, c, h, w), dtype=torch.float32, device=gout.device)
+    elif tuple(gin.shape) != (n, c, h, w) or gin.dtype != torch.float32 or not gin.is_contiguous() or gin.device != gout.device:
+        raise PconvError("remap_backward_f32: gin must be contiguous float32 (%d, %d, %d, %d) on the gradient's device" % (n, c, h, w))
+    table = _viewport_phases(gout.device)
+    frame = c * vh * vw
+    # per plane: every entry (4 bytes), its record and its gradient value (what the caches make of their reuse is not
+    # counted away), the starts, and gin written (and read, when accumulating)
+    counted = n * ((c + 3) // 4) * (4.0 * entries + 8.0 * entries + 4.0 * (h * w + 1)) + 4.0 * n * c * entries \
+        + 4.0 * gin.numel() * (2 if accumulate else 1)
+    with _HbmTimed("remap_backward_f32_kernel", "RemapBackward %dx%d<-%dx%d ss%d n%d" % (w, h, vw, vh, ss, n), counted,
+                   gout.device):
+        call("pconv_remap_backward_f32", gout.data_ptr() + 4 * slot * frame, _ptr(gin), _ptr(map), _ptr(table), _ptr(start),
+             _ptr(entry), n, c, h, w, vh, vw, ss, views * frame, 1 if accumulate else 0, _stream(gout.device))
+    return gin
+
+
+WS_WEIGHTINGS = {"ws": 0, "uniform": 1}  # PCONV_WS_WEIGHT_SPHERE, PCONV_WS_WEIGHT_UNIFORM
 
 
 def ws_metrics(x, y, weighting="ws"):

@@ -66,6 +66,9 @@ _HIP_SIGNATURES = {
     "pconv_host_viewport_basis": [I, I, I, I, I, P],
     "pconv_viewport_map": [P, I, I, I, I, I, I, I, I, I, P],
     "pconv_viewport_render_f32": [P, P, P, P, I, I, I, I, I, I, I, LL, I, P],
+    "pconv_host_remap_reverse_size": [I, I],
+    "pconv_host_remap_reverse": [P, I, I, I, I, P, P],
+    "pconv_remap_backward_f32": [P, P, P, P, P, P, I, I, I, I, I, I, I, LL, I, P],
     "pconv_project": [P, P, P, I, I, I, I, I, I, I, I, P],
     "pconv_context_reshape": [P, P, I, I, I, I, I, P],
     "pconv_mask_constrain": [P, I, I, I, I, I, P],
@@ -219,6 +222,7 @@ def hip_lib():
         lib.pconv_erp_resample_workspace_bytes.restype = c_longlong
         lib.pconv_host_tap_reverse_size.restype = c_longlong
         lib.pconv_host_project_reverse_size.restype = c_longlong
+        lib.pconv_host_remap_reverse_size.restype = c_longlong
         lib.pconv_quant_backward_ordered_workspace_bytes.restype = c_longlong
         lib.pconv_conv2d_dgrad_workspace_bytes.restype = c_longlong
         lib.pconv_conv2d_wgrad_workspace_bytes.restype = c_longlong

@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "erp_resample.hip",  # sphere-aware Lanczos-3 resize of ERP frames (seam wrapped, poles continued)
     "erp_rotate.hip",  # sphere rotation of ERP frames: the source map and the 6 x 6 Lanczos-3 sampler
     "viewport.hip",    # rectilinear viewports of ERP frames: the gnomonic source map and the supersampled renderer
+    "remap_backward.hip",  # the ordered backward of the renderer and of the sphere rotation: a gather over reverse lists
     "sphere_metrics.hip",  # WS-PSNR / WS-SSIM / WS-MS-SSIM of ERP frames, forward and backward
     "entropy.hip",
     "entropy_engine.hip",

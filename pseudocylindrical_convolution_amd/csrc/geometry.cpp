@@ -681,3 +681,61 @@ extern "C" int pconv_host_project_reverse(const float *tf, int nview, int inner,
   }
   return (int)total;
 }
+
+extern "C" long long pconv_host_remap_reverse_size(int gh, int gw) {
+  PCONV_REQUIRE(gh > 0 && gw > 0, "remap_reverse_size: bad argument");
+  const long long total = 36LL * gh * gw;
+  PCONV_REQUIRE(total <= INT32_MAX, "remap_reverse_size: the %lld list entries of a %dx%d grid do not fit int32", total, gw, gh);
+  return total;
+}
+
+// the source pixel that tap (a, b) of the record (qu, qv) reads: the sampler's rule of pconv_erp_remap_f32, word for word
+static inline long long remap_tap(int qu, int qv, int a, int b, int h, int w) {
+  long long r = ((long long)qv >> 8) - 2 + a;  // floor(qv / 256) for a negative qv as well
+  const bool crossed = r < 0 || r >= h;
+  if (r < 0) r = -1 - r;
+  else if (r >= h) r = 2LL * h - 1 - r;
+  r = r < 0 ? 0 : r > h - 1 ? h - 1 : r;
+  long long c = (((long long)qu >> 8) - 2 + b) % w;
+  if (c < 0) c += w;
+  if (crossed) c = (c + w / 2) % w;
+  return r * w + c;
+}
+
+// Transpose of the 6 x 6 sampler over a map as a CSR list per source pixel (the ordered backward of the viewport
+// renderer and of the sphere rotation, pconv_remap_backward_f32): the forward walk -- grid sample s = r * gw + q
+// ascending, then tap row a = 0 .. 5, then tap column b = 0 .. 5 -- sorted by the pixel the tap reads with a stable
+// counting sort.  map: the (gh, gw, 2) records the forward read, on the host.  rev_start: h * w + 1 ints; rev_entry:
+// pconv_host_remap_reverse_size entries e = s * 36 + a * 6 + b, ascending within each list.  Taps that coincide are
+// entries of their own.  Returns the number of entries; nothing is written unless every argument passes.
+extern "C" int pconv_host_remap_reverse(const int32_t *map, int gh, int gw, int h, int w, int32_t *rev_start,
+                                        int32_t *rev_entry) {
+  PCONV_REQUIRE(map && rev_start && rev_entry, "remap_reverse: null pointer");
+  PCONV_REQUIRE(h >= 2 && w >= 2 && h <= (1 << 20) && w <= (1 << 20), "remap_reverse: a source side of %dx%d is outside 2 .. 2^20",
+                w, h);
+  PCONV_REQUIRE(4LL * h * w < (1LL << 31), "remap_reverse: a source plane of %dx%d float32 is 2^31 bytes or more", w, h);
+  const int side = 4 << 20;  // PCONV_VIEWPORT_MAX_SS * 2^20
+  PCONV_REQUIRE(gh >= 2 && gw >= 2 && gh <= side && gw <= side, "remap_reverse: a grid side of %dx%d is outside 2 .. 4 * 2^20", gw,
+                gh);
+  PCONV_REQUIRE(8LL * gh * gw < (1LL << 31), "remap_reverse: a map of %dx%d records is 2^31 bytes or more", gw, gh);
+  const long long total = pconv_host_remap_reverse_size(gh, gw);
+  PCONV_REQUIRE(total > 0, "remap_reverse: the %lld entries of a %dx%d grid do not fit int32", 36LL * gh * gw, gw, gh);
+  const size_t keys = (size_t)h * w, samples = (size_t)gh * gw;
+  std::vector<int32_t> fill(keys + 1, 0);
+  for (int pass = 0; pass < 2; pass++) {
+    for (size_t s = 0; s < samples; s++) {
+      const int qu = map[s * 2], qv = map[s * 2 + 1];
+      for (int a = 0; a < 6; a++)
+        for (int b = 0; b < 6; b++) {
+          const size_t d = (size_t)remap_tap(qu, qv, a, b, h, w);
+          if (pass == 0) fill[d + 1]++;
+          else rev_entry[fill[d]++] = (int32_t)(s * 36 + a * 6 + b);
+        }
+    }
+    if (pass == 0) {
+      for (size_t k = 0; k < keys; k++) fill[k + 1] += fill[k];
+      for (size_t k = 0; k <= keys; k++) rev_start[k] = fill[k];
+    }
+  }
+  return (int)total;
+}

@@ -130,6 +130,13 @@ def _source_map(h, w, rotation, inverse, device):
     return torch.from_numpy(source_map_numpy(h, w, rotation, inverse))
 
 
+@functools.lru_cache(maxsize=4)
+def _reverse_lists(h, w, rotation, inverse, device):
+    """the reverse lists of the backward (viewport.reverse_lists) of the cached map: 144 bytes per pixel, the last 4 kept"""
+    from . import viewport
+    return viewport.reverse_lists(_source_map(h, w, rotation, inverse, device), h, w)
+
+
 def source_map(h, w, rotation, inverse=False, device=None):
     """int32 (h, w, 2) map of an h x w frame on `device`: from the HIP kernel for a GPU device, from source_map_numpy
     on the CPU (the two agree except where a position lies within 1e-10 of a rounding boundary).  The last 4 maps are
@@ -187,12 +194,23 @@ def rotate_torch(x, map, clamp=False):
 def rotate(x, rotation, inverse=False, clamp=False, out=None):
     """float32 (n, C, h, w) -> (n, C, h, w) in the orientation `rotation` (inverse=True: back from it): the HIP
     kernels for GPU tensors, the twin on the CPU.  clamp=True bounds the result to [0, 1] (Lanczos overshoots at
-    edges).  rotation None (or all zeros): x itself comes back, nothing runs"""
+    edges).  rotation None (or all zeros): x itself comes back, nothing runs.  With grad mode on and x requiring a
+    gradient the result is attached to autograd through viewport's Function with ss = 1 and the frame as the grid: the
+    ordered backward of include/pconv_hip.h (pconv_remap_backward_f32; the kernel on the GPU, its twin on the CPU: the
+    same bits), its lists built at the first backward and cached like the map; out= is refused then"""
     rotation = check(rotation)
     if rotation is None:
         return x
     h, w = _check(x)
     map = source_map(h, w, rotation, inverse, x.device)
+    if torch.is_grad_enabled() and x.requires_grad:
+        if out is not None:
+            raise PconvError("erp rotate: out= cannot be combined with a gradient: the result of an input that requires "
+                             "grad is a new tensor attached to autograd")
+        from . import viewport   # (viewport imports this module)
+        key = (h, w, rotation, bool(inverse), str(map.device))
+        views = [(map, lambda: _reverse_lists(*key), 1)]
+        return viewport._Remap.apply(x, lambda t: rotate(t, rotation, inverse).unsqueeze(1), views, bool(clamp))[:, 0]
     if x.is_cuda:
         ops = backend.ops()
         if not hasattr(ops, "erp_remap_f32"):

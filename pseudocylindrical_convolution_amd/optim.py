@@ -235,6 +235,7 @@ class TrainState(object):
     # the arguments that do not shape the trajectory: a resumed run may change them
     FREE = ("epochs", "time_budget", "stop_after", "resume", "verbose", "workers", "base_dir")
     DERIVED = ("deadline", "gpu_id")   # what train.py itself hangs on the namespace
+    LATER = ("vp_size",)   # arguments newer than the first state files: at their default (None) they leave no trace
 
     def __init__(self):
         self.epoch, self.next_batch, self.global_batch = 1, 0, 0
@@ -244,7 +245,8 @@ class TrainState(object):
 
     @classmethod
     def fingerprint(cls, args, world_size):
-        fp = {k: v for k, v in sorted(vars(args).items()) if k not in cls.FREE and k not in cls.DERIVED}
+        fp = {k: v for k, v in sorted(vars(args).items()) if k not in cls.FREE and k not in cls.DERIVED
+              and not (k in cls.LATER and v is None)}
         fp["world_size"] = int(world_size)
         return fp
 

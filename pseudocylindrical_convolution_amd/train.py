@@ -6,7 +6,8 @@
 
 The loop, the loss (gamma*viewport MSE + beta*(1 - viewport SSIM) + alpha*rate; with `--loss ws` the two
 viewport terms become the sphere-weighted WS-MSE and WS-SSIM of sphere_metrics.loss_terms, with `--loss ws-ms`
-WS-MSE and WS-MS-SSIM of sphere_metrics.ms_loss_terms), the alternating
+WS-MSE and WS-MS-SSIM of sphere_metrics.ms_loss_terms, with `--loss vp` the MSE and SSIM of the 14 anti-aliased views
+of viewport.py that --test --vp reports: viewport.loss_terms, through the renderer's ordered backward), the alternating
 optimisers (entropy model / transforms + quantiser levels, the histogram "gradient" of `quant.count`
 applied by its own SGD), gradient accumulation over `acc_batch` steps with clipping, and the
 checkpoint naming follow the reference.  What differs: ranks come from the launcher's environment
@@ -36,7 +37,7 @@ import torch
 import torch.distributed as dist
 from torch.nn.parallel import DistributedDataParallel as DDP
 
-from . import PCONV, model_zoo_v2, optim, sphere_metrics
+from . import PCONV, model_zoo_v2, optim, sphere_metrics, viewport
 from .PCONV_operator import Logger, ModuleSaver, MultiProject, SSIM, backend
 from .RDMetric import mse_tb
 from .SphereDataset import (ProceduralSphereDataSet, SphereDataSet, SyntheticSphereDataSet,
@@ -44,6 +45,31 @@ from .SphereDataset import (ProceduralSphereDataSet, SphereDataSet, SyntheticSph
 from .model_zoo_v2 import AccGrad
 
 SPHERE_LOSSES = {'ws': sphere_metrics.loss_terms, 'ws-ms': sphere_metrics.ms_loss_terms}   # --loss: read the ERP frames
+
+OWN_LOSSES = tuple(SPHERE_LOSSES) + ('vp',)   # --loss: no MultiProject, no SSIM module; test() scores by the loss itself
+_vp_renderers = {}   # (h, w, device, --vp-size) -> viewport.Renderer of the 14 paper views
+
+
+def vp_size(text):
+    """--vp-size WxH -> (vh, vw)"""
+    try:
+        vw, vh = (int(v) for v in text.lower().split('x'))
+    except ValueError:
+        raise argparse.ArgumentTypeError('--vp-size is WxH, e.g. 256x171, got {!r}'.format(text))
+    return vh, vw
+
+
+def vp_renderer(args, data):
+    """the renderer of --loss vp for frames like `data`: the 14 paper directions (viewport.paper_views) at --vp-size, by
+    default at the size --test --vp scores at (ViewportScore: vw = w // 4, vh = (2 vw + 1) // 3), anti-aliased by
+    viewport.plan; one per frame size and device, its maps built once"""
+    h, w = data.shape[2:]
+    key = (h, w, str(data.device), getattr(args, 'vp_size', None))
+    if key not in _vp_renderers:
+        size = key[3] if key[3] is not None else ((2 * (w // 4) + 1) // 3, w // 4)
+        _vp_renderers[key] = viewport.Renderer(h, w, viewport.paper_views(size), size, device=data.device)
+    return _vp_renderers[key]
+
 
 def get_params(model, ent):
     m = model.module
@@ -55,7 +81,9 @@ def get_params(model, ent):
 def forward_losses(args, model, data, pr1, pr2, sim_func):
     """(mse, ssim, rate) of one batch; rate is None for the base model.  --loss viewport: MSE and SSIM over the 14
     projected views; --loss ws: the batch means of WS-MSE and WS-SSIM over the ERP frames themselves (pr1, pr2 and
-    sim_func are None); --loss ws-ms: the same with WS-MS-SSIM in the place of WS-SSIM.  --loss viewport without a
+    sim_func are None); --loss ws-ms: the same with WS-MS-SSIM in the place of WS-SSIM; --loss vp: the batch means of
+    viewport.loss_terms, the MSE and SSIM of the 14 anti-aliased views of viewport.py that --test --vp reports, the
+    gradient through the renderer's ordered backward (pr1, pr2 and sim_func are None).  --loss viewport without a
     sim_func (--conv native-all): the SSIM term is sphere_metrics.loss_terms(uniform) over the views -- pytorch_ssim's
     map (the 11-tap sigma 1.5 window, zero padding of 5, its C1 and C2) on this project's kernels; all views have one
     size, so the mean of the frame means is the mean of the map"""
@@ -63,6 +91,9 @@ def forward_losses(args, model, data, pr1, pr2, sim_func):
     y, ent_vec, mask = out if isinstance(out, tuple) else (out, None, None)
     if args.loss in SPHERE_LOSSES:
         terms = SPHERE_LOSSES[args.loss](data, y)
+        mse, ssim = terms[:, 0].mean(), terms[:, 1].mean()
+    elif args.loss == 'vp':
+        terms = viewport.loss_terms(vp_renderer(args, data), data, y)
         mse, ssim = terms[:, 0].mean(), terms[:, 1].mean()
     else:
         py, px = pr1(y), pr2(data)
@@ -76,9 +107,9 @@ def forward_losses(args, model, data, pr1, pr2, sim_func):
 
 
 def make_sim_func(args, device):
-    """the SSIM module of the viewport loss; None where forward_losses needs none: the sphere-weighted losses, and
-    --conv native-all (SSIM(11, 3) blurs with the library's convolution and is not constructed there)"""
-    if args.loss in SPHERE_LOSSES or getattr(args, 'conv', 'vendor') == 'native-all':
+    """the SSIM module of the viewport loss; None where forward_losses needs none: the sphere-weighted losses, --loss
+    vp, and --conv native-all (SSIM(11, 3) blurs with the library's convolution and is not constructed there)"""
+    if args.loss in OWN_LOSSES or getattr(args, 'conv', 'vendor') == 'native-all':
         return None
     return SSIM(11, 3).to(device)
 
@@ -166,7 +197,7 @@ def train(args, model, device, train_loader, optimizer, optimizer_quant, epoch, 
 
 def test(args, model, device, test_loader, log, pr1, pr2):
     """viewport MSE / SSIM / rate over the test set, scored against the anchor curve
-    (reference: trainDDP_Full.py:58-86).  --loss ws / ws-ms: WS-MSE / WS-SSIM / rate, scored by the training loss itself
+    (reference: trainDDP_Full.py:58-86).  --loss ws / ws-ms / vp: the loss's own MSE / SSIM / rate, scored by the training loss itself
     (the anchor curve is one of viewport MSE)"""
     model.eval()
     sim_func = make_sim_func(args, device)
@@ -187,7 +218,7 @@ def test(args, model, device, test_loader, log, pr1, pr2):
         real_rt = vd * test_ent / 0.693
         log.log('\nTest set: MSE loss: {:.6f}  ssim loss: {:.4f} Ent: {:.3f} rt: {:.3f}bpp'.format(
             test_mse, test_ssim, test_ent, real_rt))
-        if args.loss in SPHERE_LOSSES:
+        if args.loss in OWN_LOSSES:
             rt_loss = [args.gamma * test_mse + args.beta * (1 - test_ssim) + args.alpha * test_ent]
         else:
             rt_loss = [float(test_mse - mse_tb(real_rt))]
@@ -304,8 +335,8 @@ def _job(rank, world_size, args):
     state_path = '{}/{}_state.pt'.format(save_dir, prex)
     log = Logger('{}/{:s}_logs_{}.txt'.format(save_dir, prex, cid), screen=args.verbose and rank == 0, file=(rank == 0),
                  append=resume is not None)
-    if args.loss in SPHERE_LOSSES:
-        pr1 = pr2 = None  # the sphere-weighted loss reads the ERP frames themselves
+    if args.loss in OWN_LOSSES:
+        pr1 = pr2 = None  # the sphere-weighted loss reads the ERP frames themselves, --loss vp renders its own views
     else:
         vs = args.viewport_size
         pr1 = MultiProject(vs, int(vs * 1.5), 0.5, False, cid).to(device)
@@ -383,11 +414,15 @@ def _job(rank, world_size, args):
                     '' if not PCONV.conv_grad_is_native() else
                     ', convolutions native, incl. the masked 5x5 and the viewport SSIM' if PCONV.masked_conv_is_native() else
                     ', convolutions native' + (
-                        '' if args.loss in SPHERE_LOSSES else
+                        '' if args.loss in OWN_LOSSES else
                         ' (not the 11x11 blur of the viewport loss\'s SSIM, which stays the library\'s: --loss ws / ws-ms have none)')))
     if args.loss in SPHERE_LOSSES:
         log.log('loss: WS-MSE / {} over the ERP frames (--viewport_size is ignored)'.format(
             'WS-SSIM' if args.loss == 'ws' else 'WS-MS-SSIM'))
+    if args.loss == 'vp':
+        log.log('loss: MSE / SSIM over the 14 anti-aliased views of viewport.py at {} (--viewport_size is ignored)'.format(
+            'the size of --test --vp (a quarter of the width)' if getattr(args, 'vp_size', None) is None else
+            '{}x{}'.format(args.vp_size[1], args.vp_size[0])))
     log.log('valid dims:{} \t alpha:{}'.format(args.valid_dim, args.alpha))
     history = run.history   # of a resumed run: the epochs finished before it
     args.deadline = time.monotonic() + args.time_budget if args.time_budget > 0 else None
@@ -453,14 +488,21 @@ def build_parser():
                         help='the transforms only, no entropy model (trainDDP_Base.py)')
     parser.add_argument('--latest', action='store_true', default=False)
     parser.add_argument('--restart', action='store_true', default=False)
-    parser.add_argument('--loss', default='viewport', choices=['viewport', 'ws', 'ws-ms'],
+    parser.add_argument('--loss', default='viewport', choices=['viewport', 'ws', 'ws-ms', 'vp'],
                         help='distortion terms: viewport = MSE and SSIM over 14 rectilinear views (the paper\'s loss); '
                              'ws = WS-MSE and WS-SSIM over the ERP frame (sphere_metrics.loss_terms: what --test --ws '
-                             'reports); ws-ms = WS-MSE and WS-MS-SSIM (sphere_metrics.ms_loss_terms: --test --ws --ms-ssim).  '
-                             'gamma, beta and alpha weigh the terms alike; with ws and ws-ms the best checkpoint is the '
-                             'one with the lowest gamma*mse + beta*(1 - ssim) + alpha*rate on the test set')
+                             'reports); ws-ms = WS-MSE and WS-MS-SSIM (sphere_metrics.ms_loss_terms: --test --ws --ms-ssim); '
+                             'vp = MSE and SSIM over the 14 paper directions rendered by viewport.py, anti-aliased, at a '
+                             'size that follows the frame (viewport.loss_terms: what --test --vp reports; the gradient '
+                             'runs through the renderer\'s ordered, atomic-free backward; no gradient through a '
+                             'prefiltered view, which a frame more than 4 source pixels per view pixel would need).  '
+                             'gamma, beta and alpha weigh the terms alike; with ws, ws-ms and vp the best checkpoint is '
+                             'the one with the lowest gamma*mse + beta*(1 - ssim) + alpha*rate on the test set')
+    parser.add_argument('--vp-size', type=vp_size, default=None, metavar='WxH',
+                        help='size of a view of --loss vp (default: that of --test --vp, W = width // 4, H = (2 W + 1) // 3: '
+                             '256x171 at 1024 columns)')
     parser.add_argument('--viewport_size', type=int, default=171, metavar='viewport',
-                        help='side of a projected view (ignored with --loss ws and ws-ms)')
+                        help='side of a projected view (ignored with --loss ws, ws-ms and vp)')
     parser.add_argument('--channels', type=int, default=192)
     parser.add_argument('--code-dim', type=int, default=192)
     parser.add_argument('--npart', type=int, default=16)

@@ -25,6 +25,18 @@ sampler differ.
 `Renderer` holds the maps of its views for one source size; `render` is the one-view convenience; `metrics` scores two
 batches through a renderer (plain PSNR / SSIM of the rendered views, averaged over the views).  GPU tensors take the HIP
 kernels, CPU tensors the twin (the oracle backend).
+
+Training on the views.  `Renderer.render` (and erp_rotate.rotate) of a tensor that requires grad is attached to autograd
+through one Function whose backward is the adjoint of "sampler over a map plus ss x ss average" in a defined order
+(include/pconv_hip.h, pconv_remap_backward_f32): for every source pixel one fp32 accumulator starting at +0, to which the
+terms ((g' wy[a]) wx[b]) -- g' = g[j][i] for ss = 1, else g[j][i] float32(1 / ss^2), one fp32 rounding per product and
+per addition -- are added in the order a sequential walk of the forward reaches the pixel: grid sample s = r gw + q
+ascending, then tap row a, then tap column b; the tap's pixel by the sampler's rule word for word; coinciding taps are
+terms of their own; a pixel no term reaches gets +0.  `reverse_lists` builds that order once per map on the host (a CSR
+list per source pixel from the very map the forward read), the kernel of csrc/remap_backward.hip
+(PCONV.remap_backward_f32) gathers along it without atomics, and `render_backward_torch` is its twin: the same bits on the
+same map and lists.  `loss_terms` is `metrics` as a loss (train.py --loss vp).  Limits: a list of at most 2^31 - 1
+entries, and no gradient through a prefiltered view (erp_resample.resize has no backward).
 """
 import math
 
@@ -178,6 +190,110 @@ def render_torch(x, map, vh, vw, ss, clamp=False):
     return out.clamp(0.0, 1.0) if clamp else out
 
 
+def reverse_lists(map, h, w):
+    """(start, entry): the transpose of the sampler over `map` (int32 (gh, gw, 2), the map the forward read) as one list
+    per pixel of the h x w source, int32 tensors of h w + 1 and 36 gh gw elements on the map's device
+    (pconv_host_remap_reverse: a stable counting sort of the forward walk; entry e = s 36 + a 6 + b).  A device map is
+    copied to the host once, so that forward and backward agree on every record; 144 bytes per grid sample"""
+    h, w = _check_source(h, w)
+    if map.dtype != torch.int32 or map.dim() != 3 or map.shape[2] != 2:
+        raise PconvError("viewport: a map is int32 (gh, gw, 2), got %s %s" % (map.dtype, tuple(map.shape)))
+    gh, gw = _check_grid(*map.shape[:2])
+    if 36 * gh * gw > np.iinfo(np.int32).max:
+        raise PconvError("viewport: the %d list entries of a %dx%d grid are beyond int32: no gradient through this view"
+                         % (36 * gh * gw, gw, gh))
+    count = _native.call("pconv_host_remap_reverse_size", gh, gw)
+    host = np.ascontiguousarray(map.detach().cpu().numpy())
+    start, entry = np.empty(h * w + 1, dtype=np.int32), np.empty(count, dtype=np.int32)
+    _native.call("pconv_host_remap_reverse", host.ctypes.data, gh, gw, h, w, start.ctypes.data, entry.ctypes.data)
+    return torch.from_numpy(start).to(map.device), torch.from_numpy(entry).to(map.device)
+
+
+def render_backward_torch(g, map, lists, h, w, vh, vw, ss, accumulate_into=None):
+    """the gradient of render_torch (clamp=False) with respect to x, in the order of include/pconv_hip.h
+    (pconv_remap_backward_f32), float32 operation by operation on any device (the CPU path and the kernel's twin):
+    float32 (n, C, vh, vw), the map and its `reverse_lists` -> (n, C, h, w).  Every source pixel has one accumulator,
+    starting at +0 (accumulate_into: at that tensor's values; a new tensor is returned either way), to which the terms
+    ((g' wy[a]) wx[b]) of its list are added front to back, g' = g for ss = 1 and g float32(1 / ss^2) otherwise.
+    Vectorised in rounds: round k adds the k-th entry of every list that has one"""
+    h, w = _check_source(h, w)
+    vh, vw = _size((vh, vw))
+    ss = _check_ss(ss)
+    gw = vw * ss
+    if g.dim() != 4 or g.dtype != torch.float32 or tuple(g.shape[2:]) != (vh, vw):
+        raise PconvError("viewport: a float32 (n, C, %d, %d) gradient expected, got %s %s" % (vh, vw, g.dtype, tuple(g.shape)))
+    if map.dtype != torch.int32 or tuple(map.shape) != (vh * ss, gw, 2) or map.device != g.device:
+        raise PconvError("viewport: the map must be int32 (%d, %d, 2) on the gradient's device, got %s %s on %s"
+                         % (vh * ss, gw, map.dtype, tuple(map.shape), map.device))
+    start, entry = (t.to(g.device).long() for t in lists)
+    if start.numel() != h * w + 1 or entry.numel() != 36 * vh * ss * gw:
+        raise PconvError("viewport: the lists are not those of this map and a %dx%d source" % (w, h))
+    n, c = g.shape[:2]
+    if accumulate_into is None:
+        acc = torch.zeros((n, c, h * w), dtype=torch.float32, device=g.device)
+    else:
+        if tuple(accumulate_into.shape) != (n, c, h, w) or accumulate_into.dtype != torch.float32:
+            raise PconvError("viewport: accumulate_into must be float32 (%d, %d, %d, %d)" % (n, c, h, w))
+        acc = accumulate_into.to(g.device).reshape(n, c, h * w).clone()
+    table = erp_rotate.phases().to(g.device)
+    records = map.reshape(-1, 2).long()
+    flat = g.reshape(n, c, vh * vw)
+    if ss > 1:
+        flat = flat * torch.tensor(np.float32(1.0 / (ss * ss)), device=g.device)
+    length = start[1:] - start[:-1]
+    alive = torch.nonzero(length > 0).flatten()      # the destinations that still have an entry in round k
+    k = 0
+    while alive.numel():
+        e = entry[start[alive] + k]
+        s, a, b = torch.div(e, 36, rounding_mode="floor"), torch.div(e, 6, rounding_mode="floor") % 6, e % 6
+        rec = records[s]
+        wy, wx = table[torch.remainder(rec[:, 1], PHASES), a], table[torch.remainder(rec[:, 0], PHASES), b]
+        r, q = torch.div(s, gw, rounding_mode="floor"), s % gw
+        pixel = torch.div(r, ss, rounding_mode="floor") * vw + torch.div(q, ss, rounding_mode="floor")
+        acc[:, :, alive] = acc[:, :, alive] + (flat[:, :, pixel] * wy) * wx
+        k += 1
+        alive = alive[length[alive] > k]
+    return acc.reshape(n, c, h, w)
+
+
+class _Remap(torch.autograd.Function):
+    """"sampler over maps plus ss x ss average" under autograd: (n, C, h, w) -> (n, V, C, vh, vw).  `forward` is the
+    caller's unclamped forward; `views` holds per view (map, lists, ss), lists a callable that builds them at the first
+    backward.  Backward: the views in ascending k into one gradient, accumulating from the second on -- the kernel for
+    GPU tensors, render_backward_torch for CPU tensors: the same bits on the same maps.  clamp: torch.clamp's gradient,
+    zero where the unclamped value lay outside [0, 1]"""
+
+    @staticmethod
+    def forward(ctx, x, forward, views, clamp):
+        out = forward(x)
+        ctx.views, ctx.source = views, tuple(x.shape[2:])
+        if clamp:
+            ctx.save_for_backward((out >= 0.0) & (out <= 1.0))
+            out = out.clamp_(0.0, 1.0)
+        ctx.clamp = clamp
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if ctx.clamp:
+            g = torch.where(ctx.saved_tensors[0], g, torch.zeros((), dtype=g.dtype, device=g.device))
+        g = g.contiguous()
+        (h, w), (vh, vw) = ctx.source, g.shape[3:]
+        ops = None
+        if g.is_cuda:
+            ops = backend.ops()
+            if not hasattr(ops, "remap_backward_f32"):
+                raise PconvError("viewport: the active backend has no remap_backward_f32 kernel for a GPU tensor")
+        gin = None
+        for k, (q, lists, ss) in enumerate(ctx.views):
+            if ops is not None:
+                gin = ops.remap_backward_f32(g, q, lists(), h, w, vh, vw, ss, gin, k, k > 0)
+            else:
+                gin = render_backward_torch(g[:, k], q, lists(), h, w, vh, vw, ss, gin)
+        return gin, None, None, None
+
+
 def ratio(h, w, view, vh, vw):
     """source pixels per view pixel at the centre of the view, the larger of the two axes (float64)"""
     h, w = _check_source(h, w)
@@ -237,6 +353,7 @@ class Renderer(object):
             self.plans = [(self.h, self.w, _check_ss(ss))] * len(self.views)
         self.maps = [source_map(h2, w2, self.vh * k, self.vw * k, v, self.device)
                      for v, (h2, w2, k) in zip(self.views, self.plans)]
+        self._lists = [None] * len(self.views)   # the reverse lists of the backward, built when first asked for
 
     @property
     def ss(self):
@@ -246,7 +363,37 @@ class Renderer(object):
 
     def render(self, x, clamp=False, out=None):
         """float32 (n, C, h, w) on the renderer's device -> (n, V, C, vh, vw): one render launch per view for GPU
-        tensors, the twin for CPU tensors.  clamp=True bounds the result to [0, 1]"""
+        tensors, the twin for CPU tensors.  clamp=True bounds the result to [0, 1].  With grad mode on and x requiring a
+        gradient the result is attached to autograd (one Function; `_Remap`): the values are the same, the backward is the
+        ordered one of include/pconv_hip.h (pconv_remap_backward_f32), view after view in ascending k, its lists built at
+        the first backward and held by the renderer (144 bytes per grid sample and view).  Refused then: out=, and a
+        view whose plan reads a reduced source (the resize in front carries no gradient)"""
+        if torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad:
+            if out is not None:
+                raise PconvError("viewport: out= cannot be combined with a gradient: the result of an input that requires "
+                                 "grad is a new tensor attached to autograd")
+            for k, (h2, w2, _) in enumerate(self.plans):
+                if (h2, w2) != (self.h, self.w):
+                    raise PconvError("viewport: view %d reads the source reduced to %dx%d (viewport.plan): the resize in "
+                                     "front of the renderer carries no gradient" % (k, w2, h2))
+            self._check_frames(x)
+            views = [(q, (lambda k=k: self.lists(k)), p[2]) for k, (p, q) in enumerate(zip(self.plans, self.maps))]
+            return _Remap.apply(x, self._render, views, bool(clamp))
+        return self._render(x, clamp, out)
+
+    def lists(self, k):
+        """the reverse lists of view k (reverse_lists), built at the first call and kept"""
+        if self._lists[k] is None:
+            h2, w2, _ = self.plans[k]
+            self._lists[k] = reverse_lists(self.maps[k], h2, w2)
+        return self._lists[k]
+
+    def _check_frames(self, x):
+        if x.dim() != 4 or x.dtype != torch.float32 or tuple(x.shape[2:]) != (self.h, self.w) or x.device != self.device:
+            raise PconvError("viewport: float32 (n, C, %d, %d) on %s expected, got %s %s on %s"
+                             % (self.h, self.w, self.device, x.dtype, tuple(x.shape), x.device))
+
+    def _render(self, x, clamp=False, out=None):
         if x.dim() != 4 or x.dtype != torch.float32 or tuple(x.shape[2:]) != (self.h, self.w) or x.device != self.device:
             raise PconvError("viewport: float32 (n, C, %d, %d) on %s expected, got %s %s on %s"
                              % (self.h, self.w, self.device, x.dtype, tuple(x.shape), x.device))
@@ -288,5 +435,18 @@ def metrics(renderer, x, y):
     total = None
     for k in range(len(renderer.views)):
         m = sphere_metrics.metrics(vx[:, k].contiguous(), vy[:, k].contiguous(), "uniform")
+        total = m if total is None else total + m
+    return total / len(renderer.views)
+
+
+def loss_terms(renderer, x, y):
+    """float64 (n, 2) [MSE, SSIM] of two batches seen through `renderer`, on the inputs' device and attached to autograd:
+    the values of `metrics`, as a loss.  Per view k, sphere_metrics.loss_terms(vx[:, k], vy[:, k], "uniform") of the
+    rendered views; the views summed in ascending k in float64 and divided by V -- the sum `metrics` makes, so the two
+    agree exactly.  The gradient reaches x and y through the renderer's ordered backward (Renderer.render)"""
+    vx, vy = renderer.render(x), renderer.render(y)
+    total = None
+    for k in range(len(renderer.views)):
+        m = sphere_metrics.loss_terms(vx[:, k].contiguous(), vy[:, k].contiguous(), "uniform")
         total = m if total is None else total + m
     return total / len(renderer.views)
