@@ -446,6 +446,58 @@ int pconv_viewport_map(int32_t *map, int h, int w, int gh, int gw, int yaw, int 
 int pconv_viewport_render_f32(const float *in, float *out, const int32_t *map, const float *phases, int n, int c, int h,
                               int w, int vh, int vw, int ss, long long out_frame_stride, int clamp, void *stream);
 
+/* Sphere-sampled metrics: S-PSNR-NN, S-PSNR-I, CPP-PSNR (csrc/sphere_points.hip; pseudocylindrical_convolution_amd/
+ * sphere_points.py states the same definition in torch and numpy).  Two ERP pictures of ANY two sizes are read at the
+ * same points of the sphere and the squared error is summed over the points; neither picture is resampled onto the
+ * other's grid.  The point sets (an icosphere, the pixels of a Craster parabolic picture, a file) are built on the host
+ * by sphere_points.py; 360Lib's own point file is not part of this project, so equality of the figures with 360Lib's is
+ * not claimed.
+ * Point: a direction given as two doubles, longitude t in [-pi, pi] and latitude p in [-pi/2, pi/2], in the ERP
+ *   convention of the sphere rotation above.  A point set is float64 (P, 2) of (t, p) in a fixed order, 1 <= P < 2^28.
+ * Record of a point for a picture of h x w (pconv_sphere_points_records: (P, 2) int32 on the device), all in fp64, in
+ *   THIS ORDER, every operation one rounding, never contracted, no transcendental:
+ *     u = ((t / TWO_PI) + 0.5) * w - 0.5        TWO_PI = 6.283185307179586 (the double nearest 2*pi)
+ *     v = (0.5 - (p / PI)) * h - 0.5            PI = 3.141592653589793
+ *     qu = rint(u * 256) reduced modulo w * 256 (the mathematical modulo, 0 <= qu < w * 256);  qv = rint(v * 256)
+ *   rint rounds halves to even.  These are the records of pconv_erp_rotation_map without the trigonometry, so the
+ *   kernel and a float64 evaluation on the host in the same order give EQUAL records, with no exception near a rounding
+ *   boundary.  A position is quantised to 1/256 pixel BEFORE the nearest / Lanczos choice below.
+ * Sample, mode PCONV_SPHERE_POINTS_LANCZOS (S-PSNR-I, CPP-PSNR): the sampler of pconv_erp_remap_f32, word for word, at
+ *   the record: 6 x 6 Lanczos-3 from the phase table of pconv_host_lanczos_phases, columns wrapped, rows by the pole rule
+ *   with the half turn and then clamped, both sums ascending, one fp32 rounding per product and per addition, never
+ *   contracted, no clamp of the value.  This is this project's interpolator, not 360Lib's.
+ * Sample, mode PCONV_SPHERE_POINTS_NEAREST (S-PSNR-NN): column = floor((qu + 128) / 256) mod w; row = floor((qv + 128)
+ *   / 256), then through the pole rule (r < 0 -> -1 - r; r >= h -> 2*h - 1 - r); a row that crossed a pole takes
+ *   (column + floor(w / 2)) mod w; then the row is clamped to [0, h - 1].  The value is the pixel itself, no arithmetic.
+ * pconv_sphere_points_sample_f32: in (n, C, h, w) -> out (n, C, P), out[f][c][k] the sample of plane (f, c) at record
+ *   k.  It reads a panorama at arbitrary directions and is public in its own right.
+ * Error of a point (pconv_sphere_points_mse_f32), a the sample of picture x (h1 x w1) at rec_x[k], b the sample of
+ *   picture y (h2 x w2) at rec_y[k]:  d = a - b in fp32;  e_k = d * d in fp32, widened to double.
+ * Sum, per plane (f, c), in fp64, in THIS ORDER, which depends on P alone (not on the batch, the grid or the device):
+ *   chunks of PCONV_SPHERE_POINTS_CHUNK = 1024 consecutive points, chunk q = points 1024*q .. 1024*q + 1023 (the last
+ *   one partial).  Lane l of 256 starts at +0 and adds e of the points l, l + 256, l + 512, l + 768 of its chunk that
+ *   exist, ascending.  Tree: for s = 128, 64, 32, 16, 8, 4, 2, 1: lane l < s takes lane[l] + lane[l + s].  Lane 0 holds
+ *   the chunk's partial, stored in the workspace (one double per plane and chunk).  A second launch sums a plane's
+ *   partials the same way: lane l of 256 starts at +0 and adds the partials l, l + 256, l + 512, ... ascending, then
+ *   the same tree; out[f][c] = SSE / P.  No atomics, no allocation; nothing of size P * n * C is written.
+ *   A figure is 10 * log10(1 / mean over the channels of out[f]); RGB channels are thus averaged where 360Lib reports Y,
+ *   U and V, and out keeps the per-channel values for a caller with planar data.
+ * Tensors 4-byte aligned; points, records, workspace and out 8-byte aligned; phases (256 x 6 float32) on the device in
+ *   both modes.  Every record is reduced to a position inside its frame, so no record content makes a kernel read outside
+ *   a picture.  Refused on the host, before any launch, with PCONV_EINVAL (workspace_bytes: a negative value): null or
+ *   misaligned pointers, a side outside 2 .. 2^20, a plane of 2^31 bytes or more, n * C outside 1 .. 65535, P outside
+ *   1 .. 2^28 - 1, an unknown mode, in == out (sample), out or the workspace inside x or y (mse).  x == y is allowed. */
+#define PCONV_SPHERE_POINTS_LANCZOS 0
+#define PCONV_SPHERE_POINTS_NEAREST 1
+#define PCONV_SPHERE_POINTS_CHUNK 1024
+int pconv_sphere_points_records(const double *points, int32_t *records, long long P, int h, int w, void *stream);
+int pconv_sphere_points_sample_f32(const float *in, float *out, const int32_t *records, const float *phases, int n, int c,
+                                   int h, int w, long long P, int mode, void *stream);
+long long pconv_sphere_points_mse_workspace_bytes(int n, int c, long long P);
+int pconv_sphere_points_mse_f32(const float *x, int h1, int w1, const int32_t *rec_x, const float *y, int h2, int w2,
+                                const int32_t *rec_y, const float *phases, int n, int c, long long P, int mode,
+                                void *workspace, double *out, void *stream);
+
 /* Ordered backward of the renderer and of the sphere rotation (csrc/remap_backward.hip, csrc/geometry.cpp; viewport.py
  * states the same definition in torch: render_backward_torch).  The forward of view pixel (j, i) of plane (n, c) is the
  * one above without the clamp: S = sum_a wy[a] * (sum_b wx[b] * x[r_a][c_b]) at each of the ss*ss records (j*ss + p,

@@ -1700,6 +1700,96 @@ def _viewport_phases(device):
     return _rotate_phases[device]
 
 
+SPHERE_POINTS_MODES = {"lanczos": 0, "nearest": 1}  # PCONV_SPHERE_POINTS_LANCZOS, PCONV_SPHERE_POINTS_NEAREST
+SPHERE_POINTS_MAX = (1 << 28) - 1
+
+
+def _sphere_points_mode(what, interp):
+    if interp not in SPHERE_POINTS_MODES:
+        raise PconvError("%s: interp must be one of %s, got %r" % (what, sorted(SPHERE_POINTS_MODES), interp))
+    return SPHERE_POINTS_MODES[interp]
+
+
+def _sphere_points_records_of(what, rec, x):
+    """the record count of `rec`, contiguous int32 (P, 2) on x's device"""
+    if rec.dtype != torch.int32 or rec.dim() != 2 or rec.shape[1] != 2 or not rec.is_contiguous() or rec.device != x.device \
+            or not 1 <= rec.shape[0] <= SPHERE_POINTS_MAX:
+        raise PconvError("%s: the records must be contiguous int32 (P, 2), 1 <= P < 2^28, on the input's device, got %s %s "
+                         "on %s" % (what, rec.dtype, tuple(rec.shape), rec.device))
+    return rec.shape[0]
+
+
+def sphere_points_records(points, h, w, out=None):
+    """int32 (P, 2) GPU tensor: the 1/256-pixel records of the points (float64 (P, 2) of (longitude, latitude) on the
+    device) for a picture of h x w (sphere_points.py, pconv_sphere_points_records).  One launch, fp64, no trigonometry"""
+    h, w = int(h), int(w)
+    if not points.is_cuda or points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 2 \
+            or not points.is_contiguous() or not 1 <= points.shape[0] <= SPHERE_POINTS_MAX:
+        raise PconvError("sphere_points_records: contiguous float64 (P, 2) points, 1 <= P < 2^28, on a GPU expected, got %s "
+                         "%s on %s" % (points.dtype, tuple(points.shape), points.device))
+    if not (2 <= h <= 1 << 20 and 2 <= w <= 1 << 20) or 4 * h * w >= 1 << 31:
+        raise PconvError("sphere_points_records: %dx%d: sides of 2 .. 2^20 and a plane below 2^31 bytes expected" % (w, h))
+    count = points.shape[0]
+    if out is None:
+        out = torch.empty((count, 2), dtype=torch.int32, device=points.device)
+    elif tuple(out.shape) != (count, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != points.device:
+        raise PconvError("sphere_points_records: out must be contiguous int32 (%d, 2) on the points' device" % count)
+    with _HbmTimed("sphere_points_records_kernel", "SpherePointsRecords %dx%d P%d" % (w, h, count), 24.0 * count, points.device):
+        call("pconv_sphere_points_records", _ptr(points), _ptr(out), count, h, w, _stream(points.device))
+    return out
+
+
+def sphere_points_sample_f32(x, records, interp="lanczos", out=None):
+    """float32 (n, C, h, w) GPU tensor -> (n, C, P): every plane read at the records (int32 (P, 2) on the same device,
+    from sphere_points_records for this h x w) with the 6 x 6 Lanczos-3 footprint of erp_rotate.py or, interp="nearest",
+    the nearest pixel (pconv_sphere_points_sample_f32)"""
+    _require_gpu(x, "sphere_points_sample_f32")
+    if x.dim() != 4:
+        raise PconvError("sphere_points_sample_f32: float32 (n, C, h, w) expected")
+    mode = _sphere_points_mode("sphere_points_sample_f32", interp)
+    count = _sphere_points_records_of("sphere_points_sample_f32", records, x)
+    n, c, h, w = x.shape
+    if out is None:
+        out = torch.empty((n, c, count), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, c, count) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise PconvError("sphere_points_sample_f32: out must be contiguous float32 (%d, %d, %d) on the input's device" % (n, c, count))
+    # the algorithmic bytes of the gather: one pixel (nearest) or 36 (lanczos) per point and plane, the output, the records
+    counted = 4.0 * n * c * count * ((36 if mode == 0 else 1) + 1) + 8.0 * n * count
+    with _HbmTimed("sphere_points_sample_kernel", "SpherePointsSample %dx%d n%d P%d" % (w, h, n, count), counted, x.device):
+        call("pconv_sphere_points_sample_f32", _ptr(x), _ptr(out), _ptr(records), _ptr(_viewport_phases(x.device)), n, c, h, w,
+             count, mode, _stream(x.device))
+    return out
+
+
+def sphere_points_mse_device(x, rec_x, y, rec_y, interp="lanczos"):
+    """float64 (n, C) on the inputs' device: the mean over the P points of (a - b)^2, a the sample of x (n, C, h1, w1) at
+    rec_x and b the sample of y (n, C, h2, w2) at rec_y, the difference and its square in fp32, the sum in fp64 in the
+    order of include/pconv_hip.h (pconv_sphere_points_mse_f32).  Two launches, no sample is written; nothing waits"""
+    _require_gpu(x, "sphere_points_mse")
+    _require_gpu(y, "sphere_points_mse")
+    if x.dim() != 4 or y.dim() != 4 or x.shape[:2] != y.shape[:2] or x.device != y.device:
+        raise PconvError("sphere_points_mse: two float32 (n, C, h, w) batches of equal n and C on one device expected, got "
+                         "%s on %s and %s on %s" % (tuple(x.shape), x.device, tuple(y.shape), y.device))
+    mode = _sphere_points_mode("sphere_points_mse", interp)
+    count = _sphere_points_records_of("sphere_points_mse", rec_x, x)
+    if _sphere_points_records_of("sphere_points_mse", rec_y, y) != count:
+        raise PconvError("sphere_points_mse: the two record lists differ in length: %d and %d" % (count, rec_y.shape[0]))
+    n, c = x.shape[:2]
+    nbytes = call("pconv_sphere_points_mse_workspace_bytes", n, c, count)
+    workspace = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    out = torch.empty((n, c), dtype=torch.float64, device=x.device)
+    counted = 4.0 * n * c * count * 2 * (36 if mode == 0 else 1) + 16.0 * n * c * count
+    with _HbmTimed("sphere_points_mse_kernel", "SpherePointsMse n%d P%d" % (n, count), counted, x.device):
+        call("pconv_sphere_points_mse_f32", _ptr(x), x.shape[2], x.shape[3], _ptr(rec_x), _ptr(y), y.shape[2], y.shape[3],
+             _ptr(rec_y), _ptr(_viewport_phases(x.device)), n, c, count, mode, _ptr(workspace), _ptr(out), _stream(x.device))
+    return out
+
+
+def sphere_points_mse(x, rec_x, y, rec_y, interp="lanczos"):
+    """sphere_points_mse_device with the float64 (n, C) result copied to the host"""
+    return sphere_points_mse_device(x, rec_x, y, rec_y, interp).cpu()
+
+
 def viewport_map(h, w, gh, gw, view, device=None, out=None):
     """int32 (gh, gw, 2) GPU tensor: where on the h x w source each sample of the gh x gw grid of a rectilinear view
     lies, in 1/256 pixel (viewport.py, pconv_viewport_map).  view: (yaw, pitch, roll, hfov, vfov) in units of 2^-16

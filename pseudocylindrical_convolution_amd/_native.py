@@ -69,6 +69,10 @@ _HIP_SIGNATURES = {
     "pconv_host_remap_reverse_size": [I, I],
     "pconv_host_remap_reverse": [P, I, I, I, I, P, P],
     "pconv_remap_backward_f32": [P, P, P, P, P, P, I, I, I, I, I, I, I, LL, I, P],
+    "pconv_sphere_points_records": [P, P, LL, I, I, P],
+    "pconv_sphere_points_sample_f32": [P, P, P, P, I, I, I, I, LL, I, P],
+    "pconv_sphere_points_mse_workspace_bytes": [I, I, LL],
+    "pconv_sphere_points_mse_f32": [P, I, I, P, P, I, I, P, P, I, I, LL, I, P, P, P],
     "pconv_project": [P, P, P, I, I, I, I, I, I, I, I, P],
     "pconv_context_reshape": [P, P, I, I, I, I, I, P],
     "pconv_mask_constrain": [P, I, I, I, I, I, P],
@@ -220,6 +224,7 @@ def hip_lib():
         lib.pconv_ws_msssim_workspace_bytes.restype = c_longlong
         lib.pconv_ws_msssim_backward_workspace_bytes.restype = c_longlong
         lib.pconv_erp_resample_workspace_bytes.restype = c_longlong
+        lib.pconv_sphere_points_mse_workspace_bytes.restype = c_longlong
         lib.pconv_host_tap_reverse_size.restype = c_longlong
         lib.pconv_host_project_reverse_size.restype = c_longlong
         lib.pconv_host_remap_reverse_size.restype = c_longlong

@@ -31,6 +31,7 @@ HIP_SOURCES = [
     "viewport.hip",    # rectilinear viewports of ERP frames: the gnomonic source map and the supersampled renderer
     "remap_backward.hip",  # the ordered backward of the renderer and of the sphere rotation: a gather over reverse lists
     "sphere_metrics.hip",  # WS-PSNR / WS-SSIM / WS-MS-SSIM of ERP frames, forward and backward
+    "sphere_points.hip",  # S-PSNR-NN / S-PSNR-I / CPP-PSNR: two pictures of any sizes sampled at points of the sphere
     "entropy.hip",
     "entropy_engine.hip",
     "entropy_mfma.hip",

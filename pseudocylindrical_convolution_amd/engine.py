@@ -379,21 +379,27 @@ class CodecEngine(object):
         return self._rate_of_symbols(self.symbols(frames).contiguous(), frames.shape[0], rate_map)
 
     @torch.no_grad()
-    def evaluate(self, frames, rate_map=False, code_size=None, rotation=None):
+    def evaluate(self, frames, rate_map=False, code_size=None, rotation=None, coded=False):
         """one rate-distortion point without a file: (bits, reconstruction[, map]).  The symbols are computed once;
         bits (and map) are rate()'s, the reconstruction is decode(encode(frames), H, W)'s -- the entropy decoder
         returns exactly the symbols the encoder holds (tests/test_gpu_engine.py), so neither it nor the arithmetic
         coder has to run.  code_size=(h2, w2): the frames are coded at h2 x w2 (resized as encode() resizes them) and
         the reconstruction is returned at the frames' own size, resized back with the clamp: the end-to-end point.
         rotation: the frames are coded in that orientation (as encode() turns them) and the reconstruction is returned
-        in the frames' own orientation, turned back last."""
+        in the frames' own orientation, turned back last.  coded=True: one more element at the end, the reconstruction
+        at the coded size (cropped to code_size, not resized back) -- None unless code_size changes the size and there is
+        no rotation: what sphere_points scores against the frames with no resize in between."""
         geometry = FrameGeometry(frames.shape[2:], code_size, rotation)
         frames = geometry.to_coded(frames)
         n = frames.shape[0]
         sym = self.symbols(frames).contiguous()
         res = self._rate_of_symbols(sym, n, rate_map)
-        rec = geometry.from_coded(self.reconstruct(sym, n))
-        return (res[0], rec, res[1]) if rate_map else (res, rec)
+        raw = self.reconstruct(sym, n)
+        rec = geometry.from_coded(raw)
+        out = (res[0], rec, res[1]) if rate_map else (res, rec)
+        if coded:
+            out += (geometry.from_coded(raw, to_source=False) if geometry.resized and not geometry.rotated else None,)
+        return out
 
     # frames per pipeline stage of decode(); 0 = decode all frames of a call together, then run the
     # synthesis transforms (PCONV_DECODE_CHUNK overrides)

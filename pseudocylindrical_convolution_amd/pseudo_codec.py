@@ -10,6 +10,9 @@ Differences from the reference, all additive:
     coded at coded_size(h, w), the decoder crops back (container version 2,
     command line --native-size);
   * --test --ws adds WS-PSNR / WS-SSIM (sphere_metrics.py) beside the viewport figures, --ms-ssim with it WS-MS-SSIM;
+  * --test --sphere / --rd --sphere add S-PSNR-NN / S-PSNR-I / CPP-PSNR (sphere_points.py: both pictures sampled at the
+    same points of the sphere) and, for a file coded with --code-size, the same three of the reconstruction at the coded
+    size against the source at its own;
   * --yuv / --yuv-out code raw YUV 4:2:0 files (yuv.py: yuv420p, nv12, yuv420p10le), one code file per frame, the
     colour conversion on the GPU; --test --ws then adds WS-PSNR-Y/U/V.  The stream and the container are the RGB ones:
     the decoder is told the pixel format on the command line;
@@ -556,11 +559,27 @@ class ViewportScore(object):
         return sphere_metrics.psnr(mse_loss), ssim, '({} views {}x{}, ss={})'.format(len(r.views), r.vw, r.vh, r.ss)
 
 
+class SphereScore(object):
+    """--sphere: S-PSNR-NN, S-PSNR-I (the icosphere of level 8) and CPP-PSNR (the CPP grid of the original's size) of
+    sphere_points.py.  Called on (original, decoded), float32 (1, 3, h, w) batches of ANY two sizes, it returns the three
+    figures in dB: the HIP kernels on the GPU, the torch twins on the CPU (oracle backend)"""
+
+    def __init__(self, device_id=0):
+        self.dev = torch.device(backend.device_of(device_id))
+
+    def __call__(self, original, decoded):
+        from . import sphere_points
+        x, y = original.to(self.dev).contiguous(), decoded.to(self.dev).contiguous()
+        return tuple(f(x, y)[0].item() for f in (sphere_points.s_psnr_nn, sphere_points.s_psnr_i, sphere_points.cpp_psnr))
+
+
 _VIEWPORT = 'Bitrate:{:.3f}bpp, PSNR:{:.2f}dB, SSIM:{:.4f}'
 _WS = 'WS-PSNR:{:.2f}dB, WS-SSIM:{:.4f}'
 _WS_YUV = 'WS-PSNR-Y:{:.2f}dB, WS-PSNR-U:{:.2f}dB, WS-PSNR-V:{:.2f}dB'
 _WS_MS = 'WS-MS-SSIM:{:.4f}'
 _VP = 'VP-PSNR:{:.2f}dB, VP-SSIM:{:.4f} '
+_SPHERE = 'S-PSNR-NN:{:.2f}dB, S-PSNR-I:{:.2f}dB, CPP-PSNR:{:.2f}dB'
+_SPHERE_CODED = _SPHERE + ' (coded size)'
 
 
 def _vp_row(scorer, rows, texts, original, decoded):
@@ -576,6 +595,28 @@ def _vp_line(texts):
     return _VP + (texts[0] if len(set(texts)) == 1 else '(sizes differ)')
 
 
+def _sphere_row(scorer, rows, coded, original, decoded, at_coded_size):
+    """--sphere: the three figures of the source against the end-to-end reconstruction join the image's row and its line
+    is printed; at_coded_size (the reconstruction at the coded size of a file coded with --code-size, or None) gets a
+    second line, the source at its own size against that picture at its own: no resize in between"""
+    rows[-1] += scorer(original, decoded)
+    print(' ' + _SPHERE.format(*rows[-1][-3:]))
+    coded.append(None if at_coded_size is None else scorer(original, at_coded_size))
+    if coded[-1] is not None:
+        print(' ' + _SPHERE_CODED.format(*coded[-1]))
+
+
+def _sphere_lines(rows, coded):
+    """--sphere: the formats of the average's lines; the coded-size figures join the rows (their last three columns) and
+    get their line when every image has them"""
+    if not coded:
+        return []
+    if any(c is None for c in coded):
+        return [_SPHERE]
+    rows[:] = [r + c for r, c in zip(rows, coded)]
+    return [_SPHERE, _SPHERE_CODED]
+
+
 def _report(rows, lines):
     """print the 'Average Performance' block of --test / --rd: the column averages of `rows`, each format string of
     `lines` taking the next columns it has fields for; returns rows"""
@@ -589,8 +630,12 @@ def _report(rows, lines):
 
 
 def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False,
-                      ws=False, rotation=None, ms_ssim=False, vp=None):
-    """reference: pseudo_codec.py:263-290.  vp (--vp: True, or a size (vh, vw)): two more columns and one more line, the
+                      ws=False, rotation=None, ms_ssim=False, vp=None, sphere=False):
+    """reference: pseudo_codec.py:263-290.  sphere=True (--sphere): three more columns and one more line after everything
+    else, SphereScore's S-PSNR-NN / S-PSNR-I / CPP-PSNR of the source against the end-to-end reconstruction (the float
+    tensors, both at the source size); a file coded at a reduced size and not rotated gets a second line, `(coded size)`,
+    and when every file has it three further columns: the source at its own size against the reconstruction at the
+    coded size, sampled at the same points of the sphere.  vp (--vp: True, or a size (vh, vw)): two more columns and one more line, the
     PSNR / SSIM of ViewportScore, after whatever ws adds.  ws=True (--ws): each row also carries the WS-PSNR and WS-SSIM of the
     decoded image as written (tensor2img) against the source at the image's own size: (bpp, vpsnr, vssim, ws_psnr,
     ws_ssim), with a WS line per image and for the average.  A file coded at a reduced size (--code-size, container
@@ -602,6 +647,7 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
     scorer, texts = (ViewportScore(device_id, None if vp is True else vp), []) if vp else (None, [])
+    on_sphere, coded = SphereScore(device_id) if sphere else None, []
     rows = []
     for fc, fn in zip(code_list, img_list):
         rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw)
@@ -621,11 +667,15 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
                 print(' ' + _WS_MS.format(rows[-1][-1]))
         if vp:
             _vp_row(scorer, rows, texts, img2tensor(img, dev), rdata)
-    return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp))
+        if sphere:
+            small = geometry.from_coded(rec, to_source=False) if geometry.resized and not geometry.rotated else None
+            _sphere_row(on_sphere, rows, coded, img2tensor(img, dev), rdata, small)
+    return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp)
+                   + _sphere_lines(rows, coded))
 
 
 def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False,
-                    code_size=None, rotation=None, ms_ssim=False, vp=None):
+                    code_size=None, rotation=None, ms_ssim=False, vp=None, sphere=False):
     """--rd: what encoding() + decoding_and_test() report for the images, without a file in between.  The rate is
     the code length of the CDF rows the coder would get (rate.py: within a few bits of the stream), the
     reconstruction is the synthesis of the encoder's own symbols -- what the entropy decoder would hand back.
@@ -635,7 +685,8 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     rotation (--rotate): every image is coded in that orientation (erp_rotate.py) and scored, turned back, against the
     unrotated source.
     Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim[, ws_ms_ssim]]): the last with ms_ssim=True (--ms-ssim); vp (--vp) adds
-    ViewportScore's two columns at the end, as in decoding_and_test."""
+    ViewportScore's two columns at the end, as in decoding_and_test; sphere (--sphere) then adds SphereScore's three, and
+    with code_size and no rotation the three of the coded-size line, as in decoding_and_test."""
     from .engine import CodecEngine
     from . import rate
     (enc, dev), (dec, _) = _load("encoder", model_idx, mse, device_id), _load("decoder", model_idx, mse, device_id)
@@ -643,6 +694,7 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
     scorer, texts = (ViewportScore(device_id, None if vp is True else vp), []) if vp else (None, [])
+    on_sphere, coded = SphereScore(device_id) if sphere else None, []
     rows = []
     for fn in img_list:
         img = read_image(fn)
@@ -650,7 +702,11 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
             img = check_img(img, height, width)
         h, w = img.shape[:2]
         data = img2tensor(img, dev)
-        bits, rdata = codec.evaluate(data, code_size=code_size, rotation=rotation)
+        small = None
+        if sphere:
+            bits, rdata, small = codec.evaluate(data, code_size=code_size, rotation=rotation, coded=True)
+        else:
+            bits, rdata = codec.evaluate(data, code_size=code_size, rotation=rotation)
         pr, vssim = metrics(data, rdata)
         rt = rate.bpp(bits, h, w)[0].item()
         rows.append((rt, pr, vssim))
@@ -663,7 +719,10 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
                 print(' ' + _WS_MS.format(rows[-1][-1]))
         if vp:
             _vp_row(scorer, rows, texts, data, rdata)
-    return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp))
+        if sphere:
+            _sphere_row(on_sphere, rows, coded, data, rdata, small)
+    return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp)
+                   + _sphere_lines(rows, coded))
 
 
 def _yuv_rgb(frames, h, w, yuv_opts, dev):
@@ -870,6 +929,16 @@ def _view_flags(parser, args):
     return view, size, vp
 
 
+def _sphere_flag(parser, args):
+    """the checks of --sphere: it goes with --test or --rd, on images"""
+    if args.sphere:
+        if not (args.test or args.rd) or args.enc or args.dec:
+            parser.error("--sphere goes with --test or --rd")
+        if args.yuv is not None or args.yuv_out is not None:
+            parser.error("--sphere is for images: the 4:2:0 planes of --yuv are not sampled on the sphere")
+    return args.sphere
+
+
 def read_list(fname):
     with open(fname) as f:
         return [line.rstrip('\n') for line in f.readlines()]
@@ -941,6 +1010,11 @@ def main(argv=None):
                                                           'PSNR / SSIM of 14 anti-aliased rectilinear views of '
                                                           'WIDTHxHEIGHT (default: a quarter of the picture\'s width, 3:2) '
                                                           'rendered from each picture at its own size')
+    parser.add_argument('--sphere', action='store_true', default=False,
+                        help='Testing (--test / --rd): also report S-PSNR-NN, S-PSNR-I (an icosphere of 655 362 points) and '
+                             'CPP-PSNR: both pictures sampled at the same points of the sphere.  A file coded with '
+                             '--code-size gets a second line, the source against the reconstruction at the coded size, '
+                             'with no resize in between')
     parser.add_argument('--yuv', help='Encoding / testing: a raw YUV 4:2:0 file as the source instead of images, one '
                                       'code file per frame (needs --size and --pix-fmt)')
     parser.add_argument('--yuv-out', help='Decoding: write the decoded frames to this raw YUV 4:2:0 file, in the order '
@@ -955,6 +1029,7 @@ def main(argv=None):
     code_size = _code_size_flag(parser, args)
     rotation = _rotate_flag(parser, args)
     view, view_size, vp = _view_flags(parser, args)
+    sphere = _sphere_flag(parser, args)
     yuv_call = _yuv_flags(parser, args)   # contradictory YUV flags end the run here, before anything is loaded
     assert not args.ws or ((args.test or args.rd) and not args.enc and not args.dec), '--ws needs --test or --rd'
     assert not args.ms_ssim or args.ws, '--ms-ssim needs --ws'
@@ -987,7 +1062,7 @@ def main(argv=None):
     elif args.rd:
         assert img_list is not None, 'No input images for scoring'
         rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws,
-                        code_size=code_size, rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, **size)
+                        code_size=code_size, rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere, **size)
     elif args.enc:
         assert img_list is not None, 'No input images for encoding'
         assert code_list is not None, 'No code files for saving the codes'
@@ -1008,7 +1083,7 @@ def main(argv=None):
             assert img_list is not None, 'No source images for evaluation.'
             assert len(code_list) == len(img_list), 'The number of codes and corresponding source images should be the same'
             decoding_and_test(code_list, img_list, midx, not args.ssim, args.gpu_id, raw=args.raw, ws=args.ws,
-                              rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, **size)
+                              rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere, **size)
 
 
 if __name__ == '__main__':
