@@ -365,6 +365,49 @@ int pconv_erp_resample_f32(const float *in, float *out, void *workspace, const i
                            const int32_t *first_y, const float *wy, int ty, int n, int c, int h, int w, int h2, int w2,
                            int clamp, void *stream);
 
+/* Ordered backward of the resize (csrc/erp_resample_backward.hip; erp_resample.py states the same definition in torch:
+ * resize_backward_torch).  The forward, clamp aside, is mid[r][i] = sum_t wx[i][t] * x[r][(fx[i] + t) mod w] and
+ * out[j][i] = sum_t wy[j][t] * mid[rho(fy[j] + t)][kappa], rho the pole rule followed by the clamp to [0, h - 1], kappa =
+ * i, or (i + floor(w2 / 2)) mod w2 for a tap row that crossed a pole (judged before the clamp).  The backward is the
+ * adjoint of that linear map, gx = Ax^T Ay^T g, in THIS ORDER:
+ * Vertical adjoint, g (h2, w2) -> gmid (h, w2).  Destination gmid[r][c]: one fp32 accumulator.  Its terms: every table
+ *   entry (j, t), 0 <= t < T_y, with rho(fy[j] + t) = r -- the padded entries of weight +0.0 included: the table is the
+ *   data, not a tap count.  Term: wy[j][t] * g[j][i], i = c for an entry that did not cross a pole, i = (c - floor(w2 / 2))
+ *   mod w2 for one that did.  Order: j ascending, then t ascending; taps of one j that the pole rule or the clamp sends to
+ *   the same row are terms of their own.
+ * Horizontal adjoint, gmid -> gx (h, w).  Destination gx[r][c]; its terms: every entry (i, t), 0 <= t < T_x, with
+ *   (fx[i] + t) mod w = c (several t of one i coincide when w < T_x).  Term: wx[i][t] * gmid[r][i].  Order: i ascending,
+ *   then t ascending.
+ * Arithmetic, as in the forward: one __fmul_rn per term; the first product starts the chain; one __fadd_rn per further
+ *   term, never contracted; a destination with no term gets +0; gmid is rounded to float32 between the passes, as mid
+ *   is.  The clamp of the forward is the caller's: g is replaced by +0 where the unclamped value lay outside [0, 1]
+ *   before it comes here (torch.clamp's gradient).  Nothing depends on the launch grid, the workgroup, the batch or the
+ *   neighbours: one form, no float atomics.
+ * pconv_host_lanczos_reverse_size(n_in, n_out): n_out * T, the number of list entries of one axis; negative for a side
+ *   or a shrink pconv_host_lanczos_taps refuses.
+ * pconv_host_lanczos_reverse (host): the transposed table of one axis as CSR per source index, built from the very table
+ *   pconv_host_lanczos_taps returns: rev_start n_in + 1 int32, rev_entry n_out * T int32, entry e = i * T + t (so that
+ *   its weight is weights[e]), ascending within each list: a stable counting sort of the forward walk (i ascending, then
+ *   t) by destination, (first[i] + t) mod n_in for pole == 0, rho for pole != 0; crossed: n_out * T bytes, 1 where the
+ *   entry crossed a pole, written for pole != 0 only (it may be NULL otherwise).  Returns the entry count.  Refused,
+ *   before anything is written: null pointers, a side outside 2 .. 2^20, n_in > 8 * n_out.
+ * pconv_erp_resample_backward_f32: gout (n, C, h2, w2) -> gin (n, C, h, w); wx / wy are the DEVICE copies of the
+ *   forward's weight tables, the lists device copies of pconv_host_lanczos_reverse(w, w2, 0) and (h, h2, 1); workspace
+ *   is device memory of pconv_erp_resample_backward_workspace_bytes(...) bytes (gmid).  Two gathers of 256 lanes; a list
+ *   is never split across lanes; plain vector stores, 64-bit flat indices, no atomics, no allocation, no memset.  All
+ *   tensors 4-byte aligned (16-byte alignment enables the wide accesses).  An entry outside 0 .. n_out*T - 1 is skipped
+ *   and a start outside it clamped, so no list content makes a kernel read outside its buffers.  Refused on the host,
+ *   before any launch, with PCONV_EINVAL: what pconv_erp_resample_f32 refuses, null list pointers, gin == gout, tap
+ *   counts that are not the tables', and an enlargement so large (beyond about 15:1 in width) that the gradient columns
+ *   one tile of 1024 source columns gathers from exceed 64 KiB of LDS. */
+long long pconv_host_lanczos_reverse_size(int n_in, int n_out);
+int pconv_host_lanczos_reverse(int n_in, int n_out, int pole, int32_t *rev_start, int32_t *rev_entry, uint8_t *crossed);
+long long pconv_erp_resample_backward_workspace_bytes(int n, int c, int h, int w, int h2, int w2);
+int pconv_erp_resample_backward_f32(const float *gout, float *gin, void *workspace, const float *wx, int tx,
+                                    const int32_t *rev_start_x, const int32_t *rev_entry_x, const float *wy, int ty,
+                                    const int32_t *rev_start_y, const int32_t *rev_entry_y, const uint8_t *rev_crossed_y,
+                                    int n, int c, int h, int w, int h2, int w2, void *stream);
+
 /* Sphere rotation of ERP frames (csrc/erp_rotate.hip; pseudocylindrical_convolution_amd/erp_rotate.py states the same
  * definition in torch and numpy): float32 (n, C, h, w) -> (n, C, h, w), the picture of the same sphere in a rotated
  * orientation.  A map says where on the source each output pixel lies; a sampler reads the source there.

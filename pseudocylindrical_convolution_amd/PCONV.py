@@ -1639,6 +1639,48 @@ def erp_resample_f32(x, h2, w2, clamp=False, out=None, workspace=None):
     return out
 
 
+_resample_reverse = {}   # (device, h, w, h2, w2) -> (wx, start_x, entry_x, wy, start_y, entry_y, crossed_y) on the device
+
+
+def erp_resample_backward_f32(g, h, w, gin=None, workspace=None):
+    """the gradient of erp_resample_f32 (clamp=False) with respect to its input, in the order of include/pconv_hip.h
+    (pconv_erp_resample_backward_f32): float32 (n, C, h2, w2) GPU gradient of the resize of h x w frames -> (n, C, h, w).
+    The weight tables and the transposed lists (erp_resample.reverse_taps) live on the device, cached per (h, w, h2, w2);
+    gin: a contiguous float32 (n, C, h, w) tensor to write (allocated when None; every element is written); workspace:
+    a uint8 GPU tensor of at least pconv_erp_resample_backward_workspace_bytes bytes (allocated when None)"""
+    _require_gpu(g, "erp_resample_backward_f32")
+    if g.dim() != 4 or g.dtype != torch.float32 or not g.is_contiguous():
+        raise PconvError("erp_resample_backward_f32: a contiguous float32 (n, C, h2, w2) gradient expected, got %s %s"
+                         % (g.dtype, tuple(g.shape)))
+    n, c, h2, w2 = g.shape
+    h, w = int(h), int(w)
+    nbytes = call("pconv_erp_resample_backward_workspace_bytes", n, c, h, w, h2, w2)
+    key = (g.device, h, w, h2, w2)
+    if key not in _resample_reverse:
+        from .erp_resample import reverse_taps, taps
+        tables = (taps(w, w2)[1],) + reverse_taps(w, w2, 0)[:2] + (taps(h, h2)[1],) + reverse_taps(h, h2, 1)
+        _resample_reverse[key] = tuple(t.to(g.device) for t in tables)
+    wx, start_x, entry_x, wy, start_y, entry_y, crossed_y = _resample_reverse[key]
+    if gin is None:
+        gin = torch.empty((n, c, h, w), dtype=torch.float32, device=g.device)
+    elif tuple(gin.shape) != (n, c, h, w) or gin.dtype != torch.float32 or not gin.is_contiguous() or gin.device != g.device:
+        raise PconvError("erp_resample_backward_f32: gin must be contiguous float32 (%d, %d, %d, %d) on the gradient's device"
+                         % (n, c, h, w))
+    if workspace is None:
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=g.device)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous() or workspace.device != g.device:
+        raise PconvError("erp_resample_backward_f32: workspace must be a contiguous uint8 tensor of %d bytes on the gradient's "
+                         "device" % nbytes)
+    # gradient read + intermediate written and read + input gradient written
+    counted = 4.0 * (g.numel() + 2.0 * n * c * h * w2 + gin.numel())
+    with _HbmTimed("erp_resample_backward_kernels", "ErpResampleBackward %dx%d<-%dx%d n%d" % (w, h, w2, h2, n), counted,
+                   g.device):
+        call("pconv_erp_resample_backward_f32", _ptr(g), _ptr(gin), _ptr(workspace), _ptr(wx), wx.shape[1], _ptr(start_x),
+             _ptr(entry_x), _ptr(wy), wy.shape[1], _ptr(start_y), _ptr(entry_y), _ptr(crossed_y), n, c, h, w, h2, w2,
+             _stream(g.device))
+    return gin
+
+
 _rotate_phases = {}   # device -> the phase table of erp_rotate.phases() on the device
 
 

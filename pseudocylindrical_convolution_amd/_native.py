@@ -59,6 +59,10 @@ _HIP_SIGNATURES = {
     "pconv_host_lanczos_taps": [I, I, P, P, P],
     "pconv_erp_resample_workspace_bytes": [I, I, I, I, I, I],
     "pconv_erp_resample_f32": [P, P, P, P, P, I, P, P, I, I, I, I, I, I, I, I, P],
+    "pconv_host_lanczos_reverse_size": [I, I],
+    "pconv_host_lanczos_reverse": [I, I, I, P, P, P],
+    "pconv_erp_resample_backward_workspace_bytes": [I, I, I, I, I, I],
+    "pconv_erp_resample_backward_f32": [P, P, P, P, I, P, P, P, I, P, P, P, I, I, I, I, I, I, P],
     "pconv_host_erp_rotation_matrix": [I, I, I, I, P],
     "pconv_host_lanczos_phases": [P],
     "pconv_erp_rotation_map": [P, I, I, I, I, I, I, P],
@@ -224,6 +228,8 @@ def hip_lib():
         lib.pconv_ws_msssim_workspace_bytes.restype = c_longlong
         lib.pconv_ws_msssim_backward_workspace_bytes.restype = c_longlong
         lib.pconv_erp_resample_workspace_bytes.restype = c_longlong
+        lib.pconv_erp_resample_backward_workspace_bytes.restype = c_longlong
+        lib.pconv_host_lanczos_reverse_size.restype = c_longlong
         lib.pconv_sphere_points_mse_workspace_bytes.restype = c_longlong
         lib.pconv_host_tap_reverse_size.restype = c_longlong
         lib.pconv_host_project_reverse_size.restype = c_longlong

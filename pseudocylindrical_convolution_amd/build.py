@@ -27,6 +27,7 @@ HIP_SOURCES = [
     "erp_size.hip",    # pole / seam padding of ERP frames of any size, and the crop back
     "yuv.hip",         # YUV 4:2:0 frames: colour conversion fused with the pad / the crop
     "erp_resample.hip",  # sphere-aware Lanczos-3 resize of ERP frames (seam wrapped, poles continued)
+    "erp_resample_backward.hip",  # its ordered backward: two gathers over the transposed tap tables
     "erp_rotate.hip",  # sphere rotation of ERP frames: the source map and the 6 x 6 Lanczos-3 sampler
     "viewport.hip",    # rectilinear viewports of ERP frames: the gnomonic source map and the supersampled renderer
     "remap_backward.hip",  # the ordered backward of the renderer and of the sphere rotation: a gather over reverse lists

@@ -23,7 +23,10 @@ convolution of a training step is the vendor library's then, and `--optim native
 optimisers (accumulated gradient, global norm, clip, update) to optim.Adam, whose every operation include/pconv_hip.h
 defines.  The whole state of a run is written to `<prefix>_state.pt` at the end of every epoch and at an early stop
 (`--time-budget`, `--stop-after N` batches); `--resume` continues from it at the recorded epoch and batch and ends
-with the bits of the run that was never interrupted (optim.TrainState)."""
+with the bits of the run that was never interrupted (optim.TrainState).  `--code-size WxH` trains the reduced-size
+pipeline that `--test --code-size` scores: the batch is resized down (erp_resample.resize, clamped), the model runs at
+the coded size, its output is resized back under autograd (the resize's ordered backward) and every loss reads the
+frames at the source size; the rate counts bits over the source's pixels."""
 from __future__ import print_function
 
 import argparse
@@ -37,7 +40,7 @@ import torch
 import torch.distributed as dist
 from torch.nn.parallel import DistributedDataParallel as DDP
 
-from . import PCONV, model_zoo_v2, optim, sphere_metrics, viewport
+from . import PCONV, erp_resample, erp_size, model_zoo_v2, optim, sphere_metrics, viewport
 from .PCONV_operator import Logger, ModuleSaver, MultiProject, SSIM, backend
 from .RDMetric import mse_tb
 from .SphereDataset import (ProceduralSphereDataSet, SphereDataSet, SyntheticSphereDataSet,
@@ -59,15 +62,42 @@ def vp_size(text):
     return vh, vw
 
 
+def code_size(text):
+    """--code-size WxH -> (h2, w2); a size the codec does not take as it is (erp_size.codable) is refused"""
+    try:
+        w2, h2 = (int(v) for v in text.lower().split('x'))
+    except ValueError:
+        raise argparse.ArgumentTypeError('--code-size is WxH, e.g. 1024x512, got {!r}'.format(text))
+    if not erp_size.codable(h2, w2):
+        raise argparse.ArgumentTypeError('--code-size {}x{}: the model codes widths that are multiples of {} and heights '
+                                         'that are multiples of {}'.format(w2, h2, erp_size.COLS, erp_size.TILE_ROWS))
+    return h2, w2
+
+
+class _Parser(argparse.ArgumentParser):
+    """the checks that need two arguments at once are parser errors too"""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super(_Parser, self).parse_args(args, namespace)
+        if ns.code_size is not None:
+            for name, n_in, n_out in (('height', ns.height, ns.code_size[0]), ('width', ns.width, ns.code_size[1])):
+                if max(n_in, n_out) > erp_resample.MAX_SHRINK * min(n_in, n_out):   # the way there, or the way back
+                    self.error('--code-size: a {} of {} -> {} shrinks by more than {}:1 on the way there or back'.format(
+                        name, n_in, n_out, erp_resample.MAX_SHRINK))
+        return ns
+
+
 def vp_renderer(args, data):
     """the renderer of --loss vp for frames like `data`: the 14 paper directions (viewport.paper_views) at --vp-size, by
     default at the size --test --vp scores at (ViewportScore: vw = w // 4, vh = (2 vw + 1) // 3), anti-aliased by
-    viewport.plan; one per frame size and device, its maps built once"""
+    viewport.plan; one per frame size and device, its maps built once.  prefilter_grad: a view that plan renders from a
+    reduced source (more than 4 source pixels per view pixel) carries its gradient through the resize's ordered backward"""
     h, w = data.shape[2:]
     key = (h, w, str(data.device), getattr(args, 'vp_size', None))
     if key not in _vp_renderers:
         size = key[3] if key[3] is not None else ((2 * (w // 4) + 1) // 3, w // 4)
-        _vp_renderers[key] = viewport.Renderer(h, w, viewport.paper_views(size), size, device=data.device)
+        _vp_renderers[key] = viewport.Renderer(h, w, viewport.paper_views(size), size, device=data.device,
+                                               prefilter_grad=True)
     return _vp_renderers[key]
 
 
@@ -86,9 +116,15 @@ def forward_losses(args, model, data, pr1, pr2, sim_func):
     gradient through the renderer's ordered backward (pr1, pr2 and sim_func are None).  --loss viewport without a
     sim_func (--conv native-all): the SSIM term is sphere_metrics.loss_terms(uniform) over the views -- pytorch_ssim's
     map (the 11-tap sigma 1.5 window, zero padding of 5, its C1 and C2) on this project's kernels; all views have one
-    size, so the mean of the frame means is the mean of the map"""
-    out = model(data)
+    size, so the mean of the frame means is the mean of the map.  --code-size: the chain of FrameGeometry.to_coded /
+    from_coded -- the model sees the batch resized to the coded size (clamped; no gradient: it is data), its output comes
+    back to the source size through erp_resample.resize under autograd (clamped), every distortion term reads the
+    frames at the source size, and the rate per coded pixel is scaled by (h2 w2) / (h w): bits over the source's pixels"""
+    coded = getattr(args, 'code_size', None)
+    out = model(data if coded is None else erp_resample.resize(data, coded[0], coded[1], clamp=True))
     y, ent_vec, mask = out if isinstance(out, tuple) else (out, None, None)
+    if coded is not None:
+        y = erp_resample.resize(y, data.shape[2], data.shape[3], clamp=True)
     if args.loss in SPHERE_LOSSES:
         terms = SPHERE_LOSSES[args.loss](data, y)
         mse, ssim = terms[:, 0].mean(), terms[:, 1].mean()
@@ -103,6 +139,8 @@ def forward_losses(args, model, data, pr1, pr2, sim_func):
         else:
             ssim = sim_func(px, py)
     rate = None if ent_vec is None else torch.sum(ent_vec) / torch.sum(mask).item()
+    if rate is not None and coded is not None:
+        rate = rate * (float(coded[0] * coded[1]) / float(data.shape[2] * data.shape[3]))
     return mse, ssim, rate
 
 
@@ -423,6 +461,9 @@ def _job(rank, world_size, args):
         log.log('loss: MSE / SSIM over the 14 anti-aliased views of viewport.py at {} (--viewport_size is ignored)'.format(
             'the size of --test --vp (a quarter of the width)' if getattr(args, 'vp_size', None) is None else
             '{}x{}'.format(args.vp_size[1], args.vp_size[0])))
+    if getattr(args, 'code_size', None) is not None:
+        log.log('code size: the model runs at {}x{}; losses and rate are those of the frames at their own size'.format(
+            args.code_size[1], args.code_size[0]))
     log.log('valid dims:{} \t alpha:{}'.format(args.valid_dim, args.alpha))
     history = run.history   # of a resumed run: the epochs finished before it
     args.deadline = time.monotonic() + args.time_budget if args.time_budget > 0 else None
@@ -462,7 +503,7 @@ def _job(rank, world_size, args):
 
 
 def build_parser():
-    parser = argparse.ArgumentParser(description='PyTorch 360 Compression (MI355X)')
+    parser = _Parser(description='PyTorch 360 Compression (MI355X)')
     parser.add_argument('--gpus', type=int, default=0,
                         help='start this many ranks on this node (0: ranks come from the launcher environment)')
     parser.add_argument('--device', default='cuda', choices=['cuda', 'cpu'],
@@ -494,13 +535,18 @@ def build_parser():
                              'reports); ws-ms = WS-MSE and WS-MS-SSIM (sphere_metrics.ms_loss_terms: --test --ws --ms-ssim); '
                              'vp = MSE and SSIM over the 14 paper directions rendered by viewport.py, anti-aliased, at a '
                              'size that follows the frame (viewport.loss_terms: what --test --vp reports; the gradient '
-                             'runs through the renderer\'s ordered, atomic-free backward; no gradient through a '
-                             'prefiltered view, which a frame more than 4 source pixels per view pixel would need).  '
+                             'runs through the renderer\'s ordered, atomic-free backward, and for a view of more than 4 '
+                             'source pixels per view pixel through that of the resize in front of it).  '
                              'gamma, beta and alpha weigh the terms alike; with ws, ws-ms and vp the best checkpoint is '
                              'the one with the lowest gamma*mse + beta*(1 - ssim) + alpha*rate on the test set')
     parser.add_argument('--vp-size', type=vp_size, default=None, metavar='WxH',
                         help='size of a view of --loss vp (default: that of --test --vp, W = width // 4, H = (2 W + 1) // 3: '
                              '256x171 at 1024 columns)')
+    parser.add_argument('--code-size', type=code_size, default=None, metavar='WxH',
+                        help='train the reduced-size pipeline of --test --code-size: the batch is resized to WxH '
+                             '(erp_resample.resize), the model runs there, its output is resized back under autograd and '
+                             'every loss reads the frames at their own size; the rate is bits over the source\'s pixels.  '
+                             'WxH must be a size the model codes as it is, and no more than 8:1 below --width x --height')
     parser.add_argument('--viewport_size', type=int, default=171, metavar='viewport',
                         help='side of a projected view (ignored with --loss ws, ws-ms and vp)')
     parser.add_argument('--channels', type=int, default=192)

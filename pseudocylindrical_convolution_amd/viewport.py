@@ -35,8 +35,10 @@ ascending, then tap row a, then tap column b; the tap's pixel by the sampler's r
 terms of their own; a pixel no term reaches gets +0.  `reverse_lists` builds that order once per map on the host (a CSR
 list per source pixel from the very map the forward read), the kernel of csrc/remap_backward.hip
 (PCONV.remap_backward_f32) gathers along it without atomics, and `render_backward_torch` is its twin: the same bits on the
-same map and lists.  `loss_terms` is `metrics` as a loss (train.py --loss vp).  Limits: a list of at most 2^31 - 1
-entries, and no gradient through a prefiltered view (erp_resample.resize has no backward).
+same map and lists.  `loss_terms` is `metrics` as a loss (train.py --loss vp).  A view whose plan reads a reduced source
+carries a gradient only through a Renderer made with prefilter_grad=True: the reduced source is then made by
+erp_resample.resize under autograd, whose backward has a stated order as well (pconv_erp_resample_backward_f32), and
+the gradient of x is the sum over the source sizes.  Limit: a list of at most 2^31 - 1 entries.
 """
 import math
 
@@ -336,9 +338,12 @@ class Renderer(object):
     """The views `views` (quintuples of `view`) of h x w sources at `size` = (vh, vw), their maps built once on `device`
     (the HIP map kernel on a GPU, numpy on the CPU; 8 ss^2 bytes per pixel and view, held by this object alone).
     ss=None: every view takes `plan`'s supersampling and, where plan asks for it, its reduced source (resized once per
-    render call and size); ss=k: that supersampling on the source as it is."""
+    render call and size); ss=k: that supersampling on the source as it is.  prefilter_grad=True: under autograd a view
+    on a reduced source carries its gradient through erp_resample.resize's ordered backward; by default such a view
+    is refused then."""
 
-    def __init__(self, h, w, views, size, ss=None, device=None):
+    def __init__(self, h, w, views, size, ss=None, device=None, prefilter_grad=False):
+        self.prefilter_grad = bool(prefilter_grad)
         self.h, self.w = _check_source(h, w)
         self.vh, self.vw = _size(size)
         self.views = [check(v) for v in views]
@@ -366,20 +371,56 @@ class Renderer(object):
         tensors, the twin for CPU tensors.  clamp=True bounds the result to [0, 1].  With grad mode on and x requiring a
         gradient the result is attached to autograd (one Function; `_Remap`): the values are the same, the backward is the
         ordered one of include/pconv_hip.h (pconv_remap_backward_f32), view after view in ascending k, its lists built at
-        the first backward and held by the renderer (144 bytes per grid sample and view).  Refused then: out=, and a
-        view whose plan reads a reduced source (the resize in front carries no gradient)"""
+        the first backward and held by the renderer (144 bytes per grid sample and view).  Refused then: out=, and,
+        unless the renderer was made with prefilter_grad=True, a view whose plan reads a reduced source (the resize in
+        front carries no gradient by default).  With prefilter_grad=True each reduced source is made once per size by
+        erp_resample.resize under autograd (its ordered backward, pconv_erp_resample_backward_f32), the views of each
+        source size go through one `_Remap`, the result holds the views in their order, and the gradient of x is the
+        sum over the source sizes, made by autograd"""
         if torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad:
             if out is not None:
                 raise PconvError("viewport: out= cannot be combined with a gradient: the result of an input that requires "
                                  "grad is a new tensor attached to autograd")
+            sizes = []   # the source sizes of the plans, in the order the views first ask for them
             for k, (h2, w2, _) in enumerate(self.plans):
-                if (h2, w2) != (self.h, self.w):
+                if (h2, w2) != (self.h, self.w) and not self.prefilter_grad:
                     raise PconvError("viewport: view %d reads the source reduced to %dx%d (viewport.plan): the resize in "
                                      "front of the renderer carries no gradient" % (k, w2, h2))
+                if (h2, w2) not in sizes:
+                    sizes.append((h2, w2))
             self._check_frames(x)
-            views = [(q, (lambda k=k: self.lists(k)), p[2]) for k, (p, q) in enumerate(zip(self.plans, self.maps))]
-            return _Remap.apply(x, self._render, views, bool(clamp))
+            if sizes == [(self.h, self.w)]:
+                views = [(q, (lambda k=k: self.lists(k)), p[2]) for k, (p, q) in enumerate(zip(self.plans, self.maps))]
+                return _Remap.apply(x, self._render, views, bool(clamp))
+            rendered = [None] * len(self.views)
+            for h2, w2 in sizes:
+                ks = [k for k, p in enumerate(self.plans) if p[:2] == (h2, w2)]
+                src = x if (h2, w2) == (self.h, self.w) else erp_resample.resize(x, h2, w2)
+                views = [(self.maps[k], (lambda k=k: self.lists(k)), self.plans[k][2]) for k in ks]
+                group = _Remap.apply(src, (lambda s, ks=ks: self._render_views(s, ks)), views, bool(clamp))
+                for slot, k in enumerate(ks):
+                    rendered[k] = group[:, slot]
+            return torch.stack(rendered, dim=1)
         return self._render(x, clamp, out)
+
+    def _render_views(self, src, ks):
+        """the views `ks`, unclamped, of `src`, a source of the size their plans name: (n, len(ks), C, vh, vw)"""
+        n, c = src.shape[:2]
+        out = torch.empty((n, len(ks), c, self.vh, self.vw), dtype=torch.float32, device=src.device)
+        ops = backend.ops() if src.is_cuda else None
+        if ops is not None and not hasattr(ops, "viewport_render_f32"):
+            raise PconvError("viewport: the active backend has no viewport_render_f32 kernel for a GPU tensor")
+        src = src.contiguous()
+        for slot, k in enumerate(ks):
+            self._render_slot(ops, src, k, out, slot)
+        return out
+
+    def _render_slot(self, ops, src, k, out, slot, clamp=False):
+        """view k of `src` into out[:, slot]: one render launch (ops: the GPU backend) or the twin (ops=None)"""
+        if ops is not None:
+            ops.viewport_render_f32(src, self.maps[k], self.vh, self.vw, self.plans[k][2], clamp, out, slot)
+        else:
+            out[:, slot] = render_torch(src, self.maps[k], self.vh, self.vw, self.plans[k][2], clamp)
 
     def lists(self, k):
         """the reverse lists of view k (reverse_lists), built at the first call and kept"""
@@ -410,14 +451,10 @@ class Renderer(object):
                 raise PconvError("viewport: the active backend has no viewport_render_f32 kernel for a GPU tensor")
             x = x.contiguous()
         sources = {(self.h, self.w): x}
-        for k, ((h2, w2, ss), q) in enumerate(zip(self.plans, self.maps)):
+        for k, (h2, w2, _) in enumerate(self.plans):
             if (h2, w2) not in sources:
                 sources[(h2, w2)] = erp_resample.resize(x, h2, w2)
-            src = sources[(h2, w2)]
-            if ops is not None:
-                ops.viewport_render_f32(src, q, self.vh, self.vw, ss, clamp, out, k)
-            else:
-                out[:, k] = render_torch(src, q, self.vh, self.vw, ss, clamp)
+            self._render_slot(ops, sources[(h2, w2)], k, out, k, clamp)
         return out
 
 
