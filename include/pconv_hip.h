@@ -1080,6 +1080,9 @@ int pconv_ee_encoder_form(const pconv_entropy_engine *e, int layer);
  *     _CLEAR_EVERY_CALL, _ENCODE_INTERLEAVE, _RATE_STREAMS (1 = group), PCONV_EE_BULK and _BULK0 (1 = valu),
  *     _MFMA_FORM (1 = 16x4), _MFMA_WSRC (1 = ring), _FUSE_TABLES, PCONV_CONV_SMALL (0 = off);
  *   PCONV_CONV1X1: 0 auto, 1 tiled, 2 resident; PCONV_CONV1X1_WAYOUT: 0 quads, 1 pipe, 2 batch;
+ *   PCONV_ENGINE_ALLOC_FILL: -1 unset, else the byte 0 .. 255 (decimal or 0x..) that pconv_ee_create writes over every
+ *     device and pinned-host buffer of a group right after allocating it (a diagnostic: no result of the engine may
+ *     depend on what fresh memory held; the context / activation buffers are then zeroed by the first call as always);
  *   PCONV_ENGINE_CU_MASK=first:count is reported under the two names PCONV_ENGINE_CU_MASK_FIRST and _COUNT. */
 #define PCONV_OPTION_AUTO (-2147483647 - 1)
 int pconv_option(const pconv_entropy_engine *e, const char *name, int *value);
@@ -1102,6 +1105,8 @@ int pconv_ee_encode_begin(pconv_entropy_engine *e, const float *symbols, void *s
  * last: ranges re-evaluate the blocks on their boundaries.  Same streams for every value. */
 int pconv_ee_set_encode_ranges(pconv_entropy_engine *e, int nrange);
 int pconv_ee_encode_end(pconv_entropy_engine *e, void *stream);
+/* frame `img`'s byte stream of the last encode: *nbytes bytes; whatever the engine's buffer holds beyond them is
+ * undefined and must not be read. */
 const uint8_t *pconv_ee_stream(const pconv_entropy_engine *e, int img, size_t *nbytes);
 int pconv_ee_decode(pconv_entropy_engine *e, const uint8_t *const *streams, const size_t *nbytes,
                     float *symbols_out, void *stream);

@@ -408,8 +408,26 @@ struct pconv_entropy_engine {
     HIP_TRY(hipHostMalloc(&g.flags_h, 64, hipHostMallocCoherent | hipHostMallocMapped));
     HIP_TRY(hipMalloc(&g.counter_d, 64));
     HIP_TRY(hipMemset(g.counter_d, 0, 64));
-    if (rate_capable())  // (a few hundred KB: here, so that pconv_ee_rate never allocates)
-      HIP_TRY(hipMalloc(&g.rate_partial, (size_t)n * npart * ee_rate_blocks(h, w) * ngroup * sizeof(double)));
+    const size_t rate_bytes = rate_capable() ? (size_t)n * npart * ee_rate_blocks(h, w) * ngroup * sizeof(double) : 0;
+    if (rate_bytes)  // (a few hundred KB: here, so that pconv_ee_rate never allocates)
+      HIP_TRY(hipMalloc(&g.rate_partial, rate_bytes));
+    // PCONV_ENGINE_ALLOC_FILL=<byte>: a diagnostic, off by default -- what the driver handed out is overwritten, so
+    // that a buffer nobody writes before it is read shows.  ctx / act[] too: clear() zeroes them as always, the zeros
+    // the kernels rely on are clear()'s and not the allocator's.
+    if (opt.alloc_fill >= 0) {
+      const int b = opt.alloc_fill;
+      HIP_TRY(hipMemset(g.ctx, b, ctx_elems(n) * 4));
+      for (int l = 0; l < kLayers; l++) HIP_TRY(hipMemset(g.act[l], b, act_elems(l, n) * 4));
+      HIP_TRY(hipMemset(g.tables_d, b, all_rows * row_bytes()));
+      memset(g.tables_h, b, all_rows * row_bytes());
+      if (!packed) {
+        HIP_TRY(hipMemset(g.labels_d, b, all_rows * 4));
+        memset(g.labels_h, b, all_rows * 4);
+      }
+      memset(g.packed_h, b, (size_t)n * max_len * 4);
+      if (rate_bytes) HIP_TRY(hipMemset(g.rate_partial, b, rate_bytes));
+      HIP_TRY(hipDeviceSynchronize());
+    }
     return PCONV_OK;
   }
 

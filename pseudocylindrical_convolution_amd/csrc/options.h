@@ -39,6 +39,7 @@ constexpr int kOptionAuto = INT_MIN;  // PCONV_OPTION_AUTO: not set, the library
   X("PCONV_ENGINE_ROWS", rows_int32, 0, s[0] == 'i')                   /* int32 rows + labels across PCIe */         \
   X("PCONV_ENGINE_STEPWISE_ENCODER", stepwise_encoder, 0, 1)           /* set at all: the debugging encoder */       \
   X("PCONV_ENGINE_CLEAR_EVERY_CALL", clear_every_call, 0, atoi(s) != 0)                                              \
+  X("PCONV_ENGINE_ALLOC_FILL", alloc_fill, -1, (int)(strtol(s, nullptr, 0) & 255)) /* byte over new buffers (tests) */ \
   X("PCONV_ENGINE_ENCODE_RANGES", encode_ranges, 4, atoi(s))           /* step ranges of a call's last group */      \
   X("PCONV_ENGINE_ENCODE_INTERLEAVE", encode_interleave, 1, atoi(s) != 0)                                            \
   X("PCONV_ENGINE_RATE_STREAMS", rate_group_streams, 0, s[0] == 'g')   /* rate(): each group on its own stream */    \

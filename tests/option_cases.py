@@ -158,6 +158,7 @@ REST_SETS = [{"PCONV_EE_BULK0": "valu"}, {"PCONV_ENGINE_WORKERS": "1"}, {"PCONV_
              {"PCONV_ENGINE_TIMING": "1"}]
 _REST = (NEW, "test_host_side_engine_options_keep_the_streams")
 STAGGER = ("1", "3")
+ALLOC_FILL = ("0xFF", "0x3F")     # the two float patterns of tests/stale_memory.py over every buffer an engine allocates
 
 OPTIONS = {
     "PCONV_EE_BLOCK": Row(_values("PCONV_EE_BLOCK", EE_SETS, WIDE_SETS), *_STEP),
@@ -177,6 +178,7 @@ OPTIONS = {
     "PCONV_ENGINE_ROWS": Row(("int32",), *_KNOBS),
     "PCONV_ENGINE_STEPWISE_ENCODER": Row(("1",), *_KNOBS),
     "PCONV_ENGINE_CLEAR_EVERY_CALL": Row(("1",), NEW, "test_clear_every_call_keeps_the_streams"),
+    "PCONV_ENGINE_ALLOC_FILL": Row(ALLOC_FILL, "test_gpu_stale_memory.py", "test_engine_results_do_not_depend_on_fresh_memory"),
     "PCONV_ENGINE_ENCODE_RANGES": Row(("1", "7"), *_KNOBS),
     "PCONV_ENGINE_ENCODE_INTERLEAVE": Row(("0",), *_KNOBS),
     "PCONV_ENGINE_RATE_STREAMS": Row(("groups",), NEW, "test_rate_on_group_streams_gives_the_same_bits"),

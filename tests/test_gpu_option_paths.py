@@ -229,7 +229,9 @@ class _Probe(object):
 def _poison(shape, ring=0, dtype=torch.float32):
     """NaN where the next torch.empty of this shape lands (the caching allocator hands the freed block out again): a
     workgroup that skips its tile must not find the right values of an earlier call there.  The tests below also keep
-    every result alive, so that no block holding right values is ever free."""
+    every result alive, so that no block holding right values is ever free.
+    (tests/test_gpu_stale_memory.py holds the same calls -- tile_conv2d with its epilogues and rings, the data gradient,
+    rate() -- with the stronger mechanism: torch.empty itself returns filled memory, whatever block the allocator picks.)"""
     shape = tuple(shape[:-2]) + (shape[-2] + 2 * ring, shape[-1] + 2 * ring)
     del_me = torch.full(shape, float("nan"), dtype=dtype, device=DEV)
     del del_me

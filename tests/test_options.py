@@ -16,7 +16,8 @@ DEFAULTS = {
     "PCONV_EE_FUSE_PPW": 4, "PCONV_EE_MFMA_WSRC": 0, "PCONV_EE_MFMA_WAVES": 4, "PCONV_EE_MFMA_NT": 1,
     "PCONV_ENGINE_GROUPS": AUTO, "PCONV_ENGINE_WORKERS": AUTO, "PCONV_ENGINE_CHAIN": AUTO,
     "PCONV_ENGINE_BLOCKING_SYNC": AUTO, "PCONV_ENGINE_SPIN_US": AUTO, "PCONV_ENGINE_ROWS": 0,
-    "PCONV_ENGINE_STEPWISE_ENCODER": 0, "PCONV_ENGINE_CLEAR_EVERY_CALL": 0, "PCONV_ENGINE_ENCODE_RANGES": 4,
+    "PCONV_ENGINE_STEPWISE_ENCODER": 0, "PCONV_ENGINE_CLEAR_EVERY_CALL": 0, "PCONV_ENGINE_ALLOC_FILL": -1,
+    "PCONV_ENGINE_ENCODE_RANGES": 4,
     "PCONV_ENGINE_ENCODE_INTERLEAVE": 1, "PCONV_ENGINE_RATE_STREAMS": 0, "PCONV_ENGINE_TIMING": 0,
     "PCONV_EE_BULK": 0, "PCONV_EE_BULK0": 0, "PCONV_EE_MFMA_FORM": 0, "PCONV_EE_FUSE_TABLES": 0,
     "PCONV_ENGINE_CU_MASK_FIRST": 0, "PCONV_ENGINE_CU_MASK_COUNT": 0,
