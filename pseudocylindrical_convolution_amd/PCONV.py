@@ -1406,6 +1406,48 @@ def _like_output(t, out, what):
     return t if t.stride(3) == 1 else t.contiguous()
 
 
+def _gpu_device(what, device):
+    """`device` as a cuda device with its index; None: the current one"""
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise PconvError("%s: expected a GPU device (this build has no CPU path), got %s" % (what, device))
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+def _require_frames(x, what):
+    """the shape of a contiguous float32 (n, C, h, w) GPU tensor"""
+    _require_gpu(x, what)
+    if x.dim() != 4:
+        raise PconvError("%s: float32 (n, C, h, w) expected" % what)
+    return x.shape
+
+
+def _require_sides(what, h, w):
+    if not (2 <= h <= 1 << 20 and 2 <= w <= 1 << 20) or 4 * h * w >= 1 << 31:
+        raise PconvError("%s: %dx%d: sides of 2 .. 2^20 and a plane below 2^31 bytes expected" % (what, w, h))
+
+
+def _output(what, out, shape, dtype, device, where, name="out"):
+    """`out` checked -- a contiguous tensor of this shape, dtype and device (`where` names the device in the refusal) --
+    or, when it is None, a new one"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous() or out.device != device:
+        raise PconvError("%s: %s must be contiguous %s (%s) on %s"
+                         % (what, name, str(dtype).split(".")[1], ", ".join(str(int(s)) for s in shape), where))
+    return out
+
+
+def _require_view(what, vh, vw, ss):
+    if not (2 <= vh <= 1 << 20 and 2 <= vw <= 1 << 20 and 1 <= ss <= 4):
+        raise PconvError("%s: a view of %dx%d with ss = %d: sides of 2 .. 2^20 and ss of 1 .. 4 expected" % (what, vw, vh, ss))
+
+
+def _require_map(what, map, gh, gw, device, where):
+    if map.dtype != torch.int32 or tuple(map.shape) != (gh, gw, 2) or not map.is_contiguous() or map.device != device:
+        raise PconvError("%s: the map must be contiguous int32 (%d, %d, 2) on %s" % (what, gh, gw, where))
+
+
 def _require_rows(x, what):
     """GPU float32 4-D tensor whose columns are contiguous (dense, or the interior view
     of a padded buffer)"""
@@ -1610,10 +1652,7 @@ def erp_resample_f32(x, h2, w2, clamp=False, out=None, workspace=None):
     """float32 (n, C, h, w) GPU tensor -> (n, C, h2, w2): the sphere-aware Lanczos-3 resize (erp_resample.py,
     pconv_erp_resample_f32).  The tap tables live on the device, cached per (h, w, h2, w2); workspace: a uint8 GPU
     tensor of at least pconv_erp_resample_workspace_bytes bytes (allocated when None)"""
-    _require_gpu(x, "erp_resample_f32")
-    if x.dim() != 4:
-        raise PconvError("erp_resample_f32: float32 (n, C, h, w) expected")
-    n, c, h, w = x.shape
+    n, c, h, w = _require_frames(x, "erp_resample_f32")
     h2, w2 = int(h2), int(w2)
     nbytes = call("pconv_erp_resample_workspace_bytes", n, c, h, w, h2, w2)
     key = (x.device, h, w, h2, w2)
@@ -1623,10 +1662,7 @@ def erp_resample_f32(x, h2, w2, clamp=False, out=None, workspace=None):
         fy, wy = taps(h, h2)
         _resample_tables[key] = tuple(t.to(x.device) for t in (fx, wx, fy, wy))
     fx, wx, fy, wy = _resample_tables[key]
-    if out is None:
-        out = torch.empty((n, c, h2, w2), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (n, c, h2, w2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise PconvError("erp_resample_f32: out must be contiguous float32 (%d, %d, %d, %d) on the input's device" % (n, c, h2, w2))
+    out = _output("erp_resample_f32", out, (n, c, h2, w2), torch.float32, x.device, "the input's device")
     if workspace is None:
         workspace = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
     elif workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous() or workspace.device != x.device:
@@ -1661,11 +1697,7 @@ def erp_resample_backward_f32(g, h, w, gin=None, workspace=None):
         tables = (taps(w, w2)[1],) + reverse_taps(w, w2, 0)[:2] + (taps(h, h2)[1],) + reverse_taps(h, h2, 1)
         _resample_reverse[key] = tuple(t.to(g.device) for t in tables)
     wx, start_x, entry_x, wy, start_y, entry_y, crossed_y = _resample_reverse[key]
-    if gin is None:
-        gin = torch.empty((n, c, h, w), dtype=torch.float32, device=g.device)
-    elif tuple(gin.shape) != (n, c, h, w) or gin.dtype != torch.float32 or not gin.is_contiguous() or gin.device != g.device:
-        raise PconvError("erp_resample_backward_f32: gin must be contiguous float32 (%d, %d, %d, %d) on the gradient's device"
-                         % (n, c, h, w))
+    gin = _output("erp_resample_backward_f32", gin, (n, c, h, w), torch.float32, g.device, "the gradient's device", "gin")
     if workspace is None:
         workspace = torch.empty((nbytes,), dtype=torch.uint8, device=g.device)
     elif workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous() or workspace.device != g.device:
@@ -1693,17 +1725,9 @@ def erp_rotation_map(h, w, rotation, inverse=False, device=None, out=None):
         yaw, pitch, roll = (int(v) for v in rotation)
     except (TypeError, ValueError):
         raise PconvError("erp_rotation_map: a rotation is three integers in units of 2^-16 degree, got %r" % (rotation,))
-    device = torch.device("cuda" if device is None else device)
-    if device.type != "cuda":
-        raise PconvError("erp_rotation_map: expected a GPU device (this build has no CPU path), got %s" % device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if not (2 <= h <= 1 << 20 and 2 <= w <= 1 << 20) or 4 * h * w >= 1 << 31:
-        raise PconvError("erp_rotation_map: %dx%d: sides of 2 .. 2^20 and a plane below 2^31 bytes expected" % (w, h))
-    if out is None:
-        out = torch.empty((h, w, 2), dtype=torch.int32, device=device)
-    elif tuple(out.shape) != (h, w, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != device:
-        raise PconvError("erp_rotation_map: out must be contiguous int32 (%d, %d, 2) on %s" % (h, w, device))
+    device = _gpu_device("erp_rotation_map", device)
+    _require_sides("erp_rotation_map", h, w)
+    out = _output("erp_rotation_map", out, (h, w, 2), torch.int32, device, device)
     with torch.cuda.device(device), _HbmTimed("erp_rotation_map_kernel", "ErpRotationMap %dx%d" % (w, h), 8.0 * h * w, device):
         call("pconv_erp_rotation_map", _ptr(out), h, w, yaw, pitch, roll, 1 if inverse else 0, _stream(device))
     return out
@@ -1713,20 +1737,10 @@ def erp_remap_f32(x, map, clamp=False, out=None):
     """float32 (n, C, h, w) GPU tensor -> (n, C, h, w) read through `map` (int32 (h, w, 2) on the same device, from
     erp_rotation_map) with the 6 x 6 Lanczos-3 footprint of erp_rotate.py (pconv_erp_remap_f32).  The phase table lives
     on the device, cached per device; out must not be x"""
-    _require_gpu(x, "erp_remap_f32")
-    if x.dim() != 4:
-        raise PconvError("erp_remap_f32: float32 (n, C, h, w) expected")
-    n, c, h, w = x.shape
-    if map.dtype != torch.int32 or tuple(map.shape) != (h, w, 2) or not map.is_contiguous() or map.device != x.device:
-        raise PconvError("erp_remap_f32: the map must be contiguous int32 (%d, %d, 2) on the input's device" % (h, w))
-    if x.device not in _rotate_phases:
-        from .erp_rotate import phases
-        _rotate_phases[x.device] = phases().to(x.device)
-    table = _rotate_phases[x.device]
-    if out is None:
-        out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (n, c, h, w) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise PconvError("erp_remap_f32: out must be contiguous float32 (%d, %d, %d, %d) on the input's device" % (n, c, h, w))
+    n, c, h, w = _require_frames(x, "erp_remap_f32")
+    _require_map("erp_remap_f32", map, h, w, x.device, "the input's device")
+    table = _phase_table(x.device)
+    out = _output("erp_remap_f32", out, (n, c, h, w), torch.float32, x.device, "the input's device")
     # input read + output written + the map read once per frame
     counted = 4.0 * (x.numel() + out.numel()) + 8.0 * n * h * w
     with _HbmTimed("erp_remap_f32_kernel", "ErpRemap %dx%d n%d" % (w, h, n), counted, x.device):
@@ -1735,7 +1749,7 @@ def erp_remap_f32(x, map, clamp=False, out=None):
     return out
 
 
-def _viewport_phases(device):
+def _phase_table(device):
     if device not in _rotate_phases:
         from .erp_rotate import phases
         _rotate_phases[device] = phases().to(device)
@@ -1769,13 +1783,9 @@ def sphere_points_records(points, h, w, out=None):
             or not points.is_contiguous() or not 1 <= points.shape[0] <= SPHERE_POINTS_MAX:
         raise PconvError("sphere_points_records: contiguous float64 (P, 2) points, 1 <= P < 2^28, on a GPU expected, got %s "
                          "%s on %s" % (points.dtype, tuple(points.shape), points.device))
-    if not (2 <= h <= 1 << 20 and 2 <= w <= 1 << 20) or 4 * h * w >= 1 << 31:
-        raise PconvError("sphere_points_records: %dx%d: sides of 2 .. 2^20 and a plane below 2^31 bytes expected" % (w, h))
+    _require_sides("sphere_points_records", h, w)
     count = points.shape[0]
-    if out is None:
-        out = torch.empty((count, 2), dtype=torch.int32, device=points.device)
-    elif tuple(out.shape) != (count, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != points.device:
-        raise PconvError("sphere_points_records: out must be contiguous int32 (%d, 2) on the points' device" % count)
+    out = _output("sphere_points_records", out, (count, 2), torch.int32, points.device, "the points' device")
     with _HbmTimed("sphere_points_records_kernel", "SpherePointsRecords %dx%d P%d" % (w, h, count), 24.0 * count, points.device):
         call("pconv_sphere_points_records", _ptr(points), _ptr(out), count, h, w, _stream(points.device))
     return out
@@ -1785,20 +1795,14 @@ def sphere_points_sample_f32(x, records, interp="lanczos", out=None):
     """float32 (n, C, h, w) GPU tensor -> (n, C, P): every plane read at the records (int32 (P, 2) on the same device,
     from sphere_points_records for this h x w) with the 6 x 6 Lanczos-3 footprint of erp_rotate.py or, interp="nearest",
     the nearest pixel (pconv_sphere_points_sample_f32)"""
-    _require_gpu(x, "sphere_points_sample_f32")
-    if x.dim() != 4:
-        raise PconvError("sphere_points_sample_f32: float32 (n, C, h, w) expected")
+    n, c, h, w = _require_frames(x, "sphere_points_sample_f32")
     mode = _sphere_points_mode("sphere_points_sample_f32", interp)
     count = _sphere_points_records_of("sphere_points_sample_f32", records, x)
-    n, c, h, w = x.shape
-    if out is None:
-        out = torch.empty((n, c, count), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (n, c, count) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise PconvError("sphere_points_sample_f32: out must be contiguous float32 (%d, %d, %d) on the input's device" % (n, c, count))
+    out = _output("sphere_points_sample_f32", out, (n, c, count), torch.float32, x.device, "the input's device")
     # the algorithmic bytes of the gather: one pixel (nearest) or 36 (lanczos) per point and plane, the output, the records
     counted = 4.0 * n * c * count * ((36 if mode == 0 else 1) + 1) + 8.0 * n * count
     with _HbmTimed("sphere_points_sample_kernel", "SpherePointsSample %dx%d n%d P%d" % (w, h, n, count), counted, x.device):
-        call("pconv_sphere_points_sample_f32", _ptr(x), _ptr(out), _ptr(records), _ptr(_viewport_phases(x.device)), n, c, h, w,
+        call("pconv_sphere_points_sample_f32", _ptr(x), _ptr(out), _ptr(records), _ptr(_phase_table(x.device)), n, c, h, w,
              count, mode, _stream(x.device))
     return out
 
@@ -1823,7 +1827,7 @@ def sphere_points_mse_device(x, rec_x, y, rec_y, interp="lanczos"):
     counted = 4.0 * n * c * count * 2 * (36 if mode == 0 else 1) + 16.0 * n * c * count
     with _HbmTimed("sphere_points_mse_kernel", "SpherePointsMse n%d P%d" % (n, count), counted, x.device):
         call("pconv_sphere_points_mse_f32", _ptr(x), x.shape[2], x.shape[3], _ptr(rec_x), _ptr(y), y.shape[2], y.shape[3],
-             _ptr(rec_y), _ptr(_viewport_phases(x.device)), n, c, count, mode, _ptr(workspace), _ptr(out), _stream(x.device))
+             _ptr(rec_y), _ptr(_phase_table(x.device)), n, c, count, mode, _ptr(workspace), _ptr(out), _stream(x.device))
     return out
 
 
@@ -1841,17 +1845,10 @@ def viewport_map(h, w, gh, gw, view, device=None, out=None):
         yaw, pitch, roll, hfov, vfov = (int(v) for v in view)
     except (TypeError, ValueError):
         raise PconvError("viewport_map: a view is five integers in units of 2^-16 degree, got %r" % (view,))
-    device = torch.device("cuda" if device is None else device)
-    if device.type != "cuda":
-        raise PconvError("viewport_map: expected a GPU device (this build has no CPU path), got %s" % device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _gpu_device("viewport_map", device)
     if not (2 <= gh <= 1 << 22 and 2 <= gw <= 1 << 22) or 8 * gh * gw >= 1 << 31:
         raise PconvError("viewport_map: a grid of %dx%d: sides of 2 .. 2^22 and a map below 2^31 bytes expected" % (gw, gh))
-    if out is None:
-        out = torch.empty((gh, gw, 2), dtype=torch.int32, device=device)
-    elif tuple(out.shape) != (gh, gw, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != device:
-        raise PconvError("viewport_map: out must be contiguous int32 (%d, %d, 2) on %s" % (gh, gw, device))
+    out = _output("viewport_map", out, (gh, gw, 2), torch.int32, device, device)
     with torch.cuda.device(device), _HbmTimed("viewport_map_kernel", "ViewportMap %dx%d" % (gw, gh), 8.0 * gh * gw, device):
         call("pconv_viewport_map", _ptr(out), h, w, gh, gw, yaw, pitch, roll, hfov, vfov, _stream(device))
     return out
@@ -1862,18 +1859,11 @@ def viewport_render_f32(x, map, vh, vw, ss, clamp=False, out=None, slot=0):
     vw * ss, 2) on the same device, from viewport_map) and averaged over ss x ss samples per pixel (viewport.py,
     pconv_viewport_render_f32).  out: a contiguous float32 (n, V, C, vh, vw) tensor whose view `slot` is written, the
     others left alone; None: a new (n, 1, C, vh, vw)"""
-    _require_gpu(x, "viewport_render_f32")
-    if x.dim() != 4:
-        raise PconvError("viewport_render_f32: float32 (n, C, h, w) expected")
-    n, c, h, w = x.shape
+    n, c, h, w = _require_frames(x, "viewport_render_f32")
     vh, vw, ss, slot = int(vh), int(vw), int(ss), int(slot)
-    if not (2 <= vh <= 1 << 20 and 2 <= vw <= 1 << 20 and 1 <= ss <= 4):
-        raise PconvError("viewport_render_f32: a view of %dx%d with ss = %d: sides of 2 .. 2^20 and ss of 1 .. 4 expected"
-                         % (vw, vh, ss))
-    if map.dtype != torch.int32 or tuple(map.shape) != (vh * ss, vw * ss, 2) or not map.is_contiguous() or map.device != x.device:
-        raise PconvError("viewport_render_f32: the map must be contiguous int32 (%d, %d, 2) on the input's device"
-                         % (vh * ss, vw * ss))
-    table = _viewport_phases(x.device)
+    _require_view("viewport_render_f32", vh, vw, ss)
+    _require_map("viewport_render_f32", map, vh * ss, vw * ss, x.device, "the input's device")
+    table = _phase_table(x.device)
     if out is None:
         out = torch.empty((n, 1, c, vh, vw), dtype=torch.float32, device=x.device)
     elif out.dim() != 5 or out.shape[0] != n or tuple(out.shape[2:]) != (c, vh, vw) or out.dtype != torch.float32 \
@@ -1911,12 +1901,8 @@ def remap_backward_f32(gout, map, lists, h, w, vh, vw, ss, gin=None, slot=0, acc
     n, views, c = gout.shape[:3]
     if not 0 <= slot < views:
         raise PconvError("remap_backward_f32: slot %d of %d views" % (slot, views))
-    if not (2 <= vh <= 1 << 20 and 2 <= vw <= 1 << 20 and 1 <= ss <= 4):
-        raise PconvError("remap_backward_f32: a view of %dx%d with ss = %d: sides of 2 .. 2^20 and ss of 1 .. 4 expected"
-                         % (vw, vh, ss))
-    if map.dtype != torch.int32 or tuple(map.shape) != (vh * ss, vw * ss, 2) or not map.is_contiguous() or map.device != gout.device:
-        raise PconvError("remap_backward_f32: the map must be contiguous int32 (%d, %d, 2) on the gradient's device"
-                         % (vh * ss, vw * ss))
+    _require_view("remap_backward_f32", vh, vw, ss)
+    _require_map("remap_backward_f32", map, vh * ss, vw * ss, gout.device, "the gradient's device")
     entries = 36 * vh * ss * vw * ss
     try:
         start, entry = lists
@@ -1927,13 +1913,10 @@ def remap_backward_f32(gout, map, lists, h, w, vh, vw, ss, gin=None, slot=0, acc
     if not good:
         raise PconvError("remap_backward_f32: lists must be (start, entry) of viewport.reverse_lists for this map and a %dx%d "
                          "source: contiguous int32 of %d and %d elements on the gradient's device" % (w, h, h * w + 1, entries))
-    if gin is None:
-        if accumulate:
-            raise PconvError("remap_backward_f32: accumulate needs the gin to add to")
-        gin = torch.empty((n, c, h, w), dtype=torch.float32, device=gout.device)
-    elif tuple(gin.shape) != (n, c, h, w) or gin.dtype != torch.float32 or not gin.is_contiguous() or gin.device != gout.device:
-        raise PconvError("remap_backward_f32: gin must be contiguous float32 (%d, %d, %d, %d) on the gradient's device" % (n, c, h, w))
-    table = _viewport_phases(gout.device)
+    if gin is None and accumulate:
+        raise PconvError("remap_backward_f32: accumulate needs the gin to add to")
+    gin = _output("remap_backward_f32", gin, (n, c, h, w), torch.float32, gout.device, "the gradient's device", "gin")
+    table = _phase_table(gout.device)
     frame = c * vh * vw
     # per plane: every entry (4 bytes), its record and its gradient value (what the caches make of their reuse is not
     # counted away), the starts, and gin written (and read, when accumulating)

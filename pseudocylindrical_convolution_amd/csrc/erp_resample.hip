@@ -12,19 +12,13 @@
 //   columns pass: mid (n*C, h, w2) -> out (n*C, h2, w2).  A lane owns 4 adjacent columns of one output row and walks
 //                 the row's taps (row index and weight are wave-uniform): 16-byte loads where w2 % 4 == 0, for rows
 //                 that crossed a pole only where floor(w2/2) % 4 == 0 as well, else 4-byte loads.
-#include <math.h>
-#include "common.h"
+#include "sphere_sampler.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kTile = 4 * kBlock;       // output columns of one workgroup, both passes
 constexpr int kMaxLdsBytes = 64 * 1024;  // rows pass: R rows of the staged span
-
-__device__ __forceinline__ int pmod(int a, int m) {
-  int r = a % m;
-  return r < 0 ? r + m : r;
-}
 
 // Floats of LDS one staged row needs for a tile of kTile outputs: the span first[i0 + kTile - 1] + T - first[i0] is at
 // most floor((kTile - 1) * n_in / n_out) + 1 + T (first advances by floor or ceil of n_in / n_out per output), plus 3
@@ -54,13 +48,13 @@ __global__ __launch_bounds__(kBlock) void erp_resample_rows_kernel(const float *
     if (vec) {  // w % 4 == 0, base % 4 == 0, rows 16-byte aligned: a quad never straddles the seam
       for (int q = threadIdx.x; 4 * q < span; q += kBlock) {
         int c = base + 4 * q;
-        if (c < 0 || c >= w) c = pmod(c, w);
+        if (c < 0 || c >= w) c = wrap_col(c, w);
         *reinterpret_cast<float4 *>(dst + 4 * q) = *reinterpret_cast<const float4 *>(src + c);
       }
     } else {
       for (int s = threadIdx.x; s < span; s += kBlock) {
         int c = base + s;
-        if (c < 0 || c >= w) c = pmod(c, w);
+        if (c < 0 || c >= w) c = wrap_col(c, w);
         dst[s] = src[c];
       }
     }
@@ -110,16 +104,8 @@ __global__ __launch_bounds__(kBlock) void erp_resample_cols_kernel(const float *
   }
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   for (int t = 0; t < T; t++) {
-    int r = r0 + t;
-    bool flip = false;
-    if (r < 0) {
-      r = -1 - r;
-      flip = true;
-    } else if (r >= h) {
-      r = 2 * h - 1 - r;
-      flip = true;
-    }
-    r = min(max(r, 0), h - 1);
+    bool flip;
+    const int r = pole_row(r0 + t, h, &flip);
     const float *src = plane + (long long)r * w2;
     float v[4];
     if (vec == 2 || (vec == 1 && !flip)) {
@@ -195,7 +181,6 @@ extern "C" int pconv_host_lanczos_taps(int n_in, int n_out, int32_t *first, floa
   }
   *taps = T;
   if (!first) return PCONV_OK;
-  const double pi = 3.14159265358979323846;
   double raw[64];  // T <= 48: the open interval |N| < 3D holds fewer than 6 * 8 + 1 integers k
   for (long long i = 0; i < n_out; i++) {
     long long k0;
@@ -210,7 +195,7 @@ extern "C" int pconv_host_lanczos_taps(int n_in, int n_out, int32_t *first, floa
       } else if (N % D == 0) {
         r = 0.0;
       } else {
-        const double x = pi * (double)(N < 0 ? -N : N) / (double)D;
+        const double x = kPi * (double)(N < 0 ? -N : N) / (double)D;
         r = 3.0 * sin(x) * sin(x / 3.0) / (x * x);
       }
       raw[t] = r;
@@ -235,8 +220,7 @@ extern "C" int pconv_erp_resample_f32(const float *in, float *out, void *workspa
                                       const float *wx, int tx, const int32_t *first_y, const float *wy, int ty, int n,
                                       int c, int h, int w, int h2, int w2, int clamp, void *stream) {
   PCONV_REQUIRE(in && out && workspace && first_x && wx && first_y && wy, "erp_resample_f32: null pointer");
-  PCONV_REQUIRE(n > 0 && c > 0 && (long long)n * c <= 65535, "erp_resample_f32: n * C = %lld planes, the grid takes 1 .. 65535",
-                (long long)n * c);
+  if (planes_ok("erp_resample_f32", n, c) != PCONV_OK) return PCONV_EINVAL;
   if (axis_ok("erp_resample_f32", w, w2) != PCONV_OK || axis_ok("erp_resample_f32", h, h2) != PCONV_OK) return PCONV_EINVAL;
   int want_tx = 0, want_ty = 0;
   if (pconv_host_lanczos_taps(w, w2, nullptr, nullptr, &want_tx) != PCONV_OK ||

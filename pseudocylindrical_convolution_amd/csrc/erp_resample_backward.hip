@@ -16,18 +16,13 @@
 // outside it clamped) and every staged column to one inside the span, so no list content makes a kernel read outside
 // its buffers; each lane stores only its own elements.
 #include <vector>
-#include "common.h"
+#include "sphere_sampler.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kTile = 4 * kBlock;        // destination columns of one workgroup, both passes
 constexpr int kMaxLdsBytes = 64 * 1024;  // rows pass: R rows of the staged span
-
-__device__ __forceinline__ int pmod(int a, int m) {
-  int r = a % m;
-  return r < 0 ? r + m : r;
-}
 
 __host__ __device__ inline long long ceil_div(long long a, long long b) {  // b > 0
   const long long q = a / b;
@@ -110,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void erp_resample_rows_backward_kernel(
   const long long D = 2LL * max(w, w2), fix = 3 * D + w2 - w;
   const long long ia = ceil_div(2LL * w2 * (c0 - T) + fix, 2LL * w);
   const long long ib = ceil_div(2LL * w2 * (c1 - 1) + fix, 2LL * w) - 1;
-  const int wrapped = pmod((int)(ia % w2), w2);
+  const int wrapped = wrap_col((int)(ia % w2), w2);
   int base = vec ? wrapped & ~3 : wrapped;
   long long count = ib - ia + 1 + (wrapped - base);
   if (count >= w2) base = 0, count = w2;  // every column of the row: staged once, in place
@@ -165,8 +160,7 @@ __global__ __launch_bounds__(kBlock) void erp_resample_rows_backward_kernel(
 }
 
 int shape_ok(const char *what, int n, int c, int h, int w, int h2, int w2, int *tx, int *ty) {
-  PCONV_REQUIRE(n > 0 && c > 0 && (long long)n * c <= 65535, "%s: n * C = %lld planes, the grid takes 1 .. 65535", what,
-                (long long)n * c);
+  if (planes_ok(what, n, c) != PCONV_OK) return PCONV_EINVAL;
   if (pconv_host_lanczos_taps(w, w2, nullptr, nullptr, tx) != PCONV_OK ||
       pconv_host_lanczos_taps(h, h2, nullptr, nullptr, ty) != PCONV_OK)
     return PCONV_EINVAL;  // a side outside 2 .. 2^20, a shrink beyond 8:1: the message is the tap function's
@@ -203,17 +197,8 @@ extern "C" int pconv_host_lanczos_reverse(int n_in, int n_out, int pole, int32_t
   for (int pass = 0; pass < 2; pass++) {
     for (int i = 0; i < n_out; i++)
       for (int t = 0; t < T; t++) {
-        long long r = (long long)first[i] + t;
-        bool flip = false;
-        if (pole) {
-          flip = r < 0 || r >= n_in;
-          if (r < 0) r = -1 - r;
-          else if (r >= n_in) r = 2LL * n_in - 1 - r;
-          r = r < 0 ? 0 : r > n_in - 1 ? n_in - 1 : r;
-        } else {
-          r %= n_in;
-          if (r < 0) r += n_in;
-        }
+        bool flip = false;  // |first[i] + t| < 2^24: a side is at most 2^20 and a shrink at most 8:1
+        const int r = pole ? pole_row(first[i] + t, n_in, &flip) : wrap_col(first[i] + t, n_in);
         if (pass == 0) {
           fill[(size_t)r + 1]++;
         } else {

@@ -19,7 +19,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include <vector>
-#include "common.h"
+#include "sphere_sampler.h"
 
 static thread_local char g_err[512] = "";
 
@@ -533,11 +533,6 @@ extern "C" int pconv_host_project_table(const float *theta, const float *phi, in
 
 // ---- reverse lists of the ordered (atomic-free) backward kernels: include/pconv_hip.h, "the order" ----
 
-static inline int wrap_col(int col, int period) {
-  col %= period;
-  return col < 0 ? col + period : col;
-}
-
 // forward outputs per row of tile t: the tile's valid columns (slice) or every ERP column (uslice)
 static inline int tap_sources(const int32_t *widths, int t, int width, int uslice) {
   return uslice ? width : (widths[t] < width ? widths[t] : width);
@@ -689,19 +684,6 @@ extern "C" long long pconv_host_remap_reverse_size(int gh, int gw) {
   return total;
 }
 
-// the source pixel that tap (a, b) of the record (qu, qv) reads: the sampler's rule of pconv_erp_remap_f32, word for word
-static inline long long remap_tap(int qu, int qv, int a, int b, int h, int w) {
-  long long r = ((long long)qv >> 8) - 2 + a;  // floor(qv / 256) for a negative qv as well
-  const bool crossed = r < 0 || r >= h;
-  if (r < 0) r = -1 - r;
-  else if (r >= h) r = 2LL * h - 1 - r;
-  r = r < 0 ? 0 : r > h - 1 ? h - 1 : r;
-  long long c = (((long long)qu >> 8) - 2 + b) % w;
-  if (c < 0) c += w;
-  if (crossed) c = (c + w / 2) % w;
-  return r * w + c;
-}
-
 // Transpose of the 6 x 6 sampler over a map as a CSR list per source pixel (the ordered backward of the viewport
 // renderer and of the sphere rotation, pconv_remap_backward_f32): the forward walk -- grid sample s = r * gw + q
 // ascending, then tap row a = 0 .. 5, then tap column b = 0 .. 5 -- sorted by the pixel the tap reads with a stable
@@ -711,9 +693,7 @@ static inline long long remap_tap(int qu, int qv, int a, int b, int h, int w) {
 extern "C" int pconv_host_remap_reverse(const int32_t *map, int gh, int gw, int h, int w, int32_t *rev_start,
                                         int32_t *rev_entry) {
   PCONV_REQUIRE(map && rev_start && rev_entry, "remap_reverse: null pointer");
-  PCONV_REQUIRE(h >= 2 && w >= 2 && h <= (1 << 20) && w <= (1 << 20), "remap_reverse: a source side of %dx%d is outside 2 .. 2^20",
-                w, h);
-  PCONV_REQUIRE(4LL * h * w < (1LL << 31), "remap_reverse: a source plane of %dx%d float32 is 2^31 bytes or more", w, h);
+  if (frame_ok("remap_reverse", "source ", h, w) != PCONV_OK) return PCONV_EINVAL;
   const int side = 4 << 20;  // PCONV_VIEWPORT_MAX_SS * 2^20
   PCONV_REQUIRE(gh >= 2 && gw >= 2 && gh <= side && gw <= side, "remap_reverse: a grid side of %dx%d is outside 2 .. 4 * 2^20", gw,
                 gh);
@@ -727,7 +707,7 @@ extern "C" int pconv_host_remap_reverse(const int32_t *map, int gh, int gw, int 
       const int qu = map[s * 2], qv = map[s * 2 + 1];
       for (int a = 0; a < 6; a++)
         for (int b = 0; b < 6; b++) {
-          const size_t d = (size_t)remap_tap(qu, qv, a, b, h, w);
+          const size_t d = (size_t)tap_pixel(qu, qv, a, b, h, w);  // sphere_sampler.h: the pixel the sampler reads
           if (pass == 0) fill[d + 1]++;
           else rev_entry[fill[d]++] = (int32_t)(s * 36 + a * 6 + b);
         }

@@ -13,13 +13,11 @@
 // Every index read from a list is reduced to one inside the map (an entry outside 0 .. 36 gh gw - 1 is skipped, a start
 // outside it clamped), so no list content makes the kernel read outside `map` or `gout`; each lane stores only its own
 // pixel.
-#include "common.h"
+#include "sphere_sampler.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kPhases = PCONV_ERP_ROTATE_PHASES;
-constexpr int kTaps = PCONV_ERP_ROTATE_TAPS;
 constexpr int kFoot = kTaps * kTaps;  // entries per grid sample
 constexpr int kPlanes = 4;            // planes a lane carries through one walk of its list
 constexpr int kAhead = 4;             // entries of a list whose loads are in flight together
@@ -44,8 +42,7 @@ __global__ __launch_bounds__(kBlock) void remap_backward_f32_kernel(
       for (int k = 0; k < planes; k++) dst[(long long)k * hw] = 0.f;
     return;
   }
-  for (int k = threadIdx.x; k < kPhases * kTaps; k += kBlock) table[k] = phases[k];
-  __syncthreads();
+  stage_phase_table<kBlock>(table, phases);
   if (d >= hw || (accumulate && lo >= hi)) return;
   const float *g = gout + (long long)frame * gout_frame_stride + (long long)c0 * vplane;
   float acc[kPlanes];
@@ -63,8 +60,8 @@ __global__ __launch_bounds__(kBlock) void remap_backward_f32_kernel(
       const int s = live[u] ? e / kFoot : 0, tap = live[u] ? e - s * kFoot : 0;
       const int a = tap / kTaps, b = tap - a * kTaps;
       const int2 rec = map[s];
-      const float wy = table[(rec.y & (kPhases - 1)) * kTaps + a];
-      const float wx = table[(rec.x & (kPhases - 1)) * kTaps + b];
+      const float wy = table[record_phase(rec.y) * kTaps + a];
+      const float wx = table[record_phase(rec.x) * kTaps + b];
       const int r = s / gw, q = s - r * gw;
       const float *gp = g + ((long long)(r / ss) * vw + q / ss);
 #pragma unroll
@@ -93,13 +90,9 @@ extern "C" int pconv_remap_backward_f32(const float *gout, float *gin, const int
                                         int vw, int ss, long long gout_frame_stride, int accumulate, void *stream) {
   PCONV_REQUIRE(gout && gin && map && phases, "remap_backward_f32: null pointer");
   PCONV_REQUIRE(rev_start && rev_entry, "remap_backward_f32: null list pointer");
-  PCONV_REQUIRE(n > 0 && c > 0 && (long long)n * c <= 65535,
-                "remap_backward_f32: n * C = %lld planes, the grid takes 1 .. 65535", (long long)n * c);
-  PCONV_REQUIRE(h >= 2 && w >= 2 && h <= (1 << 20) && w <= (1 << 20),
-                "remap_backward_f32: a source side of %dx%d is outside 2 .. 2^20", w, h);
-  PCONV_REQUIRE(4LL * h * w < (1LL << 31), "remap_backward_f32: a source plane of %dx%d float32 is 2^31 bytes or more", w, h);
-  PCONV_REQUIRE(vh >= 2 && vw >= 2 && vh <= (1 << 20) && vw <= (1 << 20),
-                "remap_backward_f32: a view side of %dx%d is outside 2 .. 2^20", vw, vh);
+  if (planes_ok("remap_backward_f32", n, c) != PCONV_OK || frame_ok("remap_backward_f32", "source ", h, w) != PCONV_OK ||
+      side_ok("remap_backward_f32", "view ", vh, vw) != PCONV_OK)
+    return PCONV_EINVAL;
   PCONV_REQUIRE(ss >= 1 && ss <= PCONV_VIEWPORT_MAX_SS, "remap_backward_f32: ss = %d supersampling is outside 1 .. %d", ss,
                 PCONV_VIEWPORT_MAX_SS);
   PCONV_REQUIRE(8LL * ss * ss * vh * vw < (1LL << 31), "remap_backward_f32: a map of %dx%d records is 2^31 bytes or more",
@@ -112,11 +105,9 @@ extern "C" int pconv_remap_backward_f32(const float *gout, float *gin, const int
                 "or more", c, vw, vh);
   PCONV_REQUIRE(gout_frame_stride >= frame, "remap_backward_f32: the gradient frame stride %lld is below C * vh * vw = %lld",
                 gout_frame_stride, frame);
-  const uintptr_t ag = reinterpret_cast<uintptr_t>(gout), ai = reinterpret_cast<uintptr_t>(gin),
-                  am = reinterpret_cast<uintptr_t>(map), ap = reinterpret_cast<uintptr_t>(phases),
-                  as = reinterpret_cast<uintptr_t>(rev_start), ae = reinterpret_cast<uintptr_t>(rev_entry);
-  PCONV_REQUIRE(((ag | ai | ap | as | ae) & 3) == 0 && (am & 7) == 0,
-                "remap_backward_f32: the tensors and lists must be 4-byte aligned, the map 8-byte aligned");
+  if (aligned_ok("remap_backward_f32", addr(gout) | addr(gin) | addr(phases) | addr(rev_start) | addr(rev_entry),
+                 "the tensors and lists", addr(map), "the map") != PCONV_OK)
+    return PCONV_EINVAL;
   PCONV_REQUIRE(gin != gout, "remap_backward_f32: gin and gout must be distinct");
   const int hw = h * w;
   const int groups = (c + kPlanes - 1) / kPlanes;  // n * groups <= n * C <= 65535
