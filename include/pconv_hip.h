@@ -489,6 +489,76 @@ int pconv_viewport_map(int32_t *map, int h, int w, int gh, int gw, int yaw, int 
 int pconv_viewport_render_f32(const float *in, float *out, const int32_t *map, const float *phases, int n, int c, int h,
                               int w, int vh, int vw, int ss, long long out_frame_stride, int clamp, void *stream);
 
+/* Cubemap panoramas, CMP and EAC (csrc/cube.hip; pseudocylindrical_convolution_amd/cube.py states the same definition in
+ * torch and numpy).  A cube conversion is two maps for pconv_viewport_render_f32 and one kernel that continues a face
+ * across its edges; the sampler is the one above, word for word.
+ * Axes: those of the sphere rotation: the picture centre is (1, 0, 0), right is +y, up is +z.
+ * Faces, in this order, each with forward, right and up:
+ *     index  face  forward      right        up
+ *     0      F     ( 1, 0, 0)   ( 0, 1, 0)   ( 0, 0, 1)
+ *     1      R     ( 0, 1, 0)   (-1, 0, 0)   ( 0, 0, 1)
+ *     2      B     (-1, 0, 0)   ( 0,-1, 0)   ( 0, 0, 1)
+ *     3      L     ( 0,-1, 0)   ( 1, 0, 0)   ( 0, 0, 1)
+ *     4      U     ( 0, 0, 1)   ( 0, 1, 0)   (-1, 0, 0)
+ *     5      D     ( 0, 0,-1)   ( 0, 1, 0)   ( 1, 0, 0)
+ *   F, R, B, L: up = +z, right = the forward of the next face in yaw order.  U and D: the edge shared with F is U's
+ *   bottom edge and D's top edge.  right x up = forward on every face.
+ * Face coordinates of a face of a x a pixels: s, t in [-1, 1], at the centre of pixel (row r, column c)
+ *   s = 2*(c + 1/2)/a - 1,  t = 1 - 2*(r + 1/2)/a.  Plane coordinates: PCONV_CUBE_CMP p = s;  PCONV_CUBE_EAC
+ *   p = tan(pi/4 * s), inverse s = (4/pi)*atan(p).  Direction d = forward + p_s*right + p_t*up, all in fp64.
+ * Face of a direction (x, y, z): the axis of largest magnitude; ties in the order x, y, z:
+ *   |x| >= |y| and |x| >= |z| -> x >= 0 ? F : B;  else |y| >= |z| -> y >= 0 ? R : L;  else z >= 0 ? U : D
+ *   (pconv_host_cube_face_of: the rule on the host).  A tie is the one place where host and device could disagree by a
+ *   whole face: a direction within rounding of an edge or corner of the cube may land on either side.
+ *   Position on face g: p_s = (d . right_g)/(d . forward_g), p_t = (d . up_g)/(d . forward_g), s and t through the
+ *   inverse above, u' = (s + 1)*a/2 - 1/2, v' = (1 - t)*a/2 - 1/2 (pixels; the centre of pixel (r, c) is (c, r)).
+ * The canonical picture is the face stack (n, C, 6*a, a), face f in rows f*a .. f*a + a - 1.  Other layouts are index
+ *   permutations made above this interface.  a in 2 .. PCONV_CUBE_MAX_FACE, the largest a whose padded stack (below)
+ *   stays under 2^31 bytes.
+ * ERP -> cube.  pconv_cube_from_erp_map: map (6*a*ss, a*ss, 2) int32 on the device.  With gs = a*ss, sample (row R, column
+ *   Q) belongs to face R / gs; its face coordinates are those of the sample grid of that face, as in pconv_viewport_map:
+ *   s = 2*(Q + 1/2)/gs - 1, t = 1 - 2*((R mod gs) + 1/2)/gs.  The record is that of pconv_erp_rotation_map for the
+ *   direction d and the source size h x w.  The picture is pconv_viewport_render_f32 on that map: source h x w, "view"
+ *   6*a x a, ss in 1 .. 4; an ss x ss block never leaves its face.
+ * Cube -> ERP.  A face is first continued by PCONV_CUBE_PAD = 3 pixels on every side (the footprint reaches 2 pixels
+ *   before and 3 after its centre tap), A = a + 6.
+ *   pconv_cube_pad_f32: in (n, C, 6*a, a) -> out (n, C, 6*A, A), distinct.  Interior: out[f*A + 3 + r][3 + c] =
+ *   in[f*a + r][c], a copy.  Ring pixel (face f, padded row R, padded column Q, r = R - 3 or c = Q - 3 outside 0 .. a-1):
+ *   its value is the bilinear read of face g at (qu, qv) in 1/256 pixel, (g, qu, qv) its record in `table`:
+ *     x0 = qu >> 8, fx = (float)(qu & 255)/256, x1 = min(x0 + 1, a - 1); y0, fy, y1 from qv alike;
+ *     top = x[y0][x0] + fx*(x[y0][x1] - x[y0][x0]);  bot = x[y1][x0] + fx*(x[y1][x1] - x[y1][x0]);
+ *     out = top + fy*(bot - top);  every subtraction, product and addition one fp32 rounding, never contracted.
+ *   That form returns the constant for a constant face.  One level deep: the ring reads original faces only.
+ *   table: int32 (6*(A*A - a*a), 3) on the device, face after face, within a face in ring order: the pixels of the padded
+ *   face outside its interior, row after row, column after column (12*a + 36 per face).  It is built on the host in
+ *   float64 (cube.pad_table): ring pixel (R, Q) lies on f's extended plane at the s, t of its centre by the same
+ *   formulas, |s| or |t| > 1, EAC through tan as well (|s| and |t| held at 7/4 there, before the plane's horizon at 2:
+ *   only faces of a <= 6 reach it); its direction falls on face g; u', v' there are
+ *   clamped to [0, a - 1] and quantised, qu = rint(u'*256), halves to even.  The corners follow the same rule.  The kernel
+ *   reduces whatever the table holds to a face 0 .. 5 and a position inside it, so no table content makes it read
+ *   outside `in`.
+ *   pconv_cube_to_erp_map: map (h*ss, w*ss, 2) int32 on the device.  Sample (row j, column i) of the gh x gw = h*ss x w*ss
+ *   grid has the direction of pixel (j, i) of a gh x gw ERP frame (the sphere rotation above); that gives face g and u', v',
+ *   clamped to [-1/2, a - 1/2].  The record addresses the padded stack seen as one plane of 6*A x A:
+ *     qu = rint((u' + 3)*256),  qv = rint((v' + 3 + g*A)*256).
+ *   Every footprint then stays inside its own padded face; the sampler's wrap and pole rule never fire, but still
+ *   guarantee that no record reads outside the plane.  The picture is pconv_viewport_render_f32 with the padded stack
+ *   as the source (6*A x A) and the ERP frame as the view.
+ * Both maps run their trigonometry in fp64 on the device: they equal a float64 evaluation on the host except where
+ *   u*256 or v*256 lies within the evaluation error of a rounding boundary, or a direction within it of a face tie.
+ * Tensors and the table 4-byte aligned, maps 8-byte aligned; no allocation, no atomics, no workspace.  Refused on the host,
+ *   before any launch, with PCONV_EINVAL: null or misaligned pointers, a kind outside {CMP, EAC}, a outside
+ *   2 .. PCONV_CUBE_MAX_FACE, an ERP side outside 2 .. 2^20 or an ERP plane or a map of 2^31 bytes or more, n * C outside
+ *   1 .. 65535, ss outside 1 .. 4, in == out. */
+#define PCONV_CUBE_CMP 1
+#define PCONV_CUBE_EAC 2
+#define PCONV_CUBE_PAD 3
+#define PCONV_CUBE_MAX_FACE 9453
+int pconv_host_cube_face_of(double x, double y, double z);
+int pconv_cube_from_erp_map(int32_t *map, int kind, int a, int ss, int h, int w, void *stream);
+int pconv_cube_pad_f32(const float *in, float *out, const int32_t *table, int n, int c, int a, void *stream);
+int pconv_cube_to_erp_map(int32_t *map, int kind, int a, int h, int w, int ss, void *stream);
+
 /* Sphere-sampled metrics: S-PSNR-NN, S-PSNR-I, CPP-PSNR (csrc/sphere_points.hip; pseudocylindrical_convolution_amd/
  * sphere_points.py states the same definition in torch and numpy).  Two ERP pictures of ANY two sizes are read at the
  * same points of the sphere and the squared error is summed over the points; neither picture is resampled onto the

@@ -1929,6 +1929,73 @@ def remap_backward_f32(gout, map, lists, h, w, vh, vw, ss, gin=None, slot=0, acc
     return gin
 
 
+CUBE_KINDS = {"cmp": 1, "eac": 2}   # PCONV_CUBE_CMP, PCONV_CUBE_EAC
+CUBE_PAD = 3                        # PCONV_CUBE_PAD
+CUBE_MAX_FACE = 9453                # PCONV_CUBE_MAX_FACE
+
+
+def _cube_args(what, kind, a, ss):
+    if kind not in CUBE_KINDS:
+        raise PconvError("%s: kind must be one of %s, got %r" % (what, sorted(CUBE_KINDS), kind))
+    a, ss = int(a), int(ss)
+    if not (2 <= a <= CUBE_MAX_FACE and 1 <= ss <= 4):
+        raise PconvError("%s: a face size of %d with ss = %d: a of 2 .. %d and ss of 1 .. 4 expected" % (what, a, ss, CUBE_MAX_FACE))
+    return CUBE_KINDS[kind], a, ss
+
+
+def cube_from_erp_map(kind, a, ss, h, w, device=None, out=None):
+    """int32 (6 a ss, a ss, 2) GPU tensor: where on the h x w ERP source each sample of the face stack of a "cmp" / "eac"
+    cube of face size a lies, in 1/256 pixel (cube.py, pconv_cube_from_erp_map).  One launch; the trigonometry runs in
+    fp64 on the device"""
+    code, a, ss = _cube_args("cube_from_erp_map", kind, a, ss)
+    h, w = int(h), int(w)
+    device = _gpu_device("cube_from_erp_map", device)
+    _require_sides("cube_from_erp_map", h, w)
+    gs = a * ss
+    if 8 * 6 * gs * gs >= 1 << 31:
+        raise PconvError("cube_from_erp_map: a map of %dx%d records is 2^31 bytes or more" % (gs, 6 * gs))
+    out = _output("cube_from_erp_map", out, (6 * gs, gs, 2), torch.int32, device, device)
+    with torch.cuda.device(device), _HbmTimed("cube_from_erp_map_kernel", "CubeFromErpMap a%d ss%d" % (a, ss), 48.0 * gs * gs,
+                                              device):
+        call("pconv_cube_from_erp_map", _ptr(out), code, a, ss, h, w, _stream(device))
+    return out
+
+
+def cube_to_erp_map(kind, a, h, w, ss, device=None, out=None):
+    """int32 (h ss, w ss, 2) GPU tensor: where on the padded face stack (one plane of 6 (a + 6) x (a + 6)) each sample of
+    an h x w ERP frame lies, in 1/256 pixel (cube.py, pconv_cube_to_erp_map).  One launch, fp64 on the device"""
+    code, a, ss = _cube_args("cube_to_erp_map", kind, a, ss)
+    h, w = int(h), int(w)
+    device = _gpu_device("cube_to_erp_map", device)
+    _require_sides("cube_to_erp_map", h, w)
+    if 8 * h * ss * w * ss >= 1 << 31:
+        raise PconvError("cube_to_erp_map: a map of %dx%d records is 2^31 bytes or more" % (w * ss, h * ss))
+    out = _output("cube_to_erp_map", out, (h * ss, w * ss, 2), torch.int32, device, device)
+    with torch.cuda.device(device), _HbmTimed("cube_to_erp_map_kernel", "CubeToErpMap %dx%d ss%d" % (w, h, ss),
+                                              8.0 * h * w * ss * ss, device):
+        call("pconv_cube_to_erp_map", _ptr(out), code, a, h, w, ss, _stream(device))
+    return out
+
+
+def cube_pad_f32(x, table, out=None):
+    """float32 (n, C, 6 a, a) GPU face stack -> (n, C, 6 A, A), A = a + 6: every face continued by 3 pixels across its
+    edges, the ring read bilinearly from the neighbouring faces through `table` (int32 (6 (A^2 - a^2), 3) on the same
+    device, from cube.pad_table) (cube.py, pconv_cube_pad_f32).  One launch; out must not be x"""
+    n, c, h6, a = _require_frames(x, "cube_pad_f32")
+    if h6 != 6 * a or not 2 <= a <= CUBE_MAX_FACE:
+        raise PconvError("cube_pad_f32: a face stack (n, C, 6 a, a), a of 2 .. %d, expected, got %s" % (CUBE_MAX_FACE, tuple(x.shape)))
+    A = a + 2 * CUBE_PAD
+    ring = 6 * (A * A - a * a)
+    if table.dtype != torch.int32 or tuple(table.shape) != (ring, 3) or not table.is_contiguous() or table.device != x.device:
+        raise PconvError("cube_pad_f32: the table must be contiguous int32 (%d, 3) on the input's device" % ring)
+    out = _output("cube_pad_f32", out, (n, c, 6 * A, A), torch.float32, x.device, "the input's device")
+    # the faces read + the padded stack written + the ring's records and four reads per ring pixel
+    counted = 4.0 * (x.numel() + out.numel()) + n * c * ring * (12.0 + 16.0)
+    with _HbmTimed("cube_pad_f32_kernel", "CubePad a%d n%d" % (a, n), counted, x.device):
+        call("pconv_cube_pad_f32", _ptr(x), _ptr(out), _ptr(table), n, c, a, _stream(x.device))
+    return out
+
+
 WS_WEIGHTINGS = {"ws": 0, "uniform": 1}  # PCONV_WS_WEIGHT_SPHERE, PCONV_WS_WEIGHT_UNIFORM
 
 

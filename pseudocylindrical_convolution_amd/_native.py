@@ -18,6 +18,7 @@ P = c_void_p  # device or host pointer passed as an integer address
 I = c_int
 F = c_float
 LL = c_longlong
+D = ctypes.c_double
 
 _HIP_SIGNATURES = {
     # host geometry
@@ -70,6 +71,10 @@ _HIP_SIGNATURES = {
     "pconv_host_viewport_basis": [I, I, I, I, I, P],
     "pconv_viewport_map": [P, I, I, I, I, I, I, I, I, I, P],
     "pconv_viewport_render_f32": [P, P, P, P, I, I, I, I, I, I, I, LL, I, P],
+    "pconv_host_cube_face_of": [D, D, D],
+    "pconv_cube_from_erp_map": [P, I, I, I, I, I, P],
+    "pconv_cube_pad_f32": [P, P, P, I, I, I, P],
+    "pconv_cube_to_erp_map": [P, I, I, I, I, I, P],
     "pconv_host_remap_reverse_size": [I, I],
     "pconv_host_remap_reverse": [P, I, I, I, I, P, P],
     "pconv_remap_backward_f32": [P, P, P, P, P, P, I, I, I, I, I, I, I, LL, I, P],

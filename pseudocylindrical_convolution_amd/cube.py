@@ -1,0 +1,518 @@
+"""Cubemap panoramas, CMP and EAC: cube <-> ERP on the sphere sampler (include/pconv_hip.h, pconv_cube_from_erp_map /
+pconv_cube_pad_f32 / pconv_cube_to_erp_map; csrc/cube.hip).
+
+Axes are erp_rotate.py's: the picture centre is (1, 0, 0), right is +y, up is +z.  The six faces, in this order, with
+forward, right and up (`FACES`): F +x, R +y, B -x, L -y (up +z, right the next face's forward in yaw order), U +z and D -z
+(the edge shared with F is U's bottom edge and D's top edge).  A face of a x a pixels has face coordinates s = 2 (c + 1/2)
+/ a - 1, t = 1 - 2 (r + 1/2) / a at pixel centres; the plane coordinate is p = s for "cmp" and p = tan(pi/4 s) for "eac"
+(inverse s = 4/pi atan(p)); the direction is forward + p_s right + p_t up, all in float64.  The face of a direction is
+the axis of largest magnitude, ties in the order x, y, z (`>=`), the sign picking the face (`face_of`).
+
+Layouts are index permutations, done here in torch: "faces" (n, C, 6a, a), the stack in the order above, is what every
+kernel sees; "6x1" the six faces side by side, unrotated; "3x2" a top row L F R unrotated over a bottom row D B U, D and
+U turned a quarter counter-clockwise and B a quarter clockwise, so that each row is continuous across its two inner
+edges.  The 3x2 layout is meant as the CMP / EAC frame packing of 360Lib; equality with 360Lib's packing is not claimed.
+
+ERP -> cube (`from_erp`): one map (`from_erp_map`: the record, in 1/256 pixel, of every sample of the face stack on the
+ERP source) and viewport's renderer on it, the 6 x 6 Lanczos-3 sampler with an ss x ss average; an ss x ss block never
+leaves its face.  Cube -> ERP (`to_erp`): the faces are first continued by PAD = 3 pixels across their edges (`pad`: the
+ring read bilinearly from the neighbouring faces through `pad_table`, one level deep), then a second map (`to_erp_map`:
+the record of every ERP sample on the padded stack seen as one plane of 6A x A, A = a + 6) and the same renderer; every
+footprint stays inside its own padded face.  ss defaults to the source pixels per output pixel at the face centre / the
+equator, at most 4; beyond 4 the source is to be reduced first (erp_resample.resize).
+
+GPU tensors take the HIP kernels (PCONV.cube_*, PCONV.viewport_render_f32), CPU tensors the torch twins below
+(`pad_torch`, viewport.render_torch): the same bits on the same map and table.  `from_erp` of a tensor that requires grad
+goes through viewport's Function (the ordered backward of pconv_remap_backward_f32: the map is generic); `to_erp` under
+autograd is refused: the pad kernel has no backward yet.
+
+Limits.  The ring is bilinear and one level deep, so within 3 pixels of a face edge the way back reads a slightly softer
+continuation than the sphere itself.  For "eac" the extended plane ends before its horizon: |s| and |t| of a ring pixel
+are held at 7/4, which only faces of a <= 6 reach.  ss is chosen for the face centre / the equator.
+"""
+import collections
+import functools
+import math
+
+import numpy as np
+import torch
+
+from . import erp_rotate, viewport
+from ._native import PconvError
+from .PCONV_operator import backend
+
+PHASES = erp_rotate.PHASES
+KINDS = {"cmp": 1, "eac": 2}        # PCONV_CUBE_CMP, PCONV_CUBE_EAC: the container's code too
+LAYOUTS = {"faces": 0, "6x1": 1, "3x2": 2}   # the container's code
+PAD = 3                             # PCONV_CUBE_PAD
+MAX_FACE = 9453                     # PCONV_CUBE_MAX_FACE: 24 (a + 6)^2 < 2^31
+MAX_SS = viewport.MAX_SS
+RING_LIMIT = 1.75                   # |s|, |t| of an "eac" ring pixel are held here (faces of a <= 6 only)
+FACE_NAMES = "FRBLUD"
+# (6, 3, 3): forward, right, up of each face
+FACES = np.array([[[1, 0, 0], [0, 1, 0], [0, 0, 1]],
+                  [[0, 1, 0], [-1, 0, 0], [0, 0, 1]],
+                  [[-1, 0, 0], [0, -1, 0], [0, 0, 1]],
+                  [[0, -1, 0], [1, 0, 0], [0, 0, 1]],
+                  [[0, 0, 1], [0, 1, 0], [-1, 0, 0]],
+                  [[0, 0, -1], [0, 1, 0], [1, 0, 0]]], dtype=np.float64)
+FACES.setflags(write=False)
+
+Spec = collections.namedtuple("Spec", "kind layout")
+
+
+def spec(kind, layout="3x2"):
+    """the checked, hashable description of a cube picture: Spec(kind, layout), kind "cmp" or "eac", layout "faces",
+    "6x1" or "3x2".  A Spec passes through"""
+    if isinstance(kind, Spec):
+        kind, layout = kind
+    if kind not in KINDS:
+        raise PconvError("cube: kind must be one of %s, got %r" % (sorted(KINDS), kind))
+    if layout not in LAYOUTS:
+        raise PconvError("cube: layout must be one of %s, got %r" % (sorted(LAYOUTS), layout))
+    return Spec(kind, layout)
+
+
+def _spec(sp, layout=None):
+    sp = sp if isinstance(sp, Spec) else Spec(sp, "3x2")
+    return spec(sp.kind, sp.layout if layout is None else layout)
+
+
+def _kind(kind):
+    if isinstance(kind, Spec):
+        kind = kind.kind
+    if kind not in KINDS:
+        raise PconvError("cube: kind must be one of %s, got %r" % (sorted(KINDS), kind))
+    return kind
+
+
+def check_face(a):
+    if int(a) != a or not 2 <= int(a) <= MAX_FACE:
+        raise PconvError("cube: a face size of %r is outside 2 .. %d" % (a, MAX_FACE))
+    return int(a)
+
+
+def _check_ss(ss):
+    if int(ss) != ss or not 1 <= int(ss) <= MAX_SS:
+        raise PconvError("cube: ss = %r supersampling is outside 1 .. %d" % (ss, MAX_SS))
+    return int(ss)
+
+
+def _check_erp(h, w):
+    try:
+        return erp_rotate._check_size(h, w)
+    except PconvError as exc:
+        raise PconvError(str(exc).replace("erp rotate:", "cube: the ERP frame:"))
+
+
+def erp_size(a):
+    """(2a, 4a): the ERP size whose equator has the pixel density of the face centres' ring"""
+    a = check_face(a)
+    return 2 * a, 4 * a
+
+
+def face_size(h, w):
+    """round(w / 4), at least 2"""
+    return max(2, int(math.floor(int(w) / 4.0 + 0.5)))
+
+
+def picture_size(a, layout):
+    """(height, width) of a cube picture of face size a in `layout`"""
+    a = check_face(a)
+    return {"faces": (6 * a, a), "6x1": (a, 6 * a), "3x2": (2 * a, 3 * a)}[spec("cmp", layout).layout]
+
+
+def face_size_of(shape, layout):
+    """the face size of a cube picture of `shape` = (.., height, width) in `layout`; PconvError when it is none"""
+    layout = spec("cmp", layout).layout
+    hh, ww = int(shape[-2]), int(shape[-1])
+    a = {"faces": ww, "6x1": hh, "3x2": hh // 2}[layout]
+    if a < 2 or picture_size(a, layout) != (hh, ww):
+        raise PconvError("cube: a picture of %dx%d is no %r layout of square faces" % (ww, hh, layout))
+    return a
+
+
+# ---- geometry: float64 numpy ----
+
+def plane_of(kind, s):
+    return np.tan((np.pi / 4.0) * s) if _kind(kind) == "eac" else s
+
+
+def face_of_plane(kind, p):
+    return (4.0 / np.pi) * np.arctan(p) if _kind(kind) == "eac" else p
+
+
+def direction(kind, face, s, t):
+    """float64 (3, ...): forward + p_s right + p_t up of face(s) `face` at face coordinates s, t (not normalised)"""
+    face = np.asarray(face)
+    ps, pt = plane_of(kind, np.asarray(s, dtype=np.float64)), plane_of(kind, np.asarray(t, dtype=np.float64))
+    fr = FACES[face]                                   # (..., 3, 3)
+    return np.stack([fr[..., 0, k] + ps * fr[..., 1, k] + pt * fr[..., 2, k] for k in range(3)])
+
+
+def face_of(d):
+    """the face of direction(s) d (3, ...): the axis of largest magnitude, ties in the order x, y, z; the sign picks"""
+    x, y, z = (np.asarray(v, dtype=np.float64) for v in d)
+    ax, ay, az = np.abs(x), np.abs(y), np.abs(z)
+    return np.where((ax >= ay) & (ax >= az), np.where(x >= 0.0, 0, 2),
+                    np.where(ay >= az, np.where(y >= 0.0, 1, 3), np.where(z >= 0.0, 4, 5)))
+
+
+def tie_margin(d):
+    """how far, relative to the largest magnitude, direction(s) d lie from a face tie"""
+    m = np.sort(np.abs(np.stack([np.asarray(v, dtype=np.float64) for v in d])), axis=0)
+    return (m[2] - m[1]) / m[2]
+
+
+def face_st(kind, d, face=None):
+    """(g, s, t): the face direction(s) d fall on (or `face`) and the face coordinates there"""
+    x, y, z = (np.asarray(v, dtype=np.float64) for v in d)
+    g = face_of((x, y, z)) if face is None else np.asarray(face)
+    fr = FACES[g]
+    dot = lambda k: x * fr[..., k, 0] + y * fr[..., k, 1] + z * fr[..., k, 2]
+    along = dot(0)
+    return g, face_of_plane(kind, dot(1) / along), face_of_plane(kind, dot(2) / along)
+
+
+def face_position(kind, a, d):
+    """(g, u', v'): the face of d and the position on it in pixels, u' = (s + 1) a / 2 - 1/2, v' = (1 - t) a / 2 - 1/2"""
+    g, s, t = face_st(kind, d)
+    return g, (s + 1.0) * a / 2.0 - 0.5, (1.0 - t) * a / 2.0 - 0.5
+
+
+def face_grid(kind, a, ss=1):
+    """float64 (3, 6 a ss, a ss): the direction of every sample of the face stack's grid"""
+    gs = check_face(a) * _check_ss(ss)
+    s = (2.0 * (np.arange(gs, dtype=np.float64) + 0.5) / gs - 1.0)[None, :]
+    t = (1.0 - 2.0 * (np.arange(gs, dtype=np.float64) + 0.5) / gs)[:, None]
+    return np.concatenate([direction(kind, f, s, t) for f in range(6)], axis=1)
+
+
+def erp_coordinates(d, h, w):
+    """(u, v) float64: the column and row, in pixels of an h x w ERP frame, of direction(s) d (the rule before its
+    quantisation; erp_rotate.py's)"""
+    sx, sy, sz = d
+    u = (np.arctan2(sy, sx) / (2.0 * np.pi) + 0.5) * w - 0.5
+    v = (0.5 - np.arctan2(sz, np.hypot(sx, sy)) / np.pi) * h - 0.5
+    return u, v
+
+
+def from_erp_coordinates(kind, a, ss, h, w):
+    """(u, v) float64 (6 a ss, a ss): where on the h x w ERP source each sample of the face stack reads"""
+    h, w = _check_erp(h, w)
+    return erp_coordinates(face_grid(kind, a, ss), h, w)
+
+
+def from_erp_map_numpy(kind, a, ss, h, w):
+    """the ERP -> cube map in float64 on the host: int32 (6 a ss, a ss, 2) records of erp_rotate.py's form"""
+    u, v = from_erp_coordinates(kind, a, ss, h, w)
+    qu = np.mod(np.rint(u * PHASES).astype(np.int64), int(w) * PHASES)
+    qv = np.rint(v * PHASES).astype(np.int64)
+    return np.stack([qu, qv], axis=2).astype(np.int32)
+
+
+def erp_grid(gh, gw):
+    """float64 (3, gh, gw): the direction of every pixel of a gh x gw ERP frame (erp_rotate.py's)"""
+    theta = ((np.arange(gw, dtype=np.float64) + 0.5) / gw - 0.5) * (2.0 * np.pi)
+    phi = (0.5 - (np.arange(gh, dtype=np.float64) + 0.5) / gh) * np.pi
+    cp, sp = np.cos(phi)[:, None], np.sin(phi)[:, None]
+    return np.stack([cp * np.cos(theta)[None, :], cp * np.sin(theta)[None, :], sp * np.ones((1, gw))])
+
+
+def to_erp_coordinates(kind, a, h, w, ss):
+    """(g, u', v') of every sample of the (h ss) x (w ss) ERP grid: its face and the position there, clamped to
+    [-1/2, a - 1/2]"""
+    a, ss = check_face(a), _check_ss(ss)
+    h, w = _check_erp(h, w)
+    g, u, v = face_position(kind, a, erp_grid(h * ss, w * ss))
+    return g, np.clip(u, -0.5, a - 0.5), np.clip(v, -0.5, a - 0.5)
+
+
+def to_erp_map_numpy(kind, a, h, w, ss):
+    """the cube -> ERP map in float64 on the host: int32 (h ss, w ss, 2), qu = rint((u' + 3) 256), qv = rint((v' + 3 +
+    g A) 256) on the padded stack seen as one plane of 6A x A"""
+    g, u, v = to_erp_coordinates(kind, a, h, w, ss)
+    A = int(a) + 2 * PAD
+    qu = np.rint((u + PAD) * PHASES).astype(np.int64)
+    qv = np.rint((v + PAD + g.astype(np.float64) * A) * PHASES).astype(np.int64)
+    return np.stack([qu, qv], axis=2).astype(np.int32)
+
+
+def ring_pixels(a):
+    """(R, Q) int64 arrays of 12 a + 36 elements: the pixels of a padded face outside its interior, in ring order (row
+    after row, column after column)"""
+    a = check_face(a)
+    A = a + 2 * PAD
+    outside = np.ones((A, A), dtype=bool)
+    outside[PAD:PAD + a, PAD:PAD + a] = False
+    return np.nonzero(outside)
+
+
+def ring_directions(kind, a):
+    """float64 (3, 6, 12 a + 36): the direction of every ring pixel, on its own face's extended plane"""
+    R, Q = ring_pixels(a)
+    s = 2.0 * ((Q - PAD) + 0.5) / a - 1.0
+    t = 1.0 - 2.0 * ((R - PAD) + 0.5) / a
+    if _kind(kind) == "eac":
+        s, t = np.clip(s, -RING_LIMIT, RING_LIMIT), np.clip(t, -RING_LIMIT, RING_LIMIT)
+    return np.stack([direction(kind, f, s, t) for f in range(6)], axis=1)
+
+
+def ring_coordinates(kind, a):
+    """(g, u', v') (6, 12 a + 36): the face each ring pixel's direction falls on and the position there, clamped to
+    [0, a - 1]"""
+    g, u, v = face_position(kind, a, ring_directions(kind, a))
+    return g, np.clip(u, 0.0, a - 1.0), np.clip(v, 0.0, a - 1.0)
+
+
+@functools.lru_cache(maxsize=8)
+def _pad_table(kind, a):
+    g, u, v = ring_coordinates(kind, a)
+    table = np.stack([g, np.rint(u * PHASES).astype(np.int64), np.rint(v * PHASES).astype(np.int64)], axis=2)
+    table = np.ascontiguousarray(table.reshape(-1, 3).astype(np.int32))
+    table.setflags(write=False)
+    return table
+
+
+def pad_table(kind, a):
+    """int32 (6 (A^2 - a^2), 3), read-only: (g, qu, qv) of every ring pixel, face after face in ring order, built in
+    float64 on the host.  Cached per (kind, a)"""
+    return _pad_table(_kind(kind), check_face(a))
+
+
+@functools.lru_cache(maxsize=4)
+def _pad_table_on(kind, a, device):
+    return torch.from_numpy(np.array(_pad_table(kind, a))).to(device)
+
+
+def _device(device):
+    device = torch.device("cpu" if device is None else device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def pad_table_on(kind, a, device=None):
+    """pad_table as a tensor on `device`, uploaded once (the last 4 kept); do not write to it"""
+    return _pad_table_on(_kind(kind), check_face(a), str(_device(device)))
+
+
+# ---- layouts ----
+
+def _check_stack(y, what="cube"):
+    if y.dim() != 4 or y.dtype != torch.float32 or y.shape[2] != 6 * y.shape[3]:
+        raise PconvError("%s: a float32 face stack (n, C, 6a, a) expected, got %s %s" % (what, y.dtype, tuple(y.shape)))
+    return check_face(y.shape[3])
+
+
+def pack(faces, layout):
+    """the face stack (n, C, 6a, a) in `layout`: "faces" itself, "6x1" (n, C, a, 6a), "3x2" (n, C, 2a, 3a)"""
+    layout = spec("cmp", layout).layout
+    a = _check_stack(faces)
+    if layout == "faces":
+        return faces
+    F, R, B, L, U, D = (faces[:, :, k * a:(k + 1) * a] for k in range(6))
+    if layout == "6x1":
+        return torch.cat([F, R, B, L, U, D], dim=3)
+    bottom = torch.cat([torch.rot90(D, 1, (2, 3)), torch.rot90(B, -1, (2, 3)), torch.rot90(U, 1, (2, 3))], dim=3)
+    return torch.cat([torch.cat([L, F, R], dim=3), bottom], dim=2)
+
+
+def unpack(y, layout):
+    """the face stack (n, C, 6a, a) of a cube picture in `layout`: the inverse of `pack`"""
+    layout = spec("cmp", layout).layout
+    if y.dim() != 4 or y.dtype != torch.float32:
+        raise PconvError("cube: a float32 (n, C, height, width) picture expected, got %s %s" % (y.dtype, tuple(y.shape)))
+    a = face_size_of(y.shape, layout)
+    if layout == "faces":
+        return y
+    if layout == "6x1":
+        return torch.cat([y[:, :, :, k * a:(k + 1) * a] for k in range(6)], dim=2)
+    top, bottom = y[:, :, :a], y[:, :, a:]
+    L, F, R = (top[:, :, :, k * a:(k + 1) * a] for k in range(3))
+    D, B, U = (torch.rot90(bottom[:, :, :, k * a:(k + 1) * a], q, (2, 3)) for k, q in ((0, -1), (1, 1), (2, -1)))
+    return torch.cat([F, R, B, L, U, D], dim=2)
+
+
+# ---- maps on a device ----
+
+@functools.lru_cache(maxsize=4)
+def _from_erp_map(kind, a, ss, h, w, device):
+    device = torch.device(device)
+    if device.type == "cuda":
+        ops = backend.ops()
+        if not hasattr(ops, "cube_from_erp_map"):
+            raise PconvError("cube: the active backend has no cube_from_erp_map kernel for a GPU device")
+        return ops.cube_from_erp_map(kind, a, ss, h, w, device)
+    return torch.from_numpy(from_erp_map_numpy(kind, a, ss, h, w))
+
+
+@functools.lru_cache(maxsize=4)
+def _to_erp_map(kind, a, h, w, ss, device):
+    device = torch.device(device)
+    if device.type == "cuda":
+        ops = backend.ops()
+        if not hasattr(ops, "cube_to_erp_map"):
+            raise PconvError("cube: the active backend has no cube_to_erp_map kernel for a GPU device")
+        return ops.cube_to_erp_map(kind, a, h, w, ss, device)
+    return torch.from_numpy(to_erp_map_numpy(kind, a, h, w, ss))
+
+
+@functools.lru_cache(maxsize=4)
+def _reverse_lists(kind, a, ss, h, w, device):
+    return viewport.reverse_lists(_from_erp_map(kind, a, ss, h, w, device), h, w)
+
+
+def _check_map_size(gh, gw):
+    if 8 * gh * gw >= 1 << 31:
+        raise PconvError("cube: a map of %dx%d records is 2^31 bytes or more" % (gw, gh))
+
+
+def from_erp_map(kind, a, ss, h, w, device=None):
+    """int32 (6 a ss, a ss, 2) on `device`: the HIP kernel for a GPU device, from_erp_map_numpy on the CPU (the two agree
+    except where a position lies within the evaluation error of a rounding boundary).  The last 4 maps are kept; do not
+    write to it"""
+    kind, a, ss = _kind(kind), check_face(a), _check_ss(ss)
+    h, w = _check_erp(h, w)
+    _check_map_size(6 * a * ss, a * ss)
+    return _from_erp_map(kind, a, ss, h, w, str(_device(device)))
+
+
+def to_erp_map(kind, a, h, w, ss, device=None):
+    """int32 (h ss, w ss, 2) on `device`, on the padded stack: the HIP kernel for a GPU device, to_erp_map_numpy on the
+    CPU (equal away from rounding boundaries and face ties).  The last 4 maps are kept; do not write to it"""
+    kind, a, ss = _kind(kind), check_face(a), _check_ss(ss)
+    h, w = _check_erp(h, w)
+    _check_map_size(h * ss, w * ss)
+    return _to_erp_map(kind, a, h, w, ss, str(_device(device)))
+
+
+# ---- the face continuation ----
+
+def pad_torch(y, table):
+    """the face continuation in torch, float32 operation by operation, on any device (the CPU path and the kernel's
+    twin): the face stack (n, C, 6a, a) and the int32 (6 (A^2 - a^2), 3) table -> (n, C, 6A, A)"""
+    a = _check_stack(y, "cube pad")
+    A = a + 2 * PAD
+    ring = A * A - a * a
+    if table.dtype != torch.int32 or tuple(table.shape) != (6 * ring, 3) or table.device != y.device:
+        raise PconvError("cube pad: the table must be int32 (%d, 3) on the faces' device, got %s %s on %s"
+                         % (6 * ring, table.dtype, tuple(table.shape), table.device))
+    n, c = y.shape[:2]
+    out = torch.zeros((n, c, 6, A, A), dtype=torch.float32, device=y.device)
+    out[:, :, :, PAD:PAD + a, PAD:PAD + a] = y.reshape(n, c, 6, a, a)
+    rec = table.long()
+    g = rec[:, 0].clamp(0, 5)
+    x0, y0 = (rec[:, 1] >> 8).clamp(0, a - 1), (rec[:, 2] >> 8).clamp(0, a - 1)
+    x1, y1 = (x0 + 1).clamp(max=a - 1), (y0 + 1).clamp(max=a - 1)
+    fx, fy = (rec[:, 1] & (PHASES - 1)).float() / PHASES, (rec[:, 2] & (PHASES - 1)).float() / PHASES
+    r0, r1 = g * a + y0, g * a + y1
+    x00, x01, x10, x11 = y[:, :, r0, x0], y[:, :, r0, x1], y[:, :, r1, x0], y[:, :, r1, x1]
+    top = x00 + fx * (x01 - x00)
+    bot = x10 + fx * (x11 - x10)
+    value = top + fy * (bot - top)
+    R, Q = (torch.from_numpy(v).to(y.device) for v in ring_pixels(a))
+    face = torch.arange(6, device=y.device).repeat_interleave(ring)
+    out[:, :, face, R.repeat(6), Q.repeat(6)] = value
+    return out.reshape(n, c, 6 * A, A)
+
+
+def pad_numpy(y, table):
+    """pad_torch in numpy, float32 operation by operation: a float32 array (n, C, 6a, a) and the int32 table -> (n, C,
+    6A, A)"""
+    y, rec = np.asarray(y, dtype=np.float32), np.asarray(table).astype(np.int64)
+    n, c, _, a = y.shape
+    A = a + 2 * PAD
+    out = np.zeros((n, c, 6, A, A), dtype=np.float32)
+    out[:, :, :, PAD:PAD + a, PAD:PAD + a] = y.reshape(n, c, 6, a, a)
+    g = np.clip(rec[:, 0], 0, 5)
+    x0, y0 = np.clip(rec[:, 1] >> 8, 0, a - 1), np.clip(rec[:, 2] >> 8, 0, a - 1)
+    x1, y1 = np.minimum(x0 + 1, a - 1), np.minimum(y0 + 1, a - 1)
+    fx = (rec[:, 1] & (PHASES - 1)).astype(np.float32) / np.float32(PHASES)
+    fy = (rec[:, 2] & (PHASES - 1)).astype(np.float32) / np.float32(PHASES)
+    r0, r1 = g * a + y0, g * a + y1
+    top = y[:, :, r0, x0] + fx * (y[:, :, r0, x1] - y[:, :, r0, x0])
+    bot = y[:, :, r1, x0] + fx * (y[:, :, r1, x1] - y[:, :, r1, x0])
+    R, Q = ring_pixels(a)
+    out[:, :, np.repeat(np.arange(6), R.size), np.tile(R, 6), np.tile(Q, 6)] = top + fy * (bot - top)
+    return out.reshape(n, c, 6 * A, A)
+
+
+def pad(y, kind):
+    """the face stack (n, C, 6a, a) continued by PAD pixels across every face edge: (n, C, 6A, A).  The HIP kernel for
+    GPU tensors, pad_torch for CPU tensors: the same bits"""
+    kind = _kind(kind)
+    a = _check_stack(y, "cube pad")
+    table = _pad_table_on(kind, a, str(y.device))
+    if y.is_cuda:
+        ops = backend.ops()
+        if not hasattr(ops, "cube_pad_f32"):
+            raise PconvError("cube: the active backend has no cube_pad_f32 kernel for a GPU tensor")
+        return ops.cube_pad_f32(y.contiguous(), table)
+    return pad_torch(y, table)
+
+
+# ---- the conversions ----
+
+def _render(x, map, vh, vw, ss, clamp):
+    if x.is_cuda:
+        ops = backend.ops()
+        if not hasattr(ops, "viewport_render_f32"):
+            raise PconvError("cube: the active backend has no viewport_render_f32 kernel for a GPU tensor")
+        return ops.viewport_render_f32(x.contiguous(), map, vh, vw, ss, clamp)[:, 0]
+    return viewport.render_torch(x, map, vh, vw, ss, clamp)
+
+
+def _default_ss(ratio, what, sizes):
+    if ratio > MAX_SS:
+        raise PconvError("cube: %s covers %.2f source pixels per pixel, more than %d: reduce the source first with "
+                         "erp_resample.resize" % (what % sizes, ratio, MAX_SS))
+    return min(MAX_SS, max(1, int(math.ceil(ratio - 1e-9))))
+
+
+def from_erp_ss(a, h, w):
+    """the default supersampling of from_erp: clamp(ceil(w / (4a) - 1e-9), 1, 4); a ratio above 4 is refused"""
+    return _default_ss(w / (4.0 * a), "a face of %d from a %dx%d ERP frame", (a, w, h))
+
+
+def to_erp_ss(a, h, w):
+    """the default supersampling of to_erp: clamp(ceil(4a / w - 1e-9), 1, 4); a ratio above 4 is refused"""
+    return _default_ss(4.0 * a / w, "a %dx%d ERP frame from faces of %d", (w, h, a))
+
+
+def from_erp(x, a=None, spec="cmp", ss=None, clamp=False, layout=None):
+    """float32 (n, C, h, w) ERP frames -> the cube picture of face size a (default face_size(h, w)) in the spec's layout
+    (`spec`: a Spec or a kind; layout= overrides its layout).  ss=None: from_erp_ss.  clamp=True bounds the result to
+    [0, 1].  The HIP kernels for GPU tensors, the twin on the CPU.  With grad mode on and x requiring a gradient the
+    result is attached to autograd through viewport's Function: the ordered backward of pconv_remap_backward_f32, its
+    lists built at the first backward and cached like the map"""
+    sp = _spec(spec, layout)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise PconvError("cube: float32 (n, C, h, w) expected, got %s %s" % (x.dtype, tuple(x.shape)))
+    h, w = _check_erp(*x.shape[2:])
+    a = face_size(h, w) if a is None else check_face(a)
+    ss = from_erp_ss(a, h, w) if ss is None else _check_ss(ss)
+    map = from_erp_map(sp.kind, a, ss, h, w, x.device)
+    if torch.is_grad_enabled() and x.requires_grad:
+        key = (sp.kind, a, ss, h, w, str(map.device))
+        views = [(map, lambda: _reverse_lists(*key), ss)]
+        faces = viewport._Remap.apply(x, lambda t: _render(t, map, 6 * a, a, ss, False).unsqueeze(1), views, bool(clamp))[:, 0]
+    else:
+        faces = _render(x, map, 6 * a, a, ss, clamp)
+    return pack(faces, sp.layout)
+
+
+def to_erp(y, size=None, spec="cmp", ss=None, clamp=False, layout=None):
+    """a float32 cube picture in the spec's layout -> ERP frames (n, C, h, w) of `size` = (h, w), default erp_size(a).
+    ss=None: to_erp_ss.  The HIP kernels for GPU tensors, the twins on the CPU.  Refused under autograd: the face
+    continuation (pconv_cube_pad_f32) has no backward yet"""
+    sp = _spec(spec, layout)
+    if torch.is_grad_enabled() and torch.is_tensor(y) and y.requires_grad:
+        raise PconvError("cube: to_erp of a tensor that requires grad: the face continuation (pconv_cube_pad_f32) has no "
+                         "backward yet; detach the picture, or train on the ERP side")
+    faces = unpack(y, sp.layout)
+    a = _check_stack(faces)
+    h, w = _check_erp(*(erp_size(a) if size is None else size))
+    ss = to_erp_ss(a, h, w) if ss is None else _check_ss(ss)
+    map = to_erp_map(sp.kind, a, h, w, ss, y.device)
+    return _render(pad(faces.contiguous(), sp.kind), map, h, w, ss, clamp)

@@ -300,7 +300,7 @@ class CodecEngine(object):
     ENCODE_CHUNK = int(os.environ.get("PCONV_ENCODE_CHUNK", "2"))
 
     @torch.no_grad()
-    def encode(self, frames, code_size=None, rotation=None):
+    def encode(self, frames, code_size=None, rotation=None, projection=None):
         """(n, 3, H, W) frames on the GPU -> n byte strings.  The frames of a chunk go through the
         entropy wavefront in lock-step; the chunks are pipelined: chunk k's CDF tables are coded by
         host threads while the GPU computes the symbols of chunk k+1 (each chunk has its own
@@ -311,8 +311,11 @@ class CodecEngine(object):
         decode(streams, h2, w2, out_size=(H, W)) brings the reconstruction back to the source size.
         rotation=(yaw, pitch, roll) in units of 2^-16 degree (erp_rotate.units): the frames are first of all turned
         on the device into that orientation (erp_rotate.py, clamped to [0, 1]), so that the point at longitude yaw,
-        latitude pitch is coded on the equator; decode(..., rotation=the same triple) turns the reconstruction back."""
-        frames = FrameGeometry(frames.shape[2:], code_size, rotation).to_coded(frames)
+        latitude pitch is coded on the equator; decode(..., rotation=the same triple) turns the reconstruction back.
+        projection=a cube.Spec: the frames are cube pictures (CMP or EAC, in the spec's layout); they are converted on the
+        device to the ERP frame of cube.erp_size(face size) before everything else (cube.to_erp, clamped to [0, 1]);
+        decode(streams, 2a, 4a, projection=the same spec) converts the reconstruction back last."""
+        frames = FrameGeometry.for_picture(frames.shape[2:], code_size, rotation, projection).to_coded(frames)
         n = frames.shape[0]
         chunk = self.ENCODE_CHUNK if n > self.ENCODE_CHUNK else n
         tiles = self.enc.ent.npart
@@ -368,18 +371,20 @@ class CodecEngine(object):
         return (cat(bits), cat(maps)) if rate_map else cat(bits)
 
     @torch.no_grad()
-    def rate(self, frames, rate_map=False, rotation=None):
+    def rate(self, frames, rate_map=False, rotation=None, projection=None):
         """(n, 3, H, W) frames on the GPU -> bits (n, npart, ngroup) float64 on the GPU: what encode() would spend
         per frame, latitude tile and channel group, from the CDF rows alone (rate.py) -- no arithmetic coder, no
         copy to the host, no file.  rate.bpp(bits, H, W) is the frame rate.  rate_map=True: also the bits of every
         latent position, (n, npart*2h, 2w) float32.  Sizes the codec does not take as they are are padded as
         encode() pads them (their bpp still counts their own pixels).  rotation: the frames are turned as encode()
-        turns them (rate_map is then in the coded orientation): what an orientation costs, without a file."""
-        frames = FrameGeometry(frames.shape[2:], None, rotation).to_coded(frames)
+        turns them (rate_map is then in the coded orientation): what an orientation costs, without a file.
+        projection: the frames are cube pictures, converted as encode() converts them (rate_map is that of the ERP
+        frame; their bpp counts the cube picture's pixels, FrameGeometry.pixels)."""
+        frames = FrameGeometry.for_picture(frames.shape[2:], None, rotation, projection).to_coded(frames)
         return self._rate_of_symbols(self.symbols(frames).contiguous(), frames.shape[0], rate_map)
 
     @torch.no_grad()
-    def evaluate(self, frames, rate_map=False, code_size=None, rotation=None, coded=False):
+    def evaluate(self, frames, rate_map=False, code_size=None, rotation=None, coded=False, projection=None):
         """one rate-distortion point without a file: (bits, reconstruction[, map]).  The symbols are computed once;
         bits (and map) are rate()'s, the reconstruction is decode(encode(frames), H, W)'s -- the entropy decoder
         returns exactly the symbols the encoder holds (tests/test_gpu_engine.py), so neither it nor the arithmetic
@@ -388,8 +393,10 @@ class CodecEngine(object):
         rotation: the frames are coded in that orientation (as encode() turns them) and the reconstruction is returned
         in the frames' own orientation, turned back last.  coded=True: one more element at the end, the reconstruction
         at the coded size (cropped to code_size, not resized back) -- None unless code_size changes the size and there is
-        no rotation: what sphere_points scores against the frames with no resize in between."""
-        geometry = FrameGeometry(frames.shape[2:], code_size, rotation)
+        no rotation: what sphere_points scores against the frames with no resize in between.
+        projection: the frames are cube pictures (converted as encode() converts them) and the reconstruction is
+        returned as cube pictures, converted back last."""
+        geometry = FrameGeometry.for_picture(frames.shape[2:], code_size, rotation, projection)
         frames = geometry.to_coded(frames)
         n = frames.shape[0]
         sym = self.symbols(frames).contiguous()
@@ -406,7 +413,7 @@ class CodecEngine(object):
     DECODE_CHUNK = int(os.environ.get("PCONV_DECODE_CHUNK", "0"))
 
     @torch.no_grad()
-    def decode(self, streams, height, width, out_size=None, rotation=None):
+    def decode(self, streams, height, width, out_size=None, rotation=None, projection=None):
         """n byte strings -> (n, 3, H, W).  With DECODE_CHUNK = c > 0 and more than c frames the call
         is pipelined: while the synthesis transform of chunk k runs, the entropy decoder of chunk k+1
         (a latency chain that leaves most of the GPU idle) runs beside it on a second stream, driven
@@ -414,8 +421,10 @@ class CodecEngine(object):
         of encode() of such frames, decoded at the coded size and cropped to (n, 3, height, width).
         out_size=(H, W): the reconstruction is then resized on the device to H x W by the rule of erp_resample.py,
         clamped to [0, 1] (the way back of encode(frames, code_size=(height, width))).
-        rotation: the triple encode() was given; the inverse rotation is applied last (erp_rotate.py, clamped)."""
-        geometry = FrameGeometry((height, width) if out_size is None else out_size, (height, width), rotation)
+        rotation: the triple encode() was given; the inverse rotation is applied last (erp_rotate.py, clamped).
+        projection: the cube.Spec encode() was given; the ERP reconstruction (whose size, out_size or height x width, is
+        cube.erp_size(face size)) is converted to the cube picture after everything else (cube.from_erp, clamped)."""
+        geometry = FrameGeometry((height, width) if out_size is None else out_size, (height, width), rotation, projection)
         h, w = PC.latent_shape(*geometry.coded, self.dec.npart)
         n = len(streams)
         tiles = self.dec.npart
@@ -458,12 +467,17 @@ class CodecEngine(object):
         return geometry.from_coded(torch.cat(out, 0))
 
     @torch.no_grad()
-    def decode_views(self, streams, height, width, renderer, out_size=None, rotation=None):
+    def decode_views(self, streams, height, width, renderer, out_size=None, rotation=None, projection=None):
         """n byte strings -> (frames, views): frames (n, 3, H, W) is decode() with the same arguments, views
         (n, V, 3, vh, vw) = renderer.render(frames, clamp=True), the viewports of a viewport.Renderer built for the
-        frames' size on this device.  Nothing leaves the device between the two."""
-        frames = self.decode(streams, height, width, out_size, rotation)
-        return frames, renderer.render(frames, clamp=True)
+        frames' size on this device.  Nothing leaves the device between the two.  projection: frames are the cube
+        pictures decode() returns; the views are rendered from the ERP reconstruction they were converted from."""
+        erp = self.decode(streams, height, width, out_size, rotation)
+        frames = erp
+        if projection is not None:
+            from . import cube
+            frames = cube.from_erp(erp, FrameGeometry(erp.shape[2:], None, None, projection).face, projection, clamp=True)
+        return frames, renderer.render(erp, clamp=True)
 
 
 class FramePipe(object):

@@ -215,11 +215,13 @@ class PseudoEncoder(nn.Module):
         header: dict(model_idx=, ssim=) -> the file gets the container header (container.py) in front of
         the same payload; None = the reference's raw stream.
         geometry: the FrameGeometry x is the coded frame of (frame_geometry.py) -- x was padded from, or rotated,
-        resized and padded from, another picture, which the header then records (container version 2, 3 or 4) and the
-        decoder returns to; None = x is the picture itself."""
+        resized and padded from, another picture (a cube picture among them), which the header then records (container
+        version 2 to 5) and the decoder returns to; None = x is the picture itself."""
         with torch.no_grad():
             if header is None and geometry is not None and geometry.rotated:
                 raise ValueError("a headerless stream cannot carry the rotation: give a header")
+            if header is None and geometry is not None and geometry.projected:
+                raise ValueError("a headerless stream cannot carry the projection: give a header")
             if header is not None:
                 if geometry is None:
                     geometry = FrameGeometry(x.shape[2:])
@@ -287,7 +289,8 @@ class PseudoDecoder(nn.Module):
         (container version 2) is decoded at its coded size and cropped to the original size (erp_size.py).
         A container that records a source size (version 3) is decoded the same way and then
         resized to the source size, clamped to [0, 1] (erp_resample.py); one that records a rotation (version 4) is
-        last of all turned back to the source's orientation (erp_rotate.py)."""
+        then turned back to the source's orientation (erp_rotate.py); one that records a projection (version 5) is last
+        of all converted to the cube picture (cube.py)."""
         rec, geometry = self.decode_coded(code_name, height, width, raw)
         return geometry.from_coded(rec)
 
@@ -425,7 +428,7 @@ def img2tensor_on_device(img, device):
 
 
 def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, boxed=False,
-             native=False, code_size=None, rotation=None):
+             native=False, code_size=None, rotation=None, projection=None):
     """reference: pseudo_codec.py:236-247.  The files are the reference's headerless streams unless
     boxed=True (--container): then the 16-byte header of container.py goes in front of the same
     payload and the file decodes without any size / model argument.  native=True (--native-size,
@@ -435,7 +438,14 @@ def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512,
     least 2 x 2, padded by the pole / seam rule where it is not codable); the file records both sizes (container
     version 3) and the bitrate counts the source's pixels.  rotation (--rotate, needs boxed): the triple of
     erp_rotate.units; every image is first turned into that orientation on the device (erp_rotate.py) and the file
-    records it (container version 4)."""
+    records it (container version 4).  projection (--projection, needs boxed): a cube.Spec; every image is a cube
+    picture in its layout, taken at its own size (height / width are ignored), converted on the device to the ERP frame
+    of cube.erp_size(face size) (cube.py) before everything else; the file records kind, layout and face size
+    (container version 5) and the bitrate counts the cube picture's pixels."""
+    if projection is not None and not boxed:
+        raise ValueError("--projection needs --container: a headerless file cannot carry the projection")
+    if projection is not None and native:
+        raise ValueError("--projection excludes --native-size: a cube picture is always taken at its own size")
     if rotation is not None and not boxed:
         raise ValueError("--rotate needs --container: a headerless file cannot carry the rotation")
     if native and not boxed:
@@ -446,12 +456,12 @@ def encoding(img_list, out_list, model_idx=0, mse=True, device_id=0, height=512,
     header = {"model_idx": model_idx, "ssim": not mse} if boxed else None
     for fn, fo in zip(img_list, out_list):
         img = read_image(fn)
-        if not native and code_size is None:
+        if not native and code_size is None and projection is None:
             img = check_img(img, height, width)
-        geometry = FrameGeometry(img.shape[:2], code_size, rotation)
+        geometry = FrameGeometry.for_picture(img.shape[:2], code_size, rotation, projection)
         data = img2tensor(img, dev) if code_size is None else img2tensor_on_device(img, dev)
         t1(geometry.to_coded(data), fo, header, geometry)
-        print('Encoding {}, bitrate: {:.3f}bpp'.format(fn, bitrate(fo, *geometry.source)))
+        print('Encoding {}, bitrate: {:.3f}bpp'.format(fn, bitrate(fo, *geometry.picture)))
 
 
 def _decoder_for(code_list, model_idx, mse, device_id, raw):
@@ -466,7 +476,7 @@ def _decoder_for(code_list, model_idx, mse, device_id, raw):
 def _decode_file(t1, fc, model_idx, mse, height, width, raw, to_source=True):
     """(reconstruction at the coded size, FrameGeometry) of one code file of a list: the sizes from its container
     header when it has one (which must name the model the decoder was built for), else from the arguments.
-    to_source=False refuses a file whose picture has to be resized or rotated back (version 3, 4)"""
+    to_source=False refuses a file whose picture has to be resized, rotated or converted back (version 3, 4, 5)"""
     head = None if raw else container.sniff(fc)
     if head is not None:
         if head["model_idx"] != model_idx or head["ssim"] == mse:
@@ -475,6 +485,8 @@ def _decode_file(t1, fc, model_idx, mse, height, width, raw, to_source=True):
             raise container.ContainerError("%s was coded at a reduced size (--code-size): decode it to images" % fc)
         if "rotation" in head and not to_source:
             raise container.ContainerError("%s was coded in a rotated orientation (--rotate): decode it to images" % fc)
+        if "projection" in head and not to_source:
+            raise container.ContainerError("%s holds a cube picture (--projection): decode it to images" % fc)
     return t1.decode_coded(fc, height, width, raw=head is None)
 
 
@@ -483,12 +495,14 @@ def decoding(code_list, decoded_img_list, model_idx=0, mse=True, device_id=0, he
     """reference: pseudo_codec.py:249-260.  view (--view: yaw, pitch, roll, hfov in degrees) with view_size = (vh, vw)
     and view_list (--view-out, one name per code file): the rectilinear view of every decoded picture (viewport.py:
     square pixels, the supersampling of viewport.plan, clamped to [0, 1]) is written beside the panorama.  A picture
-    coded with --rotate / --code-size is viewed in the source's orientation and at the source's size"""
+    coded with --rotate / --code-size is viewed in the source's orientation and at the source's size.  A file that holds a
+    cube picture (--projection, container version 5) is written as that cube picture, layout and size from the header
+    alone; its view is rendered from the ERP frame the picture was converted from"""
     t1, _, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     for k, (fc, fo) in enumerate(zip(code_list, decoded_img_list)):
         rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw)
-        picture = geometry.from_coded(rec)
-        write_image(fo, tensor2img(picture))
+        picture = geometry.from_coded(rec, to_source="erp")
+        write_image(fo, tensor2img(geometry.from_coded(rec) if geometry.projected else picture))
         print('Decoding {}, output to {}'.format(fc, fo))
         if view is not None:
             from . import viewport
@@ -629,8 +643,44 @@ def _report(rows, lines):
     return rows
 
 
+_CUBE = 'CUBE-PSNR:{:.2f}dB'
+
+
+def _cube_picture(img, geometry, name):
+    """the image as the cube picture the geometry describes; a picture of another size is refused, not resized"""
+    if tuple(img.shape[:2]) != geometry.picture:
+        raise ValueError("%s is %dx%d, the cube picture (%s, %s, face size %d) is %dx%d"
+                         % (name, img.shape[1], img.shape[0], geometry.projection.kind, geometry.projection.layout,
+                            geometry.face, geometry.picture[1], geometry.picture[0]))
+    return img
+
+
+def _cube_sides(picture, geometry, rdata, dev):
+    """(the ERP frame the codec saw of the uint8 cube picture, the float tensor the encoder converted it to; the plain
+    PSNR in dB of the cube picture against the ERP reconstruction `rdata` converted back)"""
+    from . import cube
+    data = img2tensor(picture, dev)
+    erp = cube.to_erp(data, geometry.source, geometry.projection, clamp=True)
+    back = cube.from_erp(rdata, geometry.face, geometry.projection, clamp=True)
+    return erp, _plain_psnr(data, back)
+
+
+def _plain_psnr(x, y):
+    mse = ((x - y).double() ** 2).mean().item()
+    return 10.0 * math.log10(1.0 / mse) if mse > 0 else float("inf")
+
+
+def _cube_lines(rows, cubes):
+    """--projection: the format of the average's CUBE-PSNR line; the figures join the rows as their last column when
+    every file holds a cube picture"""
+    if not cubes or any(c is None for c in cubes):
+        return []
+    rows[:] = [r + (c,) for r, c in zip(rows, cubes)]
+    return [_CUBE]
+
+
 def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False,
-                      ws=False, rotation=None, ms_ssim=False, vp=None, sphere=False):
+                      ws=False, rotation=None, ms_ssim=False, vp=None, sphere=False, projection=None):
     """reference: pseudo_codec.py:263-290.  sphere=True (--sphere): three more columns and one more line after everything
     else, SphereScore's S-PSNR-NN / S-PSNR-I / CPP-PSNR of the source against the end-to-end reconstruction (the float
     tensors, both at the source size); a file coded at a reduced size and not rotated gets a second line, `(coded size)`,
@@ -642,21 +692,36 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
     version 3) is scored end to end: the picture resized back to the source size against the source, bpp over the
     source's pixels; so is a file coded in a rotated orientation (--rotate, version 4): the picture turned back against
     the unrotated source.  rotation (--test --rotate): the triple every file must record, a ContainerError otherwise.
-    ms_ssim=True (--ms-ssim, with ws): one more line and a last column, the WS-MS-SSIM of the same pair"""
+    ms_ssim=True (--ms-ssim, with ws): one more line and a last column, the WS-MS-SSIM of the same pair.
+    A file that holds a cube picture (--projection, version 5): the image is the cube picture; every line above is
+    computed on the ERP frame the codec saw (the cube picture converted as the encoder converts it) against the ERP
+    reconstruction, bpp over the cube picture's pixels, and one more line and a last column follow, CUBE-PSNR: the plain
+    PSNR of the cube picture against the reconstruction converted back.  projection (--test --projection): the spec every
+    file must record, a ContainerError otherwise"""
     t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
     scorer, texts = (ViewportScore(device_id, None if vp is True else vp), []) if vp else (None, [])
     on_sphere, coded = SphereScore(device_id) if sphere else None, []
-    rows = []
+    rows, cubes = [], []
     for fc, fn in zip(code_list, img_list):
         rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw)
         if rotation is not None and geometry.rotation != tuple(rotation):
             raise container.ContainerError("%s records the rotation %s, --rotate says %s" % (fc, geometry.rotation, tuple(rotation)))
-        rdata = geometry.from_coded(rec)
-        img = check_img(read_image(fn), *geometry.source)
-        pr, vssim = metrics(img2tensor(img, dev), rdata)
-        rt = bitrate(fc, *geometry.source)
+        if projection is not None and geometry.projection != projection:
+            raise container.ContainerError("%s records the projection %s, --projection says %s"
+                                           % (fc, geometry.projection and tuple(geometry.projection), tuple(projection)))
+        rdata = geometry.from_coded(rec, to_source="erp")
+        cube_psnr = None
+        if geometry.projected:
+            picture = _cube_picture(read_image(fn), geometry, fn)
+            data, cube_psnr = _cube_sides(picture, geometry, rdata, dev)
+            img = tensor2img(data)
+        else:
+            img = check_img(read_image(fn), *geometry.source)
+            data = img2tensor(img, dev)
+        pr, vssim = metrics(data, rdata)
+        rt = bitrate(fc, *geometry.picture)
         rows.append((rt, pr, vssim))
         print(('Decoding {}, compare it to {} \n ' + _VIEWPORT).format(fc, fn, rt, pr, vssim))
         if ws:
@@ -666,16 +731,19 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
                 rows[-1] += (spherical.ms_ssim(img, tensor2img(rdata)),)
                 print(' ' + _WS_MS.format(rows[-1][-1]))
         if vp:
-            _vp_row(scorer, rows, texts, img2tensor(img, dev), rdata)
+            _vp_row(scorer, rows, texts, data, rdata)
         if sphere:
             small = geometry.from_coded(rec, to_source=False) if geometry.resized and not geometry.rotated else None
-            _sphere_row(on_sphere, rows, coded, img2tensor(img, dev), rdata, small)
+            _sphere_row(on_sphere, rows, coded, data, rdata, small)
+        cubes.append(cube_psnr)
+        if cube_psnr is not None:
+            print(' ' + _CUBE.format(cube_psnr))
     return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp)
-                   + _sphere_lines(rows, coded))
+                   + _sphere_lines(rows, coded) + _cube_lines(rows, cubes))
 
 
 def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False,
-                    code_size=None, rotation=None, ms_ssim=False, vp=None, sphere=False):
+                    code_size=None, rotation=None, ms_ssim=False, vp=None, sphere=False, projection=None):
     """--rd: what encoding() + decoding_and_test() report for the images, without a file in between.  The rate is
     the code length of the CDF rows the coder would get (rate.py: within a few bits of the stream), the
     reconstruction is the synthesis of the encoder's own symbols -- what the entropy decoder would hand back.
@@ -686,7 +754,10 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     unrotated source.
     Rows: (bpp, vpsnr, vssim[, ws_psnr, ws_ssim[, ws_ms_ssim]]): the last with ms_ssim=True (--ms-ssim); vp (--vp) adds
     ViewportScore's two columns at the end, as in decoding_and_test; sphere (--sphere) then adds SphereScore's three, and
-    with code_size and no rotation the three of the coded-size line, as in decoding_and_test."""
+    with code_size and no rotation the three of the coded-size line, as in decoding_and_test.
+    projection (--projection): every image is a cube picture taken at its own size; the lines are computed on the ERP
+    frame the codec saw, bpp over the cube picture's pixels, and CUBE-PSNR is the last line and column, as in
+    decoding_and_test."""
     from .engine import CodecEngine
     from . import rate
     (enc, dev), (dec, _) = _load("encoder", model_idx, mse, device_id), _load("decoder", model_idx, mse, device_id)
@@ -695,13 +766,19 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     spherical = SphericalMetrics(device_id) if ws else None
     scorer, texts = (ViewportScore(device_id, None if vp is True else vp), []) if vp else (None, [])
     on_sphere, coded = SphereScore(device_id) if sphere else None, []
-    rows = []
+    rows, cubes = [], []
     for fn in img_list:
         img = read_image(fn)
-        if not native and code_size is None:
+        if not native and code_size is None and projection is None:
             img = check_img(img, height, width)
         h, w = img.shape[:2]
         data = img2tensor(img, dev)
+        picture = None
+        if projection is not None:
+            from . import cube
+            geometry = FrameGeometry.for_picture(img.shape[:2], None, None, projection)
+            picture, data = data, cube.to_erp(data, geometry.source, projection, clamp=True)
+            img = tensor2img(data)
         small = None
         if sphere:
             bits, rdata, small = codec.evaluate(data, code_size=code_size, rotation=rotation, coded=True)
@@ -721,8 +798,11 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
             _vp_row(scorer, rows, texts, data, rdata)
         if sphere:
             _sphere_row(on_sphere, rows, coded, data, rdata, small)
+        if picture is not None:
+            cubes.append(_plain_psnr(picture, cube.from_erp(rdata, geometry.face, projection, clamp=True)))
+            print(' ' + _CUBE.format(cubes[-1]))
     return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp)
-                   + _sphere_lines(rows, coded))
+                   + _sphere_lines(rows, coded) + _cube_lines(rows, cubes))
 
 
 def _yuv_rgb(frames, h, w, yuv_opts, dev):
@@ -884,6 +964,25 @@ def _rotate_flag(parser, args):
     return rotation
 
 
+def _projection_flag(parser, args):
+    """the cube.Spec of --projection cmp|eac [--cube-layout faces|6x1|3x2], or None; contradictions end the run with a
+    message"""
+    if args.projection is None:
+        if args.cube_layout is not None:
+            parser.error("--cube-layout goes with --projection")
+        return None
+    from . import cube
+    if args.yuv is not None or args.yuv_out is not None:
+        parser.error("--projection is for images: the YUV path converts and pads in one kernel and takes no cube picture")
+    if args.dec:
+        parser.error("--projection goes with --enc, --rd or --test; --dec reads the projection from the file")
+    if args.enc and not (args.container and not args.raw):
+        parser.error("--projection needs --container: a headerless file cannot carry the projection")
+    if args.native_size:
+        parser.error("--projection excludes --native-size: a cube picture is always taken at its own size")
+    return cube.spec(args.projection, args.cube_layout or "3x2")
+
+
 def _view_flags(parser, args):
     """the checks of --view / --view-size / --view-out[-file] and --vp; returns (view, view size, vp): view the four
     angles in degrees or None, view size (vh, vw) or None, vp None, True (the default size) or (vh, vw).  Contradictions
@@ -991,6 +1090,13 @@ def main(argv=None):
                                          'spends the most samples; the file records the angles, --dec turns the picture '
                                          'back and --test / --rd score against the unrotated source.  Needs --container '
                                          '(--rd: nothing; --test: checks that the files record these angles)')
+    parser.add_argument('--projection', choices=['cmp', 'eac'],
+                        help='Encoding / --rd / --test: the images are cube pictures, plain (cmp) or equi-angular (eac), '
+                             'taken at their own size; they are converted on the device to the ERP frame of twice by four '
+                             'times the face size and the file records kind, layout and face size (container version 5); '
+                             '--dec writes the cube picture back.  Needs --container on --enc; not for --yuv')
+    parser.add_argument('--cube-layout', choices=['faces', '6x1', '3x2'],
+                        help='The layout of the cube pictures of --projection (default 3x2: L F R over D B U)')
     parser.add_argument('--raw', action='store_true', default=False,
                         help='Decoding: never look for a container header (size and model from the flags)')
     parser.add_argument('--ws', action='store_true', default=False,
@@ -1028,6 +1134,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     code_size = _code_size_flag(parser, args)
     rotation = _rotate_flag(parser, args)
+    projection = _projection_flag(parser, args)
     view, view_size, vp = _view_flags(parser, args)
     sphere = _sphere_flag(parser, args)
     yuv_call = _yuv_flags(parser, args)   # contradictory YUV flags end the run here, before anything is loaded
@@ -1062,14 +1169,15 @@ def main(argv=None):
     elif args.rd:
         assert img_list is not None, 'No input images for scoring'
         rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws,
-                        code_size=code_size, rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere, **size)
+                        code_size=code_size, rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere,
+                        projection=projection, **size)
     elif args.enc:
         assert img_list is not None, 'No input images for encoding'
         assert code_list is not None, 'No code files for saving the codes'
         assert len(img_list) == len(code_list), 'The number of images and codes should be the same'
         assert not args.native_size or (args.container and not args.raw), '--native-size needs --container'
         encoding(img_list, code_list, midx, not args.ssim, args.gpu_id, boxed=args.container and not args.raw,
-                 native=args.native_size, code_size=code_size, rotation=rotation, **size)
+                 native=args.native_size, code_size=code_size, rotation=rotation, projection=projection, **size)
     else:
         assert code_list is not None, 'No code files for decoding'
         if args.dec:
@@ -1083,7 +1191,7 @@ def main(argv=None):
             assert img_list is not None, 'No source images for evaluation.'
             assert len(code_list) == len(img_list), 'The number of codes and corresponding source images should be the same'
             decoding_and_test(code_list, img_list, midx, not args.ssim, args.gpu_id, raw=args.raw, ws=args.ws,
-                              rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere, **size)
+                              rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere, projection=projection, **size)
 
 
 if __name__ == '__main__':
