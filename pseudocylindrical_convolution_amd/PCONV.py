@@ -62,6 +62,25 @@ def _require_gpu(x, what):
         raise PconvError("%s: input must be contiguous" % what)
 
 
+def _require_operand(t, what, name, shape, dtype, like, dense=True):
+    """operand `name` of `what`, checked before its address goes to the library: a tensor of element type `dtype` on the
+    device of `like` (the call's first operand).  shape: a tuple, the exact shape (None: any extent); an int, a length the
+    tensor must at least have.  dense: contiguous (False: the wrapper makes its own dense copy).  Attribute comparisons
+    only: nothing is copied and nothing waits"""
+    ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == like.device and (t.is_contiguous() or not dense)
+    if ok and isinstance(shape, int):
+        ok = t.numel() >= shape
+    elif ok:
+        ok = t.dim() == len(shape) and all(e is None or e == s for e, s in zip(shape, t.shape))
+    if not ok:
+        want = "at least %d elements" % shape if isinstance(shape, int) else \
+            "(%s)" % ", ".join("*" if e is None else str(int(e)) for e in shape)
+        got = "%s %s on %s" % (t.dtype, tuple(t.shape), t.device) if isinstance(t, torch.Tensor) else type(t).__name__
+        raise PconvError("%s: %s must be a %s%s tensor of %s on %s, got %s"
+                         % (what, name, "contiguous " if dense else "", str(dtype).split(".")[1], want, like.device, got))
+    return t
+
+
 def tile_widths(weight, npart, height, width, rule="pconv_host_tile_widths"):
     """Valid width of each latitude tile (math_cuda.cu:223-253; `rule`: the slice's variant, :177-221)."""
     w = np.ascontiguousarray(weight, dtype=np.float32)
@@ -449,6 +468,8 @@ class ContextReshapeOp(_Op):
         """(n*g*h*w, cpg) -> (n, g*cpg, h, w): the inverse permutation (context_reshape_cuda.cu:63-95)"""
         _require_gpu(grad, "ContextReshapeOp.backward")
         n, c, h, w = self._fwd_shape
+        if tuple(grad.shape) != (n * h * w * self.ngroup_, c // self.ngroup_):
+            raise PconvError("ContextReshapeOp.backward: grad %s does not fit the forward's input %s" % (tuple(grad.shape), (n, c, h, w)))
         out = self._out(1, (n, c, h, w), grad)
         call("pconv_context_reshape_backward", _ptr(grad), _ptr(out), n, c, h, w, self.ngroup_, _stream(grad.device))
         return [out]
@@ -463,11 +484,16 @@ class EntropyGmmOp(_Op):
         self.ignore_label_ = int(ignore_label)
 
     def forward(self, weight, delta, mean, label):
-        for t in (weight, delta, mean, label):
-            _require_gpu(t, "EntropyGmmOp")
-        m, ng = weight.shape[0], weight.shape[1]
-        if ng != self.num_gaussian_:
-            raise PconvError("EntropyGmmOp: last dim %d != num_gaussian %d" % (ng, self.num_gaussian_))
+        """weight, delta, mean (m, num_gaussian), label m values: contiguous float32 on one GPU"""
+        for name, t in (("weight", weight), ("delta", delta), ("mean", mean), ("label", label)):
+            _require_gpu(t, "EntropyGmmOp: " + name)
+        if weight.dim() != 2 or weight.shape[1] != self.num_gaussian_:
+            raise PconvError("EntropyGmmOp: weight %s: (m, num_gaussian = %d) expected" % (tuple(weight.shape), self.num_gaussian_))
+        m, ng = weight.shape
+        for name, t, count in (("delta", delta, m * ng), ("mean", mean, m * ng), ("label", label, m)):
+            if t.numel() != count or t.device != weight.device:
+                raise PconvError("EntropyGmmOp: %s %s on %s does not fit weight %s on %s"
+                                 % (name, tuple(t.shape), t.device, tuple(weight.shape), weight.device))
         loss = self._out(0, (m,), weight)
         dw = self._out(1, (m, ng), weight)
         dd = self._out(2, (m, ng), weight)
@@ -481,6 +507,9 @@ class EntropyGmmOp(_Op):
         """the per-row derivatives the forward kernel left in the op's buffers, times the
         incoming gradient (entropy_gmm_cuda.cu:95-127): [d weight, d delta, d mean, d label]"""
         _require_gpu(grad, "EntropyGmmOp.backward")
+        if 1 not in self._top or grad.numel() != self._top[1].shape[0] or grad.device != self._top[1].device:
+            raise PconvError("EntropyGmmOp.backward: grad %s does not fit the forward's %d rows"
+                             % (tuple(grad.shape), self._top[1].shape[0] if 1 in self._top else 0))
         g = grad.reshape(-1, 1)
         return [self._top[1] * g, self._top[2] * g, self._top[3] * g, self._top[4] * g]
 
@@ -607,14 +636,14 @@ class SphereUsliceOp(_SphereResample):
     def forward_into(self, x, out):
         """forward() with the caller's output tensor (n, c, h * npart, w), contiguous -- a frame of a batch the
         caller assembles: no op-owned buffer, no copy afterwards (engine.CodecEngine.reconstruct)"""
-        _require_gpu(x, "SphereUsliceOp")
+        _require_gpu(x, "SphereUsliceOp.forward_into: x")
         p = self.pad_
         tn, c, hp, wp = x.shape
         h, w = hp - 2 * p, wp - 2 * p
         n = tn // self.npart_
-        if tn % self.npart_ or tuple(out.shape) != (n, c, h * self.npart_, w) or not out.is_contiguous() \
-                or out.dtype != torch.float32 or out.device != x.device:
-            raise PconvError("SphereUsliceOp.forward_into: output %s does not fit input %s" % (tuple(out.shape), tuple(x.shape)))
+        if tn % self.npart_:
+            raise PconvError("SphereUsliceOp.forward_into: x: batch %d is not a multiple of npart %d" % (tn, self.npart_))
+        _require_operand(out, "SphereUsliceOp.forward_into", "out", (n, c, h * self.npart_, w), torch.float32, x)
         wd, col, coef = self._tables("pconv_host_uslice_taps", h * self.npart_, w, x)
         with _HbmTimed("uslice_kernel", "SphereUslice w%d" % out.shape[3], 8.0 * out.numel(), x.device):
             call("pconv_sphere_uslice", _ptr(x), _ptr(out), _ptr(wd), _ptr(col), _ptr(coef), n, c, h, w,
@@ -666,8 +695,18 @@ class PseudoPadOp(_Op):
         """x is the interior view of a padded buffer (`x._pconv_ring = (buffer, store)`, set by
         tile_conv2d / tile_gdn with ring > 0): fill the ring of this op's pad in place and
         return the padded view -- no copy of the tensor."""
-        buf, store = x._pconv_ring
+        ring = getattr(x, "_pconv_ring", None)
+        if ring is None or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+            raise PconvError("PseudoPadOp.forward_ring: x must be the float32 interior view of a ring buffer on a GPU "
+                             "(the result of tile_conv2d / tile_gdn with ring > 0)")
+        buf, store = ring
         tn, c, h, w = x.shape
+        if tuple(buf.shape) == (tn, c, h + 2 * store, w + 2 * store) and (
+                buf.dtype != x.dtype or buf.device != x.device or x.stride() != buf.stride()
+                or x.data_ptr() != buf.data_ptr() + 4 * store * (buf.stride(2) + 1)):
+            # (a buffer of another shape: the copying pad below reads x alone)
+            raise PconvError("PseudoPadOp.forward_ring: x %s %s on %s is not the interior view of its ring buffer %s %s on %s"
+                             % (x.dtype, tuple(x.shape), x.device, buf.dtype, tuple(buf.shape), buf.device))
         p = self.pad_
         if p <= 0 or p > store or tuple(buf.shape) != (tn, c, h + 2 * store, w + 2 * store) or not buf.is_contiguous():
             return self.forward(x.contiguous())[0]
@@ -795,12 +834,15 @@ class PseudoQuantOp(_Op):
         cnt.mul_(self.weight_decay_)
 
     def forward(self, x, weight, count, train):
-        _require_gpu(x, "PseudoQuantOp")
+        """x (tn, channel, h, w) and the level table weight (channel, bins): contiguous float32 on one GPU; count: the
+        module's running histogram, read and written by torch arithmetic in training mode only"""
+        _require_gpu(x, "PseudoQuantOp: x")
+        tn, c, h, w = x.shape
+        if c != self.channel_:
+            raise PconvError("PseudoQuantOp: x has %d channels, built for %d" % (c, self.channel_))
+        _require_operand(weight, "PseudoQuantOp", "weight", (c, self.bin_num_), torch.float32, x)
         if train:
             self.update_weight(weight, count)
-        tn, c, h, w = x.shape
-        if c != self.channel_ or tuple(weight.shape) != (c, self.bin_num_):
-            raise PconvError("PseudoQuantOp: channel/level mismatch")
         wd = self.ctx_.widths(h, w, x)
         tab = self._out("tab", (c, self.bin_num_), x)
         val = self._out(0, x.shape, x)
@@ -824,13 +866,19 @@ class PseudoQuantOp(_Op):
         """[g_val(, g_idx)], the forward's input and value output -> [g_x, g_weight, count_data_]
         (pseudo_quant_cuda.cu:197-311): straight-through for the value, the index gradient scaled
         by the local level width, the quantisation error summed into the levels at or below each
-        element's level; the per-call histogram is what the reference hands back for `count`."""
-        _require_gpu(x, "PseudoQuantOp.backward")
+        element's level; the per-call histogram is what the reference hands back for `count`.  x and out: contiguous
+        float32 of the forward's shape; the gradients: float32 of that shape on x's device, strided ones accepted (they
+        are made contiguous)."""
+        _require_gpu(x, "PseudoQuantOp.backward: x")
         tn, c, h, w = x.shape
         if self.count_data_ is None or 1 not in self._top or tuple(self._top[0].shape) != tuple(x.shape):
-            raise PconvError("PseudoQuantOp.backward: no matching forward call")
-        g_val = grads[0].contiguous()
-        g_idx = grads[1].contiguous() if self.ntop_ > 1 and len(grads) > 1 and grads[1] is not None else None
+            raise PconvError("PseudoQuantOp.backward: no matching forward call for x %s" % (tuple(x.shape),))
+        _require_operand(out, "PseudoQuantOp.backward", "out", x.shape, torch.float32, x)
+        # (the gradients are made contiguous: strided ones are accepted)
+        g_val = _require_operand(grads[0], "PseudoQuantOp.backward", "grads[0]", x.shape, torch.float32, x, dense=False).contiguous()
+        g_idx = None
+        if self.ntop_ > 1 and len(grads) > 1 and grads[1] is not None:
+            g_idx = _require_operand(grads[1], "PseudoQuantOp.backward", "grads[1]", x.shape, torch.float32, x, dense=False).contiguous()
         wd = self.ctx_.widths(h, w, x)
         g_in = self._out("g_in", x.shape, x)
         g_w = self._out("g_w", (c, self.bin_num_), x)
@@ -860,11 +908,10 @@ class PseudoDQuantOp(_Op):
         self.ctx_ = _lookup(addr)
 
     def forward(self, x, weight):
-        _require_gpu(x, "PseudoDQuantOp")
+        """x (tn, c, h, w) and the level table weight (channel, bins): contiguous float32 on one GPU"""
+        _require_gpu(x, "PseudoDQuantOp: x")
         tn, c, h, w = x.shape
-        if tuple(weight.shape) != (self.nchannel_, self.bin_num_):
-            raise PconvError("PseudoDQuantOp: weight shape %s != (%d, %d)" %
-                             (tuple(weight.shape), self.nchannel_, self.bin_num_))
+        _require_operand(weight, "PseudoDQuantOp", "weight", (self.nchannel_, self.bin_num_), torch.float32, x)
         wd = self.ctx_.widths(h, w, x)
         tab = self._out("tab", (self.nchannel_, self.bin_num_), x)
         out = self._out(0, x.shape, x)
@@ -932,6 +979,9 @@ class ProjectsOp(_Op):
         (projects_cuda.cu:257-329)"""
         _require_gpu(grad, "ProjectsOp.backward")
         n, c, h, w = self._fwd_shape
+        if tuple(grad.shape) != (n * self.nview_, c, self.h_out_, self.w_out_):
+            raise PconvError("ProjectsOp.backward: grad %s does not fit the forward's %s"
+                             % (tuple(grad.shape), (n * self.nview_, c, self.h_out_, self.w_out_)))
         gin = self._out(1, (n, c, h, w), grad)
         cnt = self._out(2, (n, c, h, w), grad)
         if ordered_backward.on:
@@ -1051,12 +1101,22 @@ class EntropyConv2Op(_WavefrontOp):
         self.pad_in_, self.pad_out_ = int(pad_in), int(pad_out)
         self.ctx_ = _lookup(addr)
 
-    def _run(self, x, weight, bias, act, nset):
-        _require_gpu(x, "EntropyConv2Op")
+    def _run(self, x, weight, bias, act, batch):
+        """x, weight (nout, channel, k, k), bias and act (nout) -- the _batch entries: nset of each in front --:
+        contiguous float32 on one GPU, all checked before the first call of the library"""
+        _require_gpu(x, "EntropyConv2Op: x")
         pi, po = self.pad_in_, self.pad_out_
         num, channel, h, w = x.shape[0], x.shape[1], x.shape[2] - 2 * pi, x.shape[3] - 2 * pi
         if channel != self.channel_:
-            raise PconvError("EntropyConv2Op: %d input channels, built for %d" % (channel, self.channel_))
+            raise PconvError("EntropyConv2Op: x has %d input channels, built for %d" % (channel, self.channel_))
+        # one weight set (nout, channel, k, k) with (nout) bias and slopes, or -- the _batch entries -- nset of them
+        _require_operand(weight, "EntropyConv2Op", "weight",
+                         ((None,) if batch else ()) + (self.nout_, channel, self.kernel_size_, self.kernel_size_), torch.float32, x)
+        nset = int(weight.shape[0]) if batch else 1
+        sets = (nset,) if batch else ()
+        _require_operand(bias, "EntropyConv2Op", "bias", sets + (self.nout_,), torch.float32, x)
+        if act is not None:
+            _require_operand(act, "EntropyConv2Op", "act", sets + (self.nout_,), torch.float32, x)
         if self._reshaped((num, channel, h, w)):
             self.pidx_ = 0
         order, start = self.ctx_.schedule(h, w, x)
@@ -1080,16 +1140,16 @@ class EntropyConv2Op(_WavefrontOp):
         return [top]
 
     def forward(self, x, weight, bias):
-        return self._run(x, weight, bias, None, 1)
+        return self._run(x, weight, bias, None, False)
 
     def forward_act(self, x, weight, bias, act):
-        return self._run(x, weight, bias, act, 1)
+        return self._run(x, weight, bias, act, False)
 
     def forward_batch(self, x, weight, bias):
-        return self._run(x, weight, bias, None, int(weight.shape[0]))
+        return self._run(x, weight, bias, None, True)
 
     def forward_act_batch(self, x, weight, bias, act):
-        return self._run(x, weight, bias, act, int(weight.shape[0]))
+        return self._run(x, weight, bias, act, True)
 
 
 class EntropyAddOp(_WavefrontOp):
@@ -1102,8 +1162,9 @@ class EntropyAddOp(_WavefrontOp):
         self.ctx_ = _lookup(addr)
 
     def forward(self, x, y):
-        _require_gpu(x, "EntropyAddOp")
-        _require_gpu(y, "EntropyAddOp")
+        """x += y at the current wavefront: x and y contiguous float32 of one shape on one GPU"""
+        _require_gpu(x, "EntropyAddOp: x")
+        _require_operand(y, "EntropyAddOp", "y", x.shape, torch.float32, x)
         p = self.pad_
         num, channel, h, w = x.shape[0], x.shape[1], x.shape[2] - 2 * p, x.shape[3] - 2 * p
         if self._reshaped((num, channel, h, w)):
@@ -1189,22 +1250,33 @@ class EntropyGmmTableOp(_Op):
             raise PconvError("EntropyGmmTableOp: at most 16 gaussians")
 
     def forward(self, weight, delta, mean, tnum):
-        for t in (weight, delta, mean):
-            _require_gpu(t, "EntropyGmmTableOp")
+        """weight, delta, mean: contiguous float32 of rows * num_gaussian elements each, read as [row][gaussian];
+        tnum[0] <= rows: the rows to make"""
+        for name, t in (("weight", weight), ("delta", delta), ("mean", mean)):
+            _require_gpu(t, "EntropyGmmTableOp: " + name)
         rows = weight.numel() // self.num_gaussian_
         if weight.dim() == 4:
             rows = weight.shape[0] * weight.shape[2] * weight.shape[3]
-        table = self._out(0, (rows, self.nstep_ + 1), weight)
+        for name, t in (("delta", delta), ("mean", mean)):
+            if t.numel() != weight.numel() or t.device != weight.device:
+                raise PconvError("EntropyGmmTableOp: %s %s on %s does not fit weight %s on %s"
+                                 % (name, tuple(t.shape), t.device, tuple(weight.shape), weight.device))
         tn = int(tnum[0])
+        if not 0 <= tn <= rows or tn * self.num_gaussian_ > weight.numel():
+            raise PconvError("EntropyGmmTableOp: tnum %d of the %d rows of weight %s" % (tn, rows, tuple(weight.shape)))
+        table = self._out(0, (rows, self.nstep_ + 1), weight)
         call("pconv_gmm_table", _ptr(weight), _ptr(delta), _ptr(mean), _ptr(table), tn, self.num_gaussian_,
              self.nstep_, self.bias_, self.total_region_, self.beta_, 0, _stream(weight.device))
         return [table]
 
     def forward_batch(self, data, tnum):
-        _require_gpu(data, "EntropyGmmTableOp")
+        _require_gpu(data, "EntropyGmmTableOp: data")
         stride = data.numel() // 3
-        table = self._out(0, (data.shape[0] * data.shape[2] * data.shape[3] // 3, self.nstep_ + 1), data)
+        rows = data.shape[0] * data.shape[2] * data.shape[3] // 3
         tn = int(tnum[0])
+        if not 0 <= tn <= rows or tn * self.num_gaussian_ > stride:
+            raise PconvError("EntropyGmmTableOp: tnum %d of the %d rows of data %s" % (tn, rows, tuple(data.shape)))
+        table = self._out(0, (rows, self.nstep_ + 1), data)
         if tn > 0:
             base = data.data_ptr()
             call("pconv_gmm_table", base, base + 4 * stride, base + 8 * stride, _ptr(table), tn,
@@ -1288,7 +1360,12 @@ def _packed_weight(owner, weight, kind, stream):
 
 
 def packed_conv_weight(owner, weight, stream):
-    """[k][cout] fp32 slab of a conv weight for pconv_conv2d / pconv_gdn (see _packed_weight)"""
+    """[k][cout] fp32 slab of a conv weight for pconv_conv2d / pconv_gdn (see _packed_weight).  weight: a 4-D float32
+    GPU tensor of any strides (the pack reads a dense copy)"""
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 4 or weight.dtype != torch.float32 or not weight.is_cuda:
+        raise PconvError("packed_conv_weight: weight must be a 4-D float32 GPU tensor, got %s"
+                         % ("%s %s on %s" % (weight.dtype, tuple(weight.shape), weight.device)
+                            if isinstance(weight, torch.Tensor) else type(weight).__name__))
     return _packed_weight(owner, weight, "direct", stream)
 
 
@@ -1406,6 +1483,19 @@ def _like_output(t, out, what):
     return t if t.stride(3) == 1 else t.contiguous()
 
 
+# the size rules _host_query may ask: integer arithmetic on the host, no tensor, no device, no launch
+HOST_QUERIES = ("pconv_erp_coded_size", "pconv_erp_resample_workspace_bytes", "pconv_erp_resample_backward_workspace_bytes",
+                "pconv_ws_msssim_workspace_bytes")
+
+
+def _host_query(fn, *args):
+    """a size rule of the library (HOST_QUERIES only), asked where an operand's check needs its answer: before the
+    wrapper's first call().  Everything else goes through call()"""
+    if fn not in HOST_QUERIES:
+        raise PconvError("%s is no host-only size rule: it goes through call()" % fn)
+    return _native.check(getattr(_native.hip_lib(), fn)(*args), fn)
+
+
 def _gpu_device(what, device):
     """`device` as a cuda device with its index; None: the current one"""
     device = torch.device("cuda" if device is None else device)
@@ -1493,9 +1583,9 @@ def frames_u8_to_f32(img, out=None):
     """device side of img2tensor (pseudo_codec.py:215-217): uint8 (n, H, W, 3) GPU tensor -> float32 (n, 3, H, W),
     float(u8) / 255 exactly as the reference's host division; the bus carried a quarter of the bytes"""
     if not img.is_cuda:
-        raise PconvError("frames_u8_to_f32: expected a GPU tensor (this build has no CPU path), got %s" % img.device)
+        raise PconvError("frames_u8_to_f32: img: expected a GPU tensor (this build has no CPU path), got %s" % img.device)
     if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3 or not img.is_contiguous():
-        raise PconvError("frames_u8_to_f32: contiguous uint8 (n, H, W, 3) expected")
+        raise PconvError("frames_u8_to_f32: img: contiguous uint8 (n, H, W, 3) expected")
     n, h, w, _ = img.shape
     if out is None:
         out = torch.empty((n, 3, h, w), dtype=torch.float32, device=img.device)
@@ -1510,9 +1600,9 @@ def frames_f32_to_u8(x, out=None):
     """device side of tensor2img (pseudo_codec.py:219-221): float32 (n, 3, H, W) -> uint8 (n, H, W, 3),
     (uint8)(int)(x * 255) as numpy's cast does it"""
     if not x.is_cuda:
-        raise PconvError("frames_f32_to_u8: expected a GPU tensor (this build has no CPU path), got %s" % x.device)
+        raise PconvError("frames_f32_to_u8: x: expected a GPU tensor (this build has no CPU path), got %s" % x.device)
     if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
-        raise PconvError("frames_f32_to_u8: contiguous float32 (n, 3, H, W) expected")
+        raise PconvError("frames_f32_to_u8: x: contiguous float32 (n, 3, H, W) expected")
     n, _, h, w = x.shape
     if out is None:
         out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=x.device)
@@ -1526,7 +1616,7 @@ def frames_f32_to_u8(x, out=None):
 def erp_coded_size(h, w):
     """(H, W, top) of an h x w ERP frame under the pole / seam padding rule (pconv_erp_coded_size)"""
     H, W, top = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    call("pconv_erp_coded_size", int(h), int(w), ctypes.byref(H), ctypes.byref(W), ctypes.byref(top))
+    _host_query("pconv_erp_coded_size", int(h), int(w), ctypes.byref(H), ctypes.byref(W), ctypes.byref(top))
     return H.value, W.value, top.value
 
 
@@ -1534,9 +1624,9 @@ def frames_u8_to_f32_erp(img, out=None):
     """frames_u8_to_f32 for any ERP size: uint8 (n, h, w, 3) GPU tensor (any width, any byte offset) -> float32
     (n, 3, H, W) padded by the pole / seam rule (erp_size.py), float(u8) / 255 as img2tensor"""
     if not img.is_cuda:
-        raise PconvError("frames_u8_to_f32_erp: expected a GPU tensor (this build has no CPU path), got %s" % img.device)
+        raise PconvError("frames_u8_to_f32_erp: img: expected a GPU tensor (this build has no CPU path), got %s" % img.device)
     if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3 or not img.is_contiguous():
-        raise PconvError("frames_u8_to_f32_erp: contiguous uint8 (n, h, w, 3) expected")
+        raise PconvError("frames_u8_to_f32_erp: img: contiguous uint8 (n, h, w, 3) expected")
     n, h, w, _ = img.shape
     H, W, _top = erp_coded_size(h, w)
     if out is None:
@@ -1550,9 +1640,9 @@ def frames_u8_to_f32_erp(img, out=None):
 
 def erp_pad_f32(x, out=None):
     """float32 (n, 3, h, w) GPU tensor -> (n, 3, H, W) padded by the pole / seam rule (erp_size.py)"""
-    _require_gpu(x, "erp_pad_f32")
+    _require_gpu(x, "erp_pad_f32: x")
     if x.dim() != 4 or x.shape[1] != 3:
-        raise PconvError("erp_pad_f32: float32 (n, 3, h, w) expected")
+        raise PconvError("erp_pad_f32: x: float32 (n, 3, h, w) expected")
     n, _, h, w = x.shape
     H, W, _top = erp_coded_size(h, w)
     if out is None:
@@ -1567,10 +1657,10 @@ def erp_pad_f32(x, out=None):
 def frames_f32_to_u8_crop(x, height, width, out=None):
     """frames_f32_to_u8 and the decoder's crop in one pass: float32 (n, 3, H, W) coded frames -> uint8
     (n, height, width, 3) of rows top..top+height-1, columns 0..width-1 (any width, any byte offset of out)"""
-    _require_gpu(x, "frames_f32_to_u8_crop")
+    _require_gpu(x, "frames_f32_to_u8_crop: x")
     H, W, _top = erp_coded_size(height, width)
     if x.dim() != 4 or tuple(x.shape[1:]) != (3, H, W):
-        raise PconvError("frames_f32_to_u8_crop: float32 (n, 3, %d, %d) expected for %dx%d, got %s"
+        raise PconvError("frames_f32_to_u8_crop: x: float32 (n, 3, %d, %d) expected for %dx%d, got %s"
                          % (H, W, width, height, tuple(x.shape)))
     n = x.shape[0]
     if out is None:
@@ -1605,10 +1695,10 @@ def frames_yuv420_to_f32(buf, h, w, fmt, matrix="bt709", range="limited", out=No
     of the format's dtype (any offset its element size allows) -> float32 (n, 3, H, W), the colour conversion fused
     with the pole / seam pad"""
     if not buf.is_cuda:
-        raise PconvError("frames_yuv420_to_f32: expected a GPU tensor (this build has no CPU path), got %s" % buf.device)
+        raise PconvError("frames_yuv420_to_f32: buf: expected a GPU tensor (this build has no CPU path), got %s" % buf.device)
     h, w, code, dtype, size, elems = _yuv_args("frames_yuv420_to_f32", h, w, fmt, matrix, range)
     if buf.dtype != dtype or buf.dim() != 2 or buf.shape[1] != elems or not buf.is_contiguous():
-        raise PconvError("frames_yuv420_to_f32: contiguous %s (n, %d) expected for %s frames of %dx%d, got %s %s"
+        raise PconvError("frames_yuv420_to_f32: buf: contiguous %s (n, %d) expected for %s frames of %dx%d, got %s %s"
                          % (dtype, elems, fmt, w, h, buf.dtype, tuple(buf.shape)))
     n = buf.shape[0]
     H, W, _top = erp_coded_size(h, w)
@@ -1627,11 +1717,11 @@ def frames_f32_to_yuv420(x, h, w, fmt, matrix="bt709", range="limited", out=None
     """RGB at the coded size -> YUV 4:2:0 frames (yuv.py, pconv_frames_f32_to_yuv420): float32 (n, 3, H, W) coded
     frames -> (n, h*w*3/2) of the format's dtype, rows top..top+h-1 and columns 0..w-1 converted, the chroma filtered
     down with the seam wrapped (any offset of out its element size allows)"""
-    _require_gpu(x, "frames_f32_to_yuv420")
+    _require_gpu(x, "frames_f32_to_yuv420: x")
     h, w, code, dtype, size, elems = _yuv_args("frames_f32_to_yuv420", h, w, fmt, matrix, range)
     H, W, _top = erp_coded_size(h, w)
     if x.dim() != 4 or tuple(x.shape[1:]) != (3, H, W):
-        raise PconvError("frames_f32_to_yuv420: float32 (n, 3, %d, %d) expected for %dx%d, got %s"
+        raise PconvError("frames_f32_to_yuv420: x: float32 (n, 3, %d, %d) expected for %dx%d, got %s"
                          % (H, W, w, h, tuple(x.shape)))
     n = x.shape[0]
     if out is None:
@@ -1652,9 +1742,13 @@ def erp_resample_f32(x, h2, w2, clamp=False, out=None, workspace=None):
     """float32 (n, C, h, w) GPU tensor -> (n, C, h2, w2): the sphere-aware Lanczos-3 resize (erp_resample.py,
     pconv_erp_resample_f32).  The tap tables live on the device, cached per (h, w, h2, w2); workspace: a uint8 GPU
     tensor of at least pconv_erp_resample_workspace_bytes bytes (allocated when None)"""
-    n, c, h, w = _require_frames(x, "erp_resample_f32")
+    n, c, h, w = _require_frames(x, "erp_resample_f32: x")
     h2, w2 = int(h2), int(w2)
-    nbytes = call("pconv_erp_resample_workspace_bytes", n, c, h, w, h2, w2)
+    nbytes = _host_query("pconv_erp_resample_workspace_bytes", n, c, h, w, h2, w2)
+    out = _output("erp_resample_f32", out, (n, c, h2, w2), torch.float32, x.device, "the input's device")
+    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous()
+                                  or workspace.device != x.device):
+        raise PconvError("erp_resample_f32: workspace must be a contiguous uint8 tensor of %d bytes on the input's device" % nbytes)
     key = (x.device, h, w, h2, w2)
     if key not in _resample_tables:
         from .erp_resample import taps
@@ -1662,11 +1756,8 @@ def erp_resample_f32(x, h2, w2, clamp=False, out=None, workspace=None):
         fy, wy = taps(h, h2)
         _resample_tables[key] = tuple(t.to(x.device) for t in (fx, wx, fy, wy))
     fx, wx, fy, wy = _resample_tables[key]
-    out = _output("erp_resample_f32", out, (n, c, h2, w2), torch.float32, x.device, "the input's device")
     if workspace is None:
         workspace = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    elif workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous() or workspace.device != x.device:
-        raise PconvError("erp_resample_f32: workspace must be a contiguous uint8 tensor of %d bytes on the input's device" % nbytes)
     # input read + intermediate written and read + output written
     counted = 4.0 * (x.numel() + 2.0 * n * c * h * w2 + out.numel())
     with _HbmTimed("erp_resample_kernels", "ErpResample %dx%d->%dx%d n%d" % (w, h, w2, h2, n), counted, x.device):
@@ -1684,25 +1775,26 @@ def erp_resample_backward_f32(g, h, w, gin=None, workspace=None):
     The weight tables and the transposed lists (erp_resample.reverse_taps) live on the device, cached per (h, w, h2, w2);
     gin: a contiguous float32 (n, C, h, w) tensor to write (allocated when None; every element is written); workspace:
     a uint8 GPU tensor of at least pconv_erp_resample_backward_workspace_bytes bytes (allocated when None)"""
-    _require_gpu(g, "erp_resample_backward_f32")
+    _require_gpu(g, "erp_resample_backward_f32: g")
     if g.dim() != 4 or g.dtype != torch.float32 or not g.is_contiguous():
-        raise PconvError("erp_resample_backward_f32: a contiguous float32 (n, C, h2, w2) gradient expected, got %s %s"
+        raise PconvError("erp_resample_backward_f32: g: a contiguous float32 (n, C, h2, w2) gradient expected, got %s %s"
                          % (g.dtype, tuple(g.shape)))
     n, c, h2, w2 = g.shape
     h, w = int(h), int(w)
-    nbytes = call("pconv_erp_resample_backward_workspace_bytes", n, c, h, w, h2, w2)
+    nbytes = _host_query("pconv_erp_resample_backward_workspace_bytes", n, c, h, w, h2, w2)
+    gin = _output("erp_resample_backward_f32", gin, (n, c, h, w), torch.float32, g.device, "the gradient's device", "gin")
+    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous()
+                                  or workspace.device != g.device):
+        raise PconvError("erp_resample_backward_f32: workspace must be a contiguous uint8 tensor of %d bytes on the gradient's "
+                         "device" % nbytes)
     key = (g.device, h, w, h2, w2)
     if key not in _resample_reverse:
         from .erp_resample import reverse_taps, taps
         tables = (taps(w, w2)[1],) + reverse_taps(w, w2, 0)[:2] + (taps(h, h2)[1],) + reverse_taps(h, h2, 1)
         _resample_reverse[key] = tuple(t.to(g.device) for t in tables)
     wx, start_x, entry_x, wy, start_y, entry_y, crossed_y = _resample_reverse[key]
-    gin = _output("erp_resample_backward_f32", gin, (n, c, h, w), torch.float32, g.device, "the gradient's device", "gin")
     if workspace is None:
         workspace = torch.empty((nbytes,), dtype=torch.uint8, device=g.device)
-    elif workspace.dtype != torch.uint8 or workspace.numel() < nbytes or not workspace.is_contiguous() or workspace.device != g.device:
-        raise PconvError("erp_resample_backward_f32: workspace must be a contiguous uint8 tensor of %d bytes on the gradient's "
-                         "device" % nbytes)
     # gradient read + intermediate written and read + input gradient written
     counted = 4.0 * (g.numel() + 2.0 * n * c * h * w2 + gin.numel())
     with _HbmTimed("erp_resample_backward_kernels", "ErpResampleBackward %dx%d<-%dx%d n%d" % (w, h, w2, h2, n), counted,
@@ -1737,7 +1829,7 @@ def erp_remap_f32(x, map, clamp=False, out=None):
     """float32 (n, C, h, w) GPU tensor -> (n, C, h, w) read through `map` (int32 (h, w, 2) on the same device, from
     erp_rotation_map) with the 6 x 6 Lanczos-3 footprint of erp_rotate.py (pconv_erp_remap_f32).  The phase table lives
     on the device, cached per device; out must not be x"""
-    n, c, h, w = _require_frames(x, "erp_remap_f32")
+    n, c, h, w = _require_frames(x, "erp_remap_f32: x")
     _require_map("erp_remap_f32", map, h, w, x.device, "the input's device")
     table = _phase_table(x.device)
     out = _output("erp_remap_f32", out, (n, c, h, w), torch.float32, x.device, "the input's device")
@@ -1766,12 +1858,12 @@ def _sphere_points_mode(what, interp):
     return SPHERE_POINTS_MODES[interp]
 
 
-def _sphere_points_records_of(what, rec, x):
+def _sphere_points_records_of(what, rec, x, name="records"):
     """the record count of `rec`, contiguous int32 (P, 2) on x's device"""
     if rec.dtype != torch.int32 or rec.dim() != 2 or rec.shape[1] != 2 or not rec.is_contiguous() or rec.device != x.device \
             or not 1 <= rec.shape[0] <= SPHERE_POINTS_MAX:
-        raise PconvError("%s: the records must be contiguous int32 (P, 2), 1 <= P < 2^28, on the input's device, got %s %s "
-                         "on %s" % (what, rec.dtype, tuple(rec.shape), rec.device))
+        raise PconvError("%s: the %s must be contiguous int32 (P, 2), 1 <= P < 2^28, on the input's device, got %s %s "
+                         "on %s" % (what, name if name == "records" else "records " + name, rec.dtype, tuple(rec.shape), rec.device))
     return rec.shape[0]
 
 
@@ -1795,7 +1887,7 @@ def sphere_points_sample_f32(x, records, interp="lanczos", out=None):
     """float32 (n, C, h, w) GPU tensor -> (n, C, P): every plane read at the records (int32 (P, 2) on the same device,
     from sphere_points_records for this h x w) with the 6 x 6 Lanczos-3 footprint of erp_rotate.py or, interp="nearest",
     the nearest pixel (pconv_sphere_points_sample_f32)"""
-    n, c, h, w = _require_frames(x, "sphere_points_sample_f32")
+    n, c, h, w = _require_frames(x, "sphere_points_sample_f32: x")
     mode = _sphere_points_mode("sphere_points_sample_f32", interp)
     count = _sphere_points_records_of("sphere_points_sample_f32", records, x)
     out = _output("sphere_points_sample_f32", out, (n, c, count), torch.float32, x.device, "the input's device")
@@ -1811,15 +1903,15 @@ def sphere_points_mse_device(x, rec_x, y, rec_y, interp="lanczos"):
     """float64 (n, C) on the inputs' device: the mean over the P points of (a - b)^2, a the sample of x (n, C, h1, w1) at
     rec_x and b the sample of y (n, C, h2, w2) at rec_y, the difference and its square in fp32, the sum in fp64 in the
     order of include/pconv_hip.h (pconv_sphere_points_mse_f32).  Two launches, no sample is written; nothing waits"""
-    _require_gpu(x, "sphere_points_mse")
-    _require_gpu(y, "sphere_points_mse")
+    _require_gpu(x, "sphere_points_mse: x")
+    _require_gpu(y, "sphere_points_mse: y")
     if x.dim() != 4 or y.dim() != 4 or x.shape[:2] != y.shape[:2] or x.device != y.device:
-        raise PconvError("sphere_points_mse: two float32 (n, C, h, w) batches of equal n and C on one device expected, got "
+        raise PconvError("sphere_points_mse: x and y: two float32 (n, C, h, w) batches of equal n and C on one device expected, got "
                          "%s on %s and %s on %s" % (tuple(x.shape), x.device, tuple(y.shape), y.device))
     mode = _sphere_points_mode("sphere_points_mse", interp)
-    count = _sphere_points_records_of("sphere_points_mse", rec_x, x)
-    if _sphere_points_records_of("sphere_points_mse", rec_y, y) != count:
-        raise PconvError("sphere_points_mse: the two record lists differ in length: %d and %d" % (count, rec_y.shape[0]))
+    count = _sphere_points_records_of("sphere_points_mse", rec_x, x, "rec_x")
+    if _sphere_points_records_of("sphere_points_mse", rec_y, y, "rec_y") != count:
+        raise PconvError("sphere_points_mse: the two record lists rec_x and rec_y differ in length: %d and %d" % (count, rec_y.shape[0]))
     n, c = x.shape[:2]
     nbytes = call("pconv_sphere_points_mse_workspace_bytes", n, c, count)
     workspace = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
@@ -1859,7 +1951,7 @@ def viewport_render_f32(x, map, vh, vw, ss, clamp=False, out=None, slot=0):
     vw * ss, 2) on the same device, from viewport_map) and averaged over ss x ss samples per pixel (viewport.py,
     pconv_viewport_render_f32).  out: a contiguous float32 (n, V, C, vh, vw) tensor whose view `slot` is written, the
     others left alone; None: a new (n, 1, C, vh, vw)"""
-    n, c, h, w = _require_frames(x, "viewport_render_f32")
+    n, c, h, w = _require_frames(x, "viewport_render_f32: x")
     vh, vw, ss, slot = int(vh), int(vw), int(ss), int(slot)
     _require_view("viewport_render_f32", vh, vw, ss)
     _require_map("viewport_render_f32", map, vh * ss, vw * ss, x.device, "the input's device")
@@ -1891,12 +1983,12 @@ def remap_backward_f32(gout, map, lists, h, w, vh, vw, ss, gin=None, slot=0, acc
     int32 (vh * ss, vw * ss, 2) map the forward read; lists: (start, entry) of viewport.reverse_lists on the same
     device.  gin: the contiguous tensor to write (None: a new one); accumulate=True adds to what gin holds, leaving
     the pixels no sample reads untouched"""
-    _require_gpu(gout, "remap_backward_f32")
+    _require_gpu(gout, "remap_backward_f32: gout")
     h, w, vh, vw, ss, slot = int(h), int(w), int(vh), int(vw), int(ss), int(slot)
     if gout.dim() == 4:
         gout = gout.unsqueeze(1)
     if gout.dim() != 5 or tuple(gout.shape[3:]) != (vh, vw) or not gout.is_contiguous():
-        raise PconvError("remap_backward_f32: a contiguous float32 (n, V, C, %d, %d) or (n, C, %d, %d) gradient expected, got %s"
+        raise PconvError("remap_backward_f32: gout: a contiguous float32 (n, V, C, %d, %d) or (n, C, %d, %d) gradient expected, got %s"
                          % (vh, vw, vh, vw, tuple(gout.shape)))
     n, views, c = gout.shape[:3]
     if not 0 <= slot < views:
@@ -1981,7 +2073,7 @@ def cube_pad_f32(x, table, out=None):
     """float32 (n, C, 6 a, a) GPU face stack -> (n, C, 6 A, A), A = a + 6: every face continued by 3 pixels across its
     edges, the ring read bilinearly from the neighbouring faces through `table` (int32 (6 (A^2 - a^2), 3) on the same
     device, from cube.pad_table) (cube.py, pconv_cube_pad_f32).  One launch; out must not be x"""
-    n, c, h6, a = _require_frames(x, "cube_pad_f32")
+    n, c, h6, a = _require_frames(x, "cube_pad_f32: x")
     if h6 != 6 * a or not 2 <= a <= CUBE_MAX_FACE:
         raise PconvError("cube_pad_f32: a face stack (n, C, 6 a, a), a of 2 .. %d, expected, got %s" % (CUBE_MAX_FACE, tuple(x.shape)))
     A = a + 2 * CUBE_PAD
@@ -2012,12 +2104,12 @@ def _ws_frames(what, x, y, weighting, float_only, min_side, entry):
     if weighting not in WS_WEIGHTINGS:
         raise PconvError("%s: weighting must be one of %s, got %r" % (what, sorted(WS_WEIGHTINGS), weighting))
     if not (x.is_cuda and y.is_cuda):
-        raise PconvError("%s: expected GPU tensors (this build has no CPU path), got %s and %s" % (what, x.device, y.device))
+        raise PconvError("%s: x and y: expected GPU tensors (this build has no CPU path), got %s and %s" % (what, x.device, y.device))
     if x.device != y.device or x.dtype != y.dtype or x.shape != y.shape:
-        raise PconvError("%s: the two batches differ: %s %s %s vs %s %s %s"
+        raise PconvError("%s: the two batches x and y differ: %s %s %s vs %s %s %s"
                          % (what, x.device, x.dtype, tuple(x.shape), y.device, y.dtype, tuple(y.shape)))
     if not (x.is_contiguous() and y.is_contiguous()) or x.dim() != 4:
-        raise PconvError("%s: contiguous 4-D tensors expected" % what)
+        raise PconvError("%s: x and y: contiguous 4-D tensors expected" % what)
     if x.dtype == torch.float32:
         n, c, h, w = x.shape
         fn = entry + "_f32"
@@ -2117,7 +2209,7 @@ def ws_msssim_backward(x, y, workspace, values, gout, weighting="ws", swapped=Fa
             or not values.is_contiguous():
         raise PconvError("ws_msssim_backward: values must be contiguous float64 (%d, 7) on the inputs' device, got %s %s %s"
                          % (n, values.device, values.dtype, tuple(values.shape)))
-    nbytes = call("pconv_ws_msssim_workspace_bytes", n, c, h, w)
+    nbytes = _host_query("pconv_ws_msssim_workspace_bytes", n, c, h, w)
     if workspace.device != x.device or workspace.dtype != torch.uint8 or workspace.numel() != nbytes \
             or not workspace.is_contiguous():
         raise PconvError("ws_msssim_backward: the workspace must be the %d bytes ws_msssim_device returned, got %s %s %s"
@@ -2133,13 +2225,18 @@ def ws_msssim_backward(x, y, workspace, values, gout, weighting="ws", swapped=Fa
 def tile_gdn(owner, x, gamma, beta, inverse, col_limit=None, npart=0, residual=None, ring=0):
     """PseudoGDNV2.forward in one launch: x / sqrt(beta + gamma x^2) (inverse: x * sqrt)
     (+ residual), zeros from each tile's col_limit on.  gamma (ch, ch), beta (ch):
-    effective values.  ring: see tile_conv2d."""
-    x = _require_rows(x, "tile_gdn")
+    effective values.  ring: see tile_conv2d.  x and residual: row-strided views accepted (any other view is
+    copied); gamma and beta: any strides (packed / copied dense); col_limit: contiguous int32, at least npart long."""
+    x = _require_rows(x, "tile_gdn: x")
     tn, ch, h, w = x.shape
+    _require_operand(gamma, "tile_gdn", "gamma", (ch, ch), torch.float32, x, dense=False)
+    _require_operand(beta, "tile_gdn", "beta", (ch,), torch.float32, x, dense=False)
+    if col_limit is not None:
+        _require_operand(col_limit, "tile_gdn", "col_limit", int(npart), torch.int32, x)
     stream = _stream(x.device)
-    packed = packed_conv_weight(owner, gamma.view(ch, ch, 1, 1), stream)
     out = _ring_output((tn, ch, h, w), ring, x)
     residual = _like_output(residual, out, "tile_gdn: residual")
+    packed = packed_conv_weight(owner, gamma.view(ch, ch, 1, 1), stream)      # (the first call of the library)
     views = _views(x, out, residual)
 
     def describe():
@@ -2148,8 +2245,9 @@ def tile_gdn(owner, x, gamma, beta, inverse, col_limit=None, npart=0, residual=N
                 2.0 * ch * ch * tn * h * w * _VALID_FRACTION,
                 4.0 * ch * tn * h * w * _VALID_FRACTION * (3 if residual is not None else 2))
 
+    beta = beta.detach().contiguous()      # (kept for the duration of the call)
     with _ConvTimed(x.device, describe):
-        call("pconv_gdn", _ptr(x), _ptr(packed), _ptr(beta.detach().contiguous()), _ptr(out), tn, ch, h, w,
+        call("pconv_gdn", _ptr(x), _ptr(packed), _ptr(beta), _ptr(out), tn, ch, h, w,
              1 if inverse else 0, _ptr(col_limit), int(npart), _ptr(residual), ctypes.addressof(views), stream)
     return out
 
@@ -2165,12 +2263,21 @@ def tile_conv2d(owner, x, weight, bias, stride, slope=None, col_limit=None, npar
     residual may be interior views of padded buffers.  ring > 0: the result is written
     into the interior of a buffer padded by `ring` (returned as that view), so that a
     following PseudoPad only has to fill the ring.  d2w: DtowOp(2, True) applied by the
-    store, the result is (tn, cout/4, 2*ho, 2*wo)."""
-    x = _require_rows(x, "tile_conv2d")
+    store, the result is (tn, cout/4, 2*ho, 2*wo).  x, gate and residual: row-strided views accepted (any other
+    view is copied); weight: any strides (it is packed); bias and slope: contiguous float32 (cout); col_limit:
+    contiguous int32, at least npart long.  Every operand is checked before the first call of the library."""
+    x = _require_rows(x, "tile_conv2d: x")
     tn, cin, h, w = x.shape
+    _require_operand(weight, "tile_conv2d", "weight", (None, cin, None, None), torch.float32, x, dense=False)
     cout, cin_w, k, k2 = weight.shape
-    if cin != cin_w or k != k2:
+    if k != k2:
         raise PconvError("tile_conv2d: weight %s does not fit input %s" % (tuple(weight.shape), tuple(x.shape)))
+    if bias is not None:
+        _require_operand(bias, "tile_conv2d", "bias", (cout,), torch.float32, x)
+    if slope is not None:
+        _require_operand(slope, "tile_conv2d", "slope", (cout,), torch.float32, x)
+    if col_limit is not None:
+        _require_operand(col_limit, "tile_conv2d", "col_limit", int(npart), torch.int32, x)
     stream = _stream(x.device)
     ho, wo = (h - k) // stride + 1, (w - k) // stride + 1
     out = _ring_output((tn, cout // 4, 2 * ho, 2 * wo) if d2w else (tn, cout, ho, wo), ring, x)
@@ -2181,8 +2288,17 @@ def tile_conv2d(owner, x, weight, bias, stride, slope=None, col_limit=None, npar
     gate = _like_output(gate, out, "tile_conv2d: gate")
     residual = _like_output(residual, out, "tile_conv2d: residual")
     # (only a 3x3 layer can go to the kernels that ask for it)
+    fused = sigmoid or gate is not None
     aligned = k == 3 and _aligned8(out) and (residual is None or _aligned8(residual))
-    launches, fallback = conv_plan(cin, h, w, cout, k, stride, d2w, sigmoid or gate is not None, aligned)
+    launches, fallback = conv_plan(cin, h, w, cout, k, stride, d2w, fused, aligned)
+    if fallback and not aligned and _aligned8(out) and residual.data_ptr() % 8 and \
+            residual.stride(0) % 2 == 0 and residual.stride(1) % 2 == 0 and residual.stride(2) % 2 == 0:
+        # the residual's start alone keeps the layer off its kernel: where a dense copy has 8-byte aligned rows, the
+        # layer takes the kernel -- and gives the bits -- of the same call with an aligned residual
+        wanted = conv_plan(cin, h, w, cout, k, stride, d2w, fused, True)
+        if not wanted[1] and wo % 2 == 0 and (ho * wo) % 2 == 0:      # (a kernel takes the layer; the copy's strides are even)
+            residual, aligned = residual.clone(memory_format=torch.contiguous_format), True
+            launches, fallback = wanted
     if fallback:
         # a plain 3x3 stride-1 layer that Winograd was selected for went to the direct kernel (shape not
         # taken, or output / residual rows not 8-byte aligned): counted, so that the choice is never silent
@@ -2333,14 +2449,21 @@ def optim_segments(counts, device):
 def optim_step(records, segments, clip, device):
     """pconv_optim_sqnorm + pconv_optim_adam over the device table `records` ((ntensor, 9) int64: pconv_optim_tensor)
     in THE ORDER of include/pconv_hip.h: two launches and the closing launch of the norm.  Returns the workspace as
-    float64: [0] total, [1] norm, the low half of [2] the fp32 clip coefficient, then the segment partials."""
-    if records.dtype != torch.int64 or tuple(records.shape) != (segments.ntensor, 9) or not records.is_cuda or \
-            not records.is_contiguous() or records.device != segments.table.device or records.device != torch.device(device):
+    float64: [0] total, [1] norm, the low half of [2] the fp32 clip coefficient, then the segment partials.  records and
+    segments.table: contiguous, on `device`; the tensors behind the records' addresses are the caller's to check
+    (optim.Adam does)."""
+    table = segments.table
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (segments.nsegment, 2) or \
+            not table.is_cuda or not table.is_contiguous() or table.device != torch.device(device):
+        raise PconvError("optim_step: the table of segments must be a contiguous (%d, 2) int32 tensor on %s (optim_segments)"
+                         % (segments.nsegment, device))
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.int64 or tuple(records.shape) != (segments.ntensor, 9) or \
+            not records.is_cuda or not records.is_contiguous() or records.device != table.device:
         raise PconvError("optim_step: records must be a contiguous (%d, 9) int64 tensor on %s" % (segments.ntensor, device))
     stream = _stream(records.device)
     nbytes = call("pconv_optim_workspace_bytes", segments.ntensor, segments.nsegment)
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=records.device)
-    args = (_ptr(records), _ptr(segments.table), _np_ptr(segments.counts), segments.ntensor, segments.nsegment)
+    args = (_ptr(records), _ptr(table), _np_ptr(segments.counts), segments.ntensor, segments.nsegment)
     call("pconv_optim_sqnorm", *args + (float(clip), _ptr(ws), stream))
     call("pconv_optim_adam", *args + (_ptr(ws), stream))
     return ws
@@ -2365,8 +2488,10 @@ def conv5x5(owner, x, weight, bias):
     _conv_tensors("conv5x5", [("x", x, 4), ("weight", weight, 4)] + ([("bias", bias, 1)] if bias is not None else []))
     tn, cin, h, w = x.shape
     cout, cin_w, k, k2 = weight.shape
-    if cin != cin_w or (k, k2) != (5, 5) or h < 5 or w < 5 or (bias is not None and bias.shape[0] != cout):
+    if cin != cin_w or (k, k2) != (5, 5) or h < 5 or w < 5:
         raise PconvError("conv5x5: weight %s does not fit input %s" % (tuple(weight.shape), tuple(x.shape)))
+    if bias is not None and bias.shape[0] != cout:
+        raise PconvError("conv5x5: bias %s does not fit weight %s" % (tuple(bias.shape), tuple(weight.shape)))
     stream = _stream(x.device)
     out = torch.empty((tn, cout, h - 4, w - 4), dtype=torch.float32, device=x.device)
     call("pconv_conv5", _ptr(x), _ptr(_cached_pack(owner, "_pconv_packed5", weight, _pack5, stream)),
