@@ -611,6 +611,65 @@ int pconv_sphere_points_mse_f32(const float *x, int h1, int w1, const int32_t *r
                                 const int32_t *rec_y, const float *phases, int n, int c, long long P, int mode,
                                 void *workspace, double *out, void *stream);
 
+/* Points of the sphere on a cube picture (csrc/cube.hip; cube.point_records_numpy states the same definition in numpy):
+ * the record that lets pconv_sphere_points_sample_f32 / pconv_sphere_points_mse_f32 read a cube picture, on either side,
+ * with no conversion to ERP in between.  The picture they are given is the padded stack of pconv_cube_pad_f32, seen as
+ * one plane of 6*A x A, A = a + 6.
+ * dirs: float64 (P, 3) on the device, d = (cos p * cos t, cos p * sin t, sin p) of the point (t, p), built on the host:
+ *   kernel and host twin read the same array, so no device trigonometry enters for CMP.
+ * Record of a point (pconv_cube_points_records: (P, 2) int32 on the device), all in fp64, in THIS ORDER, every operation one
+ *   rounding, never contracted:
+ *     g = the face of d by the rule above (ties x, y, z with >=);
+ *     along = d . forward_g;  ps = (d . right_g) / along;  pt = (d . up_g) / along   (the dot products have two zero terms);
+ *     s = ps for CMP, (4/pi) * atan(ps) for EAC;  t from pt alike;
+ *     u' = ((s + 1) * a) / 2 - 0.5;  v' = ((1 - t) * a) / 2 - 0.5;  both clamped to [-0.5, a - 0.5 - 1/256];
+ *     qu = rint((u' + 3) * 256);  qv = rint((v' + 3 + g*A) * 256).
+ *   The upper clamp is 1/256 tighter than pconv_cube_to_erp_map's, so that one record serves both modes: the nearest rule
+ *   (floor((q + 128) / 256)) always lands on a pixel of face g itself, never on its ring, and the Lanczos footprint stays
+ *   inside g's own padded face.  CMP records equal the host twin's with no exception; EAC records are equal except where
+ *   u'*256 or v'*256 lies within the evaluation error of atan (about 1e-10) of a rounding boundary; a direction within
+ *   rounding of a face tie lands on the same face on both sides, since both read the same doubles.
+ * dirs and records 8-byte aligned; no allocation, no atomics, no workspace, one store per point.  Refused on the host, before
+ *   any launch, with PCONV_EINVAL: null or misaligned pointers, a kind outside {CMP, EAC}, a outside 2 .. PCONV_CUBE_MAX_FACE,
+ *   P outside 1 .. 2^28 - 1, records that overlap dirs. */
+int pconv_cube_points_records(const double *dirs, int32_t *records, long long P, int kind, int a, void *stream);
+
+/* Weighted squared error over a weight plane (csrc/weighted_metrics.hip; pseudocylindrical_convolution_amd/
+ * weighted_metrics.py states the same definition in torch).  WS-PSNR is defined for every projection by its area weights:
+ * the weights of a cube picture are the solid angles of its pixels (cube.area_weights); a mask of inactive regions, a half
+ * sphere or a region of interest is the same call.
+ * Inputs: x and y float32 (n, C, H, W), contiguous, 4-byte aligned (pconv_weighted_mse_f32), or uint8 (n, H, W, 3)
+ *   interleaved, each value read as float(u8) / 255.f, correctly rounded (pconv_weighted_mse_u8, C = 3): the same image
+ *   gives the same bits in both forms, as in pconv_ws_metrics_u8.
+ * Weights: a float64 (H, W) plane on the device, 8-byte aligned, shared by all frames and channels; `total` is W, the
+ *   plane's total, which the HOST supplies (weighted_metrics.WeightPlane: math.fsum of the plane, the exactly rounded sum,
+ *   which has no order to state).  The kernels never sum the weights.
+ * Error of pixel p (the row-major index in the plane): d = x - y in fp32; e = d * d in fp32, widened to double; the term
+ *   is w_p * e, one fp64 product.
+ * Sum, per plane (f, c), in fp64, in the order stated above for pconv_sphere_points_mse_f32 with "point" read as "pixel":
+ *   chunks of PCONV_SPHERE_POINTS_CHUNK = 1024 consecutive pixels; lane l of 256 starts at +0 and adds the terms of the
+ *   pixels l, l + 256, l + 512, l + 768 of its chunk that exist, ascending; the tree s = 128 .. 1, lane l < s taking
+ *   lane[l] + lane[l + s]; one partial per plane and chunk in the workspace; a second launch adds a plane's partials the same
+ *   way (lane l adds the partials l, l + 256, ... ascending, then the tree); out[f][c] = sum / W.  The order depends on H*W
+ *   alone: not on the batch, the grid, or the alignment of the pointers.
+ * Backward (pconv_weighted_mse_backward_f32): of sum over (f, c) of gout[f][c] * out[f][c], with respect to y.  gout is n*C
+ *   doubles on the device.  k = ((2 * gout[f][c]) * w_p) / W in fp64, rounded once to fp32; grad[f][c][p] = k * (y - x), the
+ *   difference and the product in fp32.  One launch, every element stored exactly once, no atomics, no workspace.  Where all
+ *   four pointers are 16-byte aligned and H*W is a multiple of 4 the kernel moves 16 bytes per access; elsewhere 4; the bits
+ *   are the same.  The gradient with respect to x is the same call with x and y swapped.
+ * pconv_weighted_mse_workspace_bytes(n, c, h, w) = 8 * n * c * ceil(h*w / 1024) (a negative value when refused); the entry
+ *   points allocate nothing.  Refused on the host, before any launch, with PCONV_EINVAL: null or misaligned pointers, a side
+ *   outside 1 .. 2^20, a float32 plane of 2^31 bytes or more, n * C outside 1 .. 65535 (u8: C other than 3), a total that is
+ *   not finite or not positive, out or the workspace inside an input or each other, a gradient inside an input.  x == y is
+ *   allowed. */
+long long pconv_weighted_mse_workspace_bytes(int n, int c, int h, int w);
+int pconv_weighted_mse_f32(const float *x, const float *y, const double *weights, double total, int n, int c, int h, int w,
+                           void *workspace, double *out, void *stream);
+int pconv_weighted_mse_u8(const uint8_t *x, const uint8_t *y, const double *weights, double total, int n, int c, int h, int w,
+                          void *workspace, double *out, void *stream);
+int pconv_weighted_mse_backward_f32(const float *x, const float *y, const double *weights, double total, const double *gout,
+                                    int n, int c, int h, int w, float *grad, void *stream);
+
 /* Ordered backward of the renderer and of the sphere rotation (csrc/remap_backward.hip, csrc/geometry.cpp; viewport.py
  * states the same definition in torch: render_backward_torch).  The forward of view pixel (j, i) of plane (n, c) is the
  * one above without the clamp: S = sum_a wy[a] * (sum_b wx[b] * x[r_a][c_b]) at each of the ss*ss records (j*ss + p,

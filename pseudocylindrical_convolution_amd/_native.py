@@ -82,6 +82,11 @@ _HIP_SIGNATURES = {
     "pconv_sphere_points_sample_f32": [P, P, P, P, I, I, I, I, LL, I, P],
     "pconv_sphere_points_mse_workspace_bytes": [I, I, LL],
     "pconv_sphere_points_mse_f32": [P, I, I, P, P, I, I, P, P, I, I, LL, I, P, P, P],
+    "pconv_cube_points_records": [P, P, LL, I, I, P],
+    "pconv_weighted_mse_workspace_bytes": [I, I, I, I],
+    "pconv_weighted_mse_f32": [P, P, P, D, I, I, I, I, P, P, P],
+    "pconv_weighted_mse_u8": [P, P, P, D, I, I, I, I, P, P, P],
+    "pconv_weighted_mse_backward_f32": [P, P, P, D, P, I, I, I, I, P, P],
     "pconv_project": [P, P, P, I, I, I, I, I, I, I, I, P],
     "pconv_context_reshape": [P, P, I, I, I, I, I, P],
     "pconv_mask_constrain": [P, I, I, I, I, I, P],
@@ -236,6 +241,7 @@ def hip_lib():
         lib.pconv_erp_resample_backward_workspace_bytes.restype = c_longlong
         lib.pconv_host_lanczos_reverse_size.restype = c_longlong
         lib.pconv_sphere_points_mse_workspace_bytes.restype = c_longlong
+        lib.pconv_weighted_mse_workspace_bytes.restype = c_longlong
         lib.pconv_host_tap_reverse_size.restype = c_longlong
         lib.pconv_host_project_reverse_size.restype = c_longlong
         lib.pconv_host_remap_reverse_size.restype = c_longlong

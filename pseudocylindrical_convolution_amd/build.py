@@ -34,6 +34,7 @@ HIP_SOURCES = [
     "remap_backward.hip", # the ordered backward of the renderer and of the sphere rotation: a gather over reverse lists
     "sphere_metrics.hip",  # WS-PSNR / WS-SSIM / WS-MS-SSIM of ERP frames, forward and backward
     "sphere_points.hip",  # S-PSNR-NN / S-PSNR-I / CPP-PSNR: two pictures of any sizes sampled at points of the sphere
+    "weighted_metrics.hip",  # squared error over a float64 weight plane, forward and backward: WS-PSNR of cube pictures, masks
     "entropy.hip",
     "entropy_engine.hip",
     "entropy_mfma.hip",

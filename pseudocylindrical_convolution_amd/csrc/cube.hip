@@ -12,6 +12,8 @@
 //                             from the host's table and is the bilinear read of face g there, four loads, three lerps.
 //                             No trigonometry on the device: the ring is 12 a + 36 pixels per face, the table is built
 //                             once per (kind, a) on the host.  One pass, every pixel stored by its own lane.
+//   cube_points_records_kernel  one lane per point of a point set: the direction the host gives -> the record on the padded
+//                             stack, so that the sphere-sampled metrics (sphere_points.hip) read a cube picture (§4k).
 #include "sphere_sampler.h"
 
 namespace {
@@ -84,6 +86,27 @@ __global__ __launch_bounds__(kBlock) void cube_to_erp_map_kernel(int2 *__restric
   const double v = fmin(fmax((1.0 - t) * a / 2.0 - 0.5, lo), hi);
   const int A = a + 2 * kPad;
   map[(long long)j * gw + i] = make_int2((int)rint((u + kPad) * kPhases), (int)rint((v + kPad + (double)g * A) * kPhases));
+}
+
+// one lane per point: the record of a direction on the padded stack.  The position is cube_to_erp_map_kernel's, word for
+// word, from a direction the host computed (no sin / cos here, and for CMP no transcendental at all); the upper clamp is
+// 1/256 pixel tighter, so that the nearest pixel of the record is always a pixel of the face itself.
+__global__ __launch_bounds__(kBlock) void cube_points_records_kernel(const double *__restrict__ dirs, int2 *__restrict__ records,
+                                                                     long long P, int kind, int a) {
+  const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= P) return;
+  const double dx = dirs[3 * k], dy = dirs[3 * k + 1], dz = dirs[3 * k + 2];
+  const int g = face_of(dx, dy, dz);
+  const Frame3 B = face_frame(g);
+  const double along = dx * B.f[0] + dy * B.f[1] + dz * B.f[2];
+  const double s = face_of_plane(kind, (dx * B.r[0] + dy * B.r[1] + dz * B.r[2]) / along);
+  const double t = face_of_plane(kind, (dx * B.u[0] + dy * B.u[1] + dz * B.u[2]) / along);
+  // fmax / fmin return the other operand for a NaN (a zero direction): every record stays inside its padded face
+  const double lo = -0.5, hi = a - 0.5 - 1.0 / kPhases;
+  const double u = fmin(fmax((s + 1.0) * a / 2.0 - 0.5, lo), hi);
+  const double v = fmin(fmax((1.0 - t) * a / 2.0 - 0.5, lo), hi);
+  const int A = a + 2 * kPad;
+  records[k] = make_int2((int)rint((u + kPad) * kPhases), (int)rint((v + kPad + (double)g * A) * kPhases));
 }
 
 __device__ __forceinline__ float lerp_rn(float x0, float x1, float f) {
@@ -170,6 +193,21 @@ extern "C" int pconv_cube_to_erp_map(int32_t *map, int kind, int a, int h, int w
   const int tiles = ((int)gw + kBlock - 1) / kBlock;  // gh * tiles < 2^28 / 256 + 2^22
   hipLaunchKernelGGL(cube_to_erp_map_kernel, dim3((unsigned)gh * tiles), dim3(kBlock), 0, as_stream(stream),
                      reinterpret_cast<int2 *>(map), kind, a, (int)gh, (int)gw, tiles);
+  PCONV_LAUNCH_CHECK(what);
+  return PCONV_OK;
+}
+
+extern "C" int pconv_cube_points_records(const double *dirs, int32_t *records, long long P, int kind, int a, void *stream) {
+  const char *what = "cube_points_records";
+  PCONV_REQUIRE(dirs && records, "%s: null pointer", what);
+  if (kind_ok(what, kind) != PCONV_OK || face_ok(what, a) != PCONV_OK) return PCONV_EINVAL;
+  PCONV_REQUIRE(P >= 1 && P <= (1LL << 28) - 1, "%s: %lld points, 1 .. 2^28 - 1 expected", what, P);
+  if (aligned8_ok(what, addr(dirs) | addr(records), "the directions and the records") != PCONV_OK) return PCONV_EINVAL;
+  PCONV_REQUIRE(addr(dirs) >= addr(records) + (uintptr_t)(8 * P) || addr(records) >= addr(dirs) + (uintptr_t)(24 * P),
+                "%s: the records overlap the directions", what);
+  const long long blocks = (P + kBlock - 1) / kBlock;  // below 2^20
+  hipLaunchKernelGGL(cube_points_records_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), dirs,
+                     reinterpret_cast<int2 *>(records), P, kind, a);
   PCONV_LAUNCH_CHECK(what);
   return PCONV_OK;
 }

@@ -26,6 +26,11 @@ GPU tensors take the HIP kernels (PCONV.cube_*, PCONV.viewport_render_f32), CPU 
 goes through viewport's Function (the ordered backward of pconv_remap_backward_f32: the map is generic); `to_erp` under
 autograd is refused: the pad kernel has no backward yet.
 
+Scoring (the last section of this module): `area_weights` is the solid angle of every pixel of a cube
+picture, `ws_mse` / `ws_psnr` / `ws_loss_terms` weigh two cube pictures by it (weighted_metrics.py), and `point_records` puts
+the points of a sphere_points.PointSet on the padded stack, so that `points_mse`, `s_psnr_nn`, `s_psnr_i` and `cpp_psnr` read
+cube and ERP pictures in any mix at the same points of the sphere, with no conversion in between.
+
 Limits.  The ring is bilinear and one level deep, so within 3 pixels of a face edge the way back reads a slightly softer
 continuation than the sphere itself.  For "eac" the extended plane ends before its horizon: |s| and |t| of a ring pixel
 are held at 7/4, which only faces of a <= 6 reach.  ss is chosen for the face centre / the equator.
@@ -516,3 +521,212 @@ def to_erp(y, size=None, spec="cmp", ss=None, clamp=False, layout=None):
     ss = to_erp_ss(a, h, w) if ss is None else _check_ss(ss)
     map = to_erp_map(sp.kind, a, h, w, ss, y.device)
     return _render(pad(faces.contiguous(), sp.kind), map, h, w, ss, clamp)
+
+
+# ---- scoring cube pictures on the sphere: area weights (WS-PSNR) and points of the sphere (S-PSNR, CPP-PSNR) ----
+#
+# Weights.  Pixel (r, c) of a face covers, on the face's plane, the rectangle between the edges p_c, p_c+1 and q_r, q_r+1,
+# edge k at plane_of(kind, (2k - a) / a).  With F(p, q) = atan(p q / sqrt(1 + (p^2 + q^2))) its solid angle is
+#   omega = (F(p1, q1) + F(p0, q0)) - (F(p0, q1) + F(p1, q0))
+# -- the four-corner formula grouped so that the plane is symmetric under the eight symmetries of the square bit for bit (the
+# edges are odd in k - a/2, F is odd in each argument and symmetric in the two): the plane is the same on all six faces and
+# in every orientation a layout turns a face to.  rule="density" is the pointwise Jacobian at the pixel centre times the
+# pixel's area (2/a)^2 in face coordinates: p'(s) p'(t) / (1 + p_s^2 + p_t^2)^(3/2), p' = 1 for "cmp" -- the (1 + d^2/r^2)^
+# (-3/2) of the JVET WS-PSNR proposal -- and (pi/4)(1 + p^2) for "eac".  It is offered so that a figure can be compared with
+# tools that use it; equality with 360Lib's figures is not claimed.
+#
+# Points.  `point_records` is the record of a point of the sphere on the padded stack (pconv_cube_points_records): with it
+# sphere_points' fused kernel reads a cube picture on either side, with no conversion to ERP in between.
+
+RULES = ("solid-angle", "density")
+
+
+def _pack_numpy(stack, layout):
+    """`pack` of one (6a, a) plane in numpy, any dtype"""
+    a = stack.shape[1]
+    if layout == "faces":
+        return stack
+    F, R, B, L, U, D = (stack[k * a:(k + 1) * a] for k in range(6))
+    if layout == "6x1":
+        return np.concatenate([F, R, B, L, U, D], axis=1)
+    bottom = np.concatenate([np.rot90(D, 1), np.rot90(B, -1), np.rot90(U, 1)], axis=1)
+    return np.concatenate([np.concatenate([L, F, R], axis=1), bottom], axis=0)
+
+
+def face_weights(kind, a, rule="solid-angle"):
+    """float64 (a, a): the weight of every pixel of one face (the same on all six)"""
+    kind, a = _kind(kind), check_face(a)
+    if rule not in RULES:
+        raise PconvError("cube: rule must be one of %s, got %r" % (RULES, rule))
+    if rule == "density":
+        p = plane_of(kind, (2.0 * np.arange(a, dtype=np.float64) + 1.0 - a) / a)
+        dp = (np.pi / 4.0) * (1.0 + p * p) if kind == "eac" else np.ones_like(p)
+        return (dp[None, :] * dp[:, None]) / (1.0 + (p[None, :] ** 2 + p[:, None] ** 2)) ** 1.5 * (2.0 / a) ** 2
+    e = plane_of(kind, (2.0 * np.arange(a + 1, dtype=np.float64) - a) / a)
+    p, q = e[None, :], e[:, None]
+    corner = np.arctan((p * q) / np.sqrt(1.0 + (p * p + q * q)))
+    return (corner[1:, 1:] + corner[:-1, :-1]) - (corner[1:, :-1] + corner[:-1, 1:])
+
+
+def area_weights(kind, a, layout="faces", rule="solid-angle"):
+    """float64 numpy of picture_size(a, layout): the area on the sphere of every pixel of a cube picture -- its exact solid
+    angle (the faces sum to 4 pi), or with rule="density" the Jacobian at its centre times (2/a)^2 -- laid out by the
+    layout's own permutation"""
+    layout = spec(kind, layout).layout
+    return np.ascontiguousarray(_pack_numpy(np.tile(face_weights(kind, a, rule), (6, 1)), layout))
+
+
+@functools.lru_cache(maxsize=8)
+def _weight_plane(sp, a, rule):
+    from . import weighted_metrics
+    return weighted_metrics.WeightPlane(area_weights(sp.kind, a, sp.layout, rule))
+
+
+def weight_plane(spec, a, rule="solid-angle"):
+    """the cached weighted_metrics.WeightPlane of area_weights(spec.kind, a, spec.layout, rule)"""
+    if rule not in RULES:
+        raise PconvError("cube: rule must be one of %s, got %r" % (RULES, rule))
+    return _weight_plane(_spec(spec), check_face(a), rule)
+
+
+def _picture_face(x, sp):
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise PconvError("cube: a 4-D batch of cube pictures expected")
+    return face_size_of(x.shape[1:3] if x.dtype == torch.uint8 else x.shape[2:], sp.layout)
+
+
+def ws_mse(x, y, spec):
+    """float64 CPU tensor (n, C): the squared error of two cube pictures of one spec, every pixel weighted by its solid
+    angle (weighted_metrics.mse on weight_plane(spec, a)).  float32 (n, C, height, width) or uint8 (n, height, width, 3)"""
+    from . import weighted_metrics
+    sp = _spec(spec)
+    return weighted_metrics.mse(x, y, weight_plane(sp, _picture_face(x, sp)))
+
+
+def ws_psnr(x, y, spec):
+    """float64 (n,) WS-PSNR in dB of each cube picture: 10 log10(1 / mean over the channels of ws_mse)"""
+    from . import weighted_metrics
+    sp = _spec(spec)
+    return weighted_metrics.psnr(x, y, weight_plane(sp, _picture_face(x, sp)))
+
+
+def ws_loss_terms(x, y, spec):
+    """float64 (n,) on the pictures' device, attached to autograd: the per-frame mean over the channels of ws_mse
+    (weighted_metrics.loss_terms).  With from_erp's backward a model's ERP output is trained against a cube original:
+    ws_loss_terms(from_erp(output, a, spec), original, spec)"""
+    from . import weighted_metrics
+    sp = _spec(spec)
+    return weighted_metrics.loss_terms(x, y, weight_plane(sp, _picture_face(x, sp)))
+
+
+def point_directions(pointset):
+    """float64 (P, 3), C order: (cos p cos t, cos p sin t, sin p) of the points (t, p) of a PointSet or a (P, 2) array: the
+    array the record kernel and its twin both read"""
+    pts = pointset.points if hasattr(pointset, "points") else np.asarray(pointset, dtype=np.float64)
+    cp = np.cos(pts[:, 1])
+    return np.ascontiguousarray(np.stack([cp * np.cos(pts[:, 0]), cp * np.sin(pts[:, 0]), np.sin(pts[:, 1])], axis=1))
+
+
+def point_positions(kind, a, dirs):
+    """(g, u', v') of directions (P, 3): the face and the position on it before the clamp, in the kernel's order"""
+    return face_position(kind, check_face(a), np.asarray(dirs, dtype=np.float64).T)
+
+
+def point_records_numpy(pointset, kind, a):
+    """int32 (P, 2): the records of a point set on the padded stack of a cube of face size a, in float64 on the host,
+    operation by operation in the kernel's order (pconv_cube_points_records).  The upper clamp is a - 1/2 - 1/256"""
+    kind, a = _kind(kind), check_face(a)
+    g, u, v = point_positions(kind, a, point_directions(pointset))
+    hi = a - 0.5 - 1.0 / PHASES
+    u, v = np.clip(u, -0.5, hi), np.clip(v, -0.5, hi)
+    A = a + 2 * PAD
+    qu = np.rint((u + PAD) * PHASES).astype(np.int64)
+    qv = np.rint((v + PAD + g.astype(np.float64) * A) * PHASES).astype(np.int64)
+    return np.stack([qu, qv], axis=1).astype(np.int32)
+
+
+KEPT_RECORDS = 4     # record tensors kept per point set
+
+
+def point_records(pointset, kind, a, device=None):
+    """int32 (P, 2) on `device`: the HIP kernel for a GPU device, point_records_numpy on the CPU -- equal for "cmp", and for
+    "eac" away from rounding boundaries.  A PointSet keeps its last KEPT_RECORDS; do not write to it"""
+    from . import _metric_ops, sphere_points
+    kind, a, device = _kind(kind), check_face(a), _device(device)
+    ps = sphere_points._pointset(pointset)
+    kept = ps.__dict__.setdefault("_cube_records", collections.OrderedDict())
+    key = (kind, a, str(device))
+    if key in kept:
+        kept.move_to_end(key)
+        return kept[key]
+    if device.type == "cuda":
+        rec = _metric_ops.cube_points_records(torch.from_numpy(point_directions(ps)).to(device), kind, a)
+    else:
+        rec = torch.from_numpy(point_records_numpy(ps, kind, a))
+    kept[key] = rec
+    while len(kept) > KEPT_RECORDS:
+        kept.popitem(last=False)
+    return rec
+
+
+def _points_operand(t, sp, ps):
+    """(the plane the sampler reads, its records): the padded stack of a cube picture, or an ERP picture as it is"""
+    from . import sphere_points
+    t = sphere_points._as_planes(t)
+    if sp is None:
+        return t, ps.records(t.shape[2], t.shape[3], t.device)
+    sp = _spec(sp)
+    faces = unpack(t, sp.layout).contiguous()
+    return pad(faces, sp.kind), point_records(ps, sp.kind, _check_stack(faces), t.device)
+
+
+def points_mse(x, y, pointset, interp="lanczos", x_spec=None, y_spec=None):
+    """float64 CPU tensor (n, C): sphere_points.mse with either operand a cube picture.  An operand with a spec is a cube
+    picture in that spec's layout (unpack, pad, point_records); an operand with None is an ERP picture (sphere_points'
+    own records).  Any mix of projections, kinds and sizes.  GPU tensors: the fused pconv_sphere_points_mse_f32; CPU
+    tensors: sphere_points.mse_records_torch's samples and errors, summed in the header's order (weighted_metrics.
+    ordered_sum) instead of torch's: the same bits as the kernel"""
+    from . import sphere_points, weighted_metrics
+    sphere_points._check_interp(interp)
+    ps = sphere_points._pointset(pointset)
+    px, rx = _points_operand(x, x_spec, ps)
+    py, ry = _points_operand(y, y_spec, ps)
+    sphere_points._check_pair(px, py)
+    if px.is_cuda:
+        ops = backend.ops()
+        if not hasattr(ops, "sphere_points_mse"):
+            raise PconvError("cube: the active backend has no sphere_points_mse kernel for a GPU tensor")
+        return ops.sphere_points_mse(px.contiguous(), rx, py.contiguous(), ry, interp)
+    d = sphere_points.sample_torch(px, rx, interp) - sphere_points.sample_torch(py, ry, interp)
+    return (weighted_metrics.ordered_sum((d * d).double()) / rx.shape[0]).cpu()
+
+
+def _level_set(level):
+    from . import sphere_points
+    return sphere_points.icosphere_set(sphere_points.LEVEL if level is None else int(level))
+
+
+def s_psnr_nn(x, y, x_spec=None, y_spec=None, level=None):
+    """float64 (n,) S-PSNR-NN in dB: icosphere(level, default 8), the nearest pixel of each picture"""
+    from . import sphere_points
+    return sphere_points.psnr_of(points_mse(x, y, _level_set(level), "nearest", x_spec, y_spec))
+
+
+def s_psnr_i(x, y, x_spec=None, y_spec=None, level=None):
+    """float64 (n,) S-PSNR-I in dB: icosphere(level, default 8), the 6 x 6 Lanczos-3 sampler"""
+    from . import sphere_points
+    return sphere_points.psnr_of(points_mse(x, y, _level_set(level), "lanczos", x_spec, y_spec))
+
+
+def cpp_psnr(x, y, x_spec=None, y_spec=None, size=None):
+    """float64 (n,) CPP-PSNR in dB: both pictures read at the valid pixels of a Craster parabolic picture of `size`, by
+    default erp_size(a) of the first cube operand (x's own size when neither is one)"""
+    from . import sphere_points
+    if size is None:
+        for t, sp in ((x, x_spec), (y, y_spec)):
+            if sp is not None:
+                size = erp_size(_picture_face(t, _spec(sp)))
+                break
+        else:
+            size = x.shape[1:3] if x.dtype == torch.uint8 else x.shape[2:]
+    return sphere_points.psnr_of(points_mse(x, y, sphere_points.cpp_set(int(size[0]), int(size[1])), "lanczos", x_spec, y_spec))

@@ -13,6 +13,8 @@ Differences from the reference, all additive:
   * --test --sphere / --rd --sphere add S-PSNR-NN / S-PSNR-I / CPP-PSNR (sphere_points.py: both pictures sampled at the
     same points of the sphere) and, for a file coded with --code-size, the same three of the reconstruction at the coded
     size against the source at its own;
+  * --test / --rd --projection --cube-metrics add CUBE-WS-PSNR and CUBE-S-PSNR-NN / -I / CUBE-CPP-PSNR: the cube picture
+    against the reconstructed cube picture, both read as cube pictures (cube.py, weighted_metrics.py);
   * --yuv / --yuv-out code raw YUV 4:2:0 files (yuv.py: yuv420p, nv12, yuv420p10le), one code file per frame, the
     colour conversion on the GPU; --test --ws then adds WS-PSNR-Y/U/V.  The stream and the container are the RGB ones:
     the decoder is told the pixel format on the command line;
@@ -644,6 +646,8 @@ def _report(rows, lines):
 
 
 _CUBE = 'CUBE-PSNR:{:.2f}dB'
+_CUBE_WS = 'CUBE-WS-PSNR:{:.2f}dB'
+_CUBE_SPHERE = 'CUBE-S-PSNR-NN:{:.2f}dB, CUBE-S-PSNR-I:{:.2f}dB, CUBE-CPP-PSNR:{:.2f}dB'
 
 
 def _cube_picture(img, geometry, name):
@@ -657,12 +661,27 @@ def _cube_picture(img, geometry, name):
 
 def _cube_sides(picture, geometry, rdata, dev):
     """(the ERP frame the codec saw of the uint8 cube picture, the float tensor the encoder converted it to; the plain
-    PSNR in dB of the cube picture against the ERP reconstruction `rdata` converted back)"""
+    PSNR in dB of the cube picture against the ERP reconstruction `rdata` converted back; that pair of cube pictures, for
+    _cube_metrics)"""
     from . import cube
     data = img2tensor(picture, dev)
     erp = cube.to_erp(data, geometry.source, geometry.projection, clamp=True)
     back = cube.from_erp(rdata, geometry.face, geometry.projection, clamp=True)
-    return erp, _plain_psnr(data, back)
+    return erp, _plain_psnr(data, back), (data, back)
+
+
+def _cube_metrics(picture, back, projection):
+    """--cube-metrics: (CUBE-WS-PSNR, CUBE-S-PSNR-NN, CUBE-S-PSNR-I, CUBE-CPP-PSNR) in dB of the original cube picture
+    against the reconstructed cube picture, both read as cube pictures: every pixel weighted by its solid angle, and both
+    sampled at the same points of the sphere with no conversion in between (cube.ws_psnr, cube.s_psnr_nn / s_psnr_i /
+    cpp_psnr); the lines are printed"""
+    from . import cube
+    x, y = picture.contiguous(), back.contiguous()
+    figures = (cube.ws_psnr(x, y, projection)[0].item(),) + tuple(
+        f(x, y, projection, projection)[0].item() for f in (cube.s_psnr_nn, cube.s_psnr_i, cube.cpp_psnr))
+    print(' ' + _CUBE_WS.format(figures[0]))
+    print(' ' + _CUBE_SPHERE.format(*figures[1:]))
+    return figures
 
 
 def _plain_psnr(x, y):
@@ -670,17 +689,21 @@ def _plain_psnr(x, y):
     return 10.0 * math.log10(1.0 / mse) if mse > 0 else float("inf")
 
 
-def _cube_lines(rows, cubes):
+def _cube_lines(rows, cubes, on_cube=()):
     """--projection: the format of the average's CUBE-PSNR line; the figures join the rows as their last column when
-    every file holds a cube picture"""
+    every file holds a cube picture.  on_cube (--cube-metrics: _cube_metrics' four figures per image): four more columns
+    and two more lines"""
     if not cubes or any(c is None for c in cubes):
         return []
     rows[:] = [r + (c,) for r, c in zip(rows, cubes)]
-    return [_CUBE]
+    if not on_cube:
+        return [_CUBE]
+    rows[:] = [r + tuple(m) for r, m in zip(rows, on_cube)]
+    return [_CUBE, _CUBE_WS, _CUBE_SPHERE]
 
 
 def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False,
-                      ws=False, rotation=None, ms_ssim=False, vp=None, sphere=False, projection=None):
+                      ws=False, rotation=None, ms_ssim=False, vp=None, sphere=False, projection=None, cube_metrics=False):
     """reference: pseudo_codec.py:263-290.  sphere=True (--sphere): three more columns and one more line after everything
     else, SphereScore's S-PSNR-NN / S-PSNR-I / CPP-PSNR of the source against the end-to-end reconstruction (the float
     tensors, both at the source size); a file coded at a reduced size and not rotated gets a second line, `(coded size)`,
@@ -697,13 +720,15 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
     computed on the ERP frame the codec saw (the cube picture converted as the encoder converts it) against the ERP
     reconstruction, bpp over the cube picture's pixels, and one more line and a last column follow, CUBE-PSNR: the plain
     PSNR of the cube picture against the reconstruction converted back.  projection (--test --projection): the spec every
-    file must record, a ContainerError otherwise"""
+    file must record, a ContainerError otherwise.  cube_metrics (--cube-metrics, with projection): after the CUBE-PSNR
+    line two more lines and four more columns, _cube_metrics' figures of the cube picture against the reconstructed cube
+    picture"""
     t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
     scorer, texts = (ViewportScore(device_id, None if vp is True else vp), []) if vp else (None, [])
     on_sphere, coded = SphereScore(device_id) if sphere else None, []
-    rows, cubes = [], []
+    rows, cubes, on_cube = [], [], []
     for fc, fn in zip(code_list, img_list):
         rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw)
         if rotation is not None and geometry.rotation != tuple(rotation):
@@ -715,7 +740,7 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
         cube_psnr = None
         if geometry.projected:
             picture = _cube_picture(read_image(fn), geometry, fn)
-            data, cube_psnr = _cube_sides(picture, geometry, rdata, dev)
+            data, cube_psnr, cube_pair = _cube_sides(picture, geometry, rdata, dev)
             img = tensor2img(data)
         else:
             img = check_img(read_image(fn), *geometry.source)
@@ -738,12 +763,14 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
         cubes.append(cube_psnr)
         if cube_psnr is not None:
             print(' ' + _CUBE.format(cube_psnr))
+            if cube_metrics:
+                on_cube.append(_cube_metrics(*cube_pair, geometry.projection))
     return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp)
-                   + _sphere_lines(rows, coded) + _cube_lines(rows, cubes))
+                   + _sphere_lines(rows, coded) + _cube_lines(rows, cubes, on_cube))
 
 
 def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False,
-                    code_size=None, rotation=None, ms_ssim=False, vp=None, sphere=False, projection=None):
+                    code_size=None, rotation=None, ms_ssim=False, vp=None, sphere=False, projection=None, cube_metrics=False):
     """--rd: what encoding() + decoding_and_test() report for the images, without a file in between.  The rate is
     the code length of the CDF rows the coder would get (rate.py: within a few bits of the stream), the
     reconstruction is the synthesis of the encoder's own symbols -- what the entropy decoder would hand back.
@@ -757,7 +784,7 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     with code_size and no rotation the three of the coded-size line, as in decoding_and_test.
     projection (--projection): every image is a cube picture taken at its own size; the lines are computed on the ERP
     frame the codec saw, bpp over the cube picture's pixels, and CUBE-PSNR is the last line and column, as in
-    decoding_and_test."""
+    decoding_and_test; cube_metrics (--cube-metrics) adds _cube_metrics' two lines and four columns after it."""
     from .engine import CodecEngine
     from . import rate
     (enc, dev), (dec, _) = _load("encoder", model_idx, mse, device_id), _load("decoder", model_idx, mse, device_id)
@@ -766,7 +793,7 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     spherical = SphericalMetrics(device_id) if ws else None
     scorer, texts = (ViewportScore(device_id, None if vp is True else vp), []) if vp else (None, [])
     on_sphere, coded = SphereScore(device_id) if sphere else None, []
-    rows, cubes = [], []
+    rows, cubes, on_cube = [], [], []
     for fn in img_list:
         img = read_image(fn)
         if not native and code_size is None and projection is None:
@@ -799,10 +826,13 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
         if sphere:
             _sphere_row(on_sphere, rows, coded, data, rdata, small)
         if picture is not None:
-            cubes.append(_plain_psnr(picture, cube.from_erp(rdata, geometry.face, projection, clamp=True)))
+            back = cube.from_erp(rdata, geometry.face, projection, clamp=True)
+            cubes.append(_plain_psnr(picture, back))
             print(' ' + _CUBE.format(cubes[-1]))
+            if cube_metrics:
+                on_cube.append(_cube_metrics(picture, back, projection))
     return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp)
-                   + _sphere_lines(rows, coded) + _cube_lines(rows, cubes))
+                   + _sphere_lines(rows, coded) + _cube_lines(rows, cubes, on_cube))
 
 
 def _yuv_rgb(frames, h, w, yuv_opts, dev):
@@ -983,6 +1013,16 @@ def _projection_flag(parser, args):
     return cube.spec(args.projection, args.cube_layout or "3x2")
 
 
+def _cube_metrics_flag(parser, args, projection):
+    """the checks of --cube-metrics: it goes with --projection on --test or --rd"""
+    if args.cube_metrics:
+        if projection is None:
+            parser.error("--cube-metrics goes with --projection: it scores cube pictures as cube pictures")
+        if not (args.test or args.rd) or args.enc or args.dec:
+            parser.error("--cube-metrics goes with --test or --rd")
+    return args.cube_metrics
+
+
 def _view_flags(parser, args):
     """the checks of --view / --view-size / --view-out[-file] and --vp; returns (view, view size, vp): view the four
     angles in degrees or None, view size (vh, vw) or None, vp None, True (the default size) or (vh, vw).  Contradictions
@@ -1097,6 +1137,11 @@ def main(argv=None):
                              '--dec writes the cube picture back.  Needs --container on --enc; not for --yuv')
     parser.add_argument('--cube-layout', choices=['faces', '6x1', '3x2'],
                         help='The layout of the cube pictures of --projection (default 3x2: L F R over D B U)')
+    parser.add_argument('--cube-metrics', action='store_true', default=False,
+                        help='Testing (--test / --rd) with --projection: after CUBE-PSNR also report CUBE-WS-PSNR (every '
+                             'cube pixel weighted by its solid angle) and CUBE-S-PSNR-NN / CUBE-S-PSNR-I / CUBE-CPP-PSNR: '
+                             'the original cube picture against the reconstructed one, both read as cube pictures at the '
+                             'same points of the sphere, with no conversion to ERP in between')
     parser.add_argument('--raw', action='store_true', default=False,
                         help='Decoding: never look for a container header (size and model from the flags)')
     parser.add_argument('--ws', action='store_true', default=False,
@@ -1135,6 +1180,7 @@ def main(argv=None):
     code_size = _code_size_flag(parser, args)
     rotation = _rotate_flag(parser, args)
     projection = _projection_flag(parser, args)
+    cube_metrics = _cube_metrics_flag(parser, args, projection)
     view, view_size, vp = _view_flags(parser, args)
     sphere = _sphere_flag(parser, args)
     yuv_call = _yuv_flags(parser, args)   # contradictory YUV flags end the run here, before anything is loaded
@@ -1170,7 +1216,7 @@ def main(argv=None):
         assert img_list is not None, 'No input images for scoring'
         rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws,
                         code_size=code_size, rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere,
-                        projection=projection, **size)
+                        projection=projection, cube_metrics=cube_metrics, **size)
     elif args.enc:
         assert img_list is not None, 'No input images for encoding'
         assert code_list is not None, 'No code files for saving the codes'
@@ -1191,7 +1237,8 @@ def main(argv=None):
             assert img_list is not None, 'No source images for evaluation.'
             assert len(code_list) == len(img_list), 'The number of codes and corresponding source images should be the same'
             decoding_and_test(code_list, img_list, midx, not args.ssim, args.gpu_id, raw=args.raw, ws=args.ws,
-                              rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere, projection=projection, **size)
+                              rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere, projection=projection,
+                              cube_metrics=cube_metrics, **size)
 
 
 if __name__ == '__main__':
