@@ -549,14 +549,25 @@ int pconv_viewport_render_f32(const float *in, float *out, const int32_t *map, c
  * Tensors and the table 4-byte aligned, maps 8-byte aligned; no allocation, no atomics, no workspace.  Refused on the host,
  *   before any launch, with PCONV_EINVAL: null or misaligned pointers, a kind outside {CMP, EAC}, a outside
  *   2 .. PCONV_CUBE_MAX_FACE, an ERP side outside 2 .. 2^20 or an ERP plane or a map of 2^31 bytes or more, n * C outside
- *   1 .. 65535, ss outside 1 .. 4, in == out. */
+ *   1 .. 65535, ss outside 1 .. 4, in == out.
+ * A continuation of any depth.  pconv_cube_pad_depth_f32 is pconv_cube_pad_f32 with `depth` in 1 .. PCONV_CUBE_MAX_DEPTH
+ *   in the place of 3: A = a + 2*depth, the interior at rows and columns depth .. depth + a - 1 of every padded face, the
+ *   table int32 (6*(A*A - a*a), 3) in the same ring order (4*depth*(a + depth) pixels per face), built by the same rule
+ *   (cube.pad_table(kind, a, depth)).  The bilinear read and the reduction of every record to a face and a position
+ *   inside it are word for word those above, so depth = 3 gives the bits of pconv_cube_pad_f32 on the same table.  One
+ *   level deep at every depth: the ring reads original faces only, and for EAC |s| and |t| of a ring pixel are still held
+ *   at 7/4; the outermost ring pixel lies at 1 + (2*depth - 1)/a, beyond 7/4 for a < 4*(2*depth - 1)/3 (depth 3: a <= 6;
+ *   depth 5: a <= 11).  cube.ws_ssim uses depth 5, the radius of the SSIM window.  Refused besides the above: a depth
+ *   outside 1 .. PCONV_CUBE_MAX_DEPTH, and an a whose padded stack 24*A*A would reach 2^31 bytes. */
 #define PCONV_CUBE_CMP 1
 #define PCONV_CUBE_EAC 2
 #define PCONV_CUBE_PAD 3
+#define PCONV_CUBE_MAX_DEPTH 8
 #define PCONV_CUBE_MAX_FACE 9453
 int pconv_host_cube_face_of(double x, double y, double z);
 int pconv_cube_from_erp_map(int32_t *map, int kind, int a, int ss, int h, int w, void *stream);
 int pconv_cube_pad_f32(const float *in, float *out, const int32_t *table, int n, int c, int a, void *stream);
+int pconv_cube_pad_depth_f32(const float *in, float *out, const int32_t *table, int n, int c, int a, int depth, void *stream);
 int pconv_cube_to_erp_map(int32_t *map, int kind, int a, int h, int w, int ss, void *stream);
 
 /* Sphere-sampled metrics: S-PSNR-NN, S-PSNR-I, CPP-PSNR (csrc/sphere_points.hip; pseudocylindrical_convolution_amd/
@@ -669,6 +680,37 @@ int pconv_weighted_mse_u8(const uint8_t *x, const uint8_t *y, const double *weig
                           void *workspace, double *out, void *stream);
 int pconv_weighted_mse_backward_f32(const float *x, const float *y, const double *weights, double total, const double *gout,
                                     int n, int c, int h, int w, float *grad, void *stream);
+
+/* SSIM weighted by a weight plane (csrc/weighted_metrics.hip, the tile passes in csrc/ssim_tile.h; weighted_metrics.
+ * ssim_torch states the same definition in float64 torch).  WS-SSIM for any projection whose weights are data: what
+ * pconv_ws_metrics_f32 computes with the cosine of an ERP row, with the weight of every pixel read from a plane.  A
+ * window knows nothing of the projection: the caller lays the picture out so that a window's neighbourhood in the plane
+ * is its neighbourhood on the sphere wherever the weight is not zero (cube.ws_ssim: every face continued by 5 pixels,
+ * the ring weighted zero).
+ * Inputs: x and y float32 (n, C, H, W), contiguous, 4-byte aligned; weights a float64 (H, W) plane on the device, 8-byte
+ *   aligned, shared by all frames and channels; `total` is W, the plane's total, supplied by the host as above.  There is no
+ *   uint8 form.
+ * map_p, per plane (f, c): exactly the SSIM map of pconv_ws_metrics_f32 for that plane: the 11-tap Gaussian of sigma 1.5
+ *   in fp32 applied as g (x) g, zero padding of 5 on the four borders of the H x W plane, C1 = 0.01^2, C2 = 0.03^2, fp32,
+ *   separable, the horizontal pass first, every 11-tap sum k-ascending as fmaf(g[k], v, acc) from acc = 0, sigma^2 =
+ *   blur(x^2) - mu^2, and the quotient grouped ((2 mu_x mu_y + C1) * (2 s_xy + C2)) / ((mu_x^2 + mu_y^2 + C1) * (s_x^2 +
+ *   s_y^2 + C2)).  The two kernels run the same device functions.
+ * out[f][c] = (sum over the pixels p of w_p * (double)map_p) / W, float64 (n, C): per plane, as pconv_weighted_mse_f32, not
+ *   per frame.  Each term is one fp64 product.
+ * Sum, per plane, in fp64, in THIS ORDER, which depends on (H, W) alone (not on the batch, the grid or the alignment of
+ *   the pointers): tiles of 32 rows x 64 columns from the plane's origin, row-major, the last of a row or column partial.
+ *   Within a tile, 256 lanes: lane (column c = l mod 64, row group q = l / 64) starts at +0 and adds the terms of the rows
+ *   8*q .. 8*q + 7 of column c that exist, ascending.  The 64 lanes of a row group: for m = 32, 16, 8, 4, 2, 1 every lane
+ *   takes its value + that of lane (c xor m), so all 64 end with the same bits.  The tile's partial is ((q0 + q1) + q2) +
+ *   q3, stored in the workspace (one double per plane and tile).  A second launch adds a plane's partials as stated for
+ *   pconv_sphere_points_mse_f32: lane l of 256 starts at +0 and adds the partials l, l + 256, ... ascending, then the tree
+ *   s = 128 .. 1; out = sum / W.  No atomics, no allocation.
+ * pconv_weighted_ssim_workspace_bytes(n, c, h, w) = 8 * n * c * ceil(h / 32) * ceil(w / 64) (a negative value when
+ *   refused).  Refused on the host, before any launch, with PCONV_EINVAL: what pconv_weighted_mse_f32 refuses, so also out or
+ *   the workspace inside x, y, the weights or each other.  x == y is allowed.  Non-finite inputs: unspecified.  Forward only. */
+long long pconv_weighted_ssim_workspace_bytes(int n, int c, int h, int w);
+int pconv_weighted_ssim_f32(const float *x, const float *y, const double *weights, double total, int n, int c, int h, int w,
+                            void *workspace, double *out, void *stream);
 
 /* Ordered backward of the renderer and of the sphere rotation (csrc/remap_backward.hip, csrc/geometry.cpp; viewport.py
  * states the same definition in torch: render_backward_torch).  The forward of view pixel (j, i) of plane (n, c) is the

@@ -1,5 +1,5 @@
-"""Bindings of the weighted metric and of the cube's point records (include/pconv_hip.h, pconv_weighted_mse_* and
-pconv_cube_points_records): what PCONV.py's wrappers are for the older entry points, kept here because PCONV.py's public
+"""Bindings of the weighted metrics, of the cube's point records and of its face continuation of any depth (include/
+pconv_hip.h, pconv_weighted_mse_*, pconv_weighted_ssim_f32, pconv_cube_points_records, pconv_cube_pad_depth_f32): what PCONV.py's wrappers are for the older entry points, kept here because PCONV.py's public
 names are closed.  weighted_metrics.py and cube.py are the users.
 
 Every wrapper holds PCONV.py's operand contract: an operand of the wrong type, device, shape or layout is refused with a
@@ -13,6 +13,7 @@ from ._native import PconvError
 
 CUBE_KINDS = {"cmp": 1, "eac": 2}   # PCONV_CUBE_CMP, PCONV_CUBE_EAC
 CUBE_MAX_FACE = 9453                # PCONV_CUBE_MAX_FACE
+CUBE_MAX_DEPTH = 8                  # PCONV_CUBE_MAX_DEPTH
 POINTS_MAX = (1 << 28) - 1
 MAX_SIDE = 1 << 20
 MAX_PLANES = 65535
@@ -90,6 +91,44 @@ def weighted_mse_backward(x, y, weights, total, gout):
     _native.call("pconv_weighted_mse_backward_f32", _ptr(x), _ptr(y), _ptr(weights), total, _ptr(gout), n, c, h, w, _ptr(grad),
                  _stream(x.device))
     return grad
+
+
+def weighted_ssim_device(x, y, weights, total):
+    """float64 (n, C) on the inputs' device: (sum over the pixels of weights * the SSIM map of (x, y)) / total per plane, in
+    the order of include/pconv_hip.h (pconv_weighted_ssim_f32).  x, y: contiguous float32 (n, C, H, W) GPU tensors of one
+    shape; weights: contiguous float64 (H, W) on the same device; total: a positive finite float.  Two launches; nothing
+    waits"""
+    what = "weighted_ssim"
+    (n, c, h, w), _ = _frames(what, x, y, weights, True)
+    total = _total(what, total)
+    nbytes = _native.call("pconv_weighted_ssim_workspace_bytes", n, c, h, w)
+    workspace = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)   # one fp64 partial per plane and tile
+    out = torch.empty((n, c), dtype=torch.float64, device=x.device)
+    _native.call("pconv_weighted_ssim_f32", _ptr(x), _ptr(y), _ptr(weights), total, n, c, h, w, _ptr(workspace), _ptr(out),
+                 _stream(x.device))
+    return out
+
+
+def cube_pad_depth(x, table, depth, out=None):
+    """float32 (n, C, 6 A, A), A = a + 2 depth: the face stack x (contiguous float32 (n, C, 6 a, a) on a GPU) continued by
+    `depth` pixels, 1 .. CUBE_MAX_DEPTH, across every face edge; table: contiguous int32 (6 (A^2 - a^2), 3) on the same
+    device, from cube.pad_table(kind, a, depth) (pconv_cube_pad_depth_f32).  One launch; out must not be x"""
+    what = "cube_pad_depth"
+    depth = int(depth)
+    if not 1 <= depth <= CUBE_MAX_DEPTH:
+        raise PconvError("%s: depth must be 1 .. %d, got %r" % (what, CUBE_MAX_DEPTH, depth))
+    n, c, h6, a = _operand(x, what, "x", (None,) * 4, torch.float32)
+    A = a + 2 * depth
+    if not (h6 == 6 * a and a >= 2 and 24 * A * A < 1 << 31 and 1 <= n * c <= MAX_PLANES):
+        raise PconvError("%s: x: a face stack (n, C, 6 a, a) expected, a from 2 up with the padded stack below 2^31 bytes and "
+                         "n * C of 1 .. %d, got %s at depth %d" % (what, MAX_PLANES, (n, c, h6, a), depth))
+    _operand(table, what, "table", (6 * (A * A - a * a), 3), torch.int32, x.device)
+    if out is None:
+        out = torch.empty((n, c, 6 * A, A), dtype=torch.float32, device=x.device)
+    else:
+        _operand(out, what, "out", (n, c, 6 * A, A), torch.float32, x.device)
+    _native.call("pconv_cube_pad_depth_f32", _ptr(x), _ptr(out), _ptr(table), n, c, a, depth, _stream(x.device))
+    return out
 
 
 def cube_points_records(dirs, kind, a, out=None):

@@ -11,7 +11,9 @@
 //                             a lane one pixel.  An interior pixel is a copy; a ring pixel reads its record (g, qu, qv)
 //                             from the host's table and is the bilinear read of face g there, four loads, three lerps.
 //                             No trigonometry on the device: the ring is 12 a + 36 pixels per face, the table is built
-//                             once per (kind, a) on the host.  One pass, every pixel stored by its own lane.
+//                             once per (kind, a) on the host.  One pass, every pixel stored by its own lane.  The depth of
+//                             the ring is an argument: 3 for the way back (pconv_cube_pad_f32), 1 .. 8 through
+//                             pconv_cube_pad_depth_f32 (A = a + 2 depth; cube.ws_ssim continues by 5, §4k).
 //   cube_points_records_kernel  one lane per point of a point set: the direction the host gives -> the record on the padded
 //                             stack, so that the sphere-sampled metrics (sphere_points.hip) read a cube picture (§4k).
 #include "sphere_sampler.h"
@@ -114,8 +116,8 @@ __device__ __forceinline__ float lerp_rn(float x0, float x1, float f) {
 }
 
 __global__ __launch_bounds__(kBlock) void cube_pad_f32_kernel(const float *__restrict__ in, float *__restrict__ out,
-                                                              const int *__restrict__ table, int a, int tiles) {
-  const int A = a + 2 * kPad;
+                                                              const int *__restrict__ table, int a, int pad, int tiles) {
+  const int A = a + 2 * pad;
   const int ty = blockIdx.x / tiles;
   const int Q = (blockIdx.x - ty * tiles) * kTileW + (threadIdx.x % kTileW);
   const int row = ty * kTileH + threadIdx.x / kTileW;  // 0 .. 6 A - 1
@@ -123,16 +125,16 @@ __global__ __launch_bounds__(kBlock) void cube_pad_f32_kernel(const float *__res
   const int face = row / A, R = row - face * A;
   const float *src = in + (long long)blockIdx.y * 6 * a * a;   // a plane is below 2^29 floats
   float *dst = out + (long long)blockIdx.y * 6 * A * A + (row * A + Q);
-  const int r = R - kPad, c = Q - kPad;
+  const int r = R - pad, c = Q - pad;
   if (r >= 0 && r < a && c >= 0 && c < a) {
     *dst = src[(face * a + r) * a + c];
     return;
   }
   // ring order: the pixels of the padded face outside its interior, row after row, column after column
   int k;
-  if (R < kPad) k = R * A + Q;
-  else if (R < kPad + a) k = kPad * A + (R - kPad) * 2 * kPad + (Q < kPad ? Q : Q - a);
-  else k = kPad * A + 2 * kPad * a + (R - kPad - a) * A + Q;
+  if (R < pad) k = R * A + Q;
+  else if (R < pad + a) k = pad * A + (R - pad) * 2 * pad + (Q < pad ? Q : Q - a);
+  else k = pad * A + 2 * pad * a + (R - pad - a) * A + Q;
   const int *rec = table + 3 * (face * (A * A - a * a) + k);
   // whatever the table holds is reduced to a position inside a face
   const int g = min(max(rec[0], 0), 5);
@@ -212,17 +214,33 @@ extern "C" int pconv_cube_points_records(const double *dirs, int32_t *records, l
   return PCONV_OK;
 }
 
-extern "C" int pconv_cube_pad_f32(const float *in, float *out, const int32_t *table, int n, int c, int a, void *stream) {
-  const char *what = "cube_pad_f32";
+namespace {
+
+// the face continuation of any depth: pconv_cube_pad_f32 is depth PCONV_CUBE_PAD, where face_ok has bounded the stack
+int cube_pad(const char *what, const float *in, float *out, const int32_t *table, int n, int c, int a, int depth, void *stream) {
   PCONV_REQUIRE(in && out && table, "%s: null pointer", what);
   if (planes_ok(what, n, c) != PCONV_OK || face_ok(what, a) != PCONV_OK) return PCONV_EINVAL;
+  PCONV_REQUIRE(depth >= 1 && depth <= PCONV_CUBE_MAX_DEPTH, "%s: a depth of %d is outside 1 .. %d", what, depth, PCONV_CUBE_MAX_DEPTH);
+  const int A = a + 2 * depth;
+  PCONV_REQUIRE(24LL * A * A < (1LL << 31), "%s: a face size of %d continued by %d: the padded stack is 2^31 bytes or more", what, a,
+                depth);
   PCONV_REQUIRE(((addr(in) | addr(out) | addr(table)) & 3) == 0, "%s: the tensors and the table must be 4-byte aligned", what);
   PCONV_REQUIRE(in != out, "%s: in and out must be distinct (the ring reads the faces)", what);
-  const int A = a + 2 * kPad;
   const int tiles = (A + kTileW - 1) / kTileW;
   const long long groups = (long long)tiles * ((6 * A + kTileH - 1) / kTileH);  // below 2^29 / 256 + 6 A
   hipLaunchKernelGGL(cube_pad_f32_kernel, dim3((unsigned)groups, (unsigned)(n * c)), dim3(kBlock), 0, as_stream(stream), in, out,
-                     table, a, tiles);
+                     table, a, depth, tiles);
   PCONV_LAUNCH_CHECK(what);
   return PCONV_OK;
+}
+
+}  // namespace
+
+extern "C" int pconv_cube_pad_f32(const float *in, float *out, const int32_t *table, int n, int c, int a, void *stream) {
+  return cube_pad("cube_pad_f32", in, out, table, n, c, a, kPad, stream);
+}
+
+extern "C" int pconv_cube_pad_depth_f32(const float *in, float *out, const int32_t *table, int n, int c, int a, int depth,
+                                        void *stream) {
+  return cube_pad("cube_pad_depth_f32", in, out, table, n, c, a, depth, stream);
 }

@@ -13,7 +13,8 @@
 // moment planes (mu_x, mu_y, x², y², xy: 42 x 64 each, in LDS), then the vertical pass, 8 rows x 1 column per lane,
 // evaluates the map and adds w_j·map (at the first scale also w_j·(x - y)²) into fp64 registers.  A wave butterfly and
 // a fixed-order sum over the four waves give the tile's partials, stored to partials[frame][tile].  From the staged
-// tile it also writes the tile's 16 x 32 block of the next scale of x and of y: tile origins are even, so a 2x2 block
+// tile (the staging, the two passes and the map are the device functions of ssim_tile.h, which the weighted SSIM of
+// weighted_metrics.hip calls too) it also writes the tile's 16 x 32 block of the next scale of x and of y: tile origins are even, so a 2x2 block
 // never straddles tiles, and the pyramid costs no second read of the frame.  No atomics: ms_close_kernel, one workgroup
 // per frame, adds each scale's partials in a fixed order and normalises, so a frame gives the same bits alone, in any
 // batch and on every run.
@@ -21,57 +22,18 @@
 // Backward: one launch of ms_backward_kernel per scale, coarse to fine: a gather (halo 10, five passes in LDS, every
 // output stored once) with a compile-time switch between the cs-only and the full coefficients, the fused
 // + 0.25f·g_{s+1}[r >> 1][q >> 1] read and, at scale 0, + km·(y - x).
-#include <math.h>
-
-#include "common.h"
+#include "ssim_tile.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kTileRows = 32, kTileCols = 64;
-constexpr int kHalo = 5, kTaps = 2 * kHalo + 1;
-constexpr int kInRows = kTileRows + 2 * kHalo;  // 42
-constexpr int kInCols = kTileCols + 2 * kHalo;  // 74
-constexpr int kLd = 76;                         // staged row stride: 16-byte rows, the last float4 read ends at 75
-constexpr int kQuads = kTileCols / 4;           // horizontal pass: 4 adjacent outputs per lane
-constexpr int kRowsPerLane = 8;                 // vertical pass: 8 rows of one column per lane
-constexpr int kStage = (kInRows * kInCols + kBlock - 1) / kBlock;  // staged elements per lane and input
-constexpr int kPlane = kInRows * kTileCols;
-constexpr int kMaxSide = 1 << 20;
-static_assert(kBlock == kTileCols * (kTileRows / kRowsPerLane), "vertical pass: one lane per (column, row group)");
-static_assert(4 * (kQuads - 1) + 16 <= kLd, "horizontal pass: the last float4 read stays inside the staged row");
+// the tile, its constants, the staging and the two filter passes: ssim_tile.h, shared with weighted_metrics.hip
+using namespace ssim;
 
-struct WsGeom {
-  int c, h, w, tiles_x, tiles, uniform;
-  float g[kTaps];  // the normalised 1-D Gaussian in fp32
-};
+constexpr int kMaxSide = 1 << 20;
 
 __host__ __device__ inline double row_weight(int j, int h) {
   // ((j + 0.5)/h - 0.5)·pi with an exact integer numerator: rows j and h-1-j get the same weight bit for bit
   return cos((double)(2 * j + 1 - h) / (2.0 * h) * M_PI);
-}
-
-// the frame's plane (f, ch) as a uniform base, a pixel as a 32-bit offset from it (a plane is below 2^31 bytes)
-__device__ __forceinline__ const float *plane_of(const float *__restrict__ p, const WsGeom &G, int f, int ch) {
-  return p + ((long long)f * G.c + ch) * G.h * G.w;
-}
-__device__ __forceinline__ float load_px(const float *__restrict__ plane, const WsGeom &G, int ch, int r, int col) {
-  return plane[(unsigned)(r * G.w + col)];
-}
-
-// uint8 (n, h, w, 3): the frame as the base; float(u8) / 255.f, correctly rounded, as pconv_frames_u8_to_f32
-__device__ __forceinline__ const uint8_t *plane_of(const uint8_t *__restrict__ p, const WsGeom &G, int f, int) {
-  return p + (long long)f * G.h * G.w * 3;
-}
-__device__ __forceinline__ float load_px(const uint8_t *__restrict__ frame, const WsGeom &G, int ch, int r, int col) {
-  return __fdiv_rn((float)frame[(unsigned)((r * G.w + col) * 3 + ch)], 255.f);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
 }
 
 constexpr int kScales = 5;
@@ -100,10 +62,7 @@ int ws_geom(const char *what, int scales, int n, int c, int h, int w, int weight
   G->tiles_x = (w + kTileCols - 1) / kTileCols;
   G->tiles = G->tiles_x * ((h + kTileRows - 1) / kTileRows);
   G->uniform = weighting == PCONV_WS_WEIGHT_UNIFORM;
-  // pytorch_ssim.gaussian(11, 1.5): exp(-(k - 5)² / (2·1.5²)) in double, normalised; here in fp32
-  double g[kTaps], sum = 0.0;
-  for (int k = 0; k < kTaps; k++) sum += g[k] = exp(-(double)((k - kHalo) * (k - kHalo)) / (2.0 * 1.5 * 1.5));
-  for (int k = 0; k < kTaps; k++) G->g[k] = (float)(g[k] / sum);
+  gaussian_taps(G->g);
   return PCONV_OK;
 }
 
@@ -184,27 +143,7 @@ __global__ __launch_bounds__(kBlock, 2) void ms_forward_kernel(const T *__restri
   double acc_e = 0.0, acc_s = 0.0;
   for (int ch = 0; ch < G.c; ch++) {
     const T *xp = plane_of(x, G, f, ch), *yp = plane_of(y, G, f, ch);
-    float xv[kStage], yv[kStage];
-#pragma unroll
-    for (int k = 0; k < kStage; k++) {
-      const int e = tid + k * kBlock;
-      const int rr = e / kInCols, cc = e - rr * kInCols;
-      const int gr = r0 - kHalo + rr, gc = c0 - kHalo + cc;
-      const bool in = e < kInRows * kInCols && gr >= 0 && gr < G.h && gc >= 0 && gc < G.w;
-      xv[k] = in ? load_px(xp, G, ch, gr, gc) : 0.f;
-      yv[k] = in ? load_px(yp, G, ch, gr, gc) : 0.f;
-    }
-    __syncthreads();  // the previous channel's vertical pass has read sx / sy / mom
-#pragma unroll
-    for (int k = 0; k < kStage; k++) {
-      const int e = tid + k * kBlock;
-      if (e < kInRows * kInCols) {
-        const int rr = e / kInCols, o = rr * kLd + (e - rr * kInCols);
-        sx[o] = xv[k];
-        sy[o] = yv[k];
-      }
-    }
-    __syncthreads();
+    stage_tile(xp, yp, G, ch, r0, c0, sx, sy);  // (its first barrier: the previous channel's vertical pass has read sx / sy / mom)
     // the next scale: the tile's 16 x 32 block of 2x2 means, ((p00 + p01) + (p10 + p11))·0.25f, from the staged tile.
     // A block inside the next scale lies inside this frame (2·(h >> 1) <= h) and inside this tile (even origin)
     if (!FINAL) {
@@ -219,69 +158,13 @@ __global__ __launch_bounds__(kBlock, 2) void ms_forward_kernel(const T *__restri
         }
       }
     }
-    // horizontal pass: 4 adjacent outputs of one staged row per lane, from 14 inputs read as four float4
-    for (int u = tid; u < kInRows * kQuads; u += kBlock) {
-      const int rr = u / kQuads, q = u - rr * kQuads;
-      float a[16], b[16];
-#pragma unroll
-      for (int v = 0; v < 4; v++) {
-        const float4 av = *reinterpret_cast<const float4 *>(sx + rr * kLd + 4 * q + 4 * v);
-        const float4 bv = *reinterpret_cast<const float4 *>(sy + rr * kLd + 4 * q + 4 * v);
-        a[4 * v] = av.x, a[4 * v + 1] = av.y, a[4 * v + 2] = av.z, a[4 * v + 3] = av.w;
-        b[4 * v] = bv.x, b[4 * v + 1] = bv.y, b[4 * v + 2] = bv.z, b[4 * v + 3] = bv.w;
-      }
-      float m[5][4];
-#pragma unroll
-      for (int o = 0; o < 4; o++) {
-#pragma unroll
-        for (int t = 0; t < 5; t++) m[t][o] = 0.f;
-#pragma unroll
-        for (int k = 0; k < kTaps; k++) {
-          const float p = a[o + k], s = b[o + k], g = G.g[k];
-          m[0][o] = fmaf(g, p, m[0][o]);
-          m[1][o] = fmaf(g, s, m[1][o]);
-          m[2][o] = fmaf(g, p * p, m[2][o]);
-          m[3][o] = fmaf(g, s * s, m[3][o]);
-          m[4][o] = fmaf(g, p * s, m[4][o]);
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < 5; t++)
-        *reinterpret_cast<float4 *>(&mom[t][rr * kTileCols + 4 * q]) = make_float4(m[t][0], m[t][1], m[t][2], m[t][3]);
-    }
-    __syncthreads();
-    // vertical pass: rows rg..rg+7 of column col, from moment rows rg..rg+17
     float acc[kRowsPerLane][5];
-#pragma unroll
-    for (int o = 0; o < kRowsPerLane; o++)
-#pragma unroll
-      for (int t = 0; t < 5; t++) acc[o][t] = 0.f;
-#pragma unroll
-    for (int i = 0; i < kRowsPerLane + 2 * kHalo; i++) {
-      float v[5];
-#pragma unroll
-      for (int t = 0; t < 5; t++) v[t] = mom[t][(rg + i) * kTileCols + col];
-#pragma unroll
-      for (int o = 0; o < kRowsPerLane; o++) {
-        if (i - o >= 0 && i - o < kTaps) {
-#pragma unroll
-          for (int t = 0; t < 5; t++) acc[o][t] = fmaf(G.g[i - o], v[t], acc[o][t]);
-        }
-      }
-    }
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    tile_moments(sx, sy, mom, G, rg, col, acc);
 #pragma unroll
     for (int o = 0; o < kRowsPerLane; o++) {
       const int r = rg + o;
       if (r0 + r < G.h && c0 + col < G.w) {
-        const float mu1 = acc[o][0], mu2 = acc[o][1];
-        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
-        const float s1 = acc[o][2] - mu1_sq, s2 = acc[o][3] - mu2_sq, s12 = acc[o][4] - mu1_mu2;
-        float map;
-        if (FINAL)
-          map = ((2.f * mu1_mu2 + C1) * (2.f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
-        else
-          map = (2.f * s12 + C2) / (s1 + s2 + C2);
+        const float map = ssim_map<FINAL>(acc[o]);
         acc_s += wrow[r] * (double)map;
         if (FIRST) {
           const int centre = (r + kHalo) * kLd + col + kHalo;

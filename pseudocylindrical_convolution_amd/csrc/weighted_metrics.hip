@@ -12,9 +12,17 @@
 //                                 WIDE: the four pixels are consecutive and move as 16-byte loads and one 16-byte store;
 //                                 otherwise the lane takes the forward's four pixels with 4-byte accesses.  An element's
 //                                 arithmetic does not depend on which lane holds it, so the two forms give the same bits.
+//   weighted_ssim_kernel          the SSIM map weighed by the plane (pconv_weighted_ssim_f32): a workgroup takes one tile of 32
+//                                 rows x 64 columns of one plane through the tile passes of ssim_tile.h -- the passes, and so
+//                                 the map bits, of sphere_metrics.hip's ms_forward_kernel -- then every lane reads the weights of
+//                                 its 8 rows of one column straight from global memory (a wave reads 64 consecutive doubles per
+//                                 row; nothing of the plane is staged, so the workgroup keeps the 80 KB of LDS that lets two
+//                                 share a CU) and adds w * map in fp64; a wave butterfly and the four waves in order give the
+//                                 tile's partial.  weighted_sum_kernel adds a plane's tile partials as it adds chunk partials.
 // The tree's last six steps stay inside wave 0 (lane l and lane l + s, s <= 32, are both lanes of it), so they are register
 // exchanges of the same fp64 additions in the same order: two LDS steps and two barriers instead of eight.
 #include "sphere_sampler.h"
+#include "ssim_tile.h"
 
 namespace {
 
@@ -97,6 +105,46 @@ __global__ __launch_bounds__(kBlock) void weighted_sum_kernel(const double *__re
   if (threadIdx.x == 0) out[blockIdx.x] = total / W;
 }
 
+// one workgroup per (tile, plane).  Lane (column col, row group rg) adds w * map of its rows rg .. rg + 7 that lie in the
+// plane, ascending, from +0; the 64 columns of a row group by the butterfly m = 32 .. 1 (v + partner: every lane of the
+// wave ends with the same bits); the four row groups ascending.  G.c is 1: blockIdx.y counts planes
+__global__ __launch_bounds__(ssim::kBlock, 2) void weighted_ssim_kernel(const float *__restrict__ x, const float *__restrict__ y,
+                                                                       const double *__restrict__ weights, ssim::WsGeom G,
+                                                                       double *__restrict__ partials) {
+  using namespace ssim;
+  __shared__ __attribute__((aligned(16))) float sx[kInRows * kLd];
+  __shared__ __attribute__((aligned(16))) float sy[kInRows * kLd];
+  __shared__ __attribute__((aligned(16))) float mom[5][kPlane];
+  __shared__ double red[kWaves];
+  const int tid = threadIdx.x, tile = blockIdx.x, plane = blockIdx.y;
+  const int ty = tile / G.tiles_x;
+  const int r0 = ty * kTileRows, c0 = (tile - ty * G.tiles_x) * kTileCols;
+  const int col = tid & 63, rg = (tid >> 6) * kRowsPerLane;
+  stage_tile(plane_of(x, G, plane, 0), plane_of(y, G, plane, 0), G, 0, r0, c0, sx, sy);
+  float acc[kRowsPerLane][5];
+  tile_moments(sx, sy, mom, G, rg, col, acc);
+  // the eight weights are asked for before the first is used: a pixel outside the plane reads none and adds nothing
+  double wt[kRowsPerLane];
+#pragma unroll
+  for (int o = 0; o < kRowsPerLane; o++) {
+    const int r = r0 + rg + o;
+    wt[o] = r < G.h && c0 + col < G.w ? weights[(unsigned)(r * G.w + c0 + col)] : 0.0;
+  }
+  double sum = 0.0;
+#pragma unroll
+  for (int o = 0; o < kRowsPerLane; o++)
+    if (r0 + rg + o < G.h && c0 + col < G.w) sum = sum + __dmul_rn(wt[o], (double)ssim_map<true>(acc[o]));
+  sum = wave_sum(sum);
+  if (col == 0) red[tid >> 6] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    double s = red[0];
+#pragma unroll
+    for (int k = 1; k < kWaves; k++) s = s + red[k];
+    partials[(long long)plane * G.tiles + tile] = s;
+  }
+}
+
 __device__ __forceinline__ float grad_of(double g2, double w, double W, float x, float y) {
   const float k = (float)(__dmul_rn(g2, w) / W);
   return __fmul_rn(k, __fsub_rn(y, x));
@@ -150,20 +198,28 @@ int shape_ok(const char *what, int n, int c, int h, int w, double W) {
   return PCONV_OK;
 }
 
-int forward(const char *what, bool u8, const void *x, const void *y, const double *weights, double W, int n, int c, int h, int w,
-            void *workspace, double *out, void *stream) {
+// the checks every forward shares; per_plane: the partials of one plane in the workspace
+int forward_ok(const char *what, bool u8, const void *x, const void *y, const double *weights, double W, int n, int c, int h,
+               int w, const void *workspace, const double *out, long long per_plane) {
   PCONV_REQUIRE(x && y && weights && workspace && out, "%s: null pointer", what);
   if (shape_ok(what, n, c, h, w, W) != PCONV_OK) return PCONV_EINVAL;
   PCONV_REQUIRE(!u8 || c == 3, "%s: uint8 frames are (n, H, W, 3): C = %d", what, c);
   if (aligned_ok(what, u8 ? 0 : addr(x) | addr(y), "x and y", addr(weights) | addr(workspace) | addr(out),
                  "the weights, the workspace and out") != PCONV_OK)
     return PCONV_EINVAL;
-  const long long pixels = (long long)h * w, planes = (long long)n * c, chunks = (pixels + kChunk - 1) / kChunk;
-  const long long bin = (u8 ? 1LL : 4LL) * planes * pixels, bwt = 8LL * pixels, bw = 8LL * planes * chunks, bo = 8LL * planes;
+  const long long pixels = (long long)h * w, planes = (long long)n * c;
+  const long long bin = (u8 ? 1LL : 4LL) * planes * pixels, bwt = 8LL * pixels, bw = 8LL * planes * per_plane, bo = 8LL * planes;
   PCONV_REQUIRE(!overlap(out, bo, x, bin) && !overlap(out, bo, y, bin) && !overlap(out, bo, weights, bwt) &&
                     !overlap(workspace, bw, x, bin) && !overlap(workspace, bw, y, bin) && !overlap(workspace, bw, weights, bwt) &&
                     !overlap(workspace, bw, out, bo),
                 "%s: out and the workspace must not alias an input or each other", what);
+  return PCONV_OK;
+}
+
+int forward(const char *what, bool u8, const void *x, const void *y, const double *weights, double W, int n, int c, int h, int w,
+            void *workspace, double *out, void *stream) {
+  const long long pixels = (long long)h * w, planes = (long long)n * c, chunks = (pixels + kChunk - 1) / kChunk;
+  if (forward_ok(what, u8, x, y, weights, W, n, c, h, w, workspace, out, chunks) != PCONV_OK) return PCONV_EINVAL;
   const dim3 grid((unsigned)chunks, (unsigned)planes);  // chunks <= 2^19
   double *partials = static_cast<double *>(workspace);
   if (u8)
@@ -177,6 +233,10 @@ int forward(const char *what, bool u8, const void *x, const void *y, const doubl
   PCONV_LAUNCH_CHECK(what);
   return PCONV_OK;
 }
+
+// tiles of 32 x 64 across and down a plane of h x w (both at most 2^20, the plane below 2^29 pixels: below 2^26 tiles)
+inline int tiles_across(int w) { return (w + ssim::kTileCols - 1) / ssim::kTileCols; }
+inline long long tiles_of(int h, int w) { return (long long)tiles_across(w) * ((h + ssim::kTileRows - 1) / ssim::kTileRows); }
 
 }  // namespace
 
@@ -216,6 +276,30 @@ extern "C" int pconv_weighted_mse_backward_f32(const float *x, const float *y, c
   else
     hipLaunchKernelGGL(weighted_mse_backward_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), x, y, weights, gout, total,
                        pixels, grad);
+  PCONV_LAUNCH_CHECK(what);
+  return PCONV_OK;
+}
+
+extern "C" long long pconv_weighted_ssim_workspace_bytes(int n, int c, int h, int w) {
+  if (shape_ok("weighted_ssim_workspace_bytes", n, c, h, w, 1.0) != PCONV_OK) return PCONV_EINVAL;
+  return 8LL * n * c * tiles_of(h, w);
+}
+
+extern "C" int pconv_weighted_ssim_f32(const float *x, const float *y, const double *weights, double total, int n, int c, int h,
+                                       int w, void *workspace, double *out, void *stream) {
+  const char *what = "weighted_ssim_f32";
+  PCONV_REQUIRE(x && y && weights && workspace && out, "%s: null pointer", what);
+  if (shape_ok(what, n, c, h, w, total) != PCONV_OK) return PCONV_EINVAL;  // (before tiles_of: no count of a refused size)
+  const long long tiles = tiles_of(h, w), planes = (long long)n * c;
+  if (forward_ok(what, false, x, y, weights, total, n, c, h, w, workspace, out, tiles) != PCONV_OK) return PCONV_EINVAL;
+  ssim::WsGeom G = {};
+  G.c = 1, G.h = h, G.w = w, G.tiles_x = tiles_across(w), G.tiles = (int)tiles;
+  ssim::gaussian_taps(G.g);
+  double *partials = static_cast<double *>(workspace);
+  hipLaunchKernelGGL(weighted_ssim_kernel, dim3((unsigned)tiles, (unsigned)planes), dim3(ssim::kBlock), 0, as_stream(stream), x, y,
+                     weights, G, partials);
+  PCONV_LAUNCH_CHECK(what);
+  hipLaunchKernelGGL(weighted_sum_kernel, dim3((unsigned)planes), dim3(kBlock), 0, as_stream(stream), partials, tiles, total, out);
   PCONV_LAUNCH_CHECK(what);
   return PCONV_OK;
 }

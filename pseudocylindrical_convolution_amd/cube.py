@@ -29,11 +29,15 @@ autograd is refused: the pad kernel has no backward yet.
 Scoring (the last section of this module): `area_weights` is the solid angle of every pixel of a cube
 picture, `ws_mse` / `ws_psnr` / `ws_loss_terms` weigh two cube pictures by it (weighted_metrics.py), and `point_records` puts
 the points of a sphere_points.PointSet on the padded stack, so that `points_mse`, `s_psnr_nn`, `s_psnr_i` and `cpp_psnr` read
-cube and ERP pictures in any mix at the same points of the sphere, with no conversion in between.
+cube and ERP pictures in any mix at the same points of the sphere, with no conversion in between.  `ws_ssim` is the
+structural figure: every face continued by SSIM_PAD = 5 pixels, the radius of the SSIM window (`pad` takes a depth), and
+the padded stacks scored by weighted_metrics.ssim with the ring weighted zero, so that a window at a face edge sees the
+neighbouring face and no window of a weighted pixel reads outside its own padded face.
 
 Limits.  The ring is bilinear and one level deep, so within 3 pixels of a face edge the way back reads a slightly softer
 continuation than the sphere itself.  For "eac" the extended plane ends before its horizon: |s| and |t| of a ring pixel
-are held at 7/4, which only faces of a <= 6 reach.  ss is chosen for the face centre / the equator.
+are held at 7/4, which only faces of a <= 6 reach (at depth 5, ws_ssim's: a <= 11).  ss is chosen for the face centre /
+the equator.  ws_ssim is forward only, has no multi-scale form, and claims no equality with 360Lib's figure.
 """
 import collections
 import functools
@@ -49,10 +53,12 @@ from .PCONV_operator import backend
 PHASES = erp_rotate.PHASES
 KINDS = {"cmp": 1, "eac": 2}        # PCONV_CUBE_CMP, PCONV_CUBE_EAC: the container's code too
 LAYOUTS = {"faces": 0, "6x1": 1, "3x2": 2}   # the container's code
-PAD = 3                             # PCONV_CUBE_PAD
+PAD = 3                             # PCONV_CUBE_PAD: the continuation of the way back to ERP and of the point records
+SSIM_PAD = 5                        # the continuation of ws_ssim: the radius of the 11-tap SSIM window
+MAX_DEPTH = 8                       # PCONV_CUBE_MAX_DEPTH
 MAX_FACE = 9453                     # PCONV_CUBE_MAX_FACE: 24 (a + 6)^2 < 2^31
 MAX_SS = viewport.MAX_SS
-RING_LIMIT = 1.75                   # |s|, |t| of an "eac" ring pixel are held here (faces of a <= 6 only)
+RING_LIMIT = 1.75                   # |s|, |t| of an "eac" ring pixel are held here (depth 3: faces of a <= 6; 5: a <= 11)
 FACE_NAMES = "FRBLUD"
 # (6, 3, 3): forward, right, up of each face
 FACES = np.array([[[1, 0, 0], [0, 1, 0], [0, 0, 1]],
@@ -243,51 +249,62 @@ def to_erp_map_numpy(kind, a, h, w, ss):
     return np.stack([qu, qv], axis=2).astype(np.int32)
 
 
-def ring_pixels(a):
-    """(R, Q) int64 arrays of 12 a + 36 elements: the pixels of a padded face outside its interior, in ring order (row
-    after row, column after column)"""
+def check_depth(a, depth=PAD):
+    """the checked (a, depth) of a continuation: depth in 1 .. MAX_DEPTH, the padded stack 24 (a + 2 depth)^2 below 2^31
+    bytes"""
     a = check_face(a)
-    A = a + 2 * PAD
+    if int(depth) != depth or not 1 <= int(depth) <= MAX_DEPTH:
+        raise PconvError("cube: a depth of %r is outside 1 .. %d" % (depth, MAX_DEPTH))
+    if 24 * (a + 2 * int(depth)) ** 2 >= 1 << 31:
+        raise PconvError("cube: a face size of %d continued by %d: the padded stack is 2^31 bytes or more" % (a, depth))
+    return a, int(depth)
+
+
+def ring_pixels(a, depth=PAD):
+    """(R, Q) int64 arrays of 4 depth (a + depth) elements (12 a + 36 at depth 3): the pixels of a padded face outside
+    its interior, in ring order (row after row, column after column)"""
+    a, depth = check_depth(a, depth)
+    A = a + 2 * depth
     outside = np.ones((A, A), dtype=bool)
-    outside[PAD:PAD + a, PAD:PAD + a] = False
+    outside[depth:depth + a, depth:depth + a] = False
     return np.nonzero(outside)
 
 
-def ring_directions(kind, a):
-    """float64 (3, 6, 12 a + 36): the direction of every ring pixel, on its own face's extended plane"""
-    R, Q = ring_pixels(a)
-    s = 2.0 * ((Q - PAD) + 0.5) / a - 1.0
-    t = 1.0 - 2.0 * ((R - PAD) + 0.5) / a
+def ring_directions(kind, a, depth=PAD):
+    """float64 (3, 6, 4 depth (a + depth)): the direction of every ring pixel, on its own face's extended plane"""
+    R, Q = ring_pixels(a, depth)
+    s = 2.0 * ((Q - depth) + 0.5) / a - 1.0
+    t = 1.0 - 2.0 * ((R - depth) + 0.5) / a
     if _kind(kind) == "eac":
         s, t = np.clip(s, -RING_LIMIT, RING_LIMIT), np.clip(t, -RING_LIMIT, RING_LIMIT)
     return np.stack([direction(kind, f, s, t) for f in range(6)], axis=1)
 
 
-def ring_coordinates(kind, a):
-    """(g, u', v') (6, 12 a + 36): the face each ring pixel's direction falls on and the position there, clamped to
-    [0, a - 1]"""
-    g, u, v = face_position(kind, a, ring_directions(kind, a))
+def ring_coordinates(kind, a, depth=PAD):
+    """(g, u', v') (6, 4 depth (a + depth)): the face each ring pixel's direction falls on and the position there, clamped
+    to [0, a - 1]"""
+    g, u, v = face_position(kind, a, ring_directions(kind, a, depth))
     return g, np.clip(u, 0.0, a - 1.0), np.clip(v, 0.0, a - 1.0)
 
 
 @functools.lru_cache(maxsize=8)
-def _pad_table(kind, a):
-    g, u, v = ring_coordinates(kind, a)
+def _pad_table(kind, a, depth=PAD):
+    g, u, v = ring_coordinates(kind, a, depth)
     table = np.stack([g, np.rint(u * PHASES).astype(np.int64), np.rint(v * PHASES).astype(np.int64)], axis=2)
     table = np.ascontiguousarray(table.reshape(-1, 3).astype(np.int32))
     table.setflags(write=False)
     return table
 
 
-def pad_table(kind, a):
-    """int32 (6 (A^2 - a^2), 3), read-only: (g, qu, qv) of every ring pixel, face after face in ring order, built in
-    float64 on the host.  Cached per (kind, a)"""
-    return _pad_table(_kind(kind), check_face(a))
+def pad_table(kind, a, depth=PAD):
+    """int32 (6 (A^2 - a^2), 3), A = a + 2 depth, read-only: (g, qu, qv) of every ring pixel, face after face in ring
+    order, built in float64 on the host.  Cached per (kind, a, depth)"""
+    return _pad_table(_kind(kind), *check_depth(a, depth))
 
 
 @functools.lru_cache(maxsize=4)
-def _pad_table_on(kind, a, device):
-    return torch.from_numpy(np.array(_pad_table(kind, a))).to(device)
+def _pad_table_on(kind, a, device, depth=PAD):
+    return torch.from_numpy(np.array(_pad_table(kind, a, depth))).to(device)
 
 
 def _device(device):
@@ -297,9 +314,10 @@ def _device(device):
     return device
 
 
-def pad_table_on(kind, a, device=None):
+def pad_table_on(kind, a, device=None, depth=PAD):
     """pad_table as a tensor on `device`, uploaded once (the last 4 kept); do not write to it"""
-    return _pad_table_on(_kind(kind), check_face(a), str(_device(device)))
+    a, depth = check_depth(a, depth)
+    return _pad_table_on(_kind(kind), a, str(_device(device)), depth)
 
 
 # ---- layouts ----
@@ -394,18 +412,18 @@ def to_erp_map(kind, a, h, w, ss, device=None):
 
 # ---- the face continuation ----
 
-def pad_torch(y, table):
+def pad_torch(y, table, depth=PAD):
     """the face continuation in torch, float32 operation by operation, on any device (the CPU path and the kernel's
-    twin): the face stack (n, C, 6a, a) and the int32 (6 (A^2 - a^2), 3) table -> (n, C, 6A, A)"""
-    a = _check_stack(y, "cube pad")
-    A = a + 2 * PAD
+    twin): the face stack (n, C, 6a, a) and the int32 (6 (A^2 - a^2), 3) table of `depth` -> (n, C, 6A, A), A = a + 2 depth"""
+    a, depth = check_depth(_check_stack(y, "cube pad"), depth)
+    A = a + 2 * depth
     ring = A * A - a * a
     if table.dtype != torch.int32 or tuple(table.shape) != (6 * ring, 3) or table.device != y.device:
         raise PconvError("cube pad: the table must be int32 (%d, 3) on the faces' device, got %s %s on %s"
                          % (6 * ring, table.dtype, tuple(table.shape), table.device))
     n, c = y.shape[:2]
     out = torch.zeros((n, c, 6, A, A), dtype=torch.float32, device=y.device)
-    out[:, :, :, PAD:PAD + a, PAD:PAD + a] = y.reshape(n, c, 6, a, a)
+    out[:, :, :, depth:depth + a, depth:depth + a] = y.reshape(n, c, 6, a, a)
     rec = table.long()
     g = rec[:, 0].clamp(0, 5)
     x0, y0 = (rec[:, 1] >> 8).clamp(0, a - 1), (rec[:, 2] >> 8).clamp(0, a - 1)
@@ -416,20 +434,21 @@ def pad_torch(y, table):
     top = x00 + fx * (x01 - x00)
     bot = x10 + fx * (x11 - x10)
     value = top + fy * (bot - top)
-    R, Q = (torch.from_numpy(v).to(y.device) for v in ring_pixels(a))
+    R, Q = (torch.from_numpy(v).to(y.device) for v in ring_pixels(a, depth))
     face = torch.arange(6, device=y.device).repeat_interleave(ring)
     out[:, :, face, R.repeat(6), Q.repeat(6)] = value
     return out.reshape(n, c, 6 * A, A)
 
 
-def pad_numpy(y, table):
-    """pad_torch in numpy, float32 operation by operation: a float32 array (n, C, 6a, a) and the int32 table -> (n, C,
-    6A, A)"""
+def pad_numpy(y, table, depth=PAD):
+    """pad_torch in numpy, float32 operation by operation: a float32 array (n, C, 6a, a) and the int32 table of `depth`
+    -> (n, C, 6A, A)"""
     y, rec = np.asarray(y, dtype=np.float32), np.asarray(table).astype(np.int64)
     n, c, _, a = y.shape
-    A = a + 2 * PAD
+    a, depth = check_depth(a, depth)
+    A = a + 2 * depth
     out = np.zeros((n, c, 6, A, A), dtype=np.float32)
-    out[:, :, :, PAD:PAD + a, PAD:PAD + a] = y.reshape(n, c, 6, a, a)
+    out[:, :, :, depth:depth + a, depth:depth + a] = y.reshape(n, c, 6, a, a)
     g = np.clip(rec[:, 0], 0, 5)
     x0, y0 = np.clip(rec[:, 1] >> 8, 0, a - 1), np.clip(rec[:, 2] >> 8, 0, a - 1)
     x1, y1 = np.minimum(x0 + 1, a - 1), np.minimum(y0 + 1, a - 1)
@@ -438,23 +457,27 @@ def pad_numpy(y, table):
     r0, r1 = g * a + y0, g * a + y1
     top = y[:, :, r0, x0] + fx * (y[:, :, r0, x1] - y[:, :, r0, x0])
     bot = y[:, :, r1, x0] + fx * (y[:, :, r1, x1] - y[:, :, r1, x0])
-    R, Q = ring_pixels(a)
+    R, Q = ring_pixels(a, depth)
     out[:, :, np.repeat(np.arange(6), R.size), np.tile(R, 6), np.tile(Q, 6)] = top + fy * (bot - top)
     return out.reshape(n, c, 6 * A, A)
 
 
-def pad(y, kind):
-    """the face stack (n, C, 6a, a) continued by PAD pixels across every face edge: (n, C, 6A, A).  The HIP kernel for
-    GPU tensors, pad_torch for CPU tensors: the same bits"""
+def pad(y, kind, depth=PAD):
+    """the face stack (n, C, 6a, a) continued by `depth` pixels (1 .. MAX_DEPTH, by default PAD) across every face edge:
+    (n, C, 6A, A), A = a + 2 depth.  The HIP kernel for GPU tensors (pconv_cube_pad_f32 at depth PAD, otherwise
+    pconv_cube_pad_depth_f32), pad_torch for CPU tensors: the same bits"""
     kind = _kind(kind)
-    a = _check_stack(y, "cube pad")
-    table = _pad_table_on(kind, a, str(y.device))
+    a, depth = check_depth(_check_stack(y, "cube pad"), depth)
+    table = _pad_table_on(kind, a, str(y.device), depth)
+    if y.is_cuda and depth != PAD:
+        from . import _metric_ops
+        return _metric_ops.cube_pad_depth(y.contiguous(), table, depth)
     if y.is_cuda:
         ops = backend.ops()
         if not hasattr(ops, "cube_pad_f32"):
             raise PconvError("cube: the active backend has no cube_pad_f32 kernel for a GPU tensor")
         return ops.cube_pad_f32(y.contiguous(), table)
-    return pad_torch(y, table)
+    return pad_torch(y, table, depth)
 
 
 # ---- the conversions ----
@@ -617,6 +640,59 @@ def ws_loss_terms(x, y, spec):
     from . import weighted_metrics
     sp = _spec(spec)
     return weighted_metrics.loss_terms(x, y, weight_plane(sp, _picture_face(x, sp)))
+
+
+# WS-SSIM.  An SSIM window is 11 x 11 pixels of a plane, and a cube picture is six planes that are neighbours on the
+# sphere, not in any layout.  So both pictures are unpacked to face stacks and every face is continued by SSIM_PAD = 5
+# pixels, the window's radius (`pad` at depth 5); the padded stacks (n, C, 6A, A), A = a + 10, are scored by
+# weighted_metrics.ssim with a plane that holds face_weights in every interior and zero on every ring.  The ring is as deep
+# as the window's radius, so the window of an interior pixel never leaves its own padded face: the zero padding of the
+# plane's borders and the neighbouring face's ring in the stack are read by ring pixels' windows only, and those weigh
+# zero.  What a window sees beyond a face edge is the neighbouring face, read bilinearly.
+
+@functools.lru_cache(maxsize=8)
+def _ssim_plane(kind, a, rule):
+    from . import weighted_metrics
+    A = a + 2 * SSIM_PAD
+    plane = np.zeros((6, A, A), dtype=np.float64)
+    plane[:, SSIM_PAD:SSIM_PAD + a, SSIM_PAD:SSIM_PAD + a] = face_weights(kind, a, rule)
+    return weighted_metrics.WeightPlane(plane.reshape(6 * A, A))
+
+
+def ssim_plane(kind, a, rule="solid-angle"):
+    """the cached weighted_metrics.WeightPlane (6A, A), A = a + 2 SSIM_PAD, of ws_ssim: face_weights(kind, a, rule) in the
+    interior of every padded face, zero on every ring"""
+    if rule not in RULES:
+        raise PconvError("cube: rule must be one of %s, got %r" % (RULES, rule))
+    return _ssim_plane(_kind(kind), check_depth(a, SSIM_PAD)[0], rule)
+
+
+def ws_ssim_planes(x, y, spec, rule="solid-angle"):
+    """float64 CPU tensor (n, C): the WS-SSIM of every plane of two cube pictures of one spec and face size, float32 (n, C,
+    height, width) or uint8 (n, height, width, 3): both unpacked to face stacks, every face continued by SSIM_PAD pixels
+    from its neighbours (`pad`), the SSIM map of the padded stacks weighed by each interior pixel's solid angle
+    (weighted_metrics.ssim on ssim_plane).  GPU tensors: the HIP kernels; CPU tensors: the twins (float64 map).  Forward
+    only: a tensor that requires grad is refused.
+    Limits: the ring is bilinear and one level deep, as for to_erp, so within 5 pixels of an edge a window reads a slightly
+    softer neighbour than the sphere itself; equality with 360Lib's WS-SSIM is not claimed; no multi-scale form, no 4:2:0"""
+    from . import weighted_metrics
+    sp = _spec(spec)
+    if not (torch.is_tensor(x) and torch.is_tensor(y)) or x.shape != y.shape or x.dtype != y.dtype or x.device != y.device:
+        raise PconvError("cube ws_ssim: two cube pictures of one kind, layout, face size, type and device expected, got %s and %s"
+                         % tuple("%s %s on %s" % (t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__
+                                 for t in (x, y)))
+    if x.requires_grad or y.requires_grad:
+        raise PconvError("cube ws_ssim: a tensor that requires grad: the weighted SSIM and the face continuation are forward only; "
+                         "detach the pictures")
+    a = _picture_face(x, sp)
+    stacks = [pad(unpack(weighted_metrics._as_planes(t).float(), sp.layout).contiguous(), sp.kind, SSIM_PAD) for t in (x, y)]
+    return weighted_metrics.ssim(stacks[0], stacks[1], ssim_plane(sp.kind, a, rule))
+
+
+def ws_ssim(x, y, spec, rule="solid-angle"):
+    """float64 (n,) WS-SSIM of each cube picture: the mean over the channels of ws_ssim_planes"""
+    from . import weighted_metrics
+    return weighted_metrics.channel_mean(ws_ssim_planes(x, y, spec, rule))
 
 
 def point_directions(pointset):

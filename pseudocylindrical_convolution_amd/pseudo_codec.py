@@ -14,7 +14,8 @@ Differences from the reference, all additive:
     same points of the sphere) and, for a file coded with --code-size, the same three of the reconstruction at the coded
     size against the source at its own;
   * --test / --rd --projection --cube-metrics add CUBE-WS-PSNR and CUBE-S-PSNR-NN / -I / CUBE-CPP-PSNR: the cube picture
-    against the reconstructed cube picture, both read as cube pictures (cube.py, weighted_metrics.py);
+    against the reconstructed cube picture, both read as cube pictures (cube.py, weighted_metrics.py); --cube-ssim adds
+    CUBE-WS-SSIM of the same pair (cube.ws_ssim: every face continued from its neighbours by the window's radius);
   * --yuv / --yuv-out code raw YUV 4:2:0 files (yuv.py: yuv420p, nv12, yuv420p10le), one code file per frame, the
     colour conversion on the GPU; --test --ws then adds WS-PSNR-Y/U/V.  The stream and the container are the RGB ones:
     the decoder is told the pixel format on the command line;
@@ -648,6 +649,7 @@ def _report(rows, lines):
 _CUBE = 'CUBE-PSNR:{:.2f}dB'
 _CUBE_WS = 'CUBE-WS-PSNR:{:.2f}dB'
 _CUBE_SPHERE = 'CUBE-S-PSNR-NN:{:.2f}dB, CUBE-S-PSNR-I:{:.2f}dB, CUBE-CPP-PSNR:{:.2f}dB'
+_CUBE_SSIM = 'CUBE-WS-SSIM:{:.4f}'
 
 
 def _cube_picture(img, geometry, name):
@@ -684,26 +686,41 @@ def _cube_metrics(picture, back, projection):
     return figures
 
 
+def _cube_ssim(picture, back, projection):
+    """--cube-ssim: CUBE-WS-SSIM of the original cube picture against the reconstructed cube picture (cube.ws_ssim: the
+    faces continued from their neighbours by the SSIM window's radius, every pixel weighted by its solid angle); the line
+    is printed"""
+    from . import cube
+    figure = cube.ws_ssim(picture.contiguous(), back.contiguous(), projection)[0].item()
+    print(' ' + _CUBE_SSIM.format(figure))
+    return figure
+
+
 def _plain_psnr(x, y):
     mse = ((x - y).double() ** 2).mean().item()
     return 10.0 * math.log10(1.0 / mse) if mse > 0 else float("inf")
 
 
-def _cube_lines(rows, cubes, on_cube=()):
+def _cube_lines(rows, cubes, on_cube=(), on_ssim=()):
     """--projection: the format of the average's CUBE-PSNR line; the figures join the rows as their last column when
     every file holds a cube picture.  on_cube (--cube-metrics: _cube_metrics' four figures per image): four more columns
-    and two more lines"""
+    and two more lines.  on_ssim (--cube-ssim: _cube_ssim's figure per image): one more column and line, the last"""
     if not cubes or any(c is None for c in cubes):
         return []
     rows[:] = [r + (c,) for r, c in zip(rows, cubes)]
-    if not on_cube:
-        return [_CUBE]
-    rows[:] = [r + tuple(m) for r, m in zip(rows, on_cube)]
-    return [_CUBE, _CUBE_WS, _CUBE_SPHERE]
+    lines = [_CUBE]
+    if on_cube:
+        rows[:] = [r + tuple(m) for r, m in zip(rows, on_cube)]
+        lines += [_CUBE_WS, _CUBE_SPHERE]
+    if on_ssim:
+        rows[:] = [r + (m,) for r, m in zip(rows, on_ssim)]
+        lines += [_CUBE_SSIM]
+    return lines
 
 
 def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, raw=False,
-                      ws=False, rotation=None, ms_ssim=False, vp=None, sphere=False, projection=None, cube_metrics=False):
+                      ws=False, rotation=None, ms_ssim=False, vp=None, sphere=False, projection=None, cube_metrics=False,
+                      cube_ssim=False):
     """reference: pseudo_codec.py:263-290.  sphere=True (--sphere): three more columns and one more line after everything
     else, SphereScore's S-PSNR-NN / S-PSNR-I / CPP-PSNR of the source against the end-to-end reconstruction (the float
     tensors, both at the source size); a file coded at a reduced size and not rotated gets a second line, `(coded size)`,
@@ -722,13 +739,14 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
     PSNR of the cube picture against the reconstruction converted back.  projection (--test --projection): the spec every
     file must record, a ContainerError otherwise.  cube_metrics (--cube-metrics, with projection): after the CUBE-PSNR
     line two more lines and four more columns, _cube_metrics' figures of the cube picture against the reconstructed cube
-    picture"""
+    picture.  cube_ssim (--cube-ssim, with projection): after all of these one more line and a last column, _cube_ssim's
+    CUBE-WS-SSIM of the same pair"""
     t1, dev, model_idx, mse = _decoder_for(code_list, model_idx, mse, device_id, raw)
     metrics = ViewportMetrics(device_id)
     spherical = SphericalMetrics(device_id) if ws else None
     scorer, texts = (ViewportScore(device_id, None if vp is True else vp), []) if vp else (None, [])
     on_sphere, coded = SphereScore(device_id) if sphere else None, []
-    rows, cubes, on_cube = [], [], []
+    rows, cubes, on_cube, on_ssim = [], [], [], []
     for fc, fn in zip(code_list, img_list):
         rec, geometry = _decode_file(t1, fc, model_idx, mse, height, width, raw)
         if rotation is not None and geometry.rotation != tuple(rotation):
@@ -765,12 +783,15 @@ def decoding_and_test(code_list, img_list, model_idx=0, mse=True, device_id=0, h
             print(' ' + _CUBE.format(cube_psnr))
             if cube_metrics:
                 on_cube.append(_cube_metrics(*cube_pair, geometry.projection))
+            if cube_ssim:
+                on_ssim.append(_cube_ssim(*cube_pair, geometry.projection))
     return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp)
-                   + _sphere_lines(rows, coded) + _cube_lines(rows, cubes, on_cube))
+                   + _sphere_lines(rows, coded) + _cube_lines(rows, cubes, on_cube, on_ssim))
 
 
 def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, width=1024, native=False, ws=False,
-                    code_size=None, rotation=None, ms_ssim=False, vp=None, sphere=False, projection=None, cube_metrics=False):
+                    code_size=None, rotation=None, ms_ssim=False, vp=None, sphere=False, projection=None, cube_metrics=False,
+                    cube_ssim=False):
     """--rd: what encoding() + decoding_and_test() report for the images, without a file in between.  The rate is
     the code length of the CDF rows the coder would get (rate.py: within a few bits of the stream), the
     reconstruction is the synthesis of the encoder's own symbols -- what the entropy decoder would hand back.
@@ -784,7 +805,8 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     with code_size and no rotation the three of the coded-size line, as in decoding_and_test.
     projection (--projection): every image is a cube picture taken at its own size; the lines are computed on the ERP
     frame the codec saw, bpp over the cube picture's pixels, and CUBE-PSNR is the last line and column, as in
-    decoding_and_test; cube_metrics (--cube-metrics) adds _cube_metrics' two lines and four columns after it."""
+    decoding_and_test; cube_metrics (--cube-metrics) adds _cube_metrics' two lines and four columns after it, cube_ssim
+    (--cube-ssim) _cube_ssim's line and column after those."""
     from .engine import CodecEngine
     from . import rate
     (enc, dev), (dec, _) = _load("encoder", model_idx, mse, device_id), _load("decoder", model_idx, mse, device_id)
@@ -793,7 +815,7 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
     spherical = SphericalMetrics(device_id) if ws else None
     scorer, texts = (ViewportScore(device_id, None if vp is True else vp), []) if vp else (None, [])
     on_sphere, coded = SphereScore(device_id) if sphere else None, []
-    rows, cubes, on_cube = [], [], []
+    rows, cubes, on_cube, on_ssim = [], [], [], []
     for fn in img_list:
         img = read_image(fn)
         if not native and code_size is None and projection is None:
@@ -831,8 +853,10 @@ def rate_distortion(img_list, model_idx=0, mse=True, device_id=0, height=512, wi
             print(' ' + _CUBE.format(cubes[-1]))
             if cube_metrics:
                 on_cube.append(_cube_metrics(picture, back, projection))
+            if cube_ssim:
+                on_ssim.append(_cube_ssim(picture, back, projection))
     return _report(rows, (([_VIEWPORT, _WS] + [_WS_MS] * bool(ms_ssim)) if ws else [_VIEWPORT]) + [_vp_line(texts)] * bool(vp)
-                   + _sphere_lines(rows, coded) + _cube_lines(rows, cubes, on_cube))
+                   + _sphere_lines(rows, coded) + _cube_lines(rows, cubes, on_cube, on_ssim))
 
 
 def _yuv_rgb(frames, h, w, yuv_opts, dev):
@@ -1023,6 +1047,16 @@ def _cube_metrics_flag(parser, args, projection):
     return args.cube_metrics
 
 
+def _cube_ssim_flag(parser, args, projection):
+    """the checks of --cube-ssim, those of --cube-metrics: it goes with --projection on --test or --rd"""
+    if args.cube_ssim:
+        if projection is None:
+            parser.error("--cube-ssim goes with --projection: it scores cube pictures as cube pictures")
+        if not (args.test or args.rd) or args.enc or args.dec:
+            parser.error("--cube-ssim goes with --test or --rd")
+    return args.cube_ssim
+
+
 def _view_flags(parser, args):
     """the checks of --view / --view-size / --view-out[-file] and --vp; returns (view, view size, vp): view the four
     angles in degrees or None, view size (vh, vw) or None, vp None, True (the default size) or (vh, vw).  Contradictions
@@ -1142,6 +1176,11 @@ def main(argv=None):
                              'cube pixel weighted by its solid angle) and CUBE-S-PSNR-NN / CUBE-S-PSNR-I / CUBE-CPP-PSNR: '
                              'the original cube picture against the reconstructed one, both read as cube pictures at the '
                              'same points of the sphere, with no conversion to ERP in between')
+    parser.add_argument('--cube-ssim', action='store_true', default=False,
+                        help='Testing (--test / --rd) with --projection: after every other cube line also report '
+                             'CUBE-WS-SSIM, the SSIM of the original cube picture against the reconstructed one with every '
+                             'face continued from its neighbours by the radius of the SSIM window and every pixel weighted '
+                             'by its solid angle.  Independent of --cube-metrics')
     parser.add_argument('--raw', action='store_true', default=False,
                         help='Decoding: never look for a container header (size and model from the flags)')
     parser.add_argument('--ws', action='store_true', default=False,
@@ -1181,6 +1220,7 @@ def main(argv=None):
     rotation = _rotate_flag(parser, args)
     projection = _projection_flag(parser, args)
     cube_metrics = _cube_metrics_flag(parser, args, projection)
+    cube_ssim = _cube_ssim_flag(parser, args, projection)
     view, view_size, vp = _view_flags(parser, args)
     sphere = _sphere_flag(parser, args)
     yuv_call = _yuv_flags(parser, args)   # contradictory YUV flags end the run here, before anything is loaded
@@ -1216,7 +1256,7 @@ def main(argv=None):
         assert img_list is not None, 'No input images for scoring'
         rate_distortion(img_list, midx, not args.ssim, args.gpu_id, native=args.native_size, ws=args.ws,
                         code_size=code_size, rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere,
-                        projection=projection, cube_metrics=cube_metrics, **size)
+                        projection=projection, cube_metrics=cube_metrics, cube_ssim=cube_ssim, **size)
     elif args.enc:
         assert img_list is not None, 'No input images for encoding'
         assert code_list is not None, 'No code files for saving the codes'
@@ -1238,7 +1278,7 @@ def main(argv=None):
             assert len(code_list) == len(img_list), 'The number of codes and corresponding source images should be the same'
             decoding_and_test(code_list, img_list, midx, not args.ssim, args.gpu_id, raw=args.raw, ws=args.ws,
                               rotation=rotation, ms_ssim=args.ms_ssim, vp=vp, sphere=sphere, projection=projection,
-                              cube_metrics=cube_metrics, **size)
+                              cube_metrics=cube_metrics, cube_ssim=cube_ssim, **size)
 
 
 if __name__ == '__main__':

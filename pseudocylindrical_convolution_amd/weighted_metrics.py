@@ -1,5 +1,6 @@
-"""Squared error weighted by a per-pixel weight plane (include/pconv_hip.h, pconv_weighted_mse_*; csrc/
-weighted_metrics.hip): WS-PSNR for any projection whose area weights are known, and for masks.
+"""Squared error and SSIM weighted by a per-pixel weight plane (include/pconv_hip.h, pconv_weighted_mse_* and
+pconv_weighted_ssim_f32; csrc/weighted_metrics.hip): WS-PSNR and WS-SSIM for any projection whose area weights are known,
+and for masks.
 
 WS-PSNR (Sun, Lu, Yu, IEEE SPL 2017) is defined for every projection by the area its pixels cover on the sphere.
 sphere_metrics.py knows one such weight, the cosine of an ERP row; here the weights are data: a float64 (H, W) plane shared
@@ -14,12 +15,23 @@ of the same shape: `ordered_sum`), which depends on H * W alone.  A figure is 10
 Backward, of sum(gout * MSE) with respect to y:  k = ((2 gout[f][c]) w_p) / W in fp64, rounded once to fp32;
 grad = k * (y - x) in fp32.  The gradient with respect to x is the same with x and y swapped.
 
-GPU tensors go to the HIP kernels (_metric_ops.weighted_mse_*); CPU tensors to the torch twins below, which follow the
-definition operation by operation: the bits are equal.  The twins are no fallback for GPU tensors.
+SSIM, per plane (f, c) (`ssim`): map is sphere_metrics' SSIM map of the plane -- the 11-tap Gaussian of sigma 1.5 as g (x) g,
+zero padding of 5 on the borders of the H x W plane, C1 = 0.01^2, C2 = 0.03^2 --
+  SSIM[f][c] = (sum of w_p * map_p) / W
+With erp_plane(h, w) the mean over the channels is sphere_metrics' WS-SSIM.  A window knows nothing of the projection: it
+is the caller who lays the picture out so that a window's neighbourhood in the plane is its neighbourhood on the sphere
+wherever the weight is not zero (cube.ws_ssim continues every face by the window's radius and weighs the ring zero).
+The kernel computes the map in fp32 (the passes of pconv_ws_metrics_f32) and the sum in fp64 in the header's order; the
+twin `ssim_torch` is the definition in float64: the two agree to about 1e-6, not to the bit.  Forward only.
+
+GPU tensors go to the HIP kernels (_metric_ops.weighted_mse_*, weighted_ssim_device); CPU tensors to the torch twins below;
+for the squared error they follow the definition operation by operation: the bits are equal.  The twins are no fallback
+for GPU tensors.
 
 Limits.  W is supplied by the host (`WeightPlane.total`: math.fsum, the exactly rounded sum), never summed on the device.
 A weight of zero is allowed (a mask); negative or non-finite weights and a plane that sums to zero are refused when the
-plane is made.  No SSIM form: a window would need to know the projection's neighbourhoods.  No 4:2:0.
+plane is made.  The SSIM has no uint8 kernel (uint8 frames are converted first), no multi-scale form and no gradient.
+No 4:2:0.
 """
 import collections
 import math
@@ -229,6 +241,45 @@ def loss_terms(x, y, plane):
         raise PconvError("weighted loss: float32 (n, C, H, W) batches expected (uint8 frames carry no gradient), got %s %s"
                          % (x.dtype, tuple(x.shape)))
     return channel_mean(_Mse.apply(x.contiguous(), y.contiguous(), plane))
+
+
+def _ssim_operands(x, y, plane):
+    plane = _plane(plane)
+    _check(x, y, plane, "weighted ssim")
+    if x.requires_grad or y.requires_grad:
+        raise PconvError("weighted ssim: a tensor that requires grad: the weighted SSIM is forward only; detach the pictures")
+    return _as_planes(x), _as_planes(y), plane
+
+
+def ssim_torch(x, y, plane):
+    """float64 (n, C) on the batches' device: the definition in float64 torch (the CPU path of `ssim` and the reference
+    the GPU tests compare the kernel with): sphere_metrics' full SSIM map, weighed by the plane, over plane.total"""
+    a, b, plane = _ssim_operands(x, y, plane)
+    ssim_map = sphere_metrics._ssim_map(sphere_metrics._moments(a.double(), b.double(), sphere_metrics.gaussian()), True)
+    return (ssim_map * plane.on(a.device)).sum(dim=(2, 3)) / plane.total
+
+
+def ssim_device(x, y, plane):
+    """`ssim` with the result left on the batches' device: nothing waits"""
+    a, b, plane = _ssim_operands(x, y, plane)
+    if a.is_cuda:
+        if a.dtype != torch.float32:
+            raise PconvError("weighted ssim: float32 (n, C, H, W) or uint8 (n, H, W, 3) expected on a GPU, got %s" % a.dtype)
+        return _metric_ops.weighted_ssim_device(a.contiguous(), b.contiguous(), plane.on(a.device), plane.total)
+    return ssim_torch(a, b, plane)
+
+
+def ssim(x, y, plane):
+    """float64 CPU tensor (n, C): per frame and channel (sum of w_p map_p) / W, map the SSIM map of the plane.  x, y: one
+    shape, float32 (n, C, H, W) or uint8 (n, H, W, 3); plane: a WeightPlane (or float64 (H, W) weights) of the pictures'
+    size.  GPU tensors: the HIP kernel (fp32 map); CPU tensors: ssim_torch (float64).  A tensor that requires grad is
+    refused"""
+    return ssim_device(x, y, plane).cpu()
+
+
+def ssim_figure(x, y, plane):
+    """float64 (n,): the mean over the channels of `ssim`, one number per frame"""
+    return channel_mean(ssim(x, y, plane))
 
 
 def erp_plane(h, w):
