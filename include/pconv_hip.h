@@ -570,6 +570,39 @@ int pconv_cube_pad_f32(const float *in, float *out, const int32_t *table, int n,
 int pconv_cube_pad_depth_f32(const float *in, float *out, const int32_t *table, int n, int c, int a, int depth, void *stream);
 int pconv_cube_to_erp_map(int32_t *map, int kind, int a, int h, int w, int ss, void *stream);
 
+/* Ordered backward of the face continuation (csrc/cube.hip; cube.pad_backward_torch states the same definition in torch).
+ * The forward above, as a function of real numbers, copies every interior pixel and writes ring pixel i (row i of the
+ * table: face after face, in ring order) as a convex combination of four pixels of face g: with px = qu & 255, py = qv & 255
+ *   (y0, x0) weighs (256 - px)*(256 - py)/65536,  (y0, x1) px*(256 - py)/65536,
+ *   (y1, x0) (256 - px)*py/65536,                 (y1, x1) px*py/65536,
+ * g, x0, x1, y0, y1 reduced and clamped exactly as the forward does it.  The backward is the adjoint of that linear map,
+ * gin = A^T gout, gout (n, C, 6*A, A) -> gin (n, C, 6*a, a), in THIS ORDER:
+ * Destination: pixel (face f, row r, column c) of plane (n, c): one fp32 accumulator that starts from the gradient of the
+ *   pixel's own interior copy, gout[f*A + depth + r][depth + c].
+ * Entry e = 4*i + corner: ring pixel i, corner 0 .. 3 = (y0, x0), (y0, x1), (y1, x0), (y1, x1).
+ * Term: cx = (corner & 1) ? px : 256 - px;  cy = (corner & 2) ? py : 256 - py;  coef = (float)(cx*cy) * 2^-16, exact in
+ *   fp32 since cx*cy <= 2^16;  term = __fmul_rn(g_ring, coef), g_ring the value of gout at ring pixel i;  then one
+ *   __fadd_rn into the accumulator.  Never contracted.
+ * Order of the terms of a destination: e ascending.  Where x1 == x0 or y1 == y0 (the clamp at a - 1) the corners that
+ *   coincide stay entries of their own, added one after the other; a corner whose coefficient is 0 stays an entry too.  A
+ *   destination no ring reads (most of a face) is the copy alone.  Nothing depends on the launch grid or the batch.
+ * pconv_host_cube_pad_reverse_size(a, depth) = 24*(A*A - a*a), four entries per ring pixel of six faces; with 24*A*A below
+ *   2^31 (the padded stack's own bound) this always fits int32.  A negative value when a or depth is refused.
+ * pconv_host_cube_pad_reverse (host): the lists as CSR per pixel of the face stack from a host copy of the table the forward
+ *   reads: rev_start 6*a*a + 1 int32, rev_entry 24*(A*A - a*a) int32, ascending within each list (a stable counting sort of
+ *   the walk i ascending, corner ascending).  Returns the entry count; nothing is written unless every argument passes.
+ * pconv_cube_pad_backward_f32: gout, gin, table and the two lists on the device, 4-byte aligned.  A gather: a lane owns one
+ *   destination and walks its list once, for up to four planes at a time (the decoding of an entry is shared by the planes,
+ *   the sums are not); a list is never split.  Every element of gin is stored exactly once.  No atomics, no workspace, no
+ *   allocation.  An entry outside 0 .. 24*(A*A - a*a) - 1 is skipped and a start outside it clamped, and the ring pixel of
+ *   an entry is always a pixel of the padded stack, so no list or table content makes the kernel read outside `table` or
+ *   `gout`; each lane stores only its own pixel.  Refused on the host, before any launch, with PCONV_EINVAL: what
+ *   pconv_cube_pad_depth_f32 refuses, null list pointers, gin == gout. */
+long long pconv_host_cube_pad_reverse_size(int a, int depth);
+int pconv_host_cube_pad_reverse(const int32_t *table, int a, int depth, int32_t *rev_start, int32_t *rev_entry);
+int pconv_cube_pad_backward_f32(const float *gout, float *gin, const int32_t *table, const int32_t *rev_start,
+                                const int32_t *rev_entry, int n, int c, int a, int depth, void *stream);
+
 /* Sphere-sampled metrics: S-PSNR-NN, S-PSNR-I, CPP-PSNR (csrc/sphere_points.hip; pseudocylindrical_convolution_amd/
  * sphere_points.py states the same definition in torch and numpy).  Two ERP pictures of ANY two sizes are read at the
  * same points of the sphere and the squared error is summed over the points; neither picture is resampled onto the
@@ -707,10 +740,28 @@ int pconv_weighted_mse_backward_f32(const float *x, const float *y, const double
  *   s = 128 .. 1; out = sum / W.  No atomics, no allocation.
  * pconv_weighted_ssim_workspace_bytes(n, c, h, w) = 8 * n * c * ceil(h / 32) * ceil(w / 64) (a negative value when
  *   refused).  Refused on the host, before any launch, with PCONV_EINVAL: what pconv_weighted_mse_f32 refuses, so also out or
- *   the workspace inside x, y, the weights or each other.  x == y is allowed.  Non-finite inputs: unspecified.  Forward only. */
+ *   the workspace inside x, y, the weights or each other.  x == y is allowed.  Non-finite inputs: unspecified.
+ * Backward (pconv_weighted_ssim_backward_f32; weighted_metrics.ssim_backward_torch states the same in torch): the gradient of
+ *   sum over (f, c) of gout[f][c] * out[f][c] with respect to y, x the other picture.  It is the definition of
+ *   pconv_ws_metrics_backward_f32 with the per-row factor replaced by a per-pixel one: gout is n*C doubles on the device, one
+ *   per plane, and
+ *     k_p = (gout[f][c] * w_p) / W  in fp64, rounded once to fp32 (as the squared error's backward forms its factor); zero
+ *     outside the plane;
+ *     grad_y = (blur(k*a) + (2*y)*blur(k*b)) + x*blur(k*c),
+ *   a, b, c exactly those of pconv_ws_metrics_backward_f32, in the same operation order and with its rounding rules (fp32, no
+ *   contraction, 11-tap sums k-ascending with fmaf from 0, the horizontal pass first).  There is no km term.  The passes are
+ *   those of the ERP entry's kernel (one kernel template, the factor of pass C read from the plane in global memory: nothing
+ *   of the plane is staged in LDS).  One launch, a gather: every element of grad_y (float32 (n, C, H, W)) is stored exactly
+ *   once; no atomics, no workspace, no allocation.  A pixel's result depends on its plane and that plane's gout alone.  The
+ *   gradient with respect to x is the same call with x and y swapped.  The map is fp32, so the gradient agrees with a
+ *   float64 evaluation to a bound, not to the bit.  Refused on the host, before any launch, with PCONV_EINVAL: null or
+ *   misaligned pointers (x, y, grad_y 4-byte, weights and gout 8-byte), the sizes and the total that the forward refuses,
+ *   grad_y inside x, y, the weights or gout. */
 long long pconv_weighted_ssim_workspace_bytes(int n, int c, int h, int w);
 int pconv_weighted_ssim_f32(const float *x, const float *y, const double *weights, double total, int n, int c, int h, int w,
                             void *workspace, double *out, void *stream);
+int pconv_weighted_ssim_backward_f32(const float *x, const float *y, const double *weights, double total, const double *gout,
+                                     int n, int c, int h, int w, float *grad_y, void *stream);
 
 /* Ordered backward of the renderer and of the sphere rotation (csrc/remap_backward.hip, csrc/geometry.cpp; viewport.py
  * states the same definition in torch: render_backward_torch).  The forward of view pixel (j, i) of plane (n, c) is the

@@ -1,6 +1,7 @@
-"""Bindings of the weighted metrics, of the cube's point records and of its face continuation of any depth (include/
-pconv_hip.h, pconv_weighted_mse_*, pconv_weighted_ssim_f32, pconv_cube_points_records, pconv_cube_pad_depth_f32): what PCONV.py's wrappers are for the older entry points, kept here because PCONV.py's public
-names are closed.  weighted_metrics.py and cube.py are the users.
+"""Bindings of the weighted metrics, of the cube's point records and of its face continuation of any depth, forward and
+backward (include/pconv_hip.h, pconv_weighted_mse_*, pconv_weighted_ssim_f32, pconv_weighted_ssim_backward_f32,
+pconv_cube_points_records, pconv_cube_pad_depth_f32, pconv_cube_pad_backward_f32): what PCONV.py's wrappers are for the
+older entry points, kept here because PCONV.py's public names are closed.  weighted_metrics.py and cube.py are the users.
 
 Every wrapper holds PCONV.py's operand contract: an operand of the wrong type, device, shape or layout is refused with a
 PconvError that names it, before the library is reached (`_native.call` is looked up at each call, so a test can watch
@@ -106,6 +107,53 @@ def weighted_ssim_device(x, y, weights, total):
     out = torch.empty((n, c), dtype=torch.float64, device=x.device)
     _native.call("pconv_weighted_ssim_f32", _ptr(x), _ptr(y), _ptr(weights), total, n, c, h, w, _ptr(workspace), _ptr(out),
                  _stream(x.device))
+    return out
+
+
+def weighted_ssim_backward(x, y, weights, total, gout):
+    """float32 (n, C, H, W): the gradient of sum(gout * weighted_ssim_device(x, y, weights, total)) with respect to y
+    (pconv_weighted_ssim_backward_f32); gout contiguous float64 (n, C) on the same device, read by the kernel.  One launch.
+    For the gradient with respect to x swap x and y"""
+    what = "weighted_ssim_backward"
+    (n, c, h, w), _ = _frames(what, x, y, weights, True)
+    _operand(gout, what, "gout", (n, c), torch.float64, x.device)
+    total = _total(what, total)
+    grad = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    _native.call("pconv_weighted_ssim_backward_f32", _ptr(x), _ptr(y), _ptr(weights), total, _ptr(gout), n, c, h, w, _ptr(grad),
+                 _stream(x.device))
+    return grad
+
+
+def cube_pad_backward(g, table, lists, a, depth, out=None):
+    """float32 (n, C, 6 a, a): the gradient of cube_pad_depth with respect to the face stack, in the order of include/
+    pconv_hip.h (pconv_cube_pad_backward_f32).  g: contiguous float32 (n, C, 6 A, A) on a GPU, A = a + 2 depth; table: the
+    int32 (6 (A^2 - a^2), 3) table the forward read; lists: (start, entry), int32 of 6 a^2 + 1 and 24 (A^2 - a^2) elements
+    (cube.pad_reverse_lists), all on g's device.  One launch; out must not be g"""
+    what = "cube_pad_backward"
+    a, depth = int(a), int(depth)
+    if not 1 <= depth <= CUBE_MAX_DEPTH:
+        raise PconvError("%s: depth must be 1 .. %d, got %r" % (what, CUBE_MAX_DEPTH, depth))
+    A = a + 2 * depth
+    if not (a >= 2 and 24 * A * A < 1 << 31):
+        raise PconvError("%s: a face size from 2 up with the padded stack below 2^31 bytes expected, got %d at depth %d"
+                         % (what, a, depth))
+    n, c, _, _ = _operand(g, what, "g", (None, None, 6 * A, A), torch.float32)
+    if not 1 <= n * c <= MAX_PLANES:
+        raise PconvError("%s: g: n * C of 1 .. %d expected, got %d" % (what, MAX_PLANES, n * c))
+    ring = A * A - a * a
+    _operand(table, what, "table", (6 * ring, 3), torch.int32, g.device)
+    try:
+        start, entry = lists
+    except (TypeError, ValueError):
+        raise PconvError("%s: lists must be the pair (start, entry), got %s" % (what, type(lists).__name__))
+    _operand(start, what, "lists[0]", (6 * a * a + 1,), torch.int32, g.device)
+    _operand(entry, what, "lists[1]", (24 * ring,), torch.int32, g.device)
+    if out is None:
+        out = torch.empty((n, c, 6 * a, a), dtype=torch.float32, device=g.device)
+    else:
+        _operand(out, what, "out", (n, c, 6 * a, a), torch.float32, g.device)
+    _native.call("pconv_cube_pad_backward_f32", _ptr(g), _ptr(out), _ptr(table), _ptr(start), _ptr(entry), n, c, a, depth,
+                 _stream(g.device))
     return out
 
 

@@ -76,6 +76,9 @@ _HIP_SIGNATURES = {
     "pconv_cube_pad_f32": [P, P, P, I, I, I, P],
     "pconv_cube_pad_depth_f32": [P, P, P, I, I, I, I, P],
     "pconv_cube_to_erp_map": [P, I, I, I, I, I, P],
+    "pconv_host_cube_pad_reverse_size": [I, I],
+    "pconv_host_cube_pad_reverse": [P, I, I, P, P],
+    "pconv_cube_pad_backward_f32": [P, P, P, P, P, I, I, I, I, P],
     "pconv_host_remap_reverse_size": [I, I],
     "pconv_host_remap_reverse": [P, I, I, I, I, P, P],
     "pconv_remap_backward_f32": [P, P, P, P, P, P, I, I, I, I, I, I, I, LL, I, P],
@@ -90,6 +93,7 @@ _HIP_SIGNATURES = {
     "pconv_weighted_mse_backward_f32": [P, P, P, D, P, I, I, I, I, P, P],
     "pconv_weighted_ssim_workspace_bytes": [I, I, I, I],
     "pconv_weighted_ssim_f32": [P, P, P, D, I, I, I, I, P, P, P],
+    "pconv_weighted_ssim_backward_f32": [P, P, P, D, P, I, I, I, I, P, P],
     "pconv_project": [P, P, P, I, I, I, I, I, I, I, I, P],
     "pconv_context_reshape": [P, P, I, I, I, I, I, P],
     "pconv_mask_constrain": [P, I, I, I, I, I, P],
@@ -249,6 +253,7 @@ def hip_lib():
         lib.pconv_host_tap_reverse_size.restype = c_longlong
         lib.pconv_host_project_reverse_size.restype = c_longlong
         lib.pconv_host_remap_reverse_size.restype = c_longlong
+        lib.pconv_host_cube_pad_reverse_size.restype = c_longlong
         lib.pconv_quant_backward_ordered_workspace_bytes.restype = c_longlong
         lib.pconv_conv2d_dgrad_workspace_bytes.restype = c_longlong
         lib.pconv_conv2d_wgrad_workspace_bytes.restype = c_longlong

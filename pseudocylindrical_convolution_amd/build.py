@@ -30,7 +30,7 @@ HIP_SOURCES = [
     "erp_resample_backward.hip",  # its ordered backward: two gathers over the transposed tap tables
     "erp_rotate.hip",  # sphere rotation of ERP frames: the source map and the 6 x 6 Lanczos-3 sampler
     "viewport.hip",    # rectilinear viewports of ERP frames: the gnomonic source map and the supersampled renderer
-    "cube.hip",        # cubemap panoramas (CMP, EAC): the two cube <-> ERP maps and the face continuation of the way back
+    "cube.hip",        # cubemap panoramas (CMP, EAC): the two cube <-> ERP maps, the face continuation and its ordered backward
     "remap_backward.hip", # the ordered backward of the renderer and of the sphere rotation: a gather over reverse lists
     "sphere_metrics.hip",  # WS-PSNR / WS-SSIM / WS-MS-SSIM of ERP frames, forward and backward
     "sphere_points.hip",  # S-PSNR-NN / S-PSNR-I / CPP-PSNR: two pictures of any sizes sampled at points of the sphere

@@ -14,8 +14,18 @@
 //                             once per (kind, a) on the host.  One pass, every pixel stored by its own lane.  The depth of
 //                             the ring is an argument: 3 for the way back (pconv_cube_pad_f32), 1 .. 8 through
 //                             pconv_cube_pad_depth_f32 (A = a + 2 depth; cube.ws_ssim continues by 5, §4k).
+//   cube_pad_backward_f32_kernel  the ordered backward of the continuation (pconv_cube_pad_backward_f32): a gather.  A lane owns
+//                             one pixel of the face stack, starts from the gradient of its own interior copy and walks
+//                             its list of pconv_host_cube_pad_reverse once, front to back, for up to 4 planes at a time
+//                             (the decoding of an entry -- its record, its coefficient, its ring pixel -- is shared by
+//                             the planes, the sums are not).  Most pixels have no list: only those within a few pixels of
+//                             a face edge are read by a ring, and for the others the lane is a copy.  No atomics, no
+//                             workspace, every element stored once by its own lane.
 //   cube_points_records_kernel  one lane per point of a point set: the direction the host gives -> the record on the padded
 //                             stack, so that the sphere-sampled metrics (sphere_points.hip) read a cube picture (§4k).
+#include <algorithm>
+#include <vector>
+
 #include "sphere_sampler.h"
 
 namespace {
@@ -147,6 +157,59 @@ __global__ __launch_bounds__(kBlock) void cube_pad_f32_kernel(const float *__res
   *dst = lerp_rn(top, bot, fy);
 }
 
+constexpr int kPlanes = 4;  // planes a lane carries through one walk of its list
+
+// ring pixel k of a padded face (ring order: row after row, column after column, outside the interior) -> R * A + Q; the
+// inverse of cube_pad_f32_kernel's count.  k in 0 .. A * A - a * a - 1
+__host__ __device__ inline int ring_pixel(int k, int a, int pad) {
+  const int A = a + 2 * pad, top = pad * A, sides = 2 * pad * a;
+  if (k < top) return k;
+  if (k < top + sides) {
+    const int m = k - top, row = m / (2 * pad), j = m - row * 2 * pad;
+    return (pad + row) * A + (j < pad ? j : j + a);
+  }
+  return (pad + a) * A + (k - top - sides);
+}
+
+__global__ __launch_bounds__(kBlock) void cube_pad_backward_f32_kernel(const float *__restrict__ gout, float *__restrict__ gin,
+                                                                       const int *__restrict__ table,
+                                                                       const int32_t *__restrict__ rev_start,
+                                                                       const int32_t *__restrict__ rev_entry, int C, int a,
+                                                                       int pad, int total) {
+  const int A = a + 2 * pad, ring = A * A - a * a, pixels = 6 * a * a;
+  const int d = blockIdx.x * kBlock + threadIdx.x;  // 6 a^2 < 2^29
+  if (d >= pixels) return;
+  const int groups = (C + kPlanes - 1) / kPlanes;
+  const int frame = blockIdx.y / groups, c0 = (blockIdx.y - frame * groups) * kPlanes;
+  const int planes = min(kPlanes, C - c0);
+  const long long gplane = 6LL * A * A;
+  const float *g = gout + ((long long)frame * C + c0) * gplane;
+  float *dst = gin + ((long long)frame * C + c0) * pixels + d;
+  const int lo = min(max(rev_start[d], 0), total), hi = min(max(rev_start[d + 1], 0), total);
+  const int face = d / (a * a), r = (d - face * a * a) / a, c = d - (face * a + r) * a;
+  const int own = (face * A + pad + r) * A + pad + c;
+  float acc[kPlanes];
+#pragma unroll
+  for (int k = 0; k < kPlanes; k++) acc[k] = k < planes ? g[(long long)k * gplane + own] : 0.f;
+  for (int at = lo; at < hi; at++) {
+    const int e = rev_entry[at];
+    if ((unsigned)e >= (unsigned)total) continue;  // whatever the list holds is reduced to an entry of the table
+    const int i = e >> 2, corner = e & 3;
+    const int *rec = table + 3 * i;
+    const int px = record_phase(rec[1]), py = record_phase(rec[2]);
+    const int cx = (corner & 1) ? px : kPhases - px, cy = (corner & 2) ? py : kPhases - py;
+    const float coef = (float)(cx * cy) * (1.0f / (kPhases * kPhases));  // exact: cx * cy <= 2^16
+    const int rf = i / ring;                                              // 0 .. 5, as i < 6 ring
+    const int at_ring = rf * A * A + ring_pixel(i - rf * ring, a, pad);
+#pragma unroll
+    for (int k = 0; k < kPlanes; k++)
+      if (k < planes) acc[k] = __fadd_rn(acc[k], __fmul_rn(g[(long long)k * gplane + at_ring], coef));
+  }
+#pragma unroll
+  for (int k = 0; k < kPlanes; k++)
+    if (k < planes) dst[(long long)k * pixels] = acc[k];
+}
+
 int kind_ok(const char *what, int kind) {
   PCONV_REQUIRE(kind == PCONV_CUBE_CMP || kind == PCONV_CUBE_EAC, "%s: kind %d is neither PCONV_CUBE_CMP (1) nor PCONV_CUBE_EAC (2)",
                 what, kind);
@@ -216,14 +279,21 @@ extern "C" int pconv_cube_points_records(const double *dirs, int32_t *records, l
 
 namespace {
 
-// the face continuation of any depth: pconv_cube_pad_f32 is depth PCONV_CUBE_PAD, where face_ok has bounded the stack
-int cube_pad(const char *what, const float *in, float *out, const int32_t *table, int n, int c, int a, int depth, void *stream) {
-  PCONV_REQUIRE(in && out && table, "%s: null pointer", what);
-  if (planes_ok(what, n, c) != PCONV_OK || face_ok(what, a) != PCONV_OK) return PCONV_EINVAL;
+// a face size and a depth whose padded stack stays below 2^31 bytes
+int depth_ok(const char *what, int a, int depth) {
+  if (face_ok(what, a) != PCONV_OK) return PCONV_EINVAL;
   PCONV_REQUIRE(depth >= 1 && depth <= PCONV_CUBE_MAX_DEPTH, "%s: a depth of %d is outside 1 .. %d", what, depth, PCONV_CUBE_MAX_DEPTH);
   const int A = a + 2 * depth;
   PCONV_REQUIRE(24LL * A * A < (1LL << 31), "%s: a face size of %d continued by %d: the padded stack is 2^31 bytes or more", what, a,
                 depth);
+  return PCONV_OK;
+}
+
+// the face continuation of any depth: pconv_cube_pad_f32 is depth PCONV_CUBE_PAD, where face_ok has bounded the stack
+int cube_pad(const char *what, const float *in, float *out, const int32_t *table, int n, int c, int a, int depth, void *stream) {
+  PCONV_REQUIRE(in && out && table, "%s: null pointer", what);
+  if (planes_ok(what, n, c) != PCONV_OK || depth_ok(what, a, depth) != PCONV_OK) return PCONV_EINVAL;
+  const int A = a + 2 * depth;
   PCONV_REQUIRE(((addr(in) | addr(out) | addr(table)) & 3) == 0, "%s: the tensors and the table must be 4-byte aligned", what);
   PCONV_REQUIRE(in != out, "%s: in and out must be distinct (the ring reads the faces)", what);
   const int tiles = (A + kTileW - 1) / kTileW;
@@ -243,4 +313,58 @@ extern "C" int pconv_cube_pad_f32(const float *in, float *out, const int32_t *ta
 extern "C" int pconv_cube_pad_depth_f32(const float *in, float *out, const int32_t *table, int n, int c, int a, int depth,
                                         void *stream) {
   return cube_pad("cube_pad_depth_f32", in, out, table, n, c, a, depth, stream);
+}
+
+extern "C" long long pconv_host_cube_pad_reverse_size(int a, int depth) {
+  if (depth_ok("cube_pad_reverse_size", a, depth) != PCONV_OK) return PCONV_EINVAL;
+  const long long A = a + 2 * depth;
+  return 24LL * (A * A - (long long)a * a);  // below 24 A^2 < 2^31
+}
+
+// Transpose of the face continuation as a CSR list per pixel of the face stack (pconv_cube_pad_backward_f32): the walk --
+// ring pixel i ascending, corner 0 .. 3 = (y0, x0), (y0, x1), (y1, x0), (y1, x1) -- sorted by the pixel the corner reads
+// with a stable counting sort, so every list ascends.  The face and the four positions are reduced exactly as
+// cube_pad_f32_kernel reduces them.  Corners that coincide, and corners that weigh 0, are entries of their own.
+extern "C" int pconv_host_cube_pad_reverse(const int32_t *table, int a, int depth, int32_t *rev_start, int32_t *rev_entry) {
+  const char *what = "cube_pad_reverse";
+  PCONV_REQUIRE(table && rev_start && rev_entry, "%s: null pointer", what);
+  const long long total = pconv_host_cube_pad_reverse_size(a, depth);
+  if (total < 0) return PCONV_EINVAL;
+  const size_t keys = 6 * (size_t)a * a, rings = (size_t)(total / 4);
+  std::vector<int32_t> fill(keys + 1, 0);
+  for (int pass = 0; pass < 2; pass++) {
+    for (size_t i = 0; i < rings; i++) {
+      const int32_t *rec = table + 3 * i;
+      const int g = std::min(std::max(rec[0], 0), 5);
+      const int x0 = std::min(std::max(rec[1] >> 8, 0), a - 1), y0 = std::min(std::max(rec[2] >> 8, 0), a - 1);
+      const int xs[2] = {x0, std::min(x0 + 1, a - 1)}, ys[2] = {y0, std::min(y0 + 1, a - 1)};
+      for (int corner = 0; corner < 4; corner++) {
+        const size_t d = ((size_t)g * a + ys[corner >> 1]) * a + xs[corner & 1];
+        if (pass == 0) fill[d + 1]++;
+        else rev_entry[fill[d]++] = (int32_t)(4 * i + corner);
+      }
+    }
+    if (pass == 0) {
+      for (size_t k = 0; k < keys; k++) fill[k + 1] += fill[k];
+      for (size_t k = 0; k <= keys; k++) rev_start[k] = fill[k];
+    }
+  }
+  return (int)total;
+}
+
+extern "C" int pconv_cube_pad_backward_f32(const float *gout, float *gin, const int32_t *table, const int32_t *rev_start,
+                                           const int32_t *rev_entry, int n, int c, int a, int depth, void *stream) {
+  const char *what = "cube_pad_backward_f32";
+  PCONV_REQUIRE(gout && gin && table, "%s: null pointer", what);
+  PCONV_REQUIRE(rev_start && rev_entry, "%s: null list pointer", what);
+  if (planes_ok(what, n, c) != PCONV_OK || depth_ok(what, a, depth) != PCONV_OK) return PCONV_EINVAL;
+  PCONV_REQUIRE(((addr(gout) | addr(gin) | addr(table) | addr(rev_start) | addr(rev_entry)) & 3) == 0,
+                "%s: the tensors, the table and the lists must be 4-byte aligned", what);
+  PCONV_REQUIRE(gin != gout, "%s: gin and gout must be distinct (a pixel reads its neighbours' rings)", what);
+  const long long total = pconv_host_cube_pad_reverse_size(a, depth);
+  const int groups = (c + kPlanes - 1) / kPlanes;  // n * groups <= n * C <= 65535
+  hipLaunchKernelGGL(cube_pad_backward_f32_kernel, dim3((unsigned)((6 * a * a + kBlock - 1) / kBlock), (unsigned)(n * groups)),
+                     dim3(kBlock), 0, as_stream(stream), gout, gin, table, rev_start, rev_entry, c, a, depth, (int)total);
+  PCONV_LAUNCH_CHECK(what);
+  return PCONV_OK;
 }

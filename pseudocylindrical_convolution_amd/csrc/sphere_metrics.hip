@@ -21,7 +21,8 @@
 //
 // Backward: one launch of ms_backward_kernel per scale, coarse to fine: a gather (halo 10, five passes in LDS, every
 // output stored once) with a compile-time switch between the cs-only and the full coefficients, the fused
-// + 0.25f·g_{s+1}[r >> 1][q >> 1] read and, at scale 0, + km·(y - x).
+// + 0.25f·g_{s+1}[r >> 1][q >> 1] read and, at scale 0, + km·(y - x).  The same kernel with a per-pixel factor read from
+// a float64 weight plane is the backward of the weighted SSIM (pconv_weighted_ssim_backward_f32; launch_plane_backward).
 #include "ssim_tile.h"
 
 namespace {
@@ -253,12 +254,18 @@ __global__ __launch_bounds__(kBlock) void ms_close_kernel(const double *__restri
 // FULL: the last scale, the coefficients of the full map and no coarser gradient.  Otherwise the cs-only coefficients
 // and + 0.25f·coarse[r >> 1][q >> 1].  FIRST: scale 0, + km·(y - x).  MULTI: the per-frame factor is u_s = gs·β_s·MS /
 // v_s, formed in fp64 from the forward's saved values; otherwise (WS-SSIM, one scale) it is gs and `values` is not read.
-template <bool FULL, bool FIRST, bool MULTI>
+// PLANE: the weighted SSIM over a weight plane (pconv_weighted_ssim_backward_f32): blockIdx.y counts planes (G.c is 1),
+// gout holds one value per plane, `norm` is the plane's total W, and pass C takes its factor per pixel, k_p = gout·w_p / W,
+// the weights of its 7 rows of one column read straight from global memory before the vertical pass starts (consecutive
+// lanes read consecutive doubles of a row; nothing of the plane is staged: the 154 KB of LDS are taken).  No row factors.
+template <bool FULL, bool FIRST, bool MULTI, bool PLANE = false>
 __global__ __launch_bounds__(kBBlock) void ms_backward_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                             const double *__restrict__ values,
                                                             const double *__restrict__ gout,
                                                             const float *__restrict__ coarse, float *__restrict__ gy,
-                                                            WsGeom G, double norm, int scale, int h2, int w2) {
+                                                            WsGeom G, double norm, int scale, int h2, int w2,
+                                                            const double *__restrict__ weights) {
+  static_assert(!PLANE || (FULL && !FIRST && !MULTI), "the weight plane: one scale, the full map, no squared-error term");
   __shared__ __attribute__((aligned(16))) float sx[kBRows * kBLd];
   __shared__ __attribute__((aligned(16))) float sy[kBRows * kBLd];
   __shared__ __attribute__((aligned(16))) float mom[5 * kBRows * kMLd];
@@ -270,7 +277,9 @@ __global__ __launch_bounds__(kBBlock) void ms_backward_kernel(const float *__res
   const int r0 = ty * kTileRows, c0 = (tile - ty * G.tiles_x) * kTileCols;
   // k_j = u_s·w_j / N_s with u_s = gs·β_s·MS / v_s (0 when any v_t <= 0; gs alone for one scale), and km_j =
   // 2·gm·w_j / N_0: fp64, each rounded once to fp32; k = 0 on rows outside the frame
-  if (tid < kPRows) {
+  if (PLANE) {
+    // the factor is per pixel: pass C forms it
+  } else if (tid < kPRows) {
     const int gr = r0 - kHalo + tid;
     const bool in = gr >= 0 && gr < G.h;
     const double wj = G.uniform ? 1.0 : row_weight(in ? gr : 0, G.h);
@@ -342,6 +351,16 @@ __global__ __launch_bounds__(kBBlock) void ms_backward_kernel(const float *__res
     for (int o = 0; o < kCRowsPerLane; o++)
 #pragma unroll
       for (int t = 0; t < 5; t++) acc[o][t] = 0.f;
+    // PLANE: the seven weights are asked for before the vertical pass; a pixel outside the plane reads none
+    double wt[kCRowsPerLane];
+    if (PLANE) {
+#pragma unroll
+      for (int o = 0; o < kCRowsPerLane; o++) {
+        const int gr = r0 - kHalo + rg + o, gc = c0 - kHalo + col;
+        const bool in = gr >= 0 && gr < G.h && gc >= 0 && gc < G.w;
+        wt[o] = in ? weights[(unsigned)(gr * G.w + gc)] : 0.0;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < kCRowsPerLane + 2 * kHalo; i++) {
       float v[5];
@@ -378,7 +397,7 @@ __global__ __launch_bounds__(kBBlock) void ms_backward_kernel(const float *__res
         dc = 2.f / B2;
         da = (-mux * dc) - (2.f * muy) * db;
       }
-      const float ks = ks_row[r];
+      const float ks = PLANE ? (float)(__dmul_rn(gout[f], wt[o]) / norm) : ks_row[r];
       abc[0][r * kMLd + col] = in ? ks * da : 0.f;
       abc[1][r * kMLd + col] = in ? ks * db : 0.f;
       abc[2][r * kMLd + col] = in ? ks * dc : 0.f;
@@ -519,22 +538,37 @@ int ws_backward(const char *what, int scales, const float *x, const float *y, co
     const dim3 grid(G.tiles, n, c), block(kBBlock);
     if (scales == 1)
       hipLaunchKernelGGL((ms_backward_kernel<true, true, false>), grid, block, 0, st, xs, ys, values, gout, coarse, gs, G,
-                         norm, s, h2, w2);
+                         norm, s, h2, w2, nullptr);
     else if (s == scales - 1)
       hipLaunchKernelGGL((ms_backward_kernel<true, false, true>), grid, block, 0, st, xs, ys, values, gout, coarse, gs, G,
-                         norm, s, h2, w2);
+                         norm, s, h2, w2, nullptr);
     else if (s > 0)
       hipLaunchKernelGGL((ms_backward_kernel<false, false, true>), grid, block, 0, st, xs, ys, values, gout, coarse, gs, G,
-                         norm, s, h2, w2);
+                         norm, s, h2, w2, nullptr);
     else
       hipLaunchKernelGGL((ms_backward_kernel<false, true, true>), grid, block, 0, st, xs, ys, values, gout, coarse, gs, G,
-                         norm, s, h2, w2);
+                         norm, s, h2, w2, nullptr);
     PCONV_LAUNCH_CHECK(what);
   }
   return PCONV_OK;
 }
 
 }  // namespace
+
+// the launch of pconv_weighted_ssim_backward_f32 (weighted_metrics.hip, which has checked every argument): the backward
+// kernel above with its per-pixel factor, one workgroup per (tile, plane)
+int ssim::launch_plane_backward(const char *what, const float *x, const float *y, const double *weights, double total,
+                                const double *gout, int planes, int h, int w, float *grad_y, void *stream) {
+  WsGeom G = {};
+  G.c = 1, G.h = h, G.w = w;
+  G.tiles_x = (w + kTileCols - 1) / kTileCols;
+  G.tiles = G.tiles_x * ((h + kTileRows - 1) / kTileRows);  // a plane is below 2^29 pixels: below 2^26 tiles
+  gaussian_taps(G.g);
+  hipLaunchKernelGGL((ms_backward_kernel<true, false, false, true>), dim3(G.tiles, planes, 1), dim3(kBBlock), 0,
+                     as_stream(stream), x, y, nullptr, gout, nullptr, grad_y, G, total, 0, 0, 0, weights);
+  PCONV_LAUNCH_CHECK(what);
+  return PCONV_OK;
+}
 
 extern "C" long long pconv_ws_metrics_workspace_bytes(int n, int h, int w) {
   if (ws_sizes("ws_metrics_workspace_bytes", 1, n, 1, h, w) != PCONV_OK) return PCONV_EINVAL;

@@ -32,6 +32,12 @@ struct WsGeom {
   float g[kTaps];  // the normalised 1-D Gaussian in fp32
 };
 
+// The backward of the map has one kernel, sphere_metrics.hip's ms_backward_kernel (passes A-E, 154 KB of LDS): this launches
+// its weight-plane form for weighted_metrics.hip, which checks the arguments of pconv_weighted_ssim_backward_f32 first.
+// `planes` = n * C; gout one double per plane and the weights (h, w), both on the device
+int launch_plane_backward(const char *what, const float *x, const float *y, const double *weights, double total,
+                          const double *gout, int planes, int h, int w, float *grad_y, void *stream);
+
 // pytorch_ssim.gaussian(11, 1.5): exp(-(k - 5)² / (2·1.5²)) in double, normalised; here in fp32
 inline void gaussian_taps(float *out) {
   double g[kTaps], sum = 0.0;

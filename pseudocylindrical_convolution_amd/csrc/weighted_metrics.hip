@@ -19,6 +19,8 @@
 //                                 row; nothing of the plane is staged, so the workgroup keeps the 80 KB of LDS that lets two
 //                                 share a CU) and adds w * map in fp64; a wave butterfly and the four waves in order give the
 //                                 tile's partial.  weighted_sum_kernel adds a plane's tile partials as it adds chunk partials.
+//   pconv_weighted_ssim_backward_f32  the gradient of that figure has no kernel here: the checks are below, the kernel is
+//                                 sphere_metrics.hip's ms_backward_kernel with its per-pixel factor (launch_plane_backward).
 // The tree's last six steps stay inside wave 0 (lane l and lane l + s, s <= 32, are both lanes of it), so they are register
 // exchanges of the same fp64 additions in the same order: two LDS steps and two barriers instead of eight.
 #include "sphere_sampler.h"
@@ -302,4 +304,22 @@ extern "C" int pconv_weighted_ssim_f32(const float *x, const float *y, const dou
   hipLaunchKernelGGL(weighted_sum_kernel, dim3((unsigned)planes), dim3(kBlock), 0, as_stream(stream), partials, tiles, total, out);
   PCONV_LAUNCH_CHECK(what);
   return PCONV_OK;
+}
+
+// the gradient of the weighted SSIM: the checks here, the kernel in sphere_metrics.hip (the ERP backward's passes with a
+// per-pixel factor read from the plane: ssim_tile.h, launch_plane_backward)
+extern "C" int pconv_weighted_ssim_backward_f32(const float *x, const float *y, const double *weights, double total,
+                                                const double *gout, int n, int c, int h, int w, float *grad_y, void *stream) {
+  const char *what = "weighted_ssim_backward_f32";
+  PCONV_REQUIRE(x && y && weights && gout && grad_y, "%s: null pointer", what);
+  if (shape_ok(what, n, c, h, w, total) != PCONV_OK) return PCONV_EINVAL;
+  if (aligned_ok(what, addr(x) | addr(y) | addr(grad_y), "x, y and the gradient", addr(weights) | addr(gout),
+                 "the weights and gout") != PCONV_OK)
+    return PCONV_EINVAL;
+  const long long pixels = (long long)h * w, planes = (long long)n * c;
+  const long long bin = 4LL * planes * pixels;
+  PCONV_REQUIRE(!overlap(grad_y, bin, x, bin) && !overlap(grad_y, bin, y, bin) && !overlap(grad_y, bin, weights, 8LL * pixels) &&
+                    !overlap(grad_y, bin, gout, 8LL * planes),
+                "%s: the gradient must not alias an input", what);
+  return ssim::launch_plane_backward(what, x, y, weights, total, gout, (int)planes, h, w, grad_y, stream);
 }

@@ -24,7 +24,9 @@ equator, at most 4; beyond 4 the source is to be reduced first (erp_resample.res
 GPU tensors take the HIP kernels (PCONV.cube_*, PCONV.viewport_render_f32), CPU tensors the torch twins below
 (`pad_torch`, viewport.render_torch): the same bits on the same map and table.  `from_erp` of a tensor that requires grad
 goes through viewport's Function (the ordered backward of pconv_remap_backward_f32: the map is generic); `to_erp` under
-autograd is refused: the pad kernel has no backward yet.
+autograd is refused unless grad=True is passed: then the continuation is `pad(.., grad=True)`, whose backward
+`pad_backward` is the adjoint of the continuation as an ordered gather (pconv_cube_pad_backward_f32 over
+`pad_reverse_lists`; `pad_backward_torch` is its twin, the same bits), and the renderer is viewport's Function again.
 
 Scoring (the last section of this module): `area_weights` is the solid angle of every pixel of a cube
 picture, `ws_mse` / `ws_psnr` / `ws_loss_terms` weigh two cube pictures by it (weighted_metrics.py), and `point_records` puts
@@ -32,12 +34,15 @@ the points of a sphere_points.PointSet on the padded stack, so that `points_mse`
 cube and ERP pictures in any mix at the same points of the sphere, with no conversion in between.  `ws_ssim` is the
 structural figure: every face continued by SSIM_PAD = 5 pixels, the radius of the SSIM window (`pad` takes a depth), and
 the padded stacks scored by weighted_metrics.ssim with the ring weighted zero, so that a window at a face edge sees the
-neighbouring face and no window of a weighted pixel reads outside its own padded face.
+neighbouring face and no window of a weighted pixel reads outside its own padded face.  `ws_ssim_loss_terms` is the same
+figure attached to autograd (pad(.., grad=True) and weighted_metrics.ssim_loss_terms): with `ws_loss_terms` the two terms
+of train.py --loss cube-ws.
 
 Limits.  The ring is bilinear and one level deep, so within 3 pixels of a face edge the way back reads a slightly softer
 continuation than the sphere itself.  For "eac" the extended plane ends before its horizon: |s| and |t| of a ring pixel
 are held at 7/4, which only faces of a <= 6 reach (at depth 5, ws_ssim's: a <= 11).  ss is chosen for the face centre /
-the equator.  ws_ssim is forward only, has no multi-scale form, and claims no equality with 360Lib's figure.
+the equator.  ws_ssim itself is forward only (ws_ssim_loss_terms carries the gradient, the SSIM's held to a bound, not
+to the bit), has no multi-scale form, and claims no equality with 360Lib's figure.
 """
 import collections
 import functools
@@ -462,12 +467,110 @@ def pad_numpy(y, table, depth=PAD):
     return out.reshape(n, c, 6 * A, A)
 
 
-def pad(y, kind, depth=PAD):
+@functools.lru_cache(maxsize=4)
+def _pad_reverse_lists(kind, a, depth, device):
+    from . import _native
+    table = np.ascontiguousarray(_pad_table(kind, a, depth))
+    count = _native.call("pconv_host_cube_pad_reverse_size", a, depth)
+    start, entry = np.empty(6 * a * a + 1, dtype=np.int32), np.empty(count, dtype=np.int32)
+    _native.call("pconv_host_cube_pad_reverse", table.ctypes.data, a, depth, start.ctypes.data, entry.ctypes.data)
+    return torch.from_numpy(start).to(device), torch.from_numpy(entry).to(device)
+
+
+def pad_reverse_lists(kind, a, depth=PAD, device=None):
+    """(start, entry): the transpose of the face continuation as one list per pixel of the face stack, int32 tensors of
+    6 a^2 + 1 and 24 (A^2 - a^2) elements on `device` (pconv_host_cube_pad_reverse: entry e = 4 ring_index + corner,
+    ascending within each list).  Built on the host from pad_table, once per (kind, a, depth) and device (the last 4 kept);
+    do not write to them"""
+    a, depth = check_depth(a, depth)
+    return _pad_reverse_lists(_kind(kind), a, depth, str(_device(device)))
+
+
+def _check_padded(g, a, depth, what="cube pad backward"):
+    a, depth = check_depth(a, depth)
+    A = a + 2 * depth
+    if not torch.is_tensor(g) or g.dim() != 4 or g.dtype != torch.float32 or tuple(g.shape[2:]) != (6 * A, A):
+        raise PconvError("%s: a float32 gradient (n, C, %d, %d) of the padded stack expected, got %s"
+                         % (what, 6 * A, A, "%s %s" % (g.dtype, tuple(g.shape)) if torch.is_tensor(g) else type(g).__name__))
+    return a, depth, A
+
+
+def pad_backward_torch(g, table, lists, a, depth=PAD):
+    """the gradient of pad_torch with respect to the face stack, in the order of include/pconv_hip.h
+    (pconv_cube_pad_backward_f32), float32 operation by operation on any device (the CPU path and the kernel's twin):
+    float32 (n, C, 6A, A), the table the forward read and its `pad_reverse_lists` -> (n, C, 6a, a).  Every pixel has one
+    accumulator that starts from the gradient of its own interior copy; the terms g_ring * coef of its list are added
+    front to back, coef = float(cx cy) 2^-16 with cx = px or 256 - px, cy = py or 256 - py by the entry's corner.
+    Vectorised in rounds: round k adds the k-th entry of every list that has one"""
+    a, depth, A = _check_padded(g, a, depth)
+    ring = A * A - a * a
+    if table.dtype != torch.int32 or tuple(table.shape) != (6 * ring, 3) or table.device != g.device:
+        raise PconvError("cube pad backward: the table must be int32 (%d, 3) on the gradient's device, got %s %s on %s"
+                         % (6 * ring, table.dtype, tuple(table.shape), table.device))
+    start, entry = (t.to(g.device).long() for t in lists)
+    if start.numel() != 6 * a * a + 1 or entry.numel() != 24 * ring:
+        raise PconvError("cube pad backward: the lists are not those of a face size of %d at depth %d" % (a, depth))
+    n, c = g.shape[:2]
+    g5 = g.reshape(n, c, 6, A, A)
+    acc = g5[:, :, :, depth:depth + a, depth:depth + a].reshape(n, c, 6 * a * a).clone()
+    R, Q = (torch.from_numpy(v).to(g.device) for v in ring_pixels(a, depth))
+    face = torch.arange(6, device=g.device).repeat_interleave(ring)
+    at_ring = g5[:, :, face, R.repeat(6), Q.repeat(6)]               # (n, C, 6 ring): gout at ring pixel i
+    rec = table.long()
+    px, py = rec[:, 1] & (PHASES - 1), rec[:, 2] & (PHASES - 1)
+    length = start[1:] - start[:-1]
+    alive = torch.nonzero(length > 0).flatten()      # the destinations that still have an entry in round k
+    k = 0
+    while alive.numel():
+        e = entry[start[alive] + k]
+        i, corner = e >> 2, e & 3
+        cx = torch.where((corner & 1) != 0, px[i], PHASES - px[i])
+        cy = torch.where((corner & 2) != 0, py[i], PHASES - py[i])
+        coef = (cx * cy).float() * torch.tensor(np.float32(1.0 / (PHASES * PHASES)), device=g.device)
+        acc[:, :, alive] = acc[:, :, alive] + at_ring[:, :, i] * coef
+        k += 1
+        alive = alive[length[alive] > k]
+    return acc.reshape(n, c, 6 * a, a)
+
+
+def pad_backward(g, kind, a, depth=PAD):
+    """float32 (n, C, 6a, a): the gradient of `pad` with respect to the face stack, from the gradient g (n, C, 6A, A) of the
+    padded stack: the adjoint of the continuation in the order of include/pconv_hip.h.  The HIP kernel for GPU tensors
+    (pconv_cube_pad_backward_f32: a gather over `pad_reverse_lists`, no atomics), pad_backward_torch for CPU tensors: the
+    same bits"""
+    kind = _kind(kind)
+    a, depth, _ = _check_padded(g, a, depth)
+    table = _pad_table_on(kind, a, str(g.device), depth)
+    lists = _pad_reverse_lists(kind, a, depth, str(g.device))
+    if g.is_cuda:
+        from . import _metric_ops
+        return _metric_ops.cube_pad_backward(g.contiguous(), table, lists, a, depth)
+    return pad_backward_torch(g, table, lists, a, depth)
+
+
+class _Pad(torch.autograd.Function):
+    """`pad` under autograd (pad(.., grad=True)): the forward as it is, the backward `pad_backward`, on either device"""
+
+    @staticmethod
+    def forward(ctx, y, kind, depth):
+        ctx.kind, ctx.depth, ctx.a = kind, depth, y.shape[3]
+        return pad(y, kind, depth)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return pad_backward(g.contiguous(), ctx.kind, ctx.a, ctx.depth), None, None
+
+
+def pad(y, kind, depth=PAD, grad=False):
     """the face stack (n, C, 6a, a) continued by `depth` pixels (1 .. MAX_DEPTH, by default PAD) across every face edge:
     (n, C, 6A, A), A = a + 2 depth.  The HIP kernel for GPU tensors (pconv_cube_pad_f32 at depth PAD, otherwise
-    pconv_cube_pad_depth_f32), pad_torch for CPU tensors: the same bits"""
+    pconv_cube_pad_depth_f32), pad_torch for CPU tensors: the same bits.  grad=True attaches the result to autograd: the
+    same values, and `pad_backward` as the backward (its lists built at the first backward and cached like the table)"""
     kind = _kind(kind)
     a, depth = check_depth(_check_stack(y, "cube pad"), depth)
+    if grad:
+        return _Pad.apply(y, kind, depth)
     table = _pad_table_on(kind, a, str(y.device), depth)
     if y.is_cuda and depth != PAD:
         from . import _metric_ops
@@ -530,19 +633,33 @@ def from_erp(x, a=None, spec="cmp", ss=None, clamp=False, layout=None):
     return pack(faces, sp.layout)
 
 
-def to_erp(y, size=None, spec="cmp", ss=None, clamp=False, layout=None):
+@functools.lru_cache(maxsize=4)
+def _to_erp_reverse_lists(kind, a, h, w, ss, device):
+    A = a + 2 * PAD
+    return viewport.reverse_lists(_to_erp_map(kind, a, h, w, ss, device), 6 * A, A)
+
+
+def to_erp(y, size=None, spec="cmp", ss=None, clamp=False, layout=None, grad=False):
     """a float32 cube picture in the spec's layout -> ERP frames (n, C, h, w) of `size` = (h, w), default erp_size(a).
-    ss=None: to_erp_ss.  The HIP kernels for GPU tensors, the twins on the CPU.  Refused under autograd: the face
-    continuation (pconv_cube_pad_f32) has no backward yet"""
+    ss=None: to_erp_ss.  The HIP kernels for GPU tensors, the twins on the CPU.  A picture that requires grad is refused
+    unless grad=True: the face continuation has no backward without the opt-in.  grad=True attaches the result to autograd
+    through pad(.., grad=True) (pconv_cube_pad_backward_f32) and viewport's Function (pconv_remap_backward_f32 over the
+    reverse lists of the to-ERP map on the padded stack seen as one 6A x A plane, built at the first backward and cached
+    like the map): the same values, both backwards ordered"""
     sp = _spec(spec, layout)
-    if torch.is_grad_enabled() and torch.is_tensor(y) and y.requires_grad:
-        raise PconvError("cube: to_erp of a tensor that requires grad: the face continuation (pconv_cube_pad_f32) has no "
-                         "backward yet; detach the picture, or train on the ERP side")
+    if not grad and torch.is_grad_enabled() and torch.is_tensor(y) and y.requires_grad:
+        raise PconvError("cube: to_erp of a tensor that requires grad: the face continuation (pconv_cube_pad_f32) has no backward "
+                         "without the opt-in; pass grad=True, detach the picture, or train on the ERP side")
     faces = unpack(y, sp.layout)
     a = _check_stack(faces)
     h, w = _check_erp(*(erp_size(a) if size is None else size))
     ss = to_erp_ss(a, h, w) if ss is None else _check_ss(ss)
     map = to_erp_map(sp.kind, a, h, w, ss, y.device)
+    if grad and torch.is_grad_enabled() and y.requires_grad:
+        key = (sp.kind, a, h, w, ss, str(map.device))
+        views = [(map, lambda: _to_erp_reverse_lists(*key), ss)]
+        padded = pad(faces.contiguous(), sp.kind, PAD, grad=True)
+        return viewport._Remap.apply(padded, lambda t: _render(t, map, h, w, ss, False).unsqueeze(1), views, bool(clamp))[:, 0]
     return _render(pad(faces.contiguous(), sp.kind), map, h, w, ss, clamp)
 
 
@@ -693,6 +810,27 @@ def ws_ssim(x, y, spec, rule="solid-angle"):
     """float64 (n,) WS-SSIM of each cube picture: the mean over the channels of ws_ssim_planes"""
     from . import weighted_metrics
     return weighted_metrics.channel_mean(ws_ssim_planes(x, y, spec, rule))
+
+
+def ws_ssim_loss_terms(x, y, spec, rule="solid-angle"):
+    """float64 (n,) on the pictures' device, attached to autograd: ws_ssim's figure as a loss term.  x, y: float32 (n, C,
+    height, width) cube pictures of one spec and face size (uint8 carries no gradient and is refused).  Both are unpacked,
+    continued by SSIM_PAD pixels with pad(.., grad=True) and scored by weighted_metrics.ssim_loss_terms on ssim_plane.  The
+    rings weigh zero but their gradient is not zero -- ring pixels lie in the windows of weighted pixels -- and
+    `pad_backward` carries it to the neighbouring faces.  GPU tensors: HIP kernels all the way, forward and backward; CPU
+    tensors: pad_torch / pad_backward_torch and the float64 torch statement of the SSIM.  ws_ssim's limits hold"""
+    from . import weighted_metrics
+    sp = _spec(spec)
+    if not (torch.is_tensor(x) and torch.is_tensor(y)) or x.shape != y.shape or x.dtype != y.dtype or x.device != y.device \
+            or x.dim() != 4 or x.dtype != torch.float32:
+        raise PconvError("cube ws_ssim loss: two float32 (n, C, height, width) cube pictures of one kind, layout, face size and "
+                         "device expected (uint8 frames carry no gradient), got %s and %s"
+                         % tuple("%s %s on %s" % (t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__
+                                 for t in (x, y)))
+    a = _picture_face(x, sp)
+    stacks = [pad(unpack(t, sp.layout).contiguous(), sp.kind, SSIM_PAD, grad=torch.is_grad_enabled() and t.requires_grad)
+              for t in (x, y)]
+    return weighted_metrics.ssim_loss_terms(stacks[0], stacks[1], ssim_plane(sp.kind, a, rule))
 
 
 def point_directions(pointset):

@@ -235,7 +235,7 @@ class TrainState(object):
     # the arguments that do not shape the trajectory: a resumed run may change them
     FREE = ("epochs", "time_budget", "stop_after", "resume", "verbose", "workers", "base_dir")
     DERIVED = ("deadline", "gpu_id")   # what train.py itself hangs on the namespace
-    LATER = ("vp_size", "code_size")   # arguments newer than the first state files: at their default (None) they leave no trace
+    LATER = ("vp_size", "code_size", "cube_kind", "cube_face")   # arguments newer than the first state files: at their default (None) they leave no trace
 
     def __init__(self):
         self.epoch, self.next_batch, self.global_batch = 1, 0, 0

@@ -49,7 +49,7 @@ from .model_zoo_v2 import AccGrad
 
 SPHERE_LOSSES = {'ws': sphere_metrics.loss_terms, 'ws-ms': sphere_metrics.ms_loss_terms}   # --loss: read the ERP frames
 
-OWN_LOSSES = tuple(SPHERE_LOSSES) + ('vp',)   # --loss: no MultiProject, no SSIM module; test() scores by the loss itself
+OWN_LOSSES = tuple(SPHERE_LOSSES) + ('vp', 'cube-ws')   # --loss: no MultiProject, no SSIM module; test() scores by the loss itself
 _vp_renderers = {}   # (h, w, device, --vp-size) -> viewport.Renderer of the 14 paper views
 
 
@@ -101,6 +101,22 @@ def vp_renderer(args, data):
     return _vp_renderers[key]
 
 
+def cube_ws_terms(args, data, y):
+    """the two distortion terms of --loss cube-ws, float64 (n,) each: cube.ws_loss_terms (the solid-angle weighted squared
+    error) and cube.ws_ssim_loss_terms (the cube WS-SSIM that --cube-ssim reports) of cube.from_erp(y) against
+    cube.from_erp(data), a --cube-kind picture ("3x2") of face size --cube-face, by default cube.face_size(h, w).  The
+    target is data: it is converted under no_grad.  The gradient reaches y through the ordered backwards of the weighted
+    metrics, of the face continuation and of from_erp's renderer"""
+    from . import cube
+    kind, a = getattr(args, 'cube_kind', None), getattr(args, 'cube_face', None)
+    a = cube.face_size(*data.shape[2:]) if a is None else a
+    sp = cube.spec(kind or 'cmp', '3x2')
+    with torch.no_grad():
+        target = cube.from_erp(data, a, sp)
+    picture = cube.from_erp(y, a, sp)
+    return cube.ws_loss_terms(target, picture, sp), cube.ws_ssim_loss_terms(target, picture, sp)
+
+
 def get_params(model, ent):
     m = model.module
     if ent:
@@ -131,6 +147,8 @@ def forward_losses(args, model, data, pr1, pr2, sim_func):
     elif args.loss == 'vp':
         terms = viewport.loss_terms(vp_renderer(args, data), data, y)
         mse, ssim = terms[:, 0].mean(), terms[:, 1].mean()
+    elif args.loss == 'cube-ws':
+        mse, ssim = (t.mean() for t in cube_ws_terms(args, data, y))
     else:
         py, px = pr1(y), pr2(data)
         mse = torch.mean((px - py) * (px - py))
@@ -461,6 +479,10 @@ def _job(rank, world_size, args):
         log.log('loss: MSE / SSIM over the 14 anti-aliased views of viewport.py at {} (--viewport_size is ignored)'.format(
             'the size of --test --vp (a quarter of the width)' if getattr(args, 'vp_size', None) is None else
             '{}x{}'.format(args.vp_size[1], args.vp_size[0])))
+    if args.loss == 'cube-ws':
+        log.log('loss: WS-MSE / WS-SSIM over the {} cube picture of the frames, faces of {} (--viewport_size is ignored)'.format(
+            getattr(args, 'cube_kind', None) or 'cmp',
+            'cube.face_size(h, w)' if getattr(args, 'cube_face', None) is None else args.cube_face))
     if getattr(args, 'code_size', None) is not None:
         log.log('code size: the model runs at {}x{}; losses and rate are those of the frames at their own size'.format(
             args.code_size[1], args.code_size[0]))
@@ -529,15 +551,22 @@ def build_parser():
                         help='the transforms only, no entropy model (trainDDP_Base.py)')
     parser.add_argument('--latest', action='store_true', default=False)
     parser.add_argument('--restart', action='store_true', default=False)
-    parser.add_argument('--loss', default='viewport', choices=['viewport', 'ws', 'ws-ms', 'vp'],
+    parser.add_argument('--cube-kind', default=None, choices=['cmp', 'eac'],
+                        help='the cube projection of --loss cube-ws (default: cmp)')
+    parser.add_argument('--cube-face', type=int, default=None, metavar='A',
+                        help='the face size of --loss cube-ws (default: cube.face_size(h, w), a quarter of the width)')
+    parser.add_argument('--loss', default='viewport', choices=['viewport', 'ws', 'ws-ms', 'vp', 'cube-ws'],
                         help='distortion terms: viewport = MSE and SSIM over 14 rectilinear views (the paper\'s loss); '
                              'ws = WS-MSE and WS-SSIM over the ERP frame (sphere_metrics.loss_terms: what --test --ws '
                              'reports); ws-ms = WS-MSE and WS-MS-SSIM (sphere_metrics.ms_loss_terms: --test --ws --ms-ssim); '
                              'vp = MSE and SSIM over the 14 paper directions rendered by viewport.py, anti-aliased, at a '
                              'size that follows the frame (viewport.loss_terms: what --test --vp reports; the gradient '
                              'runs through the renderer\'s ordered, atomic-free backward, and for a view of more than 4 '
-                             'source pixels per view pixel through that of the resize in front of it).  '
-                             'gamma, beta and alpha weigh the terms alike; with ws, ws-ms and vp the best checkpoint is '
+                             'source pixels per view pixel through that of the resize in front of it); '
+                             'cube-ws = the solid-angle weighted squared error and the cube WS-SSIM (what --cube-ssim '
+                             'reports) of the output and the frame, both converted to a --cube-kind cube picture of face '
+                             'size --cube-face (cube.ws_loss_terms, cube.ws_ssim_loss_terms).  '
+                             'gamma, beta and alpha weigh the terms alike; with ws, ws-ms, vp and cube-ws the best checkpoint is '
                              'the one with the lowest gamma*mse + beta*(1 - ssim) + alpha*rate on the test set')
     parser.add_argument('--vp-size', type=vp_size, default=None, metavar='WxH',
                         help='size of a view of --loss vp (default: that of --test --vp, W = width // 4, H = (2 W + 1) // 3: '

@@ -22,7 +22,12 @@ With erp_plane(h, w) the mean over the channels is sphere_metrics' WS-SSIM.  A w
 is the caller who lays the picture out so that a window's neighbourhood in the plane is its neighbourhood on the sphere
 wherever the weight is not zero (cube.ws_ssim continues every face by the window's radius and weighs the ring zero).
 The kernel computes the map in fp32 (the passes of pconv_ws_metrics_f32) and the sum in fp64 in the header's order; the
-twin `ssim_torch` is the definition in float64: the two agree to about 1e-6, not to the bit.  Forward only.
+twin `ssim_torch` is the definition in float64: the two agree to about 1e-6, not to the bit.  `ssim` and its twins are forward
+only (a tensor that requires grad is refused); the way in for training is `ssim_loss_terms`.
+Backward, of sum(gout * SSIM) with respect to y (`ssim_backward`, pconv_weighted_ssim_backward_f32): sphere_metrics' gradient
+with the per-row factor replaced by a per-pixel one, k_p = (gout[f][c] w_p) / W in fp64, rounded once to fp32 and zero
+outside the plane;  grad = (blur(k a) + (2 y) blur(k b)) + x blur(k c), a, b, c those of sphere_metrics' head; no km term.
+One kernel, the ERP backward's passes; `ssim_backward_torch` is the statement, and the kernel is held to it by a bound.
 
 GPU tensors go to the HIP kernels (_metric_ops.weighted_mse_*, weighted_ssim_device); CPU tensors to the torch twins below;
 for the squared error they follow the definition operation by operation: the bits are equal.  The twins are no fallback
@@ -30,8 +35,8 @@ for GPU tensors.
 
 Limits.  W is supplied by the host (`WeightPlane.total`: math.fsum, the exactly rounded sum), never summed on the device.
 A weight of zero is allowed (a mask); negative or non-finite weights and a plane that sums to zero are refused when the
-plane is made.  The SSIM has no uint8 kernel (uint8 frames are converted first), no multi-scale form and no gradient.
-No 4:2:0.
+plane is made.  The SSIM has no uint8 kernel (uint8 frames are converted first) and no multi-scale form; its gradient is
+held to a bound, not to the bit.  No 4:2:0.
 """
 import collections
 import math
@@ -275,6 +280,75 @@ def ssim(x, y, plane):
     size.  GPU tensors: the HIP kernel (fp32 map); CPU tensors: ssim_torch (float64).  A tensor that requires grad is
     refused"""
     return ssim_device(x, y, plane).cpu()
+
+
+def _check_gout(x, gout, what):
+    if not torch.is_tensor(gout) or tuple(gout.shape) != tuple(x.shape[:2]):
+        raise PconvError("%s: gout (n, C) = %s expected, got %s" % (what, tuple(x.shape[:2]), tuple(gout.shape)
+                                                                    if torch.is_tensor(gout) else type(gout).__name__))
+
+
+def ssim_backward_torch(x, y, plane, gout, dt=torch.float64):
+    """the gradient of sum(gout * ssim(x, y, plane)) with respect to y by the explicit formula of include/pconv_hip.h
+    (pconv_weighted_ssim_backward_f32), in torch: the statement the HIP kernel is held to.  x, y (n, C, H, W); gout (n, C).
+    k = (gout w) / W is formed in float64 and rounded once to dt; everything else runs in dt, operation by operation in the
+    kernel's order: sphere_metrics' moments, coefficients and (blur(k a) + (2 y) blur(k b)) + x blur(k c).  Returns dt
+    (n, C, H, W)"""
+    plane = _plane(plane)
+    _check(x, y, plane, "weighted ssim loss")
+    _check_gout(x, gout, "weighted ssim loss")
+    k = ((gout.detach().double().to(x.device)[:, :, None, None] * plane.on(x.device)[None, None]) / plane.total).to(dt)
+    x, y = x.detach().to(dt), y.detach().to(dt)
+    g = sphere_metrics.gaussian()
+    return sphere_metrics._own(x, y, k, sphere_metrics._coefficients(sphere_metrics._moments(x, y, g), True), g)
+
+
+def ssim_backward(x, y, plane, gout):
+    """float32 (n, C, H, W): the gradient of sum(gout * ssim_device(x, y, plane)) with respect to y; x, y float32 GPU
+    tensors, gout float64 (n, C) on their device.  The HIP kernel, one launch (the passes of sphere_metrics' backward with a
+    per-pixel factor); it agrees with ssim_backward_torch to a bound, not to the bit.  For the gradient with respect to x
+    swap x and y.  CPU tensors are refused: ssim_backward_torch is the statement there"""
+    plane = _plane(plane)
+    _check(x, y, plane, "weighted ssim loss")
+    _check_gout(x, gout, "weighted ssim loss")
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise PconvError("weighted ssim loss: ssim_backward is the HIP kernel: float32 GPU tensors expected, got %s on %s "
+                         "(ssim_backward_torch states the gradient on any device)" % (x.dtype, x.device))
+    return _metric_ops.weighted_ssim_backward(x.contiguous(), y.contiguous(), plane.on(x.device), plane.total, gout.contiguous())
+
+
+class _Ssim(torch.autograd.Function):
+    """the weighted SSIM per plane of float32 GPU batches: the forward kernel, and the backward kernel once per input that
+    needs a gradient"""
+
+    @staticmethod
+    def forward(ctx, x, y, plane):
+        ctx.save_for_backward(x, y)
+        ctx.plane = plane
+        return _metric_ops.weighted_ssim_device(x, y, plane.on(x.device), plane.total)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        x, y = ctx.saved_tensors
+        return (ssim_backward(y, x, ctx.plane, gout) if ctx.needs_input_grad[0] else None), \
+            (ssim_backward(x, y, ctx.plane, gout) if ctx.needs_input_grad[1] else None), None
+
+
+def ssim_loss_terms(x, y, plane):
+    """float64 (n,) on the inputs' device, attached to autograd: per frame the mean over the channels of the weighted SSIM
+    (`ssim`'s values), as a loss term.  x, y: float (n, C, H, W) of one shape; uint8 carries no gradient and is refused.
+    GPU tensors (float32): the HIP kernels forward and backward, no host synchronisation.  CPU tensors: the float64 torch
+    statement (ssim_torch's), differentiated by torch"""
+    plane = _plane(plane)
+    _check(x, y, plane, "weighted ssim loss")
+    if not x.is_floating_point() or (x.is_cuda and x.dtype != torch.float32):
+        raise PconvError("weighted ssim loss: float32 (n, C, H, W) batches expected (uint8 frames carry no gradient), got %s %s"
+                         % (x.dtype, tuple(x.shape)))
+    if x.is_cuda:
+        return channel_mean(_Ssim.apply(x.contiguous(), y.contiguous(), plane))
+    ssim_map = sphere_metrics._ssim_map(sphere_metrics._moments(x.double(), y.double(), sphere_metrics.gaussian()), True)
+    return channel_mean((ssim_map * plane.on(x.device)).sum(dim=(2, 3)) / plane.total)
 
 
 def ssim_figure(x, y, plane):
